@@ -40,6 +40,7 @@ os.environ["MODGPU_REQUIRE_GPU"] = "1"
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md, chip-level parameters)
+RANK_FAILURE_GRACE_S = 5.0  # launch_ranks: how long the other ranks may take to end by themselves after one has failed
 
 
 def cpu_model():
@@ -105,6 +106,29 @@ def cpu_baseline(sample_bytes):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000  # --dump-outputs: every file of every rank together
+DUMP_WINDOW = 64 << 10
+
+
+def dump_windows(n, world):
+    """Offsets of the byte windows --dump-outputs keeps from an n-byte part: the whole part when it fits, else a fixed, seeded
+    choice of windows (the first and the last always among them) that depends on n and the rank count only.  Per rank two
+    float32 arrays of at most 4 Mi / world values each: 32 MiB in all plus the offsets, inside DUMP_BUDGET_BYTES.
+    Returns (offsets, window bytes)."""
+    per_rank = max(1, (4 << 20) // world)
+    if n <= per_rank:
+        return np.zeros(1, np.int64), n
+    win = min(DUMP_WINDOW, per_rank // 2)  # (at least two windows: the first and the last)
+    rng = np.random.default_rng(0x44554D50)
+    offs = np.sort(rng.integers(0, n - win + 1, size=per_rank // win, dtype=np.int64))
+    offs[0], offs[-1] = 0, n - win
+    return offs, win
+
+
+def sample_part(part, offs, win):
+    return np.concatenate([part.download(win, offset=int(o)) for o in offs]).astype(np.float32)
+
+
 def load_traffic(n_bytes, kernel, source_hash):
     """HBM bytes per launch from the committed PMC summary (profiles/pmc_summary.json) -- but only if that
     summary was taken on THIS device code (same kernel-source hash, same instantiation, same part size).
@@ -158,8 +182,10 @@ class _StdoutToStderr:
 def launch_ranks(n_ranks, argv):
     """`python bench.py --gpus N` by itself: start N NEW processes of this script, rank r on GPU r, and wait for them.
     This process stays off the GPU (it never imports modulate_amd); no process that has opened the GPU is replaced or
-    re-executed; a failing rank is a non-zero exit, upon which the others are ended by PID.  Rank 0's stdout is relayed as the
-    last thing on this process's stdout; the other ranks' stdout goes to stderr.  Returns the worst child status."""
+    re-executed; a failing rank is a non-zero exit, upon which the others get RANK_FAILURE_GRACE_S to end by themselves (ranks
+    that meet the same error fail together) and are then ended by PID.  Every rank that does not exit 0 gets one line on stderr.
+    Rank 0's stdout is relayed as the last thing on this process's stdout; the other ranks' stdout goes to stderr.  Returns the
+    worst status of the ranks that ended by themselves."""
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
@@ -186,6 +212,7 @@ def launch_ranks(n_ranks, argv):
     reader = threading.Thread(target=lambda: rank0_out.append(procs[0].stdout.read()), daemon=True)
     reader.start()
     worst = 0
+    first_failed, grace_end = None, None
     live = set(range(n_ranks))
     while live:
         for r in sorted(live):
@@ -197,16 +224,25 @@ def launch_ranks(n_ranks, argv):
             if rc != 0:
                 print(f"bench.py: rank {r} exited with status {rc}", file=sys.stderr)
                 worst = max(worst, rc)
-        if worst and live:  # one rank failed: the others would wait for it at the next barrier
+                if first_failed is None:
+                    first_failed, grace_end = r, time.monotonic() + RANK_FAILURE_GRACE_S
+        if live and first_failed is not None and time.monotonic() >= grace_end:
+            # one rank failed and the others have not ended by themselves: they would wait for it at the next barrier
             for r in live:
                 procs[r].terminate()
             deadline = time.monotonic() + 10.0
-            for r in live:
+            for r in sorted(live):
                 try:
-                    procs[r].wait(timeout=max(0.1, deadline - time.monotonic()))
+                    rc = procs[r].wait(timeout=max(0.1, deadline - time.monotonic()))
                 except subprocess.TimeoutExpired:
                     procs[r].kill()
-                    procs[r].wait()
+                    rc = procs[r].wait()
+                if rc in (-signal.SIGTERM, -signal.SIGKILL):
+                    print(f"bench.py: rank {r} ended by the launcher after rank {first_failed} failed (status {128 - rc})", file=sys.stderr)
+                elif rc != 0:  # it ended by itself between the last poll and terminate()
+                    rc = 128 - rc if rc < 0 else rc
+                    print(f"bench.py: rank {r} exited with status {rc}", file=sys.stderr)
+                    worst = max(worst, rc)
             live.clear()
         time.sleep(0.05)
     reader.join(timeout=10.0)
@@ -232,7 +268,13 @@ def main():
                          "gloo = torch.distributed on CPU tensors; nccl = RCCL on device tensors")
     ap.add_argument("--force-device", type=int, default=None, help="rehearsal only: every rank uses this HIP device")
     ap.add_argument("--force-dist", action="store_true", help="rehearsal only: bring the control plane up even with one rank")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (the part after its encrypt pass and after its decrypt "
+                         "pass, a fixed sample of windows as float32 byte values) and the windows' offsets to DIR/rank<r>_<name>.npy, "
+                         "at most 64 MB in all")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_ranks(a.gpus, sys.argv[1:]))
     if a.force_dist:
@@ -369,6 +411,13 @@ def main():
     ms_per_launch = sharding.max_over_ranks(ms_per_launch, red_dev)
     launch = M.last_launch()  # what the library launched for this size, straight from its planner
 
+    # --dump-outputs (outside the timed region): the part now holds the last step's decrypt-pass output.  The check below cycles the
+    # same input bytes once more through the same launch path, so the part then holds the last step's encrypt-pass output again.
+    dump = None
+    if a.dump_outputs:
+        dump_offs, dump_win = dump_windows(n, world)
+        dump = {"window_offsets": dump_offs.astype(np.float64), "last_step_decrypt_pass": sample_part(part, dump_offs, dump_win)}
+
     # post-run checks (outside the timed region; no oracle code here -- committed golden DATA only):
     # an even number of passes must give the original bytes back (involution), and after one more
     # pass  ciphertext ^ plaintext  must equal the reference's own keystream samples
@@ -379,6 +428,11 @@ def main():
         ok = ok and bool(np.array_equal(part.download(ln, offset=off), np.resize(np.roll(tile, -(off % tile.size)), ln)))
     part.cycle(a.key)
     part.sync()
+    if dump is not None:
+        dump["last_step_encrypt_pass"] = sample_part(part, dump_offs, dump_win)
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, arr in dump.items():
+            np.save(os.path.join(a.dump_outputs, f"rank{rank}_{name}.npy"), arr)
     checked = 0
     if a.key == 0x90CFC0AB:
         with open(os.path.join(ROOT, "tests", "golden", "cycle_golden.json")) as f:

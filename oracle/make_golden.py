@@ -56,6 +56,15 @@ def main():
             g["plaintext_cases"].append({"key": key, "n": n, "seed": SEED + n,
                                          "pt_fnv": f"{O.fnv1a64(pt):016x}", "ct_fnv": f"{O.fnv1a64(ct):016x}",
                                          "ct_first16": ct[:16].tobytes().hex(), "ct_last16": ct[-16:].tobytes().hex()})
+    # the checker against the compiled reference (tests/test_oracle.py::test_against_compiled_reference): the edge keys and 24 drawn
+    # ones on drawn sizes below 70 000, and one 16 MiB buffer, splitmix64 plaintext
+    rng = np.random.default_rng(5)
+    ref_keys = [O.KEY_PS3, O.KEY_PS4, 0, 1, 0x7FFFFFFF, 0x80000000, 0x80000001, 0xFFFFFFFF] + [int(x) for x in rng.integers(0, 1 << 32, size=24)]
+    g["reference_cases"] = []
+    for i, (key, n) in enumerate([(k, int(rng.integers(0, 70000))) for k in ref_keys] + [(O.KEY_PS4, 1 << 24)]):
+        ct = O.ref_cycle(O.splitmix_bytes(n, 99 + i), key)
+        g["reference_cases"].append({"key": key, "n": n, "seed": 99 + i, "ct_fnv": f"{O.fnv1a64(ct):016x}",
+                                     "ct_first16": ct[:16].tobytes().hex(), "ct_last16": ct[-16:].tobytes().hex()})
     # b[i] = (i*131+7)&0xFF, 4096 B, PS4 key
     b = ((np.arange(4096, dtype=np.uint32) * 131 + 7) & 0xFF).astype(np.uint8)
     ct = O.ref_cycle(b.copy(), 0x90CFC0AB)

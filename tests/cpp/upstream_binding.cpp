@@ -1,7 +1,7 @@
-// tests/cpp/upstream_binding.cpp -- the binding INTEGRATION.md tells an upstream maintainer to add, compiled against
-// the UPSTREAM header where it lies (-I/root/reference/Modulate: their pch.h and CEncryptionCycler.h, nothing of
-// theirs is copied here) and linked against libmodgpu.so.  tests/test_host_cpu.py builds and runs it when the
-// reference tree is present: the class the reference's three call sites use, with this repo's body.
+// tests/cpp/upstream_binding.cpp -- the binding INTEGRATION.md tells an upstream maintainer to add, compiled against the
+// class declaration upstream's callers use (this repo's drop-in modulate_amd/csrc/host/CEncryptionCycler.h: same class, same
+// signature; tests/test_host_cpu.py puts an empty pch.h beside it) and linked against libmodgpu.so.  tests/test_host_cpu.py
+// builds and runs it: the class the reference's three call sites use, with the binding's body.
 #include "pch.h"
 #include "CEncryptionCycler.h"
 #include "modgpu.h"

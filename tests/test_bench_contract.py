@@ -37,6 +37,48 @@ def test_bench_gpus_n_starts_its_own_ranks(modgpu):
     assert '"metric"' not in r.stdout and "torch" not in r.stderr
 
 
+def test_launcher_reports_the_ranks_it_ends(tmp_path):
+    """One rank fails at once, the other would wait for it forever (stand-in ranks, as below): the parent reports the failed rank's
+    status, gives the other bench.RANK_FAILURE_GRACE_S to end by itself, then ends it and says so -- one line per rank -- and returns
+    the failed rank's status."""
+    stand_in = tmp_path / "bench.py"
+    stand_in.write_text("import os, sys, time\nif os.environ['RANK'] == '1':\n    sys.exit(3)\ntime.sleep(120)\n")
+    code = ("import sys, time, bench\n"  # (bench sets the library's environment at import: only in a child process)
+            f"bench.__file__ = {str(stand_in)!r}\n"
+            "t0 = time.monotonic()\n"
+            "rc = bench.launch_ranks(2, [])\n"
+            "print(bench.RANK_FAILURE_GRACE_S, time.monotonic() - t0)\n"
+            "raise SystemExit(rc)\n")
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=dict(os.environ, PYTHONPATH=ROOT), capture_output=True, text=True, timeout=60)
+    assert r.returncode == 3, r.stdout + r.stderr
+    assert r.stderr.count("bench.py: rank") == 2 and "rank 1 exited with status 3" in r.stderr, r.stderr
+    assert "rank 0 ended by the launcher after rank 1 failed (status 143)" in r.stderr, r.stderr
+    grace, took = map(float, r.stdout.split())
+    assert grace <= took < grace + 20
+
+
+def test_bench_steps_and_warmup_are_checked():
+    """`--steps K` is the number of timed steps: K < 1 (nothing to time) and a negative warm-up are usage errors before anything runs."""
+    for args in (["--steps", "0"], ["--steps", "-1"], ["--warmup", "-1"]):
+        r = _run(args + ["--part-bytes", "4096"])
+        assert r.returncode == 2 and "--steps must be at least 1" in r.stderr and "no HIP device" not in r.stderr, (args, r.stderr)
+
+
+def test_dump_outputs_sample_stays_within_budget():
+    """`--dump-outputs`: per rank two float32 samples + float64 offsets, all ranks together within bench.DUMP_BUDGET_BYTES; the
+    windows are the same for the same arguments, lie inside the part and include its first and last bytes."""
+    code = ("import numpy as np, bench\n"
+            "for n in (4096, (64 << 20) + 5, 1 << 32, 1 << 36):\n"
+            "    for world in (1, 2, 3, 8, 64, 200):\n"
+            "        offs, win = bench.dump_windows(n, world)\n"
+            "        assert np.array_equal(offs, bench.dump_windows(n, world)[0])\n"
+            "        assert world * (2 * 4 * offs.size * win + 8 * offs.size) <= bench.DUMP_BUDGET_BYTES, (n, world)\n"
+            "        assert offs[0] == 0 and offs[-1] + win == n and (offs >= 0).all() and (offs + win <= n).all(), (n, world)\n"
+            "print('DUMP_WINDOWS_OK')\n")
+    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=dict(os.environ, PYTHONPATH=ROOT), capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "DUMP_WINDOWS_OK" in r.stdout, r.stdout + r.stderr
+
+
 def _plane_rank(rank, world, address, q, die_at=None):
     from modulate_amd import rendezvous, sharding
     try:

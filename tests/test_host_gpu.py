@@ -447,6 +447,35 @@ def test_bench_gpus_two_by_itself(host):
     assert "no torch" in out["config"]["control_plane"] and "RCCL version" not in (r.stdout + r.stderr)
 
 
+def test_bench_dump_outputs(host, oracle, tmp_path):
+    """`bench.py --dump-outputs DIR`: the last step's two passes, sampled, as float32 byte values; the same bytes from run to run;
+    the encrypt pass is the oracle's keystream over the decrypt pass (= the part's plaintext) at the same offsets."""
+    import json
+    import sys
+    n = (64 << 20) + 5
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"dump{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(2 + run), "--warmup", "1", "--part-bytes", str(n),
+                            "--no-first-pass", "--no-cpu-baseline", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
+        assert out["steps"] == 2 + run and out["roofline"]["timed_launches"] == [2, 2 + 2 * (2 + run)]
+        assert sorted(os.listdir(d)) == ["rank0_last_step_decrypt_pass.npy", "rank0_last_step_encrypt_pass.npy", "rank0_window_offsets.npy"]
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64 * 1000 * 1000
+        dumps.append({f.name: np.load(f) for f in d.iterdir()})
+    for name, arr in dumps[0].items():
+        assert arr.dtype in (np.float32, np.float64) and np.array_equal(arr, dumps[1][name]), name
+    offs = dumps[0]["rank0_window_offsets.npy"].astype(np.int64)
+    plain = dumps[0]["rank0_last_step_decrypt_pass.npy"].astype(np.uint8)
+    enc = dumps[0]["rank0_last_step_encrypt_pass.npy"].astype(np.uint8)
+    win = plain.size // offs.size
+    assert offs[0] == 0 and offs[-1] == n - win and plain.size == enc.size == 4 << 20
+    for k, off in enumerate(offs):
+        w = slice(k * win, (k + 1) * win)
+        assert np.array_equal(oracle.cycle_at(plain[w].copy(), oracle.KEY_PS4, int(off)), enc[w]), int(off)
+
+
 def test_bench_two_ranks_rehearsal(host, tmp_path):
     """The driver's N>1 launch line (torch.distributed.run, one rank per GPU) rehearsed with 2 ranks on this
     box's one GPU: gloo for the barrier / MAX (RCCL wants one GPU per rank), both ranks on device 0.

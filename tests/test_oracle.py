@@ -3,11 +3,11 @@
 * the golden vectors emitted by the COMPILED REFERENCE (tests/golden/cycle_golden.json, made by
   oracle/make_golden.py over oracle/_ref), including the 2^32-1 byte run,
 * the known-answer bytes recorded in SURVEY.md 8c,
-* the compiled reference itself when oracle/_ref is present (this container), and
+* the compiled reference's own outputs on 33 more cases (the same golden file), and directly where
+  oracle/_ref is present, and
 * a third, pure-Python statement of CEncryptionCycler.cpp:4-25 on small cases.
 """
 import numpy as np
-import pytest
 
 # SURVEY.md 8c known-answer keystream prefixes (Cycle over zero bytes), captured from the
 # compiled reference during the survey.
@@ -127,16 +127,15 @@ def test_header_framing(oracle):
     assert oracle.hdr_decrypt(bad) == 3  # eError_UnknownVersionNumber
 
 
-def test_against_compiled_reference(oracle):
-    """Direct comparison with the reference's object code (only where oracle/_ref exists)."""
-    if not oracle.have_ref():
-        pytest.skip("oracle/_ref not built (no reference sources on this machine)")
-    rng = np.random.default_rng(5)
-    keys = [oracle.KEY_PS3, oracle.KEY_PS4, 0, 1, 0x7FFFFFFF, 0x80000000, 0x80000001, 0xFFFFFFFF] + \
-        [int(x) for x in rng.integers(0, 1 << 32, size=24)]
-    for key in keys:
-        n = int(rng.integers(0, 70000))
-        pt = rng.integers(0, 256, size=n, dtype=np.uint8)
-        assert np.array_equal(oracle.ref_cycle(pt.copy(), key), oracle.cycle(pt.copy(), key)), hex(key)
-    pt = oracle.splitmix_bytes(1 << 24, 99)
-    assert np.array_equal(oracle.ref_cycle(pt.copy(), oracle.KEY_PS4), oracle.cycle(pt.copy(), oracle.KEY_PS4))
+def test_against_compiled_reference(oracle, golden):
+    """The checker against the reference's object code: 32 keys (edge + drawn) on drawn sizes < 70 000 and one 16 MiB buffer, by
+    the digests the compiled reference produced (tests/golden `reference_cases`), and directly where oracle/_ref exists."""
+    cases = golden["reference_cases"]
+    assert len(cases) == 33 and cases[-1]["n"] == 1 << 24
+    for c in cases:
+        pt = oracle.splitmix_bytes(c["n"], c["seed"])
+        ct = oracle.cycle(pt.copy(), c["key"])
+        assert f"{oracle.fnv1a64(ct):016x}" == c["ct_fnv"], hex(c["key"])
+        assert ct[:16].tobytes().hex() == c["ct_first16"] and ct[-16:].tobytes().hex() == c["ct_last16"], hex(c["key"])
+        if oracle.have_ref():
+            assert np.array_equal(oracle.ref_cycle(pt.copy(), c["key"]), ct), hex(c["key"])
