@@ -92,7 +92,8 @@ extern "C" {
 #define MODGPU_KEY_PS3 0xc64eed30u
 #define MODGPU_KEY_PS4 0x90cfc0abu
 
-/* ABI version of this header (bumped on any signature change). */
+/* ABI version of this header (bumped on any signature change; ABI 8 also gained modgpu_cycle_device_to and
+ * modgpu_cycle_batch_device_to, an addition that changes no existing signature). */
 #define MODGPU_ABI_VERSION 8
 int modgpu_abi_version(void);
 
@@ -137,6 +138,33 @@ int modgpu_cycle_device(void *dev_buf, uint64_t n, int32_t key, uint64_t stream_
  * a 411 MB part and most of the time of a small one (measured: +5 % at 8 x 411 MB, +30 % at 16 x 50 MB, 3x at 16 x 1 MiB). */
 int modgpu_cycle_batch_device(void *const *dev_parts, const uint64_t *sizes, const uint64_t *stream_offs, int n_parts,
                               int32_t key, int device, void *hip_stream);
+
+/* OUT OF PLACE: dev_dst[j] = dev_src[j] ^ ks[stream_off + j], j = 0 .. n-1, in one pass (src read once, dst written once);
+ * dev_src is not modified.  Same keystream, 64-bit offsets and key reduction as modgpu_cycle_device, and the same contract:
+ * asynchronous on `hip_stream`, `device` -1 = the current device (an explicit device leaves the thread's current device as it
+ * was), allocation-free, capturable into a hipGraph; the concurrency and graph-scratch rules are the ones documented at
+ * modgpu_cycle_device (a launch that finds no scratch -- every eager line busy, or a capture with the pool used up -- copies
+ * with hipMemcpyAsync and cycles in place on the same stream: correct and capturable, two passes over HBM instead of one).  Edge cases:
+ *   - src and dst may each have any byte alignment; their phases mod 16 are independent;
+ *   - dst == src (exact alias) is allowed and gives what modgpu_cycle_device gives;
+ *   - [dst, dst+n) partly overlapping [src, src+n) is MODGPU_ERR_INVALID, returned before anything is queued;
+ *   - keys == 0 mod 2^31-1 (identity keystream) COPY: dst == src afterwards (hipMemcpyAsync on the stream);
+ *   - n == 0 does nothing; a NULL pointer with n > 0 is MODGPU_ERR_INVALID;
+ *   - either side may be page-locked host memory (modgpu_host_alloc): the kernel reaches it across PCIe -- supported, not tuned.
+ * A kernel entry point like the rest: no host loop; MODGPU_ERR_NO_DEVICE / MODGPU_ERR_HIP as usual; path_stats().gpu_launches
+ * counts its launches. */
+int modgpu_cycle_device_to(void *dev_dst, const void *dev_src, uint64_t n, int32_t key, uint64_t stream_off,
+                           int device, void *hip_stream);
+
+/* n_parts entries of ONE device, each its own out-of-place Cycle call under one key: dst_parts[i][j] = src_parts[i][j] ^
+ * ks[stream_offs[i] + j] (stream_offs NULL = 0 for every entry).  What extracting the files of a resident archive part is:
+ * src = part + o_i, dst = the file's own buffer, stream_off = o_i.  Everything modgpu_cycle_device_to says holds per entry;
+ * in addition SOURCE ranges may overlap each other (they are only read), but a destination range that meets any other
+ * entry's source or destination range makes the whole call MODGPU_ERR_INVALID (an entry's exact self-alias is allowed).
+ * Any n_parts: up to 16 non-empty entries share one launch, more take more launches, in order, on the same stream; empty
+ * entries are skipped. */
+int modgpu_cycle_batch_device_to(void *const *dst_parts, const void *const *src_parts, const uint64_t *sizes,
+                                 const uint64_t *stream_offs, int n_parts, int32_t key, int device, void *hip_stream);
 
 /* Replaces CEncryptionCycler::Cycle (CEncryptionCycler.cpp:4-14) for a caller-owned HOST buffer,
  * on the GPU.  Pageable memory is staged through page-locked slots owned by this library (memcpy ->

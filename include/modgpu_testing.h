@@ -28,13 +28,18 @@ extern "C" {
 int modgpu_time_cycle_device(void *dev_buf, uint64_t n, int32_t key, uint64_t stream_off,
                              int device, void *hip_stream, int iters, float *ms_per_launch);
 
+/* The same for modgpu_cycle_device_to: `iters` back-to-back out-of-place launches (dst is the same after every one). */
+int modgpu_time_cycle_device_to(void *dev_dst, const void *dev_src, uint64_t n, int32_t key, uint64_t stream_off,
+                                int device, void *hip_stream, int iters, float *ms_per_launch);
+
 /* The launch the calling thread made last (any entry point), as the library planned it. */
 typedef struct modgpu_launch_info {
     const char *kernel;   /* the instantiation's name as rocprofv3 prints it, e.g.
                              "modgpu_cycle_queue_kernel<4, 1024>"; static storage */
     int variant;          /* 0 = small shape, 1 = streaming shape (static chunk map), 2 = streaming shape fed by the work queue,
                              3 = the work-queue shape over several parts in one launch (modgpu_cycle_batch_device; `bytes` = all of them),
-                             4 = the host-fed kernel of a host-buffer call (one launch for the whole call; `bytes` = the call's) */
+                             4 = the host-fed kernel of a host-buffer call (one launch for the whole call; `bytes` = the call's),
+                             5 = the out-of-place kernel (modgpu_cycle_device_to / _batch_device_to; `bytes` = all entries of the launch) */
     uint32_t grid;        /* workgroups launched                                                  */
     uint32_t block;       /* threads per workgroup                                                */
     uint32_t chunk_bytes; /* bytes one workgroup trip covers                                      */
@@ -42,7 +47,8 @@ typedef struct modgpu_launch_info {
     uint32_t main_groups; /* of `grid`: workgroups that stream from the start; the other grid - main_groups are helper
                              workgroups of the work-queue shape, which join only while the shader clock is low */
     const char *source_hash; /* identity of the TU that kernel was compiled from: modgpu_kernel_source_hash() for variants 0..3,
-                                modgpu_feed_kernel_source_hash() for variant 4; static storage */
+                                modgpu_feed_kernel_source_hash() for variant 4,
+                                modgpu_to_kernel_source_hash() for variant 5; static storage */
 } modgpu_launch_info_t;
 int modgpu_last_launch(modgpu_launch_info_t *out);
 
@@ -121,6 +127,8 @@ const char *modgpu_kernel_source_hash(void);
 /* The same for the host-fed kernel's TU (cycle_feed_kernel.hip, cycle_feed_kernel.h, cycle_kernel_impl.h, lcg.h): every
  * `roofline_pcie` profile of a host-buffer route records it. */
 const char *modgpu_feed_kernel_source_hash(void);
+/* The same for the out-of-place kernel's TU (cycle_to_kernel.hip, cycle_to_kernel.h, cycle_kernel_impl.h, cycle_kernel.h, lcg.h). */
+const char *modgpu_to_kernel_source_hash(void);
 
 /* 1 in libmodgpu_testing.so, 0 in libmodgpu.so. */
 int modgpu_testing_hooks(void);
@@ -131,6 +139,11 @@ int modgpu_testing_hooks(void);
  * 4096).  With one line every second launch in flight finds the ring busy: the collision the gating exists for
  * becomes certain instead of a 1-in-4096 event. */
 void modgpu_debug_set_queue_ring(uint32_t lines);
+
+/* How the out-of-place kernel reads a source whose phase differs from the destination's by a non-whole number of dwords:
+ * 0 = one unaligned dwordx4 per word, 1 = an aligned dwordx4 and the next dword joined by v_alignbyte_b32, -1 = the shipped
+ * form.  Measurement (tools/bench_cycle_to.py) and parity tests of both. */
+void modgpu_debug_set_to_form(int form);
 
 /* Helper workgroups of the work-queue shape (one per CU the main workgroups leave idle; they join only while the shader clock is
  * low): 0 = decide by the clock they measure (the shipped behaviour), 1 = always join, 2 = launch none.  Lets the parity tests

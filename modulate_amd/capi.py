@@ -62,6 +62,8 @@ EXPORTS = {
     "modgpu_host_alloc_near": (_int, [ctypes.POINTER(_vp), _u64, _int]),
     "modgpu_host_alloc_parts": (_int, [ctypes.POINTER(_vp), ctypes.POINTER(_u64), _int, _int]),
     "modgpu_device_numa_node": (_int, [_int]),
+    "modgpu_cycle_device_to": (_int, [_vp, _vp, _u64, _i32, _u64, _int, _vp]),
+    "modgpu_cycle_batch_device_to": (_int, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64), ctypes.POINTER(_u64), _int, _i32, _int, _vp]),
 }
 
 
@@ -106,6 +108,8 @@ TESTING_EXPORTS = {
     "modgpu_host_alloc_on_node": (_int, [ctypes.POINTER(_vp), _u64, _int]),
     "modgpu_testing_hooks": (_int, []),
     "modgpu_numa_probe": (_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(_int), ctypes.POINTER(_int), _int]),
+    "modgpu_time_cycle_device_to": (_int, [_vp, _vp, _u64, _i32, _u64, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
+    "modgpu_to_kernel_source_hash": (ctypes.c_char_p, []),
 }
 # include/modgpu_testing.h, modgpu_debug_* group: ONLY in libmodgpu_testing.so
 DEBUG_EXPORTS = {
@@ -123,6 +127,7 @@ DEBUG_EXPORTS = {
     "modgpu_debug_injection_armed": (_int, []),
     "modgpu_debug_hold_slots": (_int, [_int, _int]),
     "modgpu_debug_forbid_worker_threads": (None, [_int]),
+    "modgpu_debug_set_to_form": (None, [_int]),
 }
 
 
@@ -424,6 +429,11 @@ def kernel_source_hash():
     return lib().modgpu_kernel_source_hash().decode()
 
 
+def to_kernel_source_hash():
+    """identity of the out-of-place kernel's TU (cycle_to_kernel.hip and what it includes)"""
+    return lib().modgpu_to_kernel_source_hash().decode()
+
+
 def feed_kernel_source_hash():
     """identity of the host-fed kernel's TU (cycle_feed_kernel.hip and what it includes)"""
     return lib().modgpu_feed_kernel_source_hash().decode()
@@ -549,6 +559,40 @@ def time_cycle_device(dev_ptr, n, key, stream_off=0, device=-1, stream=None, ite
     _check(lib().modgpu_time_cycle_device(_vp(dev_ptr), n, as_int32(key), stream_off, device, _vp(stream or 0),
                                           iters, ctypes.byref(ms)))
     return ms.value
+
+
+def cycle_device_to(dst_ptr, src_ptr, n, key, stream_off=0, device=-1, stream=None):
+    """Asynchronous OUT-OF-PLACE cycle: dst[j] = src[j] ^ ks[stream_off + j] for n bytes at raw device addresses; src is not
+    modified (dst == src is the in-place call; a partial overlap is refused)."""
+    _check(lib().modgpu_cycle_device_to(_vp(dst_ptr), _vp(src_ptr), n, as_int32(key), stream_off, device, _vp(stream or 0)))
+
+
+def cycle_batch_device_to(dst_ptrs, src_ptrs, sizes, key, stream_offs=None, device=-1, stream=None):
+    """Several out-of-place entries of ONE device (entry i from stream_offs[i] or 0); sources may overlap each other, a
+    destination may meet no other entry's range.  Up to 16 non-empty entries share a launch."""
+    n = len(dst_ptrs)
+    assert len(src_ptrs) == n and len(sizes) == n
+    d = (_vp * n)(*dst_ptrs)
+    s = (_vp * n)(*src_ptrs)
+    z = (_u64 * n)(*sizes)
+    o = (_u64 * n)(*stream_offs) if stream_offs is not None else None
+    _check(lib().modgpu_cycle_batch_device_to(d, s, z, o, n, as_int32(key), device, _vp(stream or 0)))
+
+
+def time_cycle_device_to(dst_ptr, src_ptr, n, key, stream_off=0, device=-1, stream=None, iters=2):
+    """Mean ms per out-of-place launch over `iters` launches, HIP events on the launch stream."""
+    ms = ctypes.c_float(0)
+    _check(lib().modgpu_time_cycle_device_to(_vp(dst_ptr), _vp(src_ptr), n, as_int32(key), stream_off, device, _vp(stream or 0),
+                                             iters, ctypes.byref(ms)))
+    return ms.value
+
+
+TO_FORMS = {None: -1, "shipped": -1, "unaligned": 0, "funnel": 1}
+
+
+def debug_set_to_form(form=None):
+    """Testing flavour: how the out-of-place kernel reads a misaligned source ("unaligned" loads / "funnel" / None = shipped)."""
+    _debug_lib().modgpu_debug_set_to_form(TO_FORMS[form])
 
 
 def state_at(key, i):

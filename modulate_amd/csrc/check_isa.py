@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""check_isa.py <cycle_kernel.s> [<cycle_feed_kernel.s>] -- build-time guard over the gfx950 assembly of the kernel TUs (run by the
+"""check_isa.py <cycle_kernel.s> [<cycle_feed_kernel.s>] | <cycle_to_kernel.s> -- build-time guard over the gfx950 assembly of the kernel TUs (run by the
 Makefile right after the TUs are compiled and before either object exists; tests/test_capi_cpu.py runs it again and feeds it
 deliberately broken builds).
 
@@ -26,6 +26,8 @@ For EVERY kernel of either TU, whatever its arithmetic (round 6):
 The host-fed kernel (cycle_feed_kernel.s) in particular: <= 64 VGPRs, no spills, no scratch, 8 bytes of LDS, exactly two
 s_barrier, data loads nt, data stores sc1 and NOT nt (nt stores across PCIe measured 15-20 % slower), the trip's ticket and ok
 word read into scalar registers (v_readfirstlane) behind the first barrier.
+The out-of-place kernel (cycle_to_kernel.s, both forms): the register budget, no spills / scratch / private segment, the keystream
+blocks' rules above, the ticket fetch not wave-aggregated (no v_mbcnt), data loads nt, data stores nt sc1.
 Exit status 0 = all of it holds; 1 = findings on stdout."""
 import re
 import sys
@@ -187,6 +189,56 @@ def check_feed(asm, name, fn):
     return bad
 
 
+def keystream_blocks(name, fn):
+    """(does the kernel carry ks_word_carry's block, findings): the fixed-temporary discipline, the trailing s_nop 0 and the
+    30 mad + 15 addc of every block"""
+    bad = []
+    carry = [b for b in BLOCK.findall(fn) if "s[94:95]" in b]
+    if not carry:
+        return False, bad  # (a kernel without the block may use any register)
+    outside = BLOCK.sub("", fn)
+    for ln in outside.splitlines():
+        if FIXED.search(ln) and not ln.strip().startswith(";"):
+            bad.append("%s: a fixed temporary is touched OUTSIDE the keystream blocks: %s" % (name, ln.strip()))
+    for b in carry:
+        lines = [ln for ln in b.splitlines() if ln.strip()]
+        for ln in lines:
+            if FIXED.search(OWN.sub("", ln)):
+                bad.append("%s: the compiler gave a block operand a fixed temporary: %s" % (name, ln.strip()))
+        if not lines or lines[-1].split(";")[0].strip() != "s_nop 0":
+            bad.append("%s: a keystream block does not end with s_nop 0 (dst_sel forwarding hazard)" % name)
+        if len([ln for ln in lines if "v_addc_co_u32_sdwa" in ln]) != 15 or len([ln for ln in lines if "v_mad_u64_u32" in ln]) != 30:
+            bad.append("%s: a keystream block is not 30 mads + 15 addc" % name)
+    return True, bad
+
+
+def check_to(asm, bodies):
+    """the out-of-place kernel's TU (cycle_to_kernel.s): every kernel in it is a form of modgpu_cycle_to_kernel"""
+    bad = []
+    for name, fn in bodies.items():
+        if "modgpu_cycle_to_kernel" not in name:
+            bad.append("%s: the out-of-place kernel's TU holds another kernel" % name)
+            continue
+        md = metadata(asm, name)
+        if md.get("vgpr_count", 999) > 128 or md.get("sgpr_count", 999) > 102:
+            bad.append("%s: register counts beyond the budget: %s" % (name, md))
+        if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0) or "scratch_" in fn:
+            bad.append("%s: spills, scratch or a private segment: %s" % (name, md))
+        found, findings = keystream_blocks(name, fn)
+        bad += findings
+        if not found:
+            bad.append("%s: no keystream block (ks_word_carry)" % name)
+        if "v_mbcnt" in fn:
+            bad.append("%s: the atomic optimizer rewrote the ticket atomic (build the TU with -mllvm -amdgpu-atomic-optimizer-strategy=None)" % name)
+        loads = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_load_dword", ln)]
+        stores = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_store_dword", ln)]
+        if not loads or not all(ln.endswith(" nt") for ln in loads):
+            bad.append("%s: a data load is not nt" % name)
+        if not stores or not all(ln.endswith(" nt sc1") for ln in stores):
+            bad.append("%s: a data store is not nt sc1" % name)
+    return bad
+
+
 def check(asm):
     """one TU's assembly: the rules for every kernel, then those of the TU it is (the streaming kernels' or the host-fed kernel's)"""
     bad = []
@@ -202,6 +254,8 @@ def check(asm):
         if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0) or "scratch_" in bodies[feed[0]]:
             bad.append("%s: spills, scratch or a private segment: %s" % (feed[0], md))
         return bad + check_feed(asm, feed[0], bodies[feed[0]])
+    if any("modgpu_cycle_to_kernel" in n for n in bodies):
+        return bad + check_to(asm, bodies)
     queue = [n for n in bodies if "modgpu_cycle_queue_kernel" in n]
     if len(queue) != 1:
         return bad + ["expected exactly one work-queue kernel, found %d" % len(queue)]
@@ -218,24 +272,9 @@ def check(asm):
         # no pipeline of its own, so it must keep 8 waves per SIMD, i.e. at most 64 VGPRs (512 per SIMD lane / 8)
         if "modgpu_cycle_kernelILi1ELi256E" in name and md.get("vgpr_count", 999) > 64:
             bad.append("%s: the small shape needs %d VGPRs -- more than 64, fewer than 8 waves per SIMD" % (name, md.get("vgpr_count", 999)))
-        blocks = BLOCK.findall(fn)
-        carry = [b for b in blocks if "s[94:95]" in b]
-        if not carry:
-            continue  # (a kernel without the block may use any register)
-        n_carry_kernels += 1
-        outside = BLOCK.sub("", fn)
-        for ln in outside.splitlines():
-            if FIXED.search(ln) and not ln.strip().startswith(";"):
-                bad.append("%s: a fixed temporary is touched OUTSIDE the keystream blocks: %s" % (name, ln.strip()))
-        for b in carry:
-            lines = [ln for ln in b.splitlines() if ln.strip()]
-            for ln in lines:
-                if FIXED.search(OWN.sub("", ln)):
-                    bad.append("%s: the compiler gave a block operand a fixed temporary: %s" % (name, ln.strip()))
-            if not lines or lines[-1].split(";")[0].strip() != "s_nop 0":
-                bad.append("%s: a keystream block does not end with s_nop 0 (dst_sel forwarding hazard)" % name)
-            if len([ln for ln in lines if "v_addc_co_u32_sdwa" in ln]) != 15 or len([ln for ln in lines if "v_mad_u64_u32" in ln]) != 30:
-                bad.append("%s: a keystream block is not 30 mads + 15 addc" % name)
+        found, findings = keystream_blocks(name, fn)
+        bad += findings
+        n_carry_kernels += 1 if found else 0
     if n_carry_kernels != 2:
         bad.append("expected the keystream block in exactly the two streaming kernels, found it in %d" % n_carry_kernels)
     q = bodies[queue[0]]

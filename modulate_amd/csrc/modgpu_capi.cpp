@@ -19,6 +19,7 @@
 #include "crossover_table.h"
 #include "cycle_feed_kernel.h"
 #include "cycle_kernel.h"
+#include "cycle_to_kernel.h"
 #include "lcg.h"
 #include "modgpu_internal.h"
 #include "numa_place.h"
@@ -26,6 +27,9 @@
 
 #ifndef MODGPU_KERNEL_SOURCE_HASH
 #define MODGPU_KERNEL_SOURCE_HASH "unknown"
+#endif
+#ifndef MODGPU_TO_KERNEL_SOURCE_HASH
+#define MODGPU_TO_KERNEL_SOURCE_HASH "unknown"
 #endif
 
 namespace modgpu {
@@ -651,6 +655,134 @@ int cycle_batch_impl(void *const *bufs, const uint64_t *sizes, const uint64_t *o
     return MODGPU_OK;
 }
 
+// ---- out of place: dst = src ^ keystream (modgpu_cycle_device_to / modgpu_cycle_batch_device_to) ---------------------------------
+namespace {
+bool ranges_meet(const void *a, uint64_t na, const void *b, uint64_t nb)
+{
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return na && nb && x < y + nb && y < x + na;
+}
+
+// How a source whose phase differs from the destination's by a non-whole number of dwords is read (cycle_to_kernel.h): the funnel,
+// measured 1.3-2.2 % faster than unaligned loads at 64 MiB .. 4 GiB (profiles/r07_cycle_to.json)
+constexpr int kToFormShipped = CYCLE_TO_FUNNEL;
+#ifdef MODGPU_TESTING_HOOKS
+std::atomic<int> g_to_form{kToFormShipped}; // modgpu_debug_set_to_form
+int to_form() { return g_to_form.load(std::memory_order_relaxed); }
+#else
+constexpr int to_form() { return kToFormShipped; }
+#endif
+
+// One launch of the out-of-place kernel over 1..kCycleBatchMax non-empty entries of the current device.  MODGPU_OK, an error, or 1:
+// no ticket pair to be had right now (or an entry beyond the three-byte chunk jump tables): the caller copies and cycles in place.
+int launch_to(uint8_t *const *dst, const uint8_t *const *src, const uint64_t *sizes, const uint64_t *offs, int n, uint32_t key_res,
+              hipStream_t stream)
+{
+    CycleToArgs a{};
+    const uint64_t chunk = modgpu_to_chunk_bytes();
+    uint64_t total = 0, bytes = 0;
+    bool misaligned = false;
+    for (int k = 0; k < n; ++k) {
+        CycleToPart &P = a.part[k];
+        const uintptr_t addr = reinterpret_cast<uintptr_t>(dst[k]);
+        const uint64_t head = std::min<uint64_t>(sizes[k], (16 - (addr & 15)) & 15);
+        const uint64_t words = (sizes[k] - head) / 16;
+        const uint64_t o = offs[k] % lcg::PERIOD;
+        P.dst_body = dst[k] + head;
+        P.src_body = src[k] + head;
+        P.head_n = (uint32_t)head;
+        P.tail_n = (uint32_t)(sizes[k] - head - words * 16);
+        // chunks sit on absolute chunk-aligned DESTINATION addresses; positions count from the chunk origin, `lead` bytes before the body
+        P.lead = (uint32_t)(reinterpret_cast<uintptr_t>(P.dst_body) & (chunk - 1));
+        P.end = P.lead + words * 16;
+        P.base_head = lcg::state_residue(key_res, o);
+        P.base_body = lcg::mulmod(lcg::state_residue(key_res, o + head), lcg::powmod(lcg::A, lcg::PERIOD - P.lead % lcg::PERIOD));
+        P.base_tail = lcg::state_residue(key_res, o + head + (words * 16) % lcg::PERIOD);
+        const uint64_t n_chunks = (P.end + chunk - 1) / chunk, first = P.lead != 0 ? 1 : 0;
+        if (n_chunks >= (1ull << 24)) return 1;
+        a.start[k] = (uint32_t)total;
+        total += n_chunks > first ? n_chunks - first : 0;
+        bytes += sizes[k];
+        misaligned |= words != 0 && ((reinterpret_cast<uintptr_t>(src[k]) - addr) & 3) != 0;
+    }
+    for (int k = n; k <= kCycleBatchMax; ++k) a.start[k] = (uint32_t)total;
+    a.n_parts = (uint32_t)n;
+    const QueuePair q = queue_pair(stream);
+    if (!q.pair) return 1;
+    a.queue = q.pair;
+    a.queue_done = q.done;
+    a.queue_seq = q.seq;
+    // the work-queue kernel's grid, main workgroups only: 25 per 32 CUs (cycle_kernel.hip), never more than there are chunks
+    uint64_t cap = 0, helpers = 0;
+    queue_grid(total, large_grid(), &cap, &helpers);
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(total, cap));
+    // a source whose phase differs from the destination's by a whole number of dwords needs no funnel: dword-aligned dwordx4 loads
+    const int form = misaligned ? to_form() : CYCLE_TO_PLAIN;
+    hipError_t e = modgpu_launch_cycle_to(a, form, grid, stream);
+    if (e != hipSuccess) {
+        queue_pair_unused(q);
+        return fail_hip(e, "cycle kernel launch (out of place)");
+    }
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    t_last_launch = {modgpu_to_kernel_name(form), CYCLE_TO, grid, modgpu_to_block(), (uint32_t)chunk, bytes, grid, MODGPU_TO_KERNEL_SOURCE_HASH};
+    return MODGPU_OK;
+}
+
+// The checks that come before any device work: a null pointer with bytes to move, a destination that partly overlaps its own source,
+// or one that meets any OTHER entry's source or destination (sources may overlap each other: they are only read).
+int check_to_entries(void *const *dst, const void *const *src, const uint64_t *sizes, int n)
+{
+    for (int i = 0; i < n; ++i) {
+        if (!sizes[i]) continue;
+        if (!dst[i] || !src[i]) return fail(MODGPU_ERR_INVALID, "null buffer");
+        if (dst[i] != src[i] && ranges_meet(dst[i], sizes[i], src[i], sizes[i]))
+            return fail(MODGPU_ERR_INVALID, "destination partly overlaps its source (only dst == src may alias)");
+    }
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j)
+            if (i != j && (ranges_meet(dst[i], sizes[i], src[j], sizes[j]) || ranges_meet(dst[i], sizes[i], dst[j], sizes[j])))
+                return fail(MODGPU_ERR_INVALID, "a destination meets another entry's source or destination");
+    return MODGPU_OK;
+}
+
+// Entries already checked (check_to_entries), on the current device, asynchronous on `stream`.  Runs of up to kCycleBatchMax
+// non-empty entries share one launch.  Keys == 0 mod m have the identity keystream: out of place that is a copy.  With no ticket
+// pair free, each entry of the run is copied (hipMemcpyAsync, capturable) and cycled in place on the same stream.
+int cycle_to_impl(void *const *dst, const void *const *src, const uint64_t *sizes, const uint64_t *offs, int n, int32_t key, hipStream_t stream)
+{
+    const uint32_t key_res = lcg::key_residue(key);
+    int i = 0;
+    while (i < n) {
+        uint8_t *gd[kCycleBatchMax];
+        const uint8_t *gs[kCycleBatchMax];
+        uint64_t gn[kCycleBatchMax], go[kCycleBatchMax];
+        int g = 0;
+        for (; i < n && g < kCycleBatchMax; ++i) {
+            if (!sizes[i]) continue;
+            gd[g] = static_cast<uint8_t *>(dst[i]);
+            gs[g] = static_cast<const uint8_t *>(src[i]);
+            gn[g] = sizes[i];
+            go[g] = offs ? offs[i] : 0;
+            ++g;
+        }
+        if (!g) break;
+        int rc = key_res ? launch_to(gd, gs, gn, go, g, key_res, stream) : 1;
+        if (rc == 1) {
+            rc = MODGPU_OK;
+            for (int k = 0; k < g && rc == MODGPU_OK; ++k) {
+                if (gd[k] != gs[k]) {
+                    const hipError_t e = hipMemcpyAsync(gd[k], gs[k], gn[k], hipMemcpyDefault, stream);
+                    if (e != hipSuccess) return fail_hip(e, "hipMemcpyAsync (out of place)");
+                }
+                if (key_res) rc = cycle_device_impl(gd[k], gn[k], key, go[k], stream);
+            }
+        }
+        if (rc != MODGPU_OK) return rc;
+    }
+    return MODGPU_OK;
+}
+} // namespace
+
 // One-time work a device's FIRST launch would otherwise pay inside the caller's timed region: loading the code object
 // (~10 ms) and setting up the ticket ring (two allocations, a stream, a memset).  modgpu_alloc calls this for the device
 // it allocates on -- a caller that keeps parts resident has paid it before its first pass (profiles/r03_first_pass.txt:
@@ -808,6 +940,28 @@ int modgpu_cycle_batch_device(void *const *dev_parts, const uint64_t *sizes, con
         DeviceScope scope(device);
         if (scope.rc) return scope.rc;
         return cycle_batch_impl(dev_parts, sizes, stream_offs, n_parts, key, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int modgpu_cycle_device_to(void *dev_dst, const void *dev_src, uint64_t n, int32_t key, uint64_t stream_off, int device, void *hip_stream)
+{
+    return guarded([&]() -> int {
+        if (int rc = check_to_entries(&dev_dst, &dev_src, &n, 1)) return rc;
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        return cycle_to_impl(&dev_dst, &dev_src, &n, &stream_off, 1, key, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int modgpu_cycle_batch_device_to(void *const *dst_parts, const void *const *src_parts, const uint64_t *sizes, const uint64_t *stream_offs,
+                                 int n_parts, int32_t key, int device, void *hip_stream)
+{
+    return guarded([&]() -> int {
+        if (n_parts < 0 || (n_parts > 0 && (!dst_parts || !src_parts || !sizes))) return fail(MODGPU_ERR_INVALID, "bad entry list");
+        if (int rc = check_to_entries(dst_parts, src_parts, sizes, n_parts)) return rc;
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        return cycle_to_impl(dst_parts, src_parts, sizes, stream_offs, n_parts, key, static_cast<hipStream_t>(hip_stream));
     });
 }
 
@@ -1414,6 +1568,34 @@ int modgpu_time_cycle_device(void *dev_buf, uint64_t n, int32_t key, uint64_t st
     });
 }
 
+int modgpu_time_cycle_device_to(void *dev_dst, const void *dev_src, uint64_t n, int32_t key, uint64_t stream_off, int device,
+                                void *hip_stream, int iters, float *ms_per_launch)
+{
+    return guarded([&]() -> int {
+        if (iters <= 0 || !ms_per_launch) return fail(MODGPU_ERR_INVALID, "bad timing arguments");
+        if (int rc = check_to_entries(&dev_dst, &dev_src, &n, 1)) return rc;
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        int rc = MODGPU_OK;
+        hipStream_t st = static_cast<hipStream_t>(hip_stream);
+        hipEvent_t e0, e1;
+        HIP_TRY(hipEventCreate(&e0));
+        HIP_TRY(hipEventCreate(&e1));
+        HIP_TRY(hipEventRecord(e0, st));
+        for (int i = 0; i < iters && rc == MODGPU_OK; ++i) rc = cycle_to_impl(&dev_dst, &dev_src, &n, &stream_off, 1, key, st);
+        hipError_t e = hipEventRecord(e1, st);
+        if (e == hipSuccess) e = hipEventSynchronize(e1);
+        float ms = 0.f;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        if (rc) return rc;
+        if (e != hipSuccess) return fail_hip(e, "event timing");
+        *ms_per_launch = ms / (float)iters;
+        return MODGPU_OK;
+    });
+}
+
 int modgpu_last_launch(modgpu_launch_info_t *out)
 {
     if (!out) return fail(MODGPU_ERR_INVALID, "null out pointer");
@@ -1453,6 +1635,7 @@ void modgpu_queue_stats(uint64_t out[6])
 
 const char *modgpu_kernel_source_hash(void) { return MODGPU_KERNEL_SOURCE_HASH; }
 const char *modgpu_feed_kernel_source_hash(void) { return MODGPU_FEED_KERNEL_SOURCE_HASH; }
+const char *modgpu_to_kernel_source_hash(void) { return MODGPU_TO_KERNEL_SOURCE_HASH; }
 
 int modgpu_testing_hooks(void)
 {
@@ -1478,6 +1661,8 @@ void modgpu_debug_set_staged_mode(int mode) { g_staged_mode.store(mode, std::mem
 void modgpu_debug_set_helpers(int mode) { g_helper_mode.store(mode >= 0 && mode <= 2 ? mode : 0, std::memory_order_relaxed); }
 
 void modgpu_debug_set_batch(int mode) { g_batch_mode.store(mode >= 0 && mode <= 2 ? mode : 0, std::memory_order_relaxed); }
+
+void modgpu_debug_set_to_form(int form) { g_to_form.store(form < 0 ? kToFormShipped : form == CYCLE_TO_FUNNEL ? CYCLE_TO_FUNNEL : CYCLE_TO_PLAIN, std::memory_order_relaxed); }
 
 void modgpu_debug_set_queue_ring(uint32_t lines)
 {
