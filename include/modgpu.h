@@ -93,7 +93,8 @@ extern "C" {
 #define MODGPU_KEY_PS4 0x90cfc0abu
 
 /* ABI version of this header (bumped on any signature change; ABI 8 also gained modgpu_cycle_device_to and
- * modgpu_cycle_batch_device_to, an addition that changes no existing signature). */
+ * modgpu_cycle_batch_device_to, and the four transfer calls modgpu_cycle_host_to_device & co., additions that change no existing
+ * signature). */
 #define MODGPU_ABI_VERSION 8
 int modgpu_abi_version(void);
 
@@ -258,6 +259,34 @@ int modgpu_cycle_file_to_host(const char *path, uint64_t file_off, uint8_t *host
 /* host_src[0..n) -> `path` (created / truncated).  host_src is not modified. */
 int modgpu_cycle_host_to_file(const uint8_t *host_src, uint64_t n, const char *path, int32_t key, uint64_t stream_off,
                               int device);
+
+/* ---- transfers: the cipher in flight between host memory (or a part file) and a buffer the caller keeps on the GPU ----------
+ * dst[j] = src[j] ^ ks[stream_off + j], j = 0 .. n-1: same keystream, 64-bit offsets and key reduction as modgpu_cycle_device.
+ *   modgpu_cycle_host_to_device   host_src -> dev_dst (upload: each byte crosses the link once, into device memory)
+ *   modgpu_cycle_device_to_host   dev_src -> host_dst (download: each byte is read from device memory and crosses the link once)
+ *   modgpu_cycle_file_to_device   n bytes at byte offset file_off of `path` -> dev_dst
+ *   modgpu_cycle_device_to_file   dev_src -> `path`, written the way modgpu_cycle_host_to_file writes it (created / truncated, 0644)
+ * THE SOURCE IS NEVER WRITTEN: host memory, file or device buffer.  A host side may be pageable memory, page-locked memory
+ * (modgpu_host_alloc / modgpu_host_register; then the GPU reads or writes it across PCIe where it lies) or a read-only mapping.
+ * SYNCHRONOUS: the result is in place when the call returns.  NO ORDERING against the caller's streams: the call does not wait for
+ * work the caller has queued on any stream (the NULL stream included) -- synchronise before the call if that work touches the
+ * device buffer.  The library's own work runs on its own non-blocking streams.  `device` -1 = the current device; the calling
+ * thread's current device is the same afterwards.  Edge cases:
+ *   - both pointers may have any byte alignment; n == 0 does nothing (the _to_file call still creates / truncates its file);
+ *   - a NULL pointer with n > 0 is MODGPU_ERR_INVALID;
+ *   - a device pointer that the runtime does not report as device memory of the call's device (hipPointerGetAttributes, both
+ *     ends of the range) is MODGPU_ERR_INVALID, returned before anything is queued;
+ *   - keys == 0 mod 2^31-1 (identity keystream) copy the bytes unchanged.
+ * Kernel entry points: no host loop behind them -- no GPU is MODGPU_ERR_NO_DEVICE, a GPU lost in the middle of the call or a transfer
+ * kernel that stops responding is MODGPU_ERR_HIP after a bounded wait (never a hang).  When a call fails the source is intact and the
+ * destination's contents are unspecified.  path_stats().gpu_launches counts the launches: one per call (calls above ~63 GiB from
+ * pageable memory or a file take one per ~63 GiB). */
+int modgpu_cycle_host_to_device(void *dev_dst, const uint8_t *host_src, uint64_t n, int32_t key, uint64_t stream_off, int device);
+int modgpu_cycle_device_to_host(uint8_t *host_dst, const void *dev_src, uint64_t n, int32_t key, uint64_t stream_off, int device);
+int modgpu_cycle_file_to_device(const char *path, uint64_t file_off, void *dev_dst, uint64_t n, int32_t key,
+                                uint64_t stream_off, int device);
+int modgpu_cycle_device_to_file(const void *dev_src, uint64_t n, const char *path, int32_t key, uint64_t stream_off,
+                                int device);
 
 /* ---- page-locked host memory -----------------------------------------------------------------
  * Replaces the `new char[total]` of CArk::LoadArkData / BuildArk (CArk.cpp:738, 780) for callers

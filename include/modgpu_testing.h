@@ -39,7 +39,8 @@ typedef struct modgpu_launch_info {
     int variant;          /* 0 = small shape, 1 = streaming shape (static chunk map), 2 = streaming shape fed by the work queue,
                              3 = the work-queue shape over several parts in one launch (modgpu_cycle_batch_device; `bytes` = all of them),
                              4 = the host-fed kernel of a host-buffer call (one launch for the whole call; `bytes` = the call's),
-                             5 = the out-of-place kernel (modgpu_cycle_device_to / _batch_device_to; `bytes` = all entries of the launch) */
+                             5 = the out-of-place kernel (modgpu_cycle_device_to / _batch_device_to; `bytes` = all entries of the launch),
+                             6 = a transfer kernel (modgpu_cycle_host_to_device & co.; one launch for the whole call; `bytes` = the call's) */
     uint32_t grid;        /* workgroups launched                                                  */
     uint32_t block;       /* threads per workgroup                                                */
     uint32_t chunk_bytes; /* bytes one workgroup trip covers                                      */
@@ -48,7 +49,8 @@ typedef struct modgpu_launch_info {
                              workgroups of the work-queue shape, which join only while the shader clock is low */
     const char *source_hash; /* identity of the TU that kernel was compiled from: modgpu_kernel_source_hash() for variants 0..3,
                                 modgpu_feed_kernel_source_hash() for variant 4,
-                                modgpu_to_kernel_source_hash() for variant 5; static storage */
+                                modgpu_to_kernel_source_hash() for variant 5,
+                                modgpu_xfer_kernel_source_hash() for variant 6; static storage */
 } modgpu_launch_info_t;
 int modgpu_last_launch(modgpu_launch_info_t *out);
 
@@ -129,6 +131,8 @@ const char *modgpu_kernel_source_hash(void);
 const char *modgpu_feed_kernel_source_hash(void);
 /* The same for the out-of-place kernel's TU (cycle_to_kernel.hip, cycle_to_kernel.h, cycle_kernel_impl.h, cycle_kernel.h, lcg.h). */
 const char *modgpu_to_kernel_source_hash(void);
+/* The same for the transfer kernels' TU (cycle_xfer_kernel.hip, cycle_xfer_kernel.h, cycle_feed_kernel.h, cycle_kernel_impl.h, lcg.h). */
+const char *modgpu_xfer_kernel_source_hash(void);
 
 /* 1 in libmodgpu_testing.so, 0 in libmodgpu.so. */
 int modgpu_testing_hooks(void);
@@ -144,6 +148,11 @@ void modgpu_debug_set_queue_ring(uint32_t lines);
  * 0 = one unaligned dwordx4 per word, 1 = an aligned dwordx4 and the next dword joined by v_alignbyte_b32, -1 = the shipped
  * form.  Measurement (tools/bench_cycle_to.py) and parity tests of both. */
 void modgpu_debug_set_to_form(int form);
+
+/* How the transfer calls (modgpu_cycle_host_to_device & co.) move their bytes: 0 = the transfer kernels (shipped), 1 = the DMA
+ * reference form -- per chunk a hipMemcpyAsync into a device slot and an out-of-place launch from there (upload), or an out-of-place
+ * launch into a device slot and a hipMemcpyAsync out (download).  Measurement (tools/bench_xfer.py) and parity tests of both. */
+void modgpu_debug_set_xfer_form(int form);
 
 /* Helper workgroups of the work-queue shape (one per CU the main workgroups leave idle; they join only while the shader clock is
  * low): 0 = decide by the clock they measure (the shipped behaviour), 1 = always join, 2 = launch none.  Lets the parity tests

@@ -64,6 +64,10 @@ EXPORTS = {
     "modgpu_device_numa_node": (_int, [_int]),
     "modgpu_cycle_device_to": (_int, [_vp, _vp, _u64, _i32, _u64, _int, _vp]),
     "modgpu_cycle_batch_device_to": (_int, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64), ctypes.POINTER(_u64), _int, _i32, _int, _vp]),
+    "modgpu_cycle_host_to_device": (_int, [_vp, _vp, _u64, _i32, _u64, _int]),
+    "modgpu_cycle_device_to_host": (_int, [_vp, _vp, _u64, _i32, _u64, _int]),
+    "modgpu_cycle_file_to_device": (_int, [ctypes.c_char_p, _u64, _vp, _u64, _i32, _u64, _int]),
+    "modgpu_cycle_device_to_file": (_int, [_vp, _u64, ctypes.c_char_p, _i32, _u64, _int]),
 }
 
 
@@ -110,6 +114,7 @@ TESTING_EXPORTS = {
     "modgpu_numa_probe": (_int, [ctypes.c_char_p, ctypes.c_char_p, ctypes.POINTER(_int), ctypes.POINTER(_int), _int]),
     "modgpu_time_cycle_device_to": (_int, [_vp, _vp, _u64, _i32, _u64, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
     "modgpu_to_kernel_source_hash": (ctypes.c_char_p, []),
+    "modgpu_xfer_kernel_source_hash": (ctypes.c_char_p, []),
 }
 # include/modgpu_testing.h, modgpu_debug_* group: ONLY in libmodgpu_testing.so
 DEBUG_EXPORTS = {
@@ -128,6 +133,7 @@ DEBUG_EXPORTS = {
     "modgpu_debug_hold_slots": (_int, [_int, _int]),
     "modgpu_debug_forbid_worker_threads": (None, [_int]),
     "modgpu_debug_set_to_form": (None, [_int]),
+    "modgpu_debug_set_xfer_form": (None, [_int]),
 }
 
 
@@ -434,6 +440,11 @@ def to_kernel_source_hash():
     return lib().modgpu_to_kernel_source_hash().decode()
 
 
+def xfer_kernel_source_hash():
+    """identity of the transfer kernels' TU (cycle_xfer_kernel.hip and what it includes)"""
+    return lib().modgpu_xfer_kernel_source_hash().decode()
+
+
 def feed_kernel_source_hash():
     """identity of the host-fed kernel's TU (cycle_feed_kernel.hip and what it includes)"""
     return lib().modgpu_feed_kernel_source_hash().decode()
@@ -593,6 +604,59 @@ TO_FORMS = {None: -1, "shipped": -1, "unaligned": 0, "funnel": 1}
 def debug_set_to_form(form=None):
     """Testing flavour: how the out-of-place kernel reads a misaligned source ("unaligned" loads / "funnel" / None = shipped)."""
     _debug_lib().modgpu_debug_set_to_form(TO_FORMS[form])
+
+
+def _xfer_src(buf):
+    """(address, bytes) of a transfer's host SOURCE: a PinnedBuffer, a C-contiguous ndarray (read-only is fine) or a bytes-like object"""
+    if isinstance(buf, PinnedBuffer):
+        return buf.ptr, buf.nbytes
+    if not isinstance(buf, np.ndarray):
+        buf = np.frombuffer(buf, dtype=np.uint8)
+    if not buf.flags["C_CONTIGUOUS"]:
+        raise TypeError("need a C-contiguous buffer")
+    return buf.ctypes.data, buf.nbytes
+
+
+def _xfer_dst(buf):
+    """(address, bytes) of a transfer's host DESTINATION: a PinnedBuffer or a writable C-contiguous ndarray"""
+    if isinstance(buf, PinnedBuffer):
+        return buf.ptr, buf.nbytes
+    if not (isinstance(buf, np.ndarray) and buf.flags["C_CONTIGUOUS"] and buf.flags["WRITEABLE"]):
+        raise TypeError("need a writable C-contiguous ndarray or a PinnedBuffer")
+    return buf.ctypes.data, buf.nbytes
+
+
+def cycle_host_to_device(dev_ptr, buf, key, stream_off=0, device=-1):
+    """Upload with the cipher in flight: dev[j] = buf[j] ^ ks[stream_off + j] for every byte of `buf`; `buf` is not modified.
+    Synchronous, and not ordered against the caller's streams (synchronise first)."""
+    p, n = _xfer_src(buf)
+    _check(lib().modgpu_cycle_host_to_device(_vp(dev_ptr), _vp(p), n, as_int32(key), stream_off, device))
+
+
+def cycle_device_to_host(buf, dev_ptr, key, stream_off=0, device=-1):
+    """Download with the cipher in flight: buf[j] = dev[j] ^ ks[stream_off + j] for every byte of `buf`; the device bytes are not
+    modified.  Returns `buf`."""
+    p, n = _xfer_dst(buf)
+    _check(lib().modgpu_cycle_device_to_host(_vp(p), _vp(dev_ptr), n, as_int32(key), stream_off, device))
+    return buf
+
+
+def cycle_file_to_device(path, dev_ptr, n, key, file_off=0, stream_off=0, device=-1):
+    """n bytes at file_off of a part file through the cipher into device memory."""
+    _check(lib().modgpu_cycle_file_to_device(os.fsencode(path), file_off, _vp(dev_ptr), n, as_int32(key), stream_off, device))
+
+
+def cycle_device_to_file(dev_ptr, n, path, key, stream_off=0, device=-1):
+    """n device bytes through the cipher into `path` (created / truncated)."""
+    _check(lib().modgpu_cycle_device_to_file(_vp(dev_ptr), n, os.fsencode(path), as_int32(key), stream_off, device))
+
+
+XFER_FORMS = {None: 0, "kernel": 0, "dma": 1}
+
+
+def debug_set_xfer_form(form=None):
+    """Testing flavour: how the transfer calls move their bytes ("kernel" = the transfer kernels, shipped; "dma" = the reference form)."""
+    _debug_lib().modgpu_debug_set_xfer_form(XFER_FORMS[form])
 
 
 def state_at(key, i):

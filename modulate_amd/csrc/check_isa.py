@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""check_isa.py <cycle_kernel.s> [<cycle_feed_kernel.s>] | <cycle_to_kernel.s> -- build-time guard over the gfx950 assembly of the kernel TUs (run by the
+"""check_isa.py <cycle_kernel.s> [<cycle_feed_kernel.s>] | <cycle_to_kernel.s> | <cycle_xfer_kernel.s> -- build-time guard over the gfx950 assembly of the kernel TUs (run by the
 Makefile right after the TUs are compiled and before either object exists; tests/test_capi_cpu.py runs it again and feeds it
 deliberately broken builds).
 
@@ -28,6 +28,9 @@ s_barrier, data loads nt, data stores sc1 and NOT nt (nt stores across PCIe meas
 word read into scalar registers (v_readfirstlane) behind the first barrier.
 The out-of-place kernel (cycle_to_kernel.s, both forms): the register budget, no spills / scratch / private segment, the keystream
 blocks' rules above, the ticket fetch not wave-aggregated (no v_mbcnt), data loads nt, data stores nt sc1.
+The transfer kernels (cycle_xfer_kernel.s, four forms): the host-fed kernel's rules -- <= 64 VGPRs, no spills / scratch, 8 bytes of
+LDS, exactly two s_barrier, the ticket and ok word in scalar registers behind the first barrier, ALG 1 --, every data load nt, the
+upload's stores into HBM nt sc1, the download's stores across PCIe sc1 and NOT nt.
 Exit status 0 = all of it holds; 1 = findings on stdout."""
 import re
 import sys
@@ -239,6 +242,40 @@ def check_to(asm, bodies):
     return bad
 
 
+def check_xfer(asm, bodies):
+    """the transfer kernels' TU (cycle_xfer_kernel.s): the upload (ILb1) and the download (ILb0), each plain and funnel"""
+    bad = []
+    for name, fn in bodies.items():
+        if "modgpu_cycle_xfer_kernel" not in name:
+            bad.append("%s: the transfer kernels' TU holds another kernel" % name)
+            continue
+        md = metadata(asm, name)
+        if md.get("vgpr_count", 999) > 64:
+            bad.append("%s: %d VGPRs -- more than 64, fewer than 8 waves per SIMD" % (name, md.get("vgpr_count", 999)))
+        if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0) or "scratch_" in fn:
+            bad.append("%s: spills, scratch or a private segment: %s" % (name, md))
+        if md.get("group_segment_fixed_size", -1) != 8:
+            bad.append("%s: LDS is %s bytes, expected the 8 of the ticket / ok mailbox" % (name, md.get("group_segment_fixed_size")))
+        if fn.count("s_barrier") != 2:
+            bad.append("%s: %d s_barrier, expected 2 (one behind thread 0's region, one at the end of the trip)" % (name, fn.count("s_barrier")))
+        ins = instructions(fn)
+        follows = [k for k, (_, op, _) in enumerate(ins) if op == "s_barrier" and any(o.startswith("ds_read") for _, o, _ in ins[k + 1:k + 3])]
+        if len(follows) != 1 or sum(1 for _, o, _ in ins[follows[0] + 1:follows[0] + 8] if o == "v_readfirstlane_b32") < 2:
+            bad.append("%s: the ticket and the ok word are not read into scalar registers right behind the trip's first barrier" % name)
+        if fn.count("v_add_u32_sdwa") != 15:
+            bad.append("%s: keystream instruction mix changed (%d v_add_u32_sdwa, expected 15: ALG 1)" % (name, fn.count("v_add_u32_sdwa")))
+        loads = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_load_dword", ln)]
+        stores = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_store_dword", ln)]
+        if not loads or not all(ln.endswith(" nt") for ln in loads):
+            bad.append("%s: a data load is not nt" % name)
+        upload = "kernelILb1E" in name
+        if upload and (not stores or not all(ln.endswith(" nt sc1") for ln in stores)):
+            bad.append("%s: an upload store into HBM is not nt sc1" % name)
+        if not upload and (not stores or not all(ln.endswith(" sc1") and " nt" not in ln for ln in stores)):
+            bad.append("%s: a download store across PCIe is not `sc1` without nt (nt stores across PCIe: -15..20 %%)" % name)
+    return bad
+
+
 def check(asm):
     """one TU's assembly: the rules for every kernel, then those of the TU it is (the streaming kernels' or the host-fed kernel's)"""
     bad = []
@@ -256,6 +293,8 @@ def check(asm):
         return bad + check_feed(asm, feed[0], bodies[feed[0]])
     if any("modgpu_cycle_to_kernel" in n for n in bodies):
         return bad + check_to(asm, bodies)
+    if any("modgpu_cycle_xfer_kernel" in n for n in bodies):
+        return bad + check_xfer(asm, bodies)
     queue = [n for n in bodies if "modgpu_cycle_queue_kernel" in n]
     if len(queue) != 1:
         return bad + ["expected exactly one work-queue kernel, found %d" % len(queue)]

@@ -1,0 +1,48 @@
+// cycle_xfer_kernel.h -- launch interface of the TRANSFER kernels (cycle_xfer_kernel.hip): the cipher in flight between host memory
+// (or a part file, through the library's page-locked slots) and a buffer the caller keeps in device memory.
+//   upload    reads each byte across PCIe once (a slot, or the caller's page-locked pages), XORs it, writes it into the device buffer;
+//   download  reads the device buffer in HBM, XORs, writes each byte across PCIe once (into a slot, or the caller's page-locked pages).
+// ONE launch per call, on the host-fed protocol of cycle_feed_kernel.h: a workgroup draws a 32 KiB ticket in stream order, waits for its
+// chunk's `ready` word, does the piece, and the workgroup that completes a chunk marks it `done`.  Upload: ready = "the host has filled the
+// slot", done = "the host may refill it".  Download: ready = "the slot is free", done = "the host may drain it".  The give-up rules are the
+// host-fed kernel's: `abort`, `patience_ticks`, work[1].  With the caller's page-locked pages as the host side (`ready` == nullptr) every
+// chunk is ready at launch and nothing is counted: the kernel never waits for the host.
+// Its own TU with a source hash of its own (modgpu_xfer_kernel_source_hash); the arithmetic is cycle_kernel_impl.h's (ALG 1, what runs
+// across PCIe), the protocol constants cycle_feed_kernel.h's.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+#include "cycle_feed_kernel.h" // kFeedSlotsMax, kFeedPieceBytes, kFeedPiecesMax
+
+// reporting only (modgpu_last_launch): a transfer launch, either direction (`bytes` = the call's)
+constexpr int CYCLE_XFER = 6;
+
+struct CycleXferArgs {
+    uint8_t *slot[kFeedSlotsMax]; // staged: chunk k is at slot[(k % pipes) * 2 + (k / pipes) % 2] + slot_phase, as the device addresses it
+    uint8_t *host;                // direct (ready == nullptr): the caller's page-locked bytes as the device addresses them, byte j at host + j
+    uint8_t *dev;                 // the caller's device buffer, byte j at dev + j
+    const uint32_t *ready;        // [chunks] host memory, written by the host; nullptr: direct, every chunk ready, nothing counted
+    const uint32_t *abort;        // host memory: the call is lost, leave
+    uint32_t *done;               // [chunks] host memory, written by the kernel (staged only)
+    uint32_t *work;               // device memory, zero at launch: [0] ticket counter, [1] workgroups that gave up, [2 + k] pieces of chunk k finished
+    uint64_t n;                   // bytes of the call
+    uint64_t patience_ticks;      // longest wait for one chunk, in ticks of the 100 MHz wall clock
+    uint32_t chunk_bytes;         // a multiple of kFeedPieceBytes; chunk_bytes + slot_phase fit in a slot
+    uint32_t pipes;               // pipelines of the call (each owns two slots)
+    uint32_t slot_phase;          // dev mod 16: a slot holds its chunk this far in, so that slot and device buffer are co-aligned mod 16
+    uint32_t base;                // canonical state of the call's first byte
+    uint32_t copy;                // 1: the identity keystream (key == 0 mod 2^31-1): the bytes are copied unchanged
+};
+
+// How a source whose phase differs from the destination's by a non-whole number of dwords is read (only the direct form can meet one:
+// a staged chunk sits in its slot co-aligned with the device buffer):
+//   XFER_PLAIN   one dwordx4 per word at the source's own address (dword-aligned)
+//   XFER_FUNNEL  a dwordx4 at the dword below it and the dword after it, joined by v_alignbyte_b32 (cycle_to_kernel.hip's funnel)
+enum XferForm : int { XFER_PLAIN = 0, XFER_FUNNEL = 1 };
+uint32_t modgpu_xfer_block();
+const char *modgpu_xfer_kernel_name(bool upload, int form);
+hipError_t modgpu_launch_cycle_xfer(const CycleXferArgs &a, bool upload, int form, uint32_t grid, hipStream_t stream);
+// The HIP device whose memory [p, p + n) is (both ends looked up with hipPointerGetAttributes), or -1: host memory, unknown, or
+// the two ends on different devices.  Lives here so that the CPU stand-in of the runtime can supply its own.
+int modgpu_xfer_device_of(const void *p, uint64_t n);

@@ -58,6 +58,7 @@
 
 #include "../../include/modgpu_testing.h"
 #include "cycle_feed_kernel.h"
+#include "cycle_xfer_kernel.h"
 #include "lcg.h"
 #include "modgpu_internal.h"
 #include "numa_place.h"
@@ -73,7 +74,9 @@ std::atomic<int> g_staged_mode{0};
 std::atomic<int> g_inject_failures{0}; // modgpu_debug_inject_failures
 std::atomic<int64_t> g_inject_piece{0}; // modgpu_debug_inject_failure_at: armed while g_inject_stage >= 0, fires once
 std::atomic<int> g_inject_stage{-1};
+std::atomic<int> g_xfer_form{0}; // modgpu_debug_set_xfer_form: 0 = the transfer kernels (shipped), 1 = the DMA reference form
 namespace {
+int xfer_form() { return g_xfer_form.load(std::memory_order_relaxed); }
 int pinned_mode() { return g_pinned_mode.load(std::memory_order_relaxed); }
 int staged_mode() { return g_staged_mode.load(std::memory_order_relaxed); }
 bool injected_failure() { return g_inject_failures.load(std::memory_order_relaxed) > 0 && g_inject_failures.fetch_sub(1) > 0; }
@@ -89,6 +92,7 @@ bool injected_at(uint64_t piece, uint64_t pieces, int stage)
 } // namespace
 #else
 namespace {
+constexpr int xfer_form() { return 0; }
 constexpr int pinned_mode() { return 0; }
 constexpr int staged_mode() { return 0; }
 constexpr bool injected_failure() { return false; }
@@ -436,6 +440,11 @@ enum class Route {
     in_dst,       // file -> page-locked caller memory: pread lands in the destination itself, a launch per chunk cycles it where it lies
     feed,         // as slot_kernel, but ONE host-fed kernel for the whole call (cycle_feed_kernel.h): a pipeline marks its chunk ready
                   // in page-locked memory and polls the chunk's done word
+    xfer,         // one side is the caller's DEVICE buffer (cycle_xfer_kernel.h): ONE transfer kernel for the whole call on the host-fed
+                  // protocol -- upload: copy / pread into the slot, mark it ready, the kernel writes the device buffer; download: mark the
+                  // slot free (ready), the kernel fills it from the device buffer, copy / pwrite out
+    xfer_dma,     // the same two directions as DMA and a launch per chunk (testing flavour, xfer form 1: the reference the kernels are
+                  // measured against): H2D into a device slot + cycle_to into the buffer / cycle_to into a device slot + D2H
 };
 
 // What a call knows about each piece of its stream.  The cipher is positional and the pieces are disjoint, so a call that loses
@@ -463,7 +472,8 @@ struct Job {
     cpu_set_t caller_mask; // the calling thread's affinity mask: a worker is never put on a CPU the caller may not use
     bool have_mask = false;
     Job(const Endpoint &s, const Endpoint &d, uint64_t n_, uint64_t chunk_, int32_t key_, uint64_t off_) : src(s), dst(d), n(n_), chunk(chunk_), key(key_), stream_off(off_) {}
-    bool fed() const { return route == Route::feed; }
+    uint32_t slot_phase = 0; // xfer: a chunk sits this far into its slot (the device buffer's phase mod 16: co-aligned)
+    bool fed() const { return route == Route::feed || route == Route::xfer; }
     // the device writes the caller's destination itself (DMA or a kernel in place): an unfinished piece of it is undefined
     bool dst_written_by_device() const { return route == Route::in_dst || (route == Route::dma && dst.mem && dst.pinned); }
     void set_plan(std::vector<Piece> p)
@@ -706,6 +716,64 @@ void stall_until_the_kernel_has_left(Pipe &p, uint64_t c)
         std::this_thread::sleep_for(std::chrono::milliseconds(1));
     }
 }
+// The caller's device buffer on one side.  Upload: the slot is filled and marked ready, the kernel writes the result into the device
+// buffer (nothing to drain).  Download: the slot is marked ready -- free: the chunk that used it before has been drained --, the kernel
+// fills it from the device buffer and marks it done, and the core drains it.
+struct RouteXfer {
+    static bool drains(const Pipe &p) { return p.j.dst.dev == nullptr; }
+    static int submit(Pipe &p, uint64_t c, int slot)
+    {
+        Job &j = p.j;
+        const uint64_t off = j.plan[c].off, len = j.plan[c].len;
+        stall_until_the_kernel_has_left(p, c);
+        if (!j.src.dev) {
+            int rc = fill_slot(j.src, p.s.pinned[slot] + j.slot_phase, off, len);
+            if (rc) return rc;
+            trace(MODGPU_TRACE_FILL_END, p.pipe, c, len);
+        }
+        MODGPU_INJECT(p, c, MODGPU_STAGE_LAUNCH);
+        __atomic_store_n(&j.feed_ready[c], 1u, __ATOMIC_RELEASE);
+        trace(MODGPU_TRACE_READY, p.pipe, c, len);
+        return MODGPU_OK;
+    }
+    static int wait(Pipe &p, uint64_t c, int) { return feed_wait(p.j, c); }
+};
+// The DMA reference form of the same: a device slot in the middle, one cycle_to launch per chunk.  Page-locked caller memory is
+// DMA'd directly (src_direct / dst_direct), anything else through the chunk's page-locked slot.
+struct RouteXferDma {
+    static bool drains(const Pipe &p) { return p.j.dst.dev == nullptr && !p.dst_direct; }
+    static int submit(Pipe &p, uint64_t c, int slot)
+    {
+        Job &j = p.j;
+        Staging &s = p.s;
+        const uint64_t off = j.plan[c].off, len = j.plan[c].len;
+        if (j.dst.dev) { // upload
+            if (p.src_direct) {
+                HIP_TRY(hipMemcpyAsync(s.dev[slot], j.src.mem + off, len, hipMemcpyHostToDevice, s.stream[slot]));
+            } else {
+                int rc = fill_slot(j.src, s.pinned[slot], off, len);
+                if (rc) return rc;
+                HIP_TRY(hipMemcpyAsync(s.dev[slot], s.pinned[slot], len, hipMemcpyHostToDevice, s.stream[slot]));
+            }
+            trace(MODGPU_TRACE_FILL_END, p.pipe, c, len);
+            MODGPU_INJECT(p, c, MODGPU_STAGE_LAUNCH);
+            int rc = cycle_to_device_impl(j.dst.dev + off, s.dev[slot], len, j.key, j.stream_off + off, s.stream[slot]);
+            if (rc) return rc;
+        } else { // download
+            MODGPU_INJECT(p, c, MODGPU_STAGE_LAUNCH);
+            int rc = cycle_to_device_impl(s.dev[slot], j.src.dev + off, len, j.key, j.stream_off + off, s.stream[slot]);
+            if (rc) return rc;
+            HIP_TRY(hipMemcpyAsync(p.dst_direct ? j.dst.mem + off : s.pinned[slot], s.dev[slot], len, hipMemcpyDeviceToHost, s.stream[slot]));
+        }
+        trace(MODGPU_TRACE_LAUNCHED, p.pipe, c, len);
+        return MODGPU_OK;
+    }
+    static int wait(Pipe &p, uint64_t, int slot)
+    {
+        HIP_TRY(hipStreamSynchronize(p.s.stream[slot]));
+        return MODGPU_OK;
+    }
+};
 struct RouteFeed { // the kernel is there already, waiting for exactly this chunk's ready word
     static bool drains(const Pipe &) { return true; }
     static int submit(Pipe &p, uint64_t c, int slot)
@@ -736,7 +804,7 @@ template <class R> int retire(Pipe &p, uint64_t c, int slot)
     if (R::drains(p)) {
         MODGPU_INJECT(p, c, MODGPU_STAGE_DRAIN);
         j.touched.store(true, std::memory_order_relaxed);
-        rc = drain_slot(j.dst, p.s.pinned[slot], off, len); // THE place a slot route writes the caller's destination
+        rc = drain_slot(j.dst, p.s.pinned[slot] + j.slot_phase, off, len); // THE place a slot route writes the caller's destination
         trace(MODGPU_TRACE_DRAIN_END, p.pipe, c, len);
         if (rc) return rc;
     }
@@ -780,6 +848,8 @@ int run_pipe(Staging &s, const int *slots, int ring, Job &j, uint64_t first, uin
     case Route::slot_kernel: rc = run_route<RouteSlotKernel>(p); break;
     case Route::in_dst: rc = run_route<RouteInDst>(p); break;
     case Route::feed: rc = run_route<RouteFeed>(p); break;
+    case Route::xfer: rc = run_route<RouteXfer>(p); break;
+    case Route::xfer_dma: rc = run_route<RouteXferDma>(p); break;
     }
     if (rc != MODGPU_OK) { // nothing of this call may still be running against the caller's memory (or its slots) once we return
         if (rc != kStopped) j.failed.store(true, std::memory_order_release);
@@ -1122,6 +1192,34 @@ struct FeedCall {
         trace(MODGPU_TRACE_LAUNCHED, -1, 0, c.n);
         return MODGPU_OK;
     }
+    // the transfer kernel instead (Route::xfer): the same slots, words and stream, the caller's device buffer on the other side
+    int launch_xfer()
+    {
+        Staging &s = c.s;
+        const bool upload = c.dst.dev != nullptr;
+        CycleXferArgs a{};
+        for (int k = 0; k < pipes * 2; ++k) HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&a.slot[k]), s.pinned[slots[(size_t)k]], 0));
+        a.dev = upload ? c.dst.dev : c.src.dev;
+        a.ready = s.feed_flags_dev[lead_slot];
+        a.done = s.feed_flags_dev[lead_slot] + kFeedChunksMax;
+        a.abort = s.feed_flags_dev[lead_slot] + 2 * kFeedChunksMax;
+        a.work = s.feed_work[lead_slot];
+        a.n = c.n;
+        a.patience_ticks = kFeedPatienceTicks;
+        a.chunk_bytes = (uint32_t)plan.chunk;
+        a.pipes = (uint32_t)pipes;
+        a.slot_phase = job.slot_phase;
+        a.base = lcg::state_residue(lcg::key_residue(c.key), c.stream_off);
+        a.copy = c.identity ? 1u : 0u;
+        const uint32_t pieces = (uint32_t)((a.n + kFeedPieceBytes - 1) / kFeedPieceBytes);
+        const uint32_t grid = std::min<uint32_t>(kFeedGrid, pieces);
+        const hipError_t e = modgpu_launch_cycle_xfer(a, upload, XFER_PLAIN, grid, job.feed_stream); // (slot and buffer are co-aligned)
+        if (e != hipSuccess) return fail_hip(e, "cycle kernel launch (transfer)");
+        job.feed_launched.store(true, std::memory_order_release);
+        note_xfer_launch(modgpu_xfer_kernel_name(upload, XFER_PLAIN), grid, c.n);
+        trace(MODGPU_TRACE_LAUNCHED, -1, 0, c.n);
+        return MODGPU_OK;
+    }
     void finish(int rc)
     {
         Staging &s = c.s;
@@ -1254,6 +1352,142 @@ int pipelined_call(CallCtx &c)
     }
     return rescue_on_host(c, job, rc);
 }
+
+// ---- the transfer routes: host memory or a part file on one side, the caller's device buffer on the other ------------------------
+// Page-locked caller memory: ONE transfer kernel reads (upload) or writes (download) the caller's pages across PCIe where they lie, every
+// chunk ready at launch -- no slot, no host thread, no waiting for the host.  A slot lends the call its stream and its counters.
+int xfer_direct(CallCtx &c)
+{
+    Staging &s = c.s;
+    const bool upload = c.dst.dev != nullptr;
+    const Endpoint &h = upload ? c.src : c.dst;
+    uint8_t *const d = upload ? c.dst.dev : c.src.dev;
+    if ((c.n + kFeedPieceBytes - 1) / kFeedPieceBytes >= kFeedPiecesMax) return fail(MODGPU_ERR_INVALID, "transfer beyond 512 GiB in one call");
+    SlotLease lease(s, c.dev);
+    lease.acquire(1, 1);
+    if (lease.ids.empty()) return fail_lost();
+    const int slot = lease.ids[0];
+    int rc = staging_reserve(s, lease.ids, 0, false, false);
+    if (!rc) rc = feed_reserve(s, slot);
+    if (rc) return rc;
+    CycleXferArgs a{};
+    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&a.host), h.mem, 0));
+    a.dev = d;
+    a.abort = s.feed_flags_dev[slot] + 2 * kFeedChunksMax;
+    s.feed_flags[slot][2 * kFeedChunksMax] = 0;
+    a.work = s.feed_work[slot]; // (zero: feed_reserve, and behind every call below)
+    a.n = c.n;
+    a.patience_ticks = kFeedPatienceTicks;
+    a.chunk_bytes = kFeedPieceBytes;
+    a.pipes = 1;
+    a.base = lcg::state_residue(lcg::key_residue(c.key), c.stream_off);
+    a.copy = c.identity ? 1u : 0u;
+    const uint8_t *const from = upload ? h.mem : d;
+    const uint8_t *const to = upload ? d : h.mem;
+    const int form = ((reinterpret_cast<uintptr_t>(from) - reinterpret_cast<uintptr_t>(to)) & 3u) != 0 ? XFER_FUNNEL : XFER_PLAIN;
+    const uint32_t grid = std::min<uint32_t>(kFeedGrid, (uint32_t)((c.n + kFeedPieceBytes - 1) / kFeedPieceBytes));
+    if (injected_at(0, 1, MODGPU_STAGE_FILL) || injected_at(0, 1, MODGPU_STAGE_LAUNCH)) return injected_here();
+    const hipError_t e = modgpu_launch_cycle_xfer(a, upload, form, grid, s.stream[slot]);
+    if (e != hipSuccess) return fail_hip(e, "cycle kernel launch (transfer, page-locked caller memory)");
+    note_xfer_launch(modgpu_xfer_kernel_name(upload, form), grid, c.n);
+    trace(MODGPU_TRACE_LAUNCHED, -1, 0, c.n);
+    hipError_t w = injected_at(0, 1, MODGPU_STAGE_SYNC) ? hipErrorLaunchFailure : hipSuccess;
+    const hipError_t q = hipStreamSynchronize(s.stream[slot]);
+    if (w == hipSuccess) w = q;
+    // the counters go back to zero behind the call, on the slot's own stream (never the NULL stream: round 6)
+    if (hipMemsetAsync(s.feed_work[slot], 0, 2 * sizeof(uint32_t), s.stream[slot]) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(s.feed_work[slot]);
+        s.feed_work[slot] = nullptr;
+    }
+    if (w != hipSuccess) return fail_hip(w, "hipStreamSynchronize (transfer kernel on the caller's page-locked memory)");
+    c.account();
+    return MODGPU_OK;
+}
+
+// Pageable memory or a part file on the host side: the stream cut into chunks for up to kPipes pipelines on the shared core, ONE transfer
+// kernel for the call (Route::xfer) -- or, in the testing flavour's xfer form 1, the DMA reference form (Route::xfer_dma).  No host loop
+// behind it: an error is the call's error (the source is intact -- it is only ever read --, the destination unspecified).
+int xfer_pipelined(CallCtx &c, bool dma)
+{
+    Staging &s = c.s;
+    const bool upload = c.dst.dev != nullptr;
+    const uint64_t n = c.n, piece = kFeedPieceBytes;
+    RoutePlan plan{};
+    plan.route = dma ? Route::xfer_dma : Route::xfer;
+    if (dma) {
+        plan.chunk = std::min<uint64_t>(kChunk, std::max<uint64_t>(kChunkMin, ((n / kSplit) + 0xFFFFF) & ~0xFFFFFull));
+    } else { // the host-fed call's chunks: as small as the flag words allow, with room for the slot phase in every slot
+        const uint64_t want = n <= (8ull << 20) ? std::max<uint64_t>(kFeedChunk / 2, piece) : kFeedChunk;
+        plan.chunk = std::max<uint64_t>((want + piece - 1) / piece * piece, ((n + kFeedChunksMax - 1) / kFeedChunksMax + piece - 1) / piece * piece);
+        if (plan.chunk > kChunk - piece) return fail(MODGPU_ERR_INVALID, "transfer too large for one host-fed call"); // (xfer_impl cuts calls below this)
+    }
+    const uint64_t n_chunks = (n + plan.chunk - 1) / plan.chunk;
+    int pipes = (int)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)kPipes, (n_chunks + 1) / 2));
+    const int ring = 2;
+    // the kernel draws chunks in stream order and waits for whichever pipeline owns the next one: the pipelines must run side by side,
+    // so a call has no more of them than there are threads to run them
+    if (!dma && pipes > 1) pipes = std::min(pipes, 1 + ensure_workers(s, pipes - 1, c.dev, physical_of(c.dev), c.caller_mask, c.have_mask));
+    if (c.dst.fd >= 0 && n >= (8ull << 20)) (void)::posix_fallocate(c.dst.fd, (off_t)c.dst.base, (off_t)n);
+    SlotLease lease(s, c.dev);
+    lease.acquire(pipes * ring, ring);
+    if (lease.ids.empty()) return fail_lost();
+    pipes = (int)lease.ids.size() / ring;
+    Job job(c.src, c.dst, n, plan.chunk, c.key, c.stream_off);
+    job.route = plan.route;
+    job.dev = c.dev;
+    job.slot_phase = dma ? 0u : (uint32_t)(reinterpret_cast<uintptr_t>(upload ? c.dst.dev : c.src.dev) & 15u);
+    job.set_plan(cut_stream(n, plan.chunk, pipes, 0));
+    trace(MODGPU_TRACE_SLOTS, -1, (uint64_t)pipes, plan.chunk);
+    const bool host_direct = (upload ? c.src : c.dst).pinned;
+    int rc = staging_reserve(s, lease.ids, plan.chunk + (dma ? 0 : 16), dma, !(dma && host_direct));
+    if (rc) return rc;
+    FeedCall fed{c, job, lease.ids, plan};
+    if (!dma) {
+        rc = fed.prepare(pipes);
+        if (rc) return rc;
+    }
+    if (pipes <= 1) {
+        if (!dma) {
+            rc = fed.launch_xfer();
+            if (rc) return rc;
+        }
+        rc = run_pipe(s, lease.ids.data(), ring, job, 0, 1);
+        if (rc == kStopped) rc = MODGPU_OK;
+    } else {
+        auto call = std::make_shared<Call>(s, job, pipes, ring, physical_of(c.dev), lease.ids);
+        const int workers = ensure_workers(s, pipes - 1, c.dev, physical_of(c.dev), c.caller_mask, c.have_mask);
+        post_to_workers(s, call, std::min(pipes - 1, workers));
+        trace(MODGPU_TRACE_POSTED, -1, (uint64_t)pipes, 0);
+        int rc_launch = MODGPU_OK;
+        std::string launch_err;
+        if (!dma) {
+            rc_launch = fed.launch_xfer();
+            if (rc_launch) {
+                launch_err = t_err;
+                job.failed.store(true, std::memory_order_release);
+            }
+        }
+        call->help(false);
+        call->wait();
+        {
+            std::lock_guard<std::mutex> lock(s.mu);
+            s.requests.erase(std::remove(s.requests.begin(), s.requests.end(), call), s.requests.end());
+        }
+        for (int p = 0; p < pipes && rc == MODGPU_OK; ++p)
+            if (call->rcs[(size_t)p]) {
+                t_err = call->errs[(size_t)p];
+                rc = call->rcs[(size_t)p];
+            }
+        if (rc_launch) {
+            t_err = launch_err;
+            rc = rc_launch;
+        }
+    }
+    if (!dma) fed.finish(rc);
+    if (rc == MODGPU_OK) c.account();
+    return rc;
+}
 } // namespace
 
 int stream_impl(const Endpoint &src, const Endpoint &dst, uint64_t n, int32_t key, uint64_t stream_off, int device,
@@ -1314,6 +1548,69 @@ int stream_impl(const Endpoint &src, const Endpoint &dst, uint64_t n, int32_t ke
     return pipelined_call(c);
 }
 
+// src -> dst with the caller's device buffer on one side (Endpoint::dev) and host memory or a file on the other.  Checked before
+// anything is queued: the device side is device memory of the call's device.  Synchronous; no host loop behind it.
+int xfer_impl(const Endpoint &src, const Endpoint &dst, uint64_t n, int32_t key, uint64_t stream_off, int device)
+{
+    if (n == 0) return MODGPU_OK;
+    stream_off %= 0x7FFFFFFEull; // (as stream_impl: chunk positions added below never wrap at 2^64)
+    int dev = 0;
+    DeviceScope scope(device);
+    int rc = scope.rc ? scope.rc : resolve_device(device, &dev);
+    if (rc) return rc;
+    if (dev >= kMaxDevices) return fail(MODGPU_ERR_INVALID, "device index beyond staging table");
+    int phys = -1;
+    HIP_TRY(hipGetDevice(&phys));
+    const uint8_t *const d = dst.dev ? dst.dev : src.dev;
+    if (modgpu_xfer_device_of(d, n) != phys) return fail(MODGPU_ERR_INVALID, "the device pointer is not device memory of the call's device");
+    if (injected_failure()) return fail(MODGPU_ERR_HIP, "injected failure (modgpu_debug_inject_failures)");
+    if (g_device_lost[dev].load(std::memory_order_acquire)) return fail_lost();
+    const bool upload = dst.dev != nullptr;
+    const Endpoint &h = upload ? src : dst;
+    const bool direct = h.mem && h.pinned;
+    // which of the device's staging sets: the one on the node the caller's pageable pages (or the file's cached pages) live on
+    int copy_node = -1;
+    cpu_set_t caller_mask;
+    CPU_ZERO(&caller_mask);
+    bool have_mask = false;
+    if (numa::enabled() && !direct) {
+        copy_node = h.mem ? numa::node_of_address(h.mem + n / 2) : upload ? numa::node_of_file_page(h.fd, h.base + n / 2) : -1;
+        if (copy_node >= 0) have_mask = ::sched_getaffinity(0, sizeof caller_mask, &caller_mask) == 0;
+    }
+    const int gpu_node = copy_node >= 0 ? device_numa_node(dev) : -1;
+    const int set = copy_node >= 0 && copy_node < kNodeSets - 1 && gpu_node >= 0 && copy_node != gpu_node && have_mask ? 1 + copy_node : 0;
+    Staging &s = staging_of(dev, set);
+    if (set != 0) {
+        if (s.node.load(std::memory_order_relaxed) != copy_node) s.node.store(copy_node, std::memory_order_relaxed);
+        g_node_set_calls.fetch_add(1, std::memory_order_relaxed);
+    }
+    trace(MODGPU_TRACE_CALL_BEGIN, -1, 0, n);
+    struct CallEnd { uint64_t n; ~CallEnd() { trace(MODGPU_TRACE_CALL_END, -1, 0, n); } } call_end{n};
+    const bool identity = (int64_t)key % 0x7FFFFFFFll == 0;
+    const bool dma = xfer_form() == 1;
+    StreamOutcome outcome;
+    if (direct && !dma) {
+        CallCtx c{src, dst, n, key, stream_off, dev, s, identity, false, src.pinned, dst.pinned, true, false, copy_node, caller_mask, have_mask, outcome};
+        return xfer_direct(c);
+    }
+    // a host-fed call takes at most kFeedChunksMax chunks of at most a slot less a piece: larger calls are cut into several, one launch each
+    const uint64_t most = dma ? n : (uint64_t)kFeedChunksMax * (kChunk - kFeedPieceBytes);
+    for (uint64_t at = 0; at < n; at += most) {
+        Endpoint ps = src, pd = dst;
+        for (Endpoint *e : {&ps, &pd}) {
+            if (e->mem) e->mem += at;
+            else if (e->dev) e->dev += at;
+            else e->base += at;
+        }
+        const uint64_t len = std::min<uint64_t>(most, n - at);
+        CallCtx c{ps, pd, len, key, (stream_off + at) % 0x7FFFFFFEull, dev, s, identity, false, ps.mem && ps.pinned, pd.mem && pd.pinned, direct, false,
+                  copy_node, caller_mask, have_mask, outcome};
+        rc = xfer_pipelined(c, dma);
+        if (rc) return rc;
+    }
+    return MODGPU_OK;
+}
+
 } // namespace modgpu
 
 // ---- file endpoints of the ABI -----------------------------------------------------------------
@@ -1337,6 +1634,7 @@ void modgpu_debug_inject_failure_at(int64_t piece, int stage)
     g_inject_stage.store(stage >= MODGPU_STAGE_FILL && stage <= MODGPU_STAGE_STALL ? stage : -1, std::memory_order_release);
 }
 void modgpu_debug_forbid_worker_threads(int forbid) { g_forbid_spawn.store(forbid ? 1 : 0); }
+void modgpu_debug_set_xfer_form(int form) { g_xfer_form.store(form == 1 ? 1 : 0, std::memory_order_relaxed); }
 int modgpu_debug_injection_armed(void) { return g_inject_stage.load(std::memory_order_acquire) >= 0 ? 1 : 0; }
 // Takes `count` PIPELINE slots of a device's own staging set, as large calls do, and keeps them until called with count = 0: with all
 // of them held, what a header-sized call still finds is exactly the slots reserved for it.  Returns how many are held now.
@@ -1475,6 +1773,64 @@ int modgpu_cycle_host_to_file(const uint8_t *host_src, uint64_t n, const char *p
         src.pinned = host_range_pinned(host_src, n);
         dst.fd = out.fd;
         return stream_impl(src, dst, n, key, stream_off, device, !gpu_required(), nullptr); // (host_src is never modified: lost pieces are done from it again)
+    });
+}
+
+// ---- the transfer routes of the ABI (include/modgpu.h: modgpu_cycle_host_to_device & co.) -----------------------------------------
+int modgpu_cycle_host_to_device(void *dev_dst, const uint8_t *host_src, uint64_t n, int32_t key, uint64_t stream_off, int device)
+{
+    return guarded([&]() -> int {
+        if (n == 0) return MODGPU_OK;
+        if (!dev_dst || !host_src) return fail(MODGPU_ERR_INVALID, "null buffer");
+        Endpoint src, dst;
+        src.mem = const_cast<uint8_t *>(host_src); // only read from
+        src.pinned = host_range_pinned(host_src, n);
+        dst.dev = static_cast<uint8_t *>(dev_dst);
+        return xfer_impl(src, dst, n, key, stream_off, device);
+    });
+}
+
+int modgpu_cycle_device_to_host(uint8_t *host_dst, const void *dev_src, uint64_t n, int32_t key, uint64_t stream_off, int device)
+{
+    return guarded([&]() -> int {
+        if (n == 0) return MODGPU_OK;
+        if (!host_dst || !dev_src) return fail(MODGPU_ERR_INVALID, "null buffer");
+        Endpoint src, dst;
+        src.dev = static_cast<uint8_t *>(const_cast<void *>(dev_src)); // only read from
+        dst.mem = host_dst;
+        dst.pinned = host_range_pinned(host_dst, n);
+        return xfer_impl(src, dst, n, key, stream_off, device);
+    });
+}
+
+int modgpu_cycle_file_to_device(const char *path, uint64_t file_off, void *dev_dst, uint64_t n, int32_t key, uint64_t stream_off, int device)
+{
+    return guarded([&]() -> int {
+        if (!path) return fail(MODGPU_ERR_INVALID, "null path");
+        if (n == 0) return MODGPU_OK;
+        if (!dev_dst) return fail(MODGPU_ERR_INVALID, "null buffer");
+        Fd in;
+        in.fd = ::open(path, O_RDONLY);
+        if (in.fd < 0) return fail_io(path);
+        Endpoint src, dst;
+        src.fd = in.fd;
+        src.base = file_off;
+        dst.dev = static_cast<uint8_t *>(dev_dst);
+        return xfer_impl(src, dst, n, key, stream_off, device);
+    });
+}
+
+int modgpu_cycle_device_to_file(const void *dev_src, uint64_t n, const char *path, int32_t key, uint64_t stream_off, int device)
+{
+    return guarded([&]() -> int {
+        if (!path || (n && !dev_src)) return fail(MODGPU_ERR_INVALID, "null path or buffer");
+        Fd out;
+        out.fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644); // (as modgpu_cycle_host_to_file)
+        if (out.fd < 0) return fail_io(path);
+        Endpoint src, dst;
+        src.dev = static_cast<uint8_t *>(const_cast<void *>(dev_src)); // only read from
+        dst.fd = out.fd;
+        return xfer_impl(src, dst, n, key, stream_off, device);
     });
 }
 

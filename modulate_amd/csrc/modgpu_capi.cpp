@@ -20,6 +20,7 @@
 #include "cycle_feed_kernel.h"
 #include "cycle_kernel.h"
 #include "cycle_to_kernel.h"
+#include "cycle_xfer_kernel.h"
 #include "lcg.h"
 #include "modgpu_internal.h"
 #include "numa_place.h"
@@ -30,6 +31,9 @@
 #endif
 #ifndef MODGPU_TO_KERNEL_SOURCE_HASH
 #define MODGPU_TO_KERNEL_SOURCE_HASH "unknown"
+#endif
+#ifndef MODGPU_XFER_KERNEL_SOURCE_HASH
+#define MODGPU_XFER_KERNEL_SOURCE_HASH "unknown"
 #endif
 
 namespace modgpu {
@@ -615,6 +619,11 @@ void note_feed_launch(uint32_t grid, uint64_t bytes)
     g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
     t_last_launch = {modgpu_feed_kernel_name(), CYCLE_FEED, grid, modgpu_feed_block(), kFeedPieceBytes, bytes, grid, MODGPU_FEED_KERNEL_SOURCE_HASH};
 }
+void note_xfer_launch(const char *kernel, uint32_t grid, uint64_t bytes)
+{
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    t_last_launch = {kernel, CYCLE_XFER, grid, modgpu_xfer_block(), kFeedPieceBytes, bytes, grid, MODGPU_XFER_KERNEL_SOURCE_HASH};
+}
 
 // n_parts buffers resident on the CURRENT device, each its own Cycle call (keystream from offs[i], or 0), asynchronous on
 // `stream`.  Runs of up to kCycleBatchMax non-empty parts share one launch when that pays (profiles/r03_parts_batched.txt,
@@ -782,6 +791,11 @@ int cycle_to_impl(void *const *dst, const void *const *src, const uint64_t *size
     return MODGPU_OK;
 }
 } // namespace
+
+int cycle_to_device_impl(void *dst, const void *src, uint64_t n, int32_t key, uint64_t stream_off, hipStream_t stream)
+{
+    return cycle_to_impl(&dst, &src, &n, &stream_off, 1, key, stream);
+}
 
 // One-time work a device's FIRST launch would otherwise pay inside the caller's timed region: loading the code object
 // (~10 ms) and setting up the ticket ring (two allocations, a stream, a memset).  modgpu_alloc calls this for the device
@@ -1636,6 +1650,7 @@ void modgpu_queue_stats(uint64_t out[6])
 const char *modgpu_kernel_source_hash(void) { return MODGPU_KERNEL_SOURCE_HASH; }
 const char *modgpu_feed_kernel_source_hash(void) { return MODGPU_FEED_KERNEL_SOURCE_HASH; }
 const char *modgpu_to_kernel_source_hash(void) { return MODGPU_TO_KERNEL_SOURCE_HASH; }
+const char *modgpu_xfer_kernel_source_hash(void) { return MODGPU_XFER_KERNEL_SOURCE_HASH; }
 
 int modgpu_testing_hooks(void)
 {

@@ -89,6 +89,10 @@ bool gpu_required(); // MODGPU_REQUIRE_GPU=1 at load
 bool host_range_pinned(const void *p, uint64_t n);
 // a host-fed launch has happened on the calling thread (host_stream.cpp): path stats and modgpu_last_launch
 void note_feed_launch(uint32_t grid, uint64_t bytes);
+// the same for a transfer kernel's launch (cycle_xfer_kernel.h)
+void note_xfer_launch(const char *kernel, uint32_t grid, uint64_t bytes);
+// modgpu_cycle_device_to on one range, asynchronous on `stream` (current device; the transfer routes' DMA reference form)
+int cycle_to_device_impl(void *dst, const void *src, uint64_t n, int32_t key, uint64_t stream_off, hipStream_t stream);
 
 // ---- host-buffer / file endpoints (host_stream.cpp) ---------------------------------------
 // Where a stream's bytes come from / go to: caller memory, or a file read / written at offsets
@@ -98,6 +102,7 @@ struct Endpoint {
     int fd = -1;            // else file descriptor, bytes at file offset base + [0..n)
     uint64_t base = 0;
     bool pinned = false;    // mem is page-locked and device-visible: DMA'd directly, no staging copy
+    uint8_t *dev = nullptr; // else, for the transfer routes (modgpu_cycle_host_to_device & co.): device memory of the call's device
 };
 struct Piece { uint64_t off, len; }; // a span of a stream, in stream bytes
 // What a call did besides succeeding or failing.
