@@ -93,8 +93,8 @@ extern "C" {
 #define MODGPU_KEY_PS4 0x90cfc0abu
 
 /* ABI version of this header (bumped on any signature change; ABI 8 also gained modgpu_cycle_device_to and
- * modgpu_cycle_batch_device_to, and the four transfer calls modgpu_cycle_host_to_device & co., additions that change no existing
- * signature). */
+ * modgpu_cycle_batch_device_to, the four transfer calls modgpu_cycle_host_to_device & co., and modgpu_rekey_device_to and
+ * modgpu_rekey_batch_device_to, additions that change no existing signature). */
 #define MODGPU_ABI_VERSION 8
 int modgpu_abi_version(void);
 
@@ -166,6 +166,32 @@ int modgpu_cycle_device_to(void *dev_dst, const void *dev_src, uint64_t n, int32
  * entries are skipped. */
 int modgpu_cycle_batch_device_to(void *const *dst_parts, const void *const *src_parts, const uint64_t *sizes,
                                  const uint64_t *stream_offs, int n_parts, int32_t key, int device, void *hip_stream);
+
+/* REKEY: dev_dst[j] = dev_src[j] ^ ks(key_from)[off_from + j] ^ ks(key_to)[off_to + j], j = 0 .. n-1, in ONE pass: ciphertext under
+ * one keystream becomes ciphertext under another without the plaintext ever reaching memory (it exists only in registers).  What
+ * converting an encrypted part between platforms is (key_from = MODGPU_KEY_PS3, key_to = MODGPU_KEY_PS4, both offsets 0), and what
+ * moving an encrypted file to another place in a part is (one key, off_from = the file's old stream offset, off_to = its new one).
+ * The contract is modgpu_cycle_device_to's, word for word where it applies: asynchronous on `hip_stream`, `device` -1 = the current
+ * device, allocation-free, capturable into a hipGraph under the same concurrency and graph-scratch rules; either side any byte
+ * alignment, the two offsets any values (their phases mod 16 independent of each other and of the pointers'); dst == src (exact alias)
+ * rekeys in place; a partial overlap is MODGPU_ERR_INVALID before anything is queued; n == 0 does nothing; a NULL pointer with n > 0
+ * is MODGPU_ERR_INVALID; a page-locked host buffer on either side is supported, not tuned; no host loop.
+ * Degenerate keystreams take the out-of-place call: key_from == 0 mod 2^31-1 is modgpu_cycle_device_to with key_to at off_to;
+ * key_to == 0 is modgpu_cycle_device_to with key_from at off_from; both zero, or the same reduced key at the same stream position
+ * (offsets equal mod 2^31-2), copy.  A launch that finds no scratch runs two passes on the same stream: out of place under
+ * key_from, then in place under key_to (correct and capturable; modgpu_last_launch then reports the in-place launch). */
+int modgpu_rekey_device_to(void *dev_dst, const void *dev_src, uint64_t n, int32_t key_from, uint64_t off_from, int32_t key_to,
+                           uint64_t off_to, int device, void *hip_stream);
+
+/* n_parts rekey entries of ONE device: dst_parts[i][j] = src_parts[i][j] ^ ks(key_from)[offs_from[i] + j] ^ ks(key_to)[offs_to[i] + j]
+ * (a NULL offs_from or offs_to means 0 for every entry).  Relocating the files of an encrypted part is this call with
+ * src = old part + o_old_i, dst = new part + o_new_i, offs_from = o_old, offs_to = o_new.  Everything modgpu_rekey_device_to says holds
+ * per entry; as in modgpu_cycle_batch_device_to SOURCE ranges may overlap each other, a destination that meets any other entry's
+ * source or destination makes the whole call MODGPU_ERR_INVALID, any n_parts is taken with up to 16 non-empty entries per launch, in
+ * order, on the same stream, and empty entries are skipped. */
+int modgpu_rekey_batch_device_to(void *const *dst_parts, const void *const *src_parts, const uint64_t *sizes,
+                                 const uint64_t *offs_from, const uint64_t *offs_to, int n_parts, int32_t key_from,
+                                 int32_t key_to, int device, void *hip_stream);
 
 /* Replaces CEncryptionCycler::Cycle (CEncryptionCycler.cpp:4-14) for a caller-owned HOST buffer,
  * on the GPU.  Pageable memory is staged through page-locked slots owned by this library (memcpy ->

@@ -32,6 +32,10 @@ int modgpu_time_cycle_device(void *dev_buf, uint64_t n, int32_t key, uint64_t st
 int modgpu_time_cycle_device_to(void *dev_dst, const void *dev_src, uint64_t n, int32_t key, uint64_t stream_off,
                                 int device, void *hip_stream, int iters, float *ms_per_launch);
 
+/* The same for modgpu_rekey_device_to: `iters` back-to-back rekey launches (dst is the same after every one). */
+int modgpu_time_rekey_device_to(void *dev_dst, const void *dev_src, uint64_t n, int32_t key_from, uint64_t off_from, int32_t key_to,
+                                uint64_t off_to, int device, void *hip_stream, int iters, float *ms_per_launch);
+
 /* The launch the calling thread made last (any entry point), as the library planned it. */
 typedef struct modgpu_launch_info {
     const char *kernel;   /* the instantiation's name as rocprofv3 prints it, e.g.
@@ -40,7 +44,8 @@ typedef struct modgpu_launch_info {
                              3 = the work-queue shape over several parts in one launch (modgpu_cycle_batch_device; `bytes` = all of them),
                              4 = the host-fed kernel of a host-buffer call (one launch for the whole call; `bytes` = the call's),
                              5 = the out-of-place kernel (modgpu_cycle_device_to / _batch_device_to; `bytes` = all entries of the launch),
-                             6 = a transfer kernel (modgpu_cycle_host_to_device & co.; one launch for the whole call; `bytes` = the call's) */
+                             6 = a transfer kernel (modgpu_cycle_host_to_device & co.; one launch for the whole call; `bytes` = the call's),
+                             7 = the rekey kernel (modgpu_rekey_device_to / _batch_device_to; `bytes` = all entries of the launch) */
     uint32_t grid;        /* workgroups launched                                                  */
     uint32_t block;       /* threads per workgroup                                                */
     uint32_t chunk_bytes; /* bytes one workgroup trip covers                                      */
@@ -50,7 +55,8 @@ typedef struct modgpu_launch_info {
     const char *source_hash; /* identity of the TU that kernel was compiled from: modgpu_kernel_source_hash() for variants 0..3,
                                 modgpu_feed_kernel_source_hash() for variant 4,
                                 modgpu_to_kernel_source_hash() for variant 5,
-                                modgpu_xfer_kernel_source_hash() for variant 6; static storage */
+                                modgpu_xfer_kernel_source_hash() for variant 6,
+                                modgpu_rekey_kernel_source_hash() for variant 7; static storage */
 } modgpu_launch_info_t;
 int modgpu_last_launch(modgpu_launch_info_t *out);
 
@@ -133,6 +139,9 @@ const char *modgpu_feed_kernel_source_hash(void);
 const char *modgpu_to_kernel_source_hash(void);
 /* The same for the transfer kernels' TU (cycle_xfer_kernel.hip, cycle_xfer_kernel.h, cycle_feed_kernel.h, cycle_kernel_impl.h, lcg.h). */
 const char *modgpu_xfer_kernel_source_hash(void);
+/* The same for the rekey kernel's TU (cycle_rekey_kernel.hip, cycle_rekey_kernel.h, cycle_rekey_impl.h, cycle_kernel_impl.h,
+ * cycle_kernel.h, lcg.h). */
+const char *modgpu_rekey_kernel_source_hash(void);
 
 /* 1 in libmodgpu_testing.so, 0 in libmodgpu.so. */
 int modgpu_testing_hooks(void);
@@ -148,6 +157,10 @@ void modgpu_debug_set_queue_ring(uint32_t lines);
  * 0 = one unaligned dwordx4 per word, 1 = an aligned dwordx4 and the next dword joined by v_alignbyte_b32, -1 = the shipped
  * form.  Measurement (tools/bench_cycle_to.py) and parity tests of both. */
 void modgpu_debug_set_to_form(int form);
+
+/* The rekey kernel's launch shape: 0 = the out-of-place kernel's grid (25 workgroups per 32 CUs, 200 on MI355X), 1 = one workgroup
+ * per CU on every CU, -1 = the shipped shape.  Measurement (tools/bench_rekey.py) and parity tests of both. */
+void modgpu_debug_set_rekey_form(int shape);
 
 /* How the transfer calls (modgpu_cycle_host_to_device & co.) move their bytes: 0 = the transfer kernels (shipped), 1 = the DMA
  * reference form -- per chunk a hipMemcpyAsync into a device slot and an out-of-place launch from there (upload), or an out-of-place

@@ -15,6 +15,7 @@ from .capi import (  # noqa: F401
     path_stats, gpu_required, last_launch, debug_set_launch, debug_set_pinned_mode, debug_set_staged_mode, kernel_source_hash, feed_kernel_source_hash, prepare, host_tunables, debug_inject_failures, debug_inject_failure_at, debug_injection_armed, debug_hold_slots, debug_forbid_worker_threads, debug_set_pcie_grid, debug_set_gpu_node, debug_set_host_tunable, HOST_TUNABLES, STAGE_FILL, STAGE_LAUNCH, STAGE_SYNC, STAGE_DRAIN, STAGE_AFTER_DRAIN, STAGE_STALL, INJECT_PIECE_LAST, INJECT_PIECE_MIDDLE, PinnedBuffer, host_register, host_unregister,
     DEBUG_EXPORTS, FLAVOURS, testing_flavour, use_testing_flavour, active_flavour, debug_set_queue_ring, debug_set_helpers, queue_stats, testing_hooks, min_gpu_bytes,
     cycle_device_to, cycle_batch_device_to, time_cycle_device_to, to_kernel_source_hash, debug_set_to_form, TO_FORMS,
+    rekey_device_to, rekey_batch_device_to, time_rekey_device_to, rekey_kernel_source_hash, debug_set_rekey_form, REKEY_FORMS,
     cycle_host_to_device, cycle_device_to_host, cycle_file_to_device, cycle_device_to_file, xfer_kernel_source_hash, debug_set_xfer_form, XFER_FORMS,
     host_loop_isa, cycle_scalar_host_isa, device_numa_node, numa_probe, host_policy, host_policy_engine, host_trace, host_trace_read, host_pool_stats, host_chunking, HOST_TRACE_KINDS,
 )

@@ -64,6 +64,9 @@ EXPORTS = {
     "modgpu_device_numa_node": (_int, [_int]),
     "modgpu_cycle_device_to": (_int, [_vp, _vp, _u64, _i32, _u64, _int, _vp]),
     "modgpu_cycle_batch_device_to": (_int, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64), ctypes.POINTER(_u64), _int, _i32, _int, _vp]),
+    "modgpu_rekey_device_to": (_int, [_vp, _vp, _u64, _i32, _u64, _i32, _u64, _int, _vp]),
+    "modgpu_rekey_batch_device_to": (_int, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64), ctypes.POINTER(_u64),
+                                            ctypes.POINTER(_u64), _int, _i32, _i32, _int, _vp]),
     "modgpu_cycle_host_to_device": (_int, [_vp, _vp, _u64, _i32, _u64, _int]),
     "modgpu_cycle_device_to_host": (_int, [_vp, _vp, _u64, _i32, _u64, _int]),
     "modgpu_cycle_file_to_device": (_int, [ctypes.c_char_p, _u64, _vp, _u64, _i32, _u64, _int]),
@@ -115,6 +118,8 @@ TESTING_EXPORTS = {
     "modgpu_time_cycle_device_to": (_int, [_vp, _vp, _u64, _i32, _u64, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
     "modgpu_to_kernel_source_hash": (ctypes.c_char_p, []),
     "modgpu_xfer_kernel_source_hash": (ctypes.c_char_p, []),
+    "modgpu_time_rekey_device_to": (_int, [_vp, _vp, _u64, _i32, _u64, _i32, _u64, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
+    "modgpu_rekey_kernel_source_hash": (ctypes.c_char_p, []),
 }
 # include/modgpu_testing.h, modgpu_debug_* group: ONLY in libmodgpu_testing.so
 DEBUG_EXPORTS = {
@@ -134,6 +139,7 @@ DEBUG_EXPORTS = {
     "modgpu_debug_forbid_worker_threads": (None, [_int]),
     "modgpu_debug_set_to_form": (None, [_int]),
     "modgpu_debug_set_xfer_form": (None, [_int]),
+    "modgpu_debug_set_rekey_form": (None, [_int]),
 }
 
 
@@ -435,6 +441,11 @@ def kernel_source_hash():
     return lib().modgpu_kernel_source_hash().decode()
 
 
+def rekey_kernel_source_hash():
+    """identity of the rekey kernel's TU (cycle_rekey_kernel.hip and what it includes)"""
+    return lib().modgpu_rekey_kernel_source_hash().decode()
+
+
 def to_kernel_source_hash():
     """identity of the out-of-place kernel's TU (cycle_to_kernel.hip and what it includes)"""
     return lib().modgpu_to_kernel_source_hash().decode()
@@ -596,6 +607,53 @@ def time_cycle_device_to(dst_ptr, src_ptr, n, key, stream_off=0, device=-1, stre
     _check(lib().modgpu_time_cycle_device_to(_vp(dst_ptr), _vp(src_ptr), n, as_int32(key), stream_off, device, _vp(stream or 0),
                                              iters, ctypes.byref(ms)))
     return ms.value
+
+
+def rekey_device_to(dst, src, key_from, key_to, off_from=0, off_to=0, device=-1, stream=None, *, n=None):
+    """Asynchronous REKEY of n bytes at raw device addresses: dst[j] = src[j] ^ ks(key_from)[off_from + j] ^ ks(key_to)[off_to + j], in
+    one pass; src is not modified (dst == src rekeys in place; a partial overlap is refused).  `dst` / `src` are addresses or
+    DeviceBuffer; n defaults to the smaller buffer's size when both are DeviceBuffer."""
+    if n is None:
+        if not (isinstance(dst, DeviceBuffer) and isinstance(src, DeviceBuffer)):
+            raise TypeError("n is needed unless both sides are DeviceBuffer")
+        n = min(dst.nbytes, src.nbytes)
+    _check(lib().modgpu_rekey_device_to(_vp(_dev_addr(dst)), _vp(_dev_addr(src)), n, as_int32(key_from), off_from, as_int32(key_to), off_to,
+                                        device, _vp(stream or 0)))
+
+
+def rekey_batch_device_to(dst_ptrs, src_ptrs, sizes, key_from, key_to, offs_from=None, offs_to=None, device=-1, stream=None):
+    """Several rekey entries of ONE device (entry i from offs_from[i] / offs_to[i], or 0); sources may overlap each other, a destination
+    may meet no other entry's range.  Up to 16 non-empty entries share a launch."""
+    n = len(dst_ptrs)
+    assert len(src_ptrs) == n and len(sizes) == n
+    d = (_vp * n)(*[_dev_addr(x) for x in dst_ptrs])
+    s = (_vp * n)(*[_dev_addr(x) for x in src_ptrs])
+    z = (_u64 * n)(*sizes)
+    of = (_u64 * n)(*offs_from) if offs_from is not None else None
+    ot = (_u64 * n)(*offs_to) if offs_to is not None else None
+    _check(lib().modgpu_rekey_batch_device_to(d, s, z, of, ot, n, as_int32(key_from), as_int32(key_to), device, _vp(stream or 0)))
+
+
+def time_rekey_device_to(dst, src, n, key_from, key_to, off_from=0, off_to=0, device=-1, stream=None, iters=2):
+    """Mean ms per rekey launch over `iters` launches, HIP events on the launch stream."""
+    ms = ctypes.c_float(0)
+    _check(lib().modgpu_time_rekey_device_to(_vp(_dev_addr(dst)), _vp(_dev_addr(src)), n, as_int32(key_from), off_from, as_int32(key_to),
+                                             off_to, device, _vp(stream or 0), iters, ctypes.byref(ms)))
+    return ms.value
+
+
+REKEY_FORMS = {None: -1, "shipped": -1, "queue": 0, "all": 1}
+
+
+def debug_set_rekey_form(form=None):
+    """Testing flavour: the rekey kernel's launch shape ("queue" = the out-of-place kernel's 200 workgroups, "all" = one per CU,
+    None = shipped)."""
+    _debug_lib().modgpu_debug_set_rekey_form(REKEY_FORMS[form])
+
+
+def _dev_addr(x):
+    """raw device address of an int address or a DeviceBuffer"""
+    return x.ptr if isinstance(x, DeviceBuffer) else x
 
 
 TO_FORMS = {None: -1, "shipped": -1, "unaligned": 0, "funnel": 1}

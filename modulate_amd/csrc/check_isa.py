@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""check_isa.py <cycle_kernel.s> [<cycle_feed_kernel.s>] | <cycle_to_kernel.s> | <cycle_xfer_kernel.s> -- build-time guard over the gfx950 assembly of the kernel TUs (run by the
+"""check_isa.py <cycle_kernel.s> [<cycle_feed_kernel.s>] | <cycle_to_kernel.s> | <cycle_xfer_kernel.s> | <cycle_rekey_kernel.s> -- build-time guard over the gfx950 assembly of the kernel TUs (run by the
 Makefile right after the TUs are compiled and before either object exists; tests/test_capi_cpu.py runs it again and feeds it
 deliberately broken builds).
 
@@ -31,6 +31,11 @@ blocks' rules above, the ticket fetch not wave-aggregated (no v_mbcnt), data loa
 The transfer kernels (cycle_xfer_kernel.s, four forms): the host-fed kernel's rules -- <= 64 VGPRs, no spills / scratch, 8 bytes of
 LDS, exactly two s_barrier, the ticket and ok word in scalar registers behind the first barrier, ALG 1 --, every data load nt, the
 upload's stores into HBM nt sc1, the download's stores across PCIe sc1 and NOT nt.
+The rekey kernel (cycle_rekey_kernel.s, both forms): the register budget, no spills / scratch / private segment, the ticket fetch not
+wave-aggregated, data loads nt, data stores nt sc1, and the two-keystream blocks' own discipline (cycle_rekey_impl.h): fixed
+temporaries v[112:127] and s[94:95] touched by nothing outside the blocks and given to no operand the compiler chose, every block
+60 mads + 30 addc ending with s_nop 0, and one three-input XOR (v_bitop3_b32 bitop3:0x96; gfx950 has no v_xor3_b32) per dword of
+every block.
 Exit status 0 = all of it holds; 1 = findings on stdout."""
 import re
 import sys
@@ -242,6 +247,59 @@ def check_to(asm, bodies):
     return bad
 
 
+REKEY_FIXED = re.compile(r"\bv11[2-9]\b|\bv12[0-7]\b|v\[\d+:(?:11[2-9]|12[0-7])\]|\bs9[45]\b|s\[\d+:9[45]\]")
+REKEY_OWN = re.compile(r"v\[(?:11[2468]|12[0246]):(?:11[3579]|12[1357])\]|s\[94:95\]|\bv(?:11[2468]|12[0246])\b|\bv12[57]\b")
+
+
+def rekey_blocks(name, fn):
+    """the two-keystream blocks of cycle_rekey_impl.h (ks_word2_carry): fixed temporaries, trailing s_nop 0, 60 mad + 30 addc each"""
+    bad = []
+    blocks = [b for b in BLOCK.findall(fn) if "s[94:95]" in b]
+    if not blocks:
+        return ["%s: no two-keystream block (ks_word2_carry)" % name]
+    outside = BLOCK.sub("", fn)
+    for ln in outside.splitlines():
+        if REKEY_FIXED.search(ln) and not ln.strip().startswith(";"):
+            bad.append("%s: a fixed temporary of the two-keystream block is touched OUTSIDE the blocks: %s" % (name, ln.strip()))
+    for b in blocks:
+        lines = [ln for ln in b.splitlines() if ln.strip()]
+        for ln in lines:
+            if REKEY_FIXED.search(REKEY_OWN.sub("", ln)):
+                bad.append("%s: the compiler gave a two-keystream block operand a fixed temporary: %s" % (name, ln.strip()))
+        if not lines or lines[-1].split(";")[0].strip() != "s_nop 0":
+            bad.append("%s: a two-keystream block does not end with s_nop 0 (dst_sel forwarding hazard)" % name)
+        if len([ln for ln in lines if "v_addc_co_u32_sdwa" in ln]) != 30 or len([ln for ln in lines if "v_mad_u64_u32" in ln]) != 60:
+            bad.append("%s: a two-keystream block is not 60 mads + 30 addc" % name)
+    xor3 = len(re.findall(r"v_bitop3_b32 .*bitop3:0x96", fn))
+    if xor3 != 4 * len(blocks):
+        bad.append("%s: %d three-input XORs (v_bitop3_b32 0x96) for %d two-keystream blocks, expected one per dword (4 per block)" % (name, xor3, len(blocks)))
+    return bad
+
+
+def check_rekey(asm, bodies):
+    """the rekey kernel's TU (cycle_rekey_kernel.s): every kernel in it is a form of modgpu_cycle_rekey_kernel"""
+    bad = []
+    for name, fn in bodies.items():
+        if "modgpu_cycle_rekey_kernel" not in name:
+            bad.append("%s: the rekey kernel's TU holds another kernel" % name)
+            continue
+        md = metadata(asm, name)
+        if md.get("vgpr_count", 999) > 128 or md.get("sgpr_count", 999) > 102:
+            bad.append("%s: register counts beyond the budget: %s" % (name, md))
+        if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0) or "scratch_" in fn:
+            bad.append("%s: spills, scratch or a private segment: %s" % (name, md))
+        bad += rekey_blocks(name, fn)
+        if "v_mbcnt" in fn:
+            bad.append("%s: the atomic optimizer rewrote the ticket atomic (build the TU with -mllvm -amdgpu-atomic-optimizer-strategy=None)" % name)
+        loads = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_load_dword", ln)]
+        stores = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_store_dword", ln)]
+        if not loads or not all(ln.endswith(" nt") for ln in loads):
+            bad.append("%s: a data load is not nt" % name)
+        if not stores or not all(ln.endswith(" nt sc1") for ln in stores):
+            bad.append("%s: a data store is not nt sc1" % name)
+    return bad
+
+
 def check_xfer(asm, bodies):
     """the transfer kernels' TU (cycle_xfer_kernel.s): the upload (ILb1) and the download (ILb0), each plain and funnel"""
     bad = []
@@ -295,6 +353,8 @@ def check(asm):
         return bad + check_to(asm, bodies)
     if any("modgpu_cycle_xfer_kernel" in n for n in bodies):
         return bad + check_xfer(asm, bodies)
+    if any("modgpu_cycle_rekey_kernel" in n for n in bodies):
+        return bad + check_rekey(asm, bodies)
     queue = [n for n in bodies if "modgpu_cycle_queue_kernel" in n]
     if len(queue) != 1:
         return bad + ["expected exactly one work-queue kernel, found %d" % len(queue)]

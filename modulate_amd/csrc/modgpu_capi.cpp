@@ -19,6 +19,7 @@
 #include "crossover_table.h"
 #include "cycle_feed_kernel.h"
 #include "cycle_kernel.h"
+#include "cycle_rekey_kernel.h"
 #include "cycle_to_kernel.h"
 #include "cycle_xfer_kernel.h"
 #include "lcg.h"
@@ -34,6 +35,9 @@
 #endif
 #ifndef MODGPU_XFER_KERNEL_SOURCE_HASH
 #define MODGPU_XFER_KERNEL_SOURCE_HASH "unknown"
+#endif
+#ifndef MODGPU_REKEY_KERNEL_SOURCE_HASH
+#define MODGPU_REKEY_KERNEL_SOURCE_HASH "unknown"
 #endif
 
 namespace modgpu {
@@ -682,6 +686,46 @@ int to_form() { return g_to_form.load(std::memory_order_relaxed); }
 constexpr int to_form() { return kToFormShipped; }
 #endif
 
+// Where one out-of-place entry lies on the chunk grid of its DESTINATION (the out-of-place and the rekey kernel share it): < 16 head
+// bytes up to the first 16-byte aligned destination byte, a body of whole words whose chunks sit on absolute chunk-aligned addresses
+// -- the first starts `lead` bytes before the body, and positions count from there --, and < 16 tail bytes.
+struct EntryGeom {
+    uint64_t head, words, tail;
+    uint32_t lead;
+    uint64_t end;      // lead + body bytes
+    uint64_t n_chunks; // chunks from the chunk origin, the cut first one included
+    uint64_t first;    // 1 if the first chunk is cut (it is the entry's own workgroup's, outside the index space)
+};
+EntryGeom entry_geom(const uint8_t *dst, uint64_t size, uint64_t chunk)
+{
+    EntryGeom g;
+    g.head = std::min<uint64_t>(size, (16 - (reinterpret_cast<uintptr_t>(dst) & 15)) & 15);
+    g.words = (size - g.head) / 16;
+    g.tail = size - g.head - g.words * 16;
+    g.lead = (uint32_t)(reinterpret_cast<uintptr_t>(dst + g.head) & (chunk - 1));
+    g.end = g.lead + g.words * 16;
+    g.n_chunks = (g.end + chunk - 1) / chunk;
+    g.first = g.lead != 0 ? 1 : 0;
+    return g;
+}
+// The three base states of a keystream from stream position o (< PERIOD) over an entry: head, body (stepped back by a^(-lead) to the
+// chunk origin), tail.
+void entry_bases(const EntryGeom &g, uint32_t key_res, uint64_t o, uint32_t &head, uint32_t &body, uint32_t &tail)
+{
+    head = lcg::state_residue(key_res, o);
+    body = lcg::mulmod(lcg::state_residue(key_res, o + g.head), lcg::powmod(lcg::A, lcg::PERIOD - g.lead % lcg::PERIOD));
+    tail = lcg::state_residue(key_res, o + g.head + (g.words * 16) % lcg::PERIOD);
+}
+
+// The next run of up to kCycleBatchMax non-empty entries from *i on that `keep` accepts (indices into the caller's arrays); 0: none left.
+template <class Keep> int next_run(const uint64_t *sizes, int n, int &i, int (&idx)[kCycleBatchMax], Keep keep)
+{
+    int g = 0;
+    for (; i < n && g < kCycleBatchMax; ++i)
+        if (sizes[i] && keep(i)) idx[g++] = i;
+    return g;
+}
+
 // One launch of the out-of-place kernel over 1..kCycleBatchMax non-empty entries of the current device.  MODGPU_OK, an error, or 1:
 // no ticket pair to be had right now (or an entry beyond the three-byte chunk jump tables): the caller copies and cycles in place.
 int launch_to(uint8_t *const *dst, const uint8_t *const *src, const uint64_t *sizes, const uint64_t *offs, int n, uint32_t key_res,
@@ -693,26 +737,19 @@ int launch_to(uint8_t *const *dst, const uint8_t *const *src, const uint64_t *si
     bool misaligned = false;
     for (int k = 0; k < n; ++k) {
         CycleToPart &P = a.part[k];
-        const uintptr_t addr = reinterpret_cast<uintptr_t>(dst[k]);
-        const uint64_t head = std::min<uint64_t>(sizes[k], (16 - (addr & 15)) & 15);
-        const uint64_t words = (sizes[k] - head) / 16;
-        const uint64_t o = offs[k] % lcg::PERIOD;
-        P.dst_body = dst[k] + head;
-        P.src_body = src[k] + head;
-        P.head_n = (uint32_t)head;
-        P.tail_n = (uint32_t)(sizes[k] - head - words * 16);
-        // chunks sit on absolute chunk-aligned DESTINATION addresses; positions count from the chunk origin, `lead` bytes before the body
-        P.lead = (uint32_t)(reinterpret_cast<uintptr_t>(P.dst_body) & (chunk - 1));
-        P.end = P.lead + words * 16;
-        P.base_head = lcg::state_residue(key_res, o);
-        P.base_body = lcg::mulmod(lcg::state_residue(key_res, o + head), lcg::powmod(lcg::A, lcg::PERIOD - P.lead % lcg::PERIOD));
-        P.base_tail = lcg::state_residue(key_res, o + head + (words * 16) % lcg::PERIOD);
-        const uint64_t n_chunks = (P.end + chunk - 1) / chunk, first = P.lead != 0 ? 1 : 0;
-        if (n_chunks >= (1ull << 24)) return 1;
+        const EntryGeom g = entry_geom(dst[k], sizes[k], chunk);
+        P.dst_body = dst[k] + g.head;
+        P.src_body = src[k] + g.head;
+        P.head_n = (uint32_t)g.head;
+        P.tail_n = (uint32_t)g.tail;
+        P.lead = g.lead;
+        P.end = g.end;
+        entry_bases(g, key_res, offs[k] % lcg::PERIOD, P.base_head, P.base_body, P.base_tail);
+        if (g.n_chunks >= (1ull << 24)) return 1;
         a.start[k] = (uint32_t)total;
-        total += n_chunks > first ? n_chunks - first : 0;
+        total += g.n_chunks > g.first ? g.n_chunks - g.first : 0;
         bytes += sizes[k];
-        misaligned |= words != 0 && ((reinterpret_cast<uintptr_t>(src[k]) - addr) & 3) != 0;
+        misaligned |= g.words != 0 && ((reinterpret_cast<uintptr_t>(src[k]) - reinterpret_cast<uintptr_t>(dst[k])) & 3) != 0;
     }
     for (int k = n; k <= kCycleBatchMax; ++k) a.start[k] = (uint32_t)total;
     a.n_parts = (uint32_t)n;
@@ -760,21 +797,17 @@ int check_to_entries(void *const *dst, const void *const *src, const uint64_t *s
 int cycle_to_impl(void *const *dst, const void *const *src, const uint64_t *sizes, const uint64_t *offs, int n, int32_t key, hipStream_t stream)
 {
     const uint32_t key_res = lcg::key_residue(key);
-    int i = 0;
-    while (i < n) {
+    int i = 0, idx[kCycleBatchMax];
+    while (const int g = next_run(sizes, n, i, idx, [](int) { return true; })) {
         uint8_t *gd[kCycleBatchMax];
         const uint8_t *gs[kCycleBatchMax];
         uint64_t gn[kCycleBatchMax], go[kCycleBatchMax];
-        int g = 0;
-        for (; i < n && g < kCycleBatchMax; ++i) {
-            if (!sizes[i]) continue;
-            gd[g] = static_cast<uint8_t *>(dst[i]);
-            gs[g] = static_cast<const uint8_t *>(src[i]);
-            gn[g] = sizes[i];
-            go[g] = offs ? offs[i] : 0;
-            ++g;
+        for (int k = 0; k < g; ++k) {
+            gd[k] = static_cast<uint8_t *>(dst[idx[k]]);
+            gs[k] = static_cast<const uint8_t *>(src[idx[k]]);
+            gn[k] = sizes[idx[k]];
+            go[k] = offs ? offs[idx[k]] : 0;
         }
-        if (!g) break;
         int rc = key_res ? launch_to(gd, gs, gn, go, g, key_res, stream) : 1;
         if (rc == 1) {
             rc = MODGPU_OK;
@@ -784,6 +817,110 @@ int cycle_to_impl(void *const *dst, const void *const *src, const uint64_t *size
                     if (e != hipSuccess) return fail_hip(e, "hipMemcpyAsync (out of place)");
                 }
                 if (key_res) rc = cycle_device_impl(gd[k], gn[k], key, go[k], stream);
+            }
+        }
+        if (rc != MODGPU_OK) return rc;
+    }
+    return MODGPU_OK;
+}
+
+// ---- rekey: dst = src ^ ks(key_from)[off_from + j] ^ ks(key_to)[off_to + j] (modgpu_rekey_device_to / modgpu_rekey_batch_device_to) ----
+// Launch shape (cycle_rekey_kernel.h): one workgroup per CU on every CU.  Two keystreams make the pass VALU-bound on the out-of-place
+// kernel's 200 workgroups (5.92 TB/s at 4 GiB); on all 256 it sits at the HBM ceiling (6.99, against 7.04 for one keystream) --
+// DESIGN.md 4.7, profiles/r08_rekey.json.
+constexpr int kRekeyShapeShipped = CYCLE_REKEY_SHAPE_ALL;
+#ifdef MODGPU_TESTING_HOOKS
+std::atomic<int> g_rekey_shape{kRekeyShapeShipped}; // modgpu_debug_set_rekey_form
+int rekey_shape() { return g_rekey_shape.load(std::memory_order_relaxed); }
+#else
+constexpr int rekey_shape() { return kRekeyShapeShipped; }
+#endif
+
+// One launch of the rekey kernel over 1..kCycleBatchMax non-empty entries of the current device, both keys non-zero residues.
+// MODGPU_OK, an error, or 1: no ticket pair to be had right now (or an entry beyond the three-byte chunk jump tables).
+int launch_rekey(uint8_t *const *dst, const uint8_t *const *src, const uint64_t *sizes, const uint64_t *offs_from, const uint64_t *offs_to,
+                 int n, uint32_t key_from, uint32_t key_to, hipStream_t stream)
+{
+    CycleRekeyArgs a{};
+    const uint64_t chunk = modgpu_rekey_chunk_bytes();
+    uint64_t total = 0, bytes = 0;
+    bool misaligned = false;
+    for (int k = 0; k < n; ++k) {
+        CycleRekeyPart &P = a.part[k];
+        const EntryGeom g = entry_geom(dst[k], sizes[k], chunk);
+        P.dst_body = dst[k] + g.head;
+        P.src_body = src[k] + g.head;
+        P.head_n = (uint32_t)g.head;
+        P.tail_n = (uint32_t)g.tail;
+        P.lead = g.lead;
+        P.end = g.end;
+        // two keystreams, two sets of bases on the same positions: differing offsets change nothing else
+        entry_bases(g, key_from, offs_from[k] % lcg::PERIOD, P.base_head[0], P.base_body[0], P.base_tail[0]);
+        entry_bases(g, key_to, offs_to[k] % lcg::PERIOD, P.base_head[1], P.base_body[1], P.base_tail[1]);
+        if (g.n_chunks >= (1ull << 24)) return 1;
+        a.start[k] = (uint32_t)total;
+        total += g.n_chunks > g.first ? g.n_chunks - g.first : 0;
+        bytes += sizes[k];
+        misaligned |= g.words != 0 && ((reinterpret_cast<uintptr_t>(src[k]) - reinterpret_cast<uintptr_t>(dst[k])) & 3) != 0;
+    }
+    for (int k = n; k <= kCycleBatchMax; ++k) a.start[k] = (uint32_t)total;
+    a.n_parts = (uint32_t)n;
+    const QueuePair q = queue_pair(stream);
+    if (!q.pair) return 1;
+    a.queue = q.pair;
+    a.queue_done = q.done;
+    a.queue_seq = q.seq;
+    uint64_t cap = 0, helpers = 0;
+    queue_grid(total, large_grid(), &cap, &helpers);
+    if (rekey_shape() == CYCLE_REKEY_SHAPE_ALL) cap = large_grid();
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(total, cap));
+    const int form = misaligned ? CYCLE_REKEY_FUNNEL : CYCLE_REKEY_PLAIN;
+    hipError_t e = modgpu_launch_cycle_rekey(a, form, grid, stream);
+    if (e != hipSuccess) {
+        queue_pair_unused(q);
+        return fail_hip(e, "cycle kernel launch (rekey)");
+    }
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    t_last_launch = {modgpu_rekey_kernel_name(form), CYCLE_REKEY, grid, modgpu_rekey_block(), (uint32_t)chunk, bytes, grid, MODGPU_REKEY_KERNEL_SOURCE_HASH};
+    return MODGPU_OK;
+}
+
+// Entries already checked (check_to_entries), on the current device, asynchronous on `stream`.  Degenerate keystreams take the
+// out-of-place call: a key == 0 mod m has the identity keystream, so only the other key is left to apply (both zero: a copy); an
+// entry with the same reduced key at the same stream position has ks ^ ks = 0 and is copied.  The rest run in groups of up to
+// kCycleBatchMax per launch; with no ticket pair free a group is done in two passes on the same stream, out of place under key_from,
+// then in place under key_to.
+int rekey_impl(void *const *dst, const void *const *src, const uint64_t *sizes, const uint64_t *offs_from, const uint64_t *offs_to, int n,
+               int32_t key_from, int32_t key_to, hipStream_t stream)
+{
+    const uint32_t kf = lcg::key_residue(key_from), kt = lcg::key_residue(key_to);
+    if (!kf) return cycle_to_impl(dst, src, sizes, offs_to, n, key_to, stream); // (key_to == 0 too: a copy)
+    if (!kt) return cycle_to_impl(dst, src, sizes, offs_from, n, key_from, stream);
+    auto at = [](const uint64_t *offs, int i) { return offs ? offs[i] % lcg::PERIOD : 0; };
+    auto identity = [&](int i) { return kf == kt && at(offs_from, i) == at(offs_to, i); };
+    for (int i = 0; i < n; ++i)
+        if (sizes[i] && identity(i))
+            if (int rc = cycle_to_impl(&dst[i], &src[i], &sizes[i], nullptr, 1, 0, stream)) return rc;
+    int i = 0, idx[kCycleBatchMax];
+    while (const int g = next_run(sizes, n, i, idx, [&](int j) { return !identity(j); })) {
+        uint8_t *gd[kCycleBatchMax];
+        const uint8_t *gs[kCycleBatchMax];
+        uint64_t gn[kCycleBatchMax], gf[kCycleBatchMax], gt[kCycleBatchMax];
+        for (int k = 0; k < g; ++k) {
+            gd[k] = static_cast<uint8_t *>(dst[idx[k]]);
+            gs[k] = static_cast<const uint8_t *>(src[idx[k]]);
+            gn[k] = sizes[idx[k]];
+            gf[k] = at(offs_from, idx[k]);
+            gt[k] = at(offs_to, idx[k]);
+        }
+        int rc = launch_rekey(gd, gs, gn, gf, gt, g, kf, kt, stream);
+        if (rc == 1) {
+            rc = MODGPU_OK;
+            for (int k = 0; k < g && rc == MODGPU_OK; ++k) {
+                void *d = gd[k];
+                const void *s = gs[k];
+                rc = cycle_to_impl(&d, &s, &gn[k], &gf[k], 1, key_from, stream);
+                if (rc == MODGPU_OK) rc = cycle_device_impl(d, gn[k], key_to, gt[k], stream);
             }
         }
         if (rc != MODGPU_OK) return rc;
@@ -976,6 +1113,29 @@ int modgpu_cycle_batch_device_to(void *const *dst_parts, const void *const *src_
         DeviceScope scope(device);
         if (scope.rc) return scope.rc;
         return cycle_to_impl(dst_parts, src_parts, sizes, stream_offs, n_parts, key, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int modgpu_rekey_device_to(void *dev_dst, const void *dev_src, uint64_t n, int32_t key_from, uint64_t off_from, int32_t key_to, uint64_t off_to,
+                           int device, void *hip_stream)
+{
+    return guarded([&]() -> int {
+        if (int rc = check_to_entries(&dev_dst, &dev_src, &n, 1)) return rc;
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        return rekey_impl(&dev_dst, &dev_src, &n, &off_from, &off_to, 1, key_from, key_to, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int modgpu_rekey_batch_device_to(void *const *dst_parts, const void *const *src_parts, const uint64_t *sizes, const uint64_t *offs_from,
+                                 const uint64_t *offs_to, int n_parts, int32_t key_from, int32_t key_to, int device, void *hip_stream)
+{
+    return guarded([&]() -> int {
+        if (n_parts < 0 || (n_parts > 0 && (!dst_parts || !src_parts || !sizes))) return fail(MODGPU_ERR_INVALID, "bad entry list");
+        if (int rc = check_to_entries(dst_parts, src_parts, sizes, n_parts)) return rc;
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        return rekey_impl(dst_parts, src_parts, sizes, offs_from, offs_to, n_parts, key_from, key_to, static_cast<hipStream_t>(hip_stream));
     });
 }
 
@@ -1610,6 +1770,34 @@ int modgpu_time_cycle_device_to(void *dev_dst, const void *dev_src, uint64_t n, 
     });
 }
 
+int modgpu_time_rekey_device_to(void *dev_dst, const void *dev_src, uint64_t n, int32_t key_from, uint64_t off_from, int32_t key_to,
+                                uint64_t off_to, int device, void *hip_stream, int iters, float *ms_per_launch)
+{
+    return guarded([&]() -> int {
+        if (iters <= 0 || !ms_per_launch) return fail(MODGPU_ERR_INVALID, "bad timing arguments");
+        if (int rc = check_to_entries(&dev_dst, &dev_src, &n, 1)) return rc;
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        int rc = MODGPU_OK;
+        hipStream_t st = static_cast<hipStream_t>(hip_stream);
+        hipEvent_t e0, e1;
+        HIP_TRY(hipEventCreate(&e0));
+        HIP_TRY(hipEventCreate(&e1));
+        HIP_TRY(hipEventRecord(e0, st));
+        for (int i = 0; i < iters && rc == MODGPU_OK; ++i) rc = rekey_impl(&dev_dst, &dev_src, &n, &off_from, &off_to, 1, key_from, key_to, st);
+        hipError_t e = hipEventRecord(e1, st);
+        if (e == hipSuccess) e = hipEventSynchronize(e1);
+        float ms = 0.f;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        if (rc) return rc;
+        if (e != hipSuccess) return fail_hip(e, "event timing");
+        *ms_per_launch = ms / (float)iters;
+        return MODGPU_OK;
+    });
+}
+
 int modgpu_last_launch(modgpu_launch_info_t *out)
 {
     if (!out) return fail(MODGPU_ERR_INVALID, "null out pointer");
@@ -1651,6 +1839,7 @@ const char *modgpu_kernel_source_hash(void) { return MODGPU_KERNEL_SOURCE_HASH; 
 const char *modgpu_feed_kernel_source_hash(void) { return MODGPU_FEED_KERNEL_SOURCE_HASH; }
 const char *modgpu_to_kernel_source_hash(void) { return MODGPU_TO_KERNEL_SOURCE_HASH; }
 const char *modgpu_xfer_kernel_source_hash(void) { return MODGPU_XFER_KERNEL_SOURCE_HASH; }
+const char *modgpu_rekey_kernel_source_hash(void) { return MODGPU_REKEY_KERNEL_SOURCE_HASH; }
 
 int modgpu_testing_hooks(void)
 {
@@ -1678,6 +1867,12 @@ void modgpu_debug_set_helpers(int mode) { g_helper_mode.store(mode >= 0 && mode 
 void modgpu_debug_set_batch(int mode) { g_batch_mode.store(mode >= 0 && mode <= 2 ? mode : 0, std::memory_order_relaxed); }
 
 void modgpu_debug_set_to_form(int form) { g_to_form.store(form < 0 ? kToFormShipped : form == CYCLE_TO_FUNNEL ? CYCLE_TO_FUNNEL : CYCLE_TO_PLAIN, std::memory_order_relaxed); }
+
+void modgpu_debug_set_rekey_form(int shape)
+{
+    g_rekey_shape.store(shape < 0 ? kRekeyShapeShipped : shape == CYCLE_REKEY_SHAPE_ALL ? CYCLE_REKEY_SHAPE_ALL : CYCLE_REKEY_SHAPE_QUEUE,
+                        std::memory_order_relaxed);
+}
 
 void modgpu_debug_set_queue_ring(uint32_t lines)
 {
