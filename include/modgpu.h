@@ -94,7 +94,7 @@ extern "C" {
 
 /* ABI version of this header (bumped on any signature change; ABI 8 also gained modgpu_cycle_device_to and
  * modgpu_cycle_batch_device_to, the four transfer calls modgpu_cycle_host_to_device & co., and modgpu_rekey_device_to and
- * modgpu_rekey_batch_device_to, additions that change no existing signature). */
+ * modgpu_rekey_batch_device_to, and the table calls modgpu_cycle_table_device & co., additions that change no existing signature). */
 #define MODGPU_ABI_VERSION 8
 int modgpu_abi_version(void);
 
@@ -163,7 +163,8 @@ int modgpu_cycle_device_to(void *dev_dst, const void *dev_src, uint64_t n, int32
  * in addition SOURCE ranges may overlap each other (they are only read), but a destination range that meets any other
  * entry's source or destination range makes the whole call MODGPU_ERR_INVALID (an entry's exact self-alias is allowed).
  * Any n_parts: up to 16 non-empty entries share one launch, more take more launches, in order, on the same stream; empty
- * entries are skipped. */
+ * entries are skipped.  For more than a handful of entries -- an archive's files -- modgpu_cycle_table_device takes a table of any
+ * length in three launches, each entry with its own key. */
 int modgpu_cycle_batch_device_to(void *const *dst_parts, const void *const *src_parts, const uint64_t *sizes,
                                  const uint64_t *stream_offs, int n_parts, int32_t key, int device, void *hip_stream);
 
@@ -192,6 +193,57 @@ int modgpu_rekey_device_to(void *dev_dst, const void *dev_src, uint64_t n, int32
 int modgpu_rekey_batch_device_to(void *const *dst_parts, const void *const *src_parts, const uint64_t *sizes,
                                  const uint64_t *offs_from, const uint64_t *offs_to, int n_parts, int32_t key_from,
                                  int32_t key_to, int device, void *hip_stream);
+
+/* ---- a TABLE of out-of-place entries in device memory: any length, three launches -----------------------------------------------
+ * One entry: dst[j] = src[j] ^ ks(key)[stream_off + j], j = 0 .. n-1 -- exactly what modgpu_cycle_device_to computes for it (any byte
+ * alignment on either side, dst == src cycles in place, n == 0 is skipped, a key == 0 mod 2^31-1 copies, 64-bit offsets).  What
+ * extracting the files of a resident archive part is, each file with its own key if need be.  The layout is pinned (40 bytes). */
+typedef struct modgpu_table_entry {
+    void *dst;
+    const void *src;
+    uint64_t n;
+    uint64_t stream_off;
+    int32_t key;
+    uint32_t flags; /* must be 0 (reserved) */
+} modgpu_table_entry_t;
+
+#define MODGPU_TABLE_MAX_ENTRIES 4194304u /* 2^22 entries per call */
+
+/* Bytes of device workspace a call over n_entries needs: about 68 per entry plus a few lines (0 above MODGPU_TABLE_MAX_ENTRIES). */
+uint64_t modgpu_table_workspace_bytes(uint64_t n_entries);
+
+/* Cycles the n_entries entries at dev_entries, a table in device memory of `device`, in THREE kernel launches whatever n_entries is
+ * (plan, finish, stream; path_stats().gpu_launches counts them, modgpu_last_launch reports the stream launch as variant 8).
+ * Asynchronous on `hip_stream`; `device` -1 = the current device; allocation-free; capturable into a hipGraph.  THE TABLE IS READ
+ * WHEN THE CALL RUNS ON THE DEVICE, not when it is queued: a captured call picks up whatever the caller wrote into the table (keys,
+ * offsets, pointers, sizes) before each replay.
+ * The WORKSPACE is the caller's: at least modgpu_table_workspace_bytes(n_entries) bytes of device memory of `device`, 8-byte aligned.
+ * It holds all the call schedules with (its ticket counter, its plan, its status): the call shares nothing with other calls, so calls
+ * with different workspaces may run at the same time on any streams, while two calls on ONE workspace must not overlap in time (a
+ * captured call owns its workspace for as long as the graph may be replayed).  The call's first kernel resets the workspace in stream
+ * order; nothing needs clearing beforehand.
+ * Checks, in three tiers:
+ *   1. on the host, before anything is queued -- MODGPU_ERR_INVALID: a NULL table or workspace with n_entries > 0, a table or
+ *      workspace that is not 8-byte aligned, a workspace smaller than required, n_entries above MODGPU_TABLE_MAX_ENTRIES, a table or
+ *      workspace that is not device memory of `device`.  n_entries == 0 queues nothing (and leaves the workspace's status as it was).
+ *   2. on the device, by the plan: an entry with a NULL dst or src and n > 0, an entry with nonzero flags, an entry of 1 TiB or more,
+ *      or entries of more than 2^31 chunks of 64 KiB together.  Any of these makes the WHOLE CALL WRITE NOTHING; modgpu_table_status
+ *      names the lowest such entry once the caller has synchronised.
+ *   3. not checked on the device: overlaps.  The rule is modgpu_cycle_batch_device_to's -- sources may overlap each other, an entry may
+ *      alias itself exactly, a destination may meet no other entry's source or destination range.  Bytes in ranges that break it are
+ *      unspecified, but nothing outside the entries' [dst, dst+n) is ever written.  modgpu_table_validate checks a host copy. */
+int modgpu_cycle_table_device(const modgpu_table_entry_t *dev_entries, uint64_t n_entries, void *dev_workspace,
+                              uint64_t workspace_bytes, int device, void *hip_stream);
+
+/* Status of the last call that ran on dev_workspace (read after the caller has synchronised): MODGPU_OK with *first_bad_entry =
+ * UINT64_MAX if it ran clean, MODGPU_ERR_INVALID with *first_bad_entry = the lowest entry the device refused (the call wrote
+ * nothing).  Synchronous (a small copy from the device). */
+int modgpu_table_status(const void *dev_workspace, int device, uint64_t *first_bad_entry);
+
+/* A host copy of a table against tiers 1-3 above, in O(n log n): MODGPU_OK, or MODGPU_ERR_INVALID with modgpu_last_error() naming
+ * an entry at fault (a NULL pointer with n > 0, nonzero flags, a destination partly overlapping its own source, a destination
+ * meeting another entry's source or destination).  No device is touched. */
+int modgpu_table_validate(const modgpu_table_entry_t *host_entries, uint64_t n_entries);
 
 /* Replaces CEncryptionCycler::Cycle (CEncryptionCycler.cpp:4-14) for a caller-owned HOST buffer,
  * on the GPU.  Pageable memory is staged through page-locked slots owned by this library (memcpy ->

@@ -35,6 +35,9 @@ int modgpu_time_cycle_device_to(void *dev_dst, const void *dev_src, uint64_t n, 
 /* The same for modgpu_rekey_device_to: `iters` back-to-back rekey launches (dst is the same after every one). */
 int modgpu_time_rekey_device_to(void *dev_dst, const void *dev_src, uint64_t n, int32_t key_from, uint64_t off_from, int32_t key_to,
                                 uint64_t off_to, int device, void *hip_stream, int iters, float *ms_per_launch);
+/* The same for modgpu_cycle_table_device: `iters` back-to-back table calls (three launches each) on one workspace. */
+int modgpu_time_cycle_table_device(const void *dev_entries, uint64_t n_entries, void *dev_workspace,
+                                   uint64_t workspace_bytes, int device, void *hip_stream, int iters, float *ms_per_call);
 
 /* The launch the calling thread made last (any entry point), as the library planned it. */
 typedef struct modgpu_launch_info {
@@ -45,7 +48,9 @@ typedef struct modgpu_launch_info {
                              4 = the host-fed kernel of a host-buffer call (one launch for the whole call; `bytes` = the call's),
                              5 = the out-of-place kernel (modgpu_cycle_device_to / _batch_device_to; `bytes` = all entries of the launch),
                              6 = a transfer kernel (modgpu_cycle_host_to_device & co.; one launch for the whole call; `bytes` = the call's),
-                             7 = the rekey kernel (modgpu_rekey_device_to / _batch_device_to; `bytes` = all entries of the launch) */
+                             7 = the rekey kernel (modgpu_rekey_device_to / _batch_device_to; `bytes` = all entries of the launch),
+                             8 = the table call's stream kernel (modgpu_cycle_table_device; `bytes` = 0: the table is only read on
+                                 the device) */
     uint32_t grid;        /* workgroups launched                                                  */
     uint32_t block;       /* threads per workgroup                                                */
     uint32_t chunk_bytes; /* bytes one workgroup trip covers                                      */
@@ -56,7 +61,8 @@ typedef struct modgpu_launch_info {
                                 modgpu_feed_kernel_source_hash() for variant 4,
                                 modgpu_to_kernel_source_hash() for variant 5,
                                 modgpu_xfer_kernel_source_hash() for variant 6,
-                                modgpu_rekey_kernel_source_hash() for variant 7; static storage */
+                                modgpu_rekey_kernel_source_hash() for variant 7,
+                                modgpu_table_kernel_source_hash() for variant 8; static storage */
 } modgpu_launch_info_t;
 int modgpu_last_launch(modgpu_launch_info_t *out);
 
@@ -142,6 +148,8 @@ const char *modgpu_xfer_kernel_source_hash(void);
 /* The same for the rekey kernel's TU (cycle_rekey_kernel.hip, cycle_rekey_kernel.h, cycle_rekey_impl.h, cycle_kernel_impl.h,
  * cycle_kernel.h, lcg.h). */
 const char *modgpu_rekey_kernel_source_hash(void);
+/* The same for the table kernels' TU (cycle_table_kernel.hip, cycle_table_kernel.h, cycle_kernel_impl.h, cycle_kernel.h, lcg.h). */
+const char *modgpu_table_kernel_source_hash(void);
 
 /* 1 in libmodgpu_testing.so, 0 in libmodgpu.so. */
 int modgpu_testing_hooks(void);
@@ -161,6 +169,10 @@ void modgpu_debug_set_to_form(int form);
 /* The rekey kernel's launch shape: 0 = the out-of-place kernel's grid (25 workgroups per 32 CUs, 200 on MI355X), 1 = one workgroup
  * per CU on every CU, -1 = the shipped shape.  Measurement (tools/bench_rekey.py) and parity tests of both. */
 void modgpu_debug_set_rekey_form(int shape);
+
+/* The table call's stream launch: `grid` workgroups (1..4096), 0 = the shipped grid (the out-of-place kernel's, 25 per 32 CUs).
+ * Measurement (tools/bench_table.py). */
+void modgpu_debug_set_table_grid(uint32_t grid);
 
 /* How the transfer calls (modgpu_cycle_host_to_device & co.) move their bytes: 0 = the transfer kernels (shipped), 1 = the DMA
  * reference form -- per chunk a hipMemcpyAsync into a device slot and an out-of-place launch from there (upload), or an out-of-place

@@ -71,7 +71,21 @@ EXPORTS = {
     "modgpu_cycle_device_to_host": (_int, [_vp, _vp, _u64, _i32, _u64, _int]),
     "modgpu_cycle_file_to_device": (_int, [ctypes.c_char_p, _u64, _vp, _u64, _i32, _u64, _int]),
     "modgpu_cycle_device_to_file": (_int, [_vp, _u64, ctypes.c_char_p, _i32, _u64, _int]),
+    "modgpu_table_workspace_bytes": (_u64, [_u64]),
+    "modgpu_cycle_table_device": (_int, [_vp, _u64, _vp, _u64, _int, _vp]),
+    "modgpu_table_status": (_int, [_vp, _int, ctypes.POINTER(_u64)]),
+    "modgpu_table_validate": (_int, [_vp, _u64]),
 }
+
+
+class TableEntry(ctypes.Structure):
+    """modgpu_table_entry_t (include/modgpu.h): 40 bytes."""
+    _fields_ = [("dst", _vp), ("src", _vp), ("n", _u64), ("stream_off", _u64), ("key", _i32), ("flags", ctypes.c_uint32)]
+
+
+# the same layout as a numpy structured dtype: a table built with numpy is the bytes the device reads
+TABLE_DTYPE = np.dtype([("dst", "<u8"), ("src", "<u8"), ("n", "<u8"), ("stream_off", "<u8"), ("key", "<i4"), ("flags", "<u4")])
+assert TABLE_DTYPE.itemsize == ctypes.sizeof(TableEntry) == 40
 
 
 class PathStats(ctypes.Structure):
@@ -120,6 +134,8 @@ TESTING_EXPORTS = {
     "modgpu_xfer_kernel_source_hash": (ctypes.c_char_p, []),
     "modgpu_time_rekey_device_to": (_int, [_vp, _vp, _u64, _i32, _u64, _i32, _u64, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
     "modgpu_rekey_kernel_source_hash": (ctypes.c_char_p, []),
+    "modgpu_time_cycle_table_device": (_int, [_vp, _u64, _vp, _u64, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
+    "modgpu_table_kernel_source_hash": (ctypes.c_char_p, []),
 }
 # include/modgpu_testing.h, modgpu_debug_* group: ONLY in libmodgpu_testing.so
 DEBUG_EXPORTS = {
@@ -140,6 +156,7 @@ DEBUG_EXPORTS = {
     "modgpu_debug_set_to_form": (None, [_int]),
     "modgpu_debug_set_xfer_form": (None, [_int]),
     "modgpu_debug_set_rekey_form": (None, [_int]),
+    "modgpu_debug_set_table_grid": (None, [ctypes.c_uint32]),
 }
 
 
@@ -649,6 +666,92 @@ def debug_set_rekey_form(form=None):
     """Testing flavour: the rekey kernel's launch shape ("queue" = the out-of-place kernel's 200 workgroups, "all" = one per CU,
     None = shipped)."""
     _debug_lib().modgpu_debug_set_rekey_form(REKEY_FORMS[form])
+
+
+def table(n):
+    """an all-zero host table of n entries (TABLE_DTYPE): fill dst, src, n, stream_off, key; flags stay 0"""
+    return np.zeros(n, dtype=TABLE_DTYPE)
+
+
+def table_workspace_bytes(n_entries):
+    """bytes of device workspace a table call over n_entries needs (0 for none, or above the limit)"""
+    return lib().modgpu_table_workspace_bytes(n_entries)
+
+
+def table_validate(entries):
+    """the overlap / pointer / flags rules over a host table (TABLE_DTYPE array); raises ModGpuError naming an entry at fault"""
+    t = np.ascontiguousarray(entries, dtype=TABLE_DTYPE)
+    _check(lib().modgpu_table_validate(_vp(t.ctypes.data if t.size else 0), t.size))
+
+
+def table_status(workspace, device=-1):
+    """None if the last table call on `workspace` (a DeviceBuffer or address) ran clean, else the lowest entry the device refused
+    (that call wrote nothing).  Synchronise the call's stream first."""
+    out = _u64(0)
+    rc = lib().modgpu_table_status(_vp(_dev_addr(workspace)), device, ctypes.byref(out))
+    if rc == 1 and out.value != (1 << 64) - 1:
+        return int(out.value)
+    _check(rc)
+    return None
+
+
+def cycle_table_device(entries, workspace=None, device=-1, stream=None, check=True, *, n=None):
+    """Cycles a TABLE of out-of-place entries -- dst_i[j] = src_i[j] ^ ks(key_i)[stream_off_i + j] -- in three launches, whatever its
+    length.  `entries` is a host table (a TABLE_DTYPE array: uploaded, and checked with table_validate first unless check=False) or a
+    table already in device memory (a DeviceBuffer or an address; then n, the entry count, is needed).  `workspace` is a DeviceBuffer
+    or address of at least table_workspace_bytes(n) bytes; None makes one.  When this function made a buffer itself (an uploaded
+    table, a workspace) it waits for the call before freeing it and raises ModGpuError if the device refused an entry; otherwise the
+    call is asynchronous on `stream` and table_status(workspace) tells the outcome after a synchronise."""
+    own = []
+    try:
+        if isinstance(entries, np.ndarray):
+            t = np.ascontiguousarray(entries, dtype=TABLE_DTYPE)
+            n = t.size
+            if check:
+                table_validate(t)
+            if n == 0:
+                return
+            buf = DeviceBuffer(t.nbytes, device)
+            own.append(buf)
+            buf.upload(t.view(np.uint8))
+            addr = buf.ptr
+        else:
+            if n is None:
+                raise TypeError("n (the entry count) is needed for a table in device memory")
+            addr = _dev_addr(entries)
+        if workspace is None and n:
+            workspace = DeviceBuffer(table_workspace_bytes(n), device)
+            own.append(workspace)
+        ws = _dev_addr(workspace) if workspace is not None else 0
+        ws_bytes = workspace.nbytes if isinstance(workspace, DeviceBuffer) else table_workspace_bytes(n)
+        _check(lib().modgpu_cycle_table_device(_vp(addr), n, _vp(ws), ws_bytes, device, _vp(stream or 0)))
+        if own:
+            _check(lib().modgpu_sync(device, _vp(stream or 0)))
+            bad = table_status(ws, device)
+            if bad is not None:
+                raise ModGpuError(1, f"the device refused table entry {bad}; nothing was written")
+    finally:
+        for b in own:
+            b.free()
+
+
+def time_cycle_table_device(entries, n, workspace, device=-1, stream=None, iters=2):
+    """Mean ms per table call (three launches) over `iters` calls, HIP events on the launch stream; table and workspace resident."""
+    ms = ctypes.c_float(0)
+    ws_bytes = workspace.nbytes if isinstance(workspace, DeviceBuffer) else table_workspace_bytes(n)
+    _check(lib().modgpu_time_cycle_table_device(_vp(_dev_addr(entries)), n, _vp(_dev_addr(workspace)), ws_bytes, device, _vp(stream or 0),
+                                                iters, ctypes.byref(ms)))
+    return ms.value
+
+
+def table_kernel_source_hash():
+    """identity of the table kernels' TU (cycle_table_kernel.hip and what it includes)"""
+    return lib().modgpu_table_kernel_source_hash().decode()
+
+
+def debug_set_table_grid(grid=0):
+    """Testing flavour: the table call's stream grid (0 = shipped)."""
+    _debug_lib().modgpu_debug_set_table_grid(grid)
 
 
 def _dev_addr(x):

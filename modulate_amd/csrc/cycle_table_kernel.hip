@@ -1,0 +1,401 @@
+// cycle_table_kernel.hip -- a TABLE of out-of-place entries that lives in device memory, any number of them, in three launches:
+// dst_i[j] = src_i[j] ^ ks(key_i)[off_i + j].  Device code of the arithmetic, the jump tables and the keystream block:
+// cycle_kernel_impl.h, included and not changed (its hash is modgpu_kernel_source_hash; this TU has its own).
+//
+//   plan    one thread per entry: reads the entry where the caller left it (when the launch RUNS, not when it is queued), checks it
+//           (a NULL pointer with bytes to move, nonzero flags, a body beyond the chunk jump tables), lays it on the chunk grid of its
+//           destination, computes its three base states on the device (key * a^(off+1) by four byte tables), and scans the chunk
+//           counts of its 1024 entries in LDS.  Workgroup 0 resets the workspace's ticket counter and status: every call starts
+//           clean in stream order, with no memset on any other stream.
+//   finish  one thread per entry again: every workgroup adds up the chunk counts of the 1024-entry records before its own (and of
+//           all of them: the total), so the entries' starts are global without a third scan pass; then either the call is refused
+//           -- a bad entry anywhere, or more chunks than 32-bit tickets hand out -- and nothing at all is written (the lowest bad
+//           index goes to the status), or each entry's start goes into the search levels and its < 16 ragged bytes at either end
+//           are cycled bytewise.
+//   stream  the out-of-place kernel's shape (cycle_to_kernel.hip): persistent 1024-thread workgroups, 64 KiB chunks on absolute
+//           chunk-aligned DESTINATION addresses handed out by a ticket counter (in the workspace) with a static prefix of two, a
+//           ping-pong load pipeline, workgroup-synchronous bursts, nt loads and nt sc1 stores.  What differs: an entry's cut first
+//           chunk is an ordinary ticket (its lanes in front of the body wrap past num_records), so small entries spread over the
+//           chip like large ones; the v_alignbyte_b32 funnel is chosen per chunk (a uniform branch on the source's phase); a
+//           chunk of an identity-key entry is copied; and a chunk's entry is FOUND rather than walked to.
+//
+// Finding a chunk's entry.  The table may be 100 000 entries long, so the stream launch cannot walk it.  The finish launch writes the
+// entries' chunk starts as a 16-ary search structure -- level k holds the start of every 16^k-th entry, padded with ~0 to whole lines
+// of 16 -- and a workgroup descends it with one s_load_dwordx16 per level (2 for 17 entries, 5 for 100 000), then loads the entry's
+// CycleTablePlan with one more.  All of it is scalar memory: lgkmcnt, not vmcnt, so the descent for the chunk about to be loaded never
+// waits for the loads still in flight for the chunk being computed (a vector-memory search would, and the pipeline would collapse to
+// one chunk in flight).  Each workgroup keeps the views of the two chunks in its pipeline; a chunk inside one of them needs no search.
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+#include "cycle_kernel_impl.h"
+#include "cycle_table_kernel.h"
+
+#include <cstdio>
+
+namespace {
+
+// a^(b * 256^k) for the four bytes of an exponent < 2^32: a^e by three multiplies
+__constant__ lcg::Table<256> c_pow_b0 = lcg::make_pow_table<256>(1);
+__constant__ lcg::Table<256> c_pow_b1 = lcg::make_pow_table<256>(256);
+__constant__ lcg::Table<256> c_pow_b2 = lcg::make_pow_table<256>(65536);
+__constant__ lcg::Table<256> c_pow_b3 = lcg::make_pow_table<256>(1u << 24);
+
+__device__ __forceinline__ uint32_t pow_a(uint32_t e)
+{
+    uint32_t p = mulmod_canon(c_pow_b0.v[e & 255], c_pow_b1.v[(e >> 8) & 255]);
+    p = mulmod_canon(p, c_pow_b2.v[(e >> 16) & 255]);
+    return mulmod_canon(p, c_pow_b3.v[e >> 24]);
+}
+
+// reads of memory no launch of this TU writes while it runs: scalar loads when the address is uniform (address space 4; the host pass
+// of the compiler only needs the types)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define TABLE_CONST_AS __attribute__((address_space(4)))
+#else
+#define TABLE_CONST_AS
+#endif
+template <class T> __device__ __forceinline__ const TABLE_CONST_AS T *as_const(const T *p) { return (const TABLE_CONST_AS T *)p; }
+struct Keys16 {
+    uint32_t v[16];
+};
+
+constexpr uint32_t kChunk = 65536; // the stream kernel's chunk: 4 words x 1024 threads x 16 bytes
+
+} // namespace
+
+// ---- plan: one thread per entry ----------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kTableBlock) void modgpu_cycle_table_plan(CycleTableArgs a)
+{
+    __shared__ uint64_t sc[kTableBlock];
+    __shared__ uint32_t sbad;
+    const uint32_t tid = threadIdx.x;
+    const uint64_t i = (uint64_t)blockIdx.x * kTableBlock + tid;
+    if (blockIdx.x == 0 && tid == 0) {
+        a.hdr->ticket = 0;
+        a.hdr->first_bad = kTableNoBad;
+        a.hdr->total = 0;
+    }
+    if (tid == 0) sbad = 0;
+    uint64_t cnt = 0;
+    uint32_t bad = 0;
+    if (i < a.n) {
+        const CycleTableEntry E = a.entries[i];
+        const uintptr_t d = reinterpret_cast<uintptr_t>(E.dst);
+        const uint64_t head = E.n < ((16 - (d & 15)) & 15) ? E.n : ((16 - (d & 15)) & 15);
+        const uint64_t words = (E.n - head) / 16;
+        const uint64_t tail = E.n - head - words * 16;
+        const uint32_t lead = (uint32_t)((d + head) & (kChunk - 1));
+        const uint64_t end = lead + words * 16;
+        cnt = words ? (end + kChunk - 1) / kChunk : 0;
+        bad = (E.n && (!E.dst || !E.src)) || E.flags != 0 || cnt > kTableMaxEntryChunks ? 1u : 0u;
+        if (bad) cnt = 0;
+        // states: key * a^(o + 1 + position), positions mod the period
+        const int64_t kr = (int64_t)E.key % (int64_t)lcg::M;
+        const uint32_t k = (uint32_t)(kr < 0 ? kr + lcg::M : kr);
+        const uint64_t o1 = E.stream_off % lcg::PERIOD + 1;
+        CycleTablePlan P;
+        P.dst_origin = reinterpret_cast<uint8_t *>(reinterpret_cast<uintptr_t>(E.dst) + head - lead); // (as integers: a refused entry's pointer may be NULL)
+        P.src_origin = reinterpret_cast<const uint8_t *>(reinterpret_cast<uintptr_t>(E.src) + head - lead);
+        P.end = end;
+        P.start = 0;
+        P.lead = lead;
+        P.chunks = (uint32_t)cnt;
+        P.base_head = mulmod_canon(k, pow_a((uint32_t)(o1 % lcg::PERIOD)));
+        P.base = mulmod_canon(k, pow_a((uint32_t)((o1 + head + lcg::PERIOD - lead) % lcg::PERIOD)));
+        P.base_tail = mulmod_canon(k, pow_a((uint32_t)((o1 + head + (words * 16) % lcg::PERIOD) % lcg::PERIOD)));
+        P.bad = bad;
+        P.head_n = (uint32_t)head;
+        P.tail_n = (uint32_t)tail;
+        a.plan[i] = P;
+    }
+    sc[tid] = cnt;
+    __syncthreads();
+    if (bad) atomicOr(&sbad, 1u);
+    // inclusive scan of the 1024 counts (Hillis-Steele; every thread reaches every barrier)
+    for (uint32_t s = 1; s < kTableBlock; s <<= 1) {
+        const uint64_t v = tid >= s ? sc[tid - s] : 0;
+        __syncthreads();
+        sc[tid] += v;
+        __syncthreads();
+    }
+    if (i < a.n) a.plan[i].start = sc[tid] - cnt;
+    if (tid == kTableBlock - 1) {
+        a.blk[blockIdx.x].chunks = sc[tid];
+        a.blk[blockIdx.x].bad = sbad;
+    }
+}
+
+// ---- finish: global starts, the status, the search levels, the ragged edges --------------------------------------------------------
+__global__ __launch_bounds__(kTableBlock) void modgpu_cycle_table_finish(CycleTableArgs a)
+{
+    __shared__ uint64_t r_before[kTableBlock], r_total[kTableBlock];
+    __shared__ uint32_t sbad;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t b = blockIdx.x;
+    const uint64_t i = (uint64_t)b * kTableBlock + tid;
+    if (tid == 0) sbad = 0;
+    uint64_t before = 0, total = 0;
+    uint32_t bad = 0;
+    for (uint32_t k = tid; k < a.n_blk; k += kTableBlock) {
+        const uint64_t c = a.blk[k].chunks;
+        total += c;
+        before += k < b ? c : 0;
+        bad |= a.blk[k].bad;
+    }
+    r_before[tid] = before;
+    r_total[tid] = total;
+    __syncthreads();
+    if (bad) atomicOr(&sbad, 1u);
+    for (uint32_t s = kTableBlock / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+            r_before[tid] += r_before[tid + s];
+            r_total[tid] += r_total[tid + s];
+        }
+        __syncthreads();
+    }
+    before = r_before[0];
+    total = r_total[0];
+    const bool ok = sbad == 0 && total <= kTableMaxChunks;
+    if (b == 0 && tid == 0) a.hdr->total = ok ? total : 0;
+    if (i < a.n) {
+        const CycleTablePlan P = a.plan[i];
+        const uint64_t start = before + P.start;
+        if (!ok) {
+            // refused: write nothing; the lowest bad entry -- a refused one, or the first whose chunks pass the ticket range
+            if (P.bad || start + P.chunks > kTableMaxChunks) atomicMin((unsigned long long *)&a.hdr->first_bad, (unsigned long long)i);
+        } else {
+            a.plan[i].start = start;
+            for (uint32_t k = 0; k < kTableLevels; ++k)
+                if (k <= a.top && (i & ((1ull << (4 * k)) - 1)) == 0) a.level[k][i >> (4 * k)] = (uint32_t)start;
+            // the < 16 bytes in front of the body and behind it: all loads first (dst may be src), then the stores
+            const uint8_t *sb = P.src_origin + P.lead;
+            uint8_t *db = P.dst_origin + P.lead;
+            const uint64_t body = P.end - P.lead;
+            uint8_t hb[15], tb[15];
+#pragma unroll
+            for (uint32_t j = 0; j < 15; ++j) {
+                if (j < P.head_n) hb[j] = sb[(int64_t)j - P.head_n];
+                if (j < P.tail_n) tb[j] = sb[body + j];
+            }
+            const bool copy = P.base_head == 0;
+#pragma unroll
+            for (uint32_t j = 0; j < 15; ++j) {
+                if (j < P.head_n) db[(int64_t)j - P.head_n] = copy ? hb[j] : cycle_byte(hb[j], mulmod_canon(P.base_head, c_pow_b0.v[j]));
+                if (j < P.tail_n) db[body + j] = copy ? tb[j] : cycle_byte(tb[j], mulmod_canon(P.base_tail, c_pow_b0.v[j]));
+            }
+        }
+    }
+    // each level padded with ~0 to a whole line of 16 keys: the descent reads 16 at a time
+    if (ok && b == 0 && tid < 16)
+        for (uint32_t k = 0; k < kTableLevels; ++k)
+            if (k <= a.top && a.level_n[k] + tid < ((a.level_n[k] + 15) & ~15ull)) a.level[k][a.level_n[k] + tid] = ~0u;
+}
+
+// ---- stream ------------------------------------------------------------------------------------------------------------------------
+namespace {
+struct Raw {
+    u32x4 d;
+    uint32_t e; // the dword after d, read when the chunk's source is not dword-aligned
+};
+__device__ __forceinline__ u32x4 funnel(const Raw &w, uint32_t sh) // sh == 0: alignbyte by 0 is the low dword itself
+{
+    u32x4 d;
+    d.x = __builtin_amdgcn_alignbyte(w.d.y, w.d.x, sh);
+    d.y = __builtin_amdgcn_alignbyte(w.d.z, w.d.y, sh);
+    d.z = __builtin_amdgcn_alignbyte(w.d.w, w.d.z, sh);
+    d.w = __builtin_amdgcn_alignbyte(w.e, w.d.w, sh);
+    return d;
+}
+} // namespace
+
+template <int U, int BLOCK>
+__global__ __launch_bounds__(BLOCK) MODGPU_KEEP_OFF_THE_FIXED_TEMPORARIES void modgpu_cycle_table_kernel(CycleTableArgs a)
+{
+    static_assert(BLOCK % 256 == 0 && BLOCK <= 1024, "BLOCK is a whole number of 4096-byte tiles");
+    constexpr int ALG = 2;
+    constexpr int SAUX = AUX_SC1 | AUX_NT;
+    constexpr int DEPTH = 1;
+    constexpr uint32_t CHUNK = (uint32_t)U * BLOCK * lcg::WORD;
+    static_assert(CHUNK == kChunk, "the plan lays entries on this chunk grid");
+    constexpr uint32_t SUB = BLOCK * lcg::WORD;
+    constexpr int NB = DEPTH + 1;
+    constexpr int PREFIX = DEPTH + 1;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t blk = blockIdx.x;
+    const uint32_t G = gridDim.x;
+    const uint32_t total = (uint32_t)*as_const(&a.hdr->total); // 0 when the finish launch refused the call
+    __shared__ uint32_t q_next[2];
+    uint32_t trip = 0;
+    const uint32_t voff = tid * lcg::WORD;
+    const uint32_t lane_mul = mulmod_canon(c_tile_lo.v[tid >> 8], c_lane_pow.v[tid & 255]);
+
+    struct View {
+        uint8_t *dst0;       // the entry's chunk origin
+        const uint8_t *src0; // the source byte that pairs with it
+        uint64_t end;
+        uint32_t lead, lo, hi; // global chunks [lo, hi) are the entry's chunks 0 .. hi - lo - 1
+        uint32_t base;         // 0: a copy
+        uint32_t lane_base;    // per lane: state of this lane's word 0 in the entry's chunk 0
+    };
+    auto in = [](uint32_t g, const View &v) { return g - v.lo < v.hi - v.lo; };
+    // the entry of chunk g < total: the last entry whose start is <= g, by a 16-ary descent of the levels
+    auto search = [&](uint32_t g, View &v) {
+        uint32_t j = 0;
+#pragma unroll 1
+        for (int k = (int)a.top; k >= 0; --k) {
+            const Keys16 keys = *as_const(reinterpret_cast<const Keys16 *>(a.level[k] + 16u * j));
+            uint32_t c = 0;
+#pragma unroll
+            for (int t = 0; t < 16; ++t) c += keys.v[t] <= g ? 1u : 0u;
+            j = 16u * j + c - 1u;
+        }
+        const CycleTablePlan P = *as_const(a.plan + j);
+        v.dst0 = P.dst_origin;
+        v.src0 = P.src_origin;
+        v.end = P.end;
+        v.lead = P.lead;
+        v.lo = (uint32_t)P.start;
+        v.hi = (uint32_t)P.start + P.chunks;
+        v.base = P.base;
+        v.lane_base = mulmod_canon(P.base, lane_mul);
+    };
+    // where chunk g lies: offset of its chunk from the entry's origin, the cut in front of the body (chunk 0 only), its bytes
+    struct Span {
+        uint64_t off;
+        uint32_t cut, bytes;
+    };
+    auto span = [&](uint32_t g, const View &v) {
+        Span s{0, 0, 0};
+        if (g >= total) return s; // past the last entry: zero-size descriptors, loads give 0, stores drop
+        const uint32_t c = g - v.lo;
+        s.off = (uint64_t)c * CHUNK;
+        s.cut = c ? 0u : v.lead;
+        const uint64_t lim = v.end < s.off + CHUNK ? v.end : s.off + CHUNK;
+        s.bytes = (uint32_t)(lim - s.off - s.cut);
+        return s;
+    };
+    View vb[NB];
+#pragma unroll
+    for (int i = 0; i < NB; ++i) vb[i] = View{nullptr, nullptr, 0, 0, 0, 0, 0, 1};
+    // chunk g into buffer q; vb[r] is the view of the chunk loaded before it
+    auto load = [&](Raw(&w)[U], View &v, const View &prev, uint32_t g) {
+        if (g < total && !in(g, v)) {
+            if (in(g, prev)) v = prev;
+            else search(g, v);
+        }
+        const Span s = span(g, v);
+        const uint8_t *p = v.src0 + s.off + s.cut;
+        const uint32_t sh = (uint32_t)(uintptr_t)p & 3u;
+        // the extra dword of the last word is the aligned dword that holds the body's last source byte: num_records grows by 4
+        const auto r = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(p - sh), 0, (int)(s.bytes + (sh && s.bytes ? 4u : 0u)), 0x00020000);
+#pragma unroll
+        for (int u = 0; u < U; ++u) w[u].d = __builtin_amdgcn_raw_buffer_load_b128(r, voff + u * SUB - s.cut, 0, AUX_NT);
+        if (sh) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) w[u].e = __builtin_amdgcn_raw_buffer_load_b32(r, voff + u * SUB - s.cut + lcg::WORD, 0, AUX_NT);
+        }
+    };
+    uint32_t pending = 0;
+    const uint32_t q_next_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)&q_next[0];
+    const uint32_t one = 1u;
+    auto process_store = [&](Raw(&w)[U], const View &v, uint32_t g) {
+        const Span s = span(g, v);
+        const uint32_t sh = (uint32_t)(uintptr_t)(v.src0 + s.off + s.cut) & 3u;
+        auto r = __builtin_amdgcn_make_buffer_rsrc(v.dst0 + s.off + s.cut, 0, (int)s.bytes, 0x00020000);
+        u32x4 d[U];
+        if (v.base != 0) {
+            const uint32_t c = g - v.lo;
+            uint32_t p = mulmod_canon(c_chunk_pow0<CHUNK>.v[c & 255], c_chunk_pow1<CHUNK>.v[(c >> 8) & 255]);
+            p = mulmod_canon(p, c_chunk_pow2<CHUNK>.v[(c >> 16) & 255]);
+            uint32_t st = mulmod_canon(v.lane_base, p);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                d[u] = cycle_word<ALG>(funnel(w[u], sh), st);
+                st = mulmod_canon(st, lcg::kTileLo.v[BLOCK / 256]);
+            }
+        } else {
+#pragma unroll
+            for (int u = 0; u < U; ++u) d[u] = funnel(w[u], sh);
+        }
+        if (tid == 0)
+            asm volatile("ds_write_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : : "v"(q_next_lds + 4u * (trip & 1u)), "v"(pending) : "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+#pragma unroll
+        for (int u = 0; u < U; ++u) __builtin_amdgcn_raw_buffer_store_b128(d[u], r, voff + u * SUB - s.cut, 0, SAUX);
+        ++trip;
+    };
+    auto take_published = [&]() {
+        uint32_t t;
+        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(t) : "v"(q_next_lds + 4u * ((trip - 1u) & 1u)) : "memory");
+        return (uint32_t)PREFIX * G + (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
+    };
+
+    uint32_t cq[NB];
+    static_assert(PREFIX == NB, "the static positions are exactly the ones cq[] starts with");
+#pragma unroll
+    for (int i = 0; i < NB; ++i) cq[i] = blk + (uint32_t)i * G;
+    if (cq[0] < total) {
+        Raw w[NB][U];
+#pragma unroll
+        for (int i = 0; i < DEPTH; ++i) load(w[i], vb[i], vb[(i + NB - 1) % NB], cq[i]);
+        bool finished = false;
+        while (!finished) {
+#pragma unroll
+            for (int p = 0; p < NB; ++p) {
+                __builtin_amdgcn_s_barrier();
+                if (tid == 0) pending = __hip_atomic_fetch_add(&a.hdr->ticket, one, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                load(w[(p + DEPTH) % NB], vb[(p + DEPTH) % NB], vb[p], cq[DEPTH]);
+                __builtin_amdgcn_sched_barrier(0);
+                process_store(w[p], vb[p], cq[0]);
+#pragma unroll
+                for (int i = 0; i < DEPTH; ++i) cq[i] = cq[i + 1];
+                cq[DEPTH] = take_published();
+                if (cq[0] >= total) {
+                    finished = true;
+                    break;
+                }
+            }
+        }
+    }
+}
+
+namespace {
+template <int U, int BLOCK> struct TableShape {
+    static constexpr uint32_t chunk = (uint32_t)U * BLOCK * lcg::WORD;
+    static constexpr uint32_t block = BLOCK;
+    static void launch(const CycleTableArgs &a, uint32_t grid, hipStream_t stream)
+    {
+        hipLaunchKernelGGL((modgpu_cycle_table_kernel<U, BLOCK>), dim3(grid), dim3(BLOCK), 0, stream, a);
+    }
+    static const char *name() // as a profiler prints it
+    {
+        static char buf[96];
+        static const int n = std::snprintf(buf, sizeof buf, "modgpu_cycle_table_kernel<%d, %d>", U, BLOCK);
+        (void)n;
+        return buf;
+    }
+};
+using TableStream = TableShape<4, 1024>; // the work-queue kernel's measured shape: 64 KiB chunks
+static_assert(TableStream::chunk == kChunk, "one chunk size for the plan and the stream");
+} // namespace
+
+uint32_t modgpu_table_chunk_bytes() { return TableStream::chunk; }
+uint32_t modgpu_table_block() { return TableStream::block; }
+const char *modgpu_table_kernel_name() { return TableStream::name(); }
+hipError_t modgpu_launch_table_plan(const CycleTableArgs &a, hipStream_t stream)
+{
+    hipLaunchKernelGGL(modgpu_cycle_table_plan, dim3(a.n_blk), dim3(kTableBlock), 0, stream, a);
+    return hipGetLastError();
+}
+hipError_t modgpu_launch_table_finish(const CycleTableArgs &a, hipStream_t stream)
+{
+    hipLaunchKernelGGL(modgpu_cycle_table_finish, dim3(a.n_blk), dim3(kTableBlock), 0, stream, a);
+    return hipGetLastError();
+}
+hipError_t modgpu_launch_table_stream(const CycleTableArgs &a, uint32_t grid, hipStream_t stream)
+{
+    TableStream::launch(a, grid, stream);
+    return hipGetLastError();
+}

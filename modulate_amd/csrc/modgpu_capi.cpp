@@ -20,6 +20,7 @@
 #include "cycle_feed_kernel.h"
 #include "cycle_kernel.h"
 #include "cycle_rekey_kernel.h"
+#include "cycle_table_kernel.h"
 #include "cycle_to_kernel.h"
 #include "cycle_xfer_kernel.h"
 #include "lcg.h"
@@ -1061,6 +1062,153 @@ void store_le32(uint8_t *p, uint32_t v)
 }
 
 } // namespace
+// ---- a table of out-of-place entries in device memory (modgpu_cycle_table_device) --------------------------------------------------
+namespace {
+static_assert(sizeof(modgpu_table_entry_t) == sizeof(CycleTableEntry) && offsetof(modgpu_table_entry_t, key) == offsetof(CycleTableEntry, key) &&
+                  offsetof(modgpu_table_entry_t, flags) == offsetof(CycleTableEntry, flags),
+              "the kernels read the public entry layout");
+static_assert(MODGPU_TABLE_MAX_ENTRIES == kTableMaxEntries, "one limit");
+
+// Where everything of a call over n entries lies in its workspace (offsets from its start, each section on a 64-byte line): the header,
+// the 1024-entry records, the plan records, then the search levels -- level k holds ceil(n / 16^k) keys padded to a multiple of 16,
+// up to the first level of at most 16 keys (the top).
+struct TableLayout {
+    uint64_t blk, plan, level[kTableLevels], level_n[kTableLevels], bytes;
+    uint32_t top, n_blk;
+};
+TableLayout table_layout(uint64_t n)
+{
+    TableLayout L{};
+    auto line = [](uint64_t x) { return (x + 63) & ~63ull; };
+    L.n_blk = (uint32_t)((n + kTableBlock - 1) / kTableBlock);
+    uint64_t at = sizeof(CycleTableHdr);
+    L.blk = at;
+    at = line(at + (uint64_t)L.n_blk * sizeof(CycleTableBlk));
+    L.plan = at;
+    at = line(at + n * sizeof(CycleTablePlan));
+    uint64_t cnt = n;
+    for (uint32_t k = 0; k < (uint32_t)kTableLevels; ++k) {
+        L.level[k] = at;
+        L.level_n[k] = cnt;
+        L.top = k;
+        at = line(at + ((cnt + 15) & ~15ull) * sizeof(uint32_t));
+        if (cnt <= 16) break;
+        cnt = (cnt + 15) / 16;
+    }
+    L.bytes = at;
+    return L;
+}
+
+// The stream launch's grid: the out-of-place kernel's (25 workgroups per 32 CUs; DESIGN.md 4.8 has the A/B against one per CU)
+#ifdef MODGPU_TESTING_HOOKS
+std::atomic<uint32_t> g_table_grid{0}; // modgpu_debug_set_table_grid
+uint32_t table_grid_forced() { return g_table_grid.load(std::memory_order_relaxed); }
+#else
+constexpr uint32_t table_grid_forced() { return 0; }
+#endif
+
+// Tier 1 (include/modgpu.h): everything checked before anything is queued; then the three launches on `stream`.
+int table_impl(const modgpu_table_entry_t *entries, uint64_t n, void *ws, uint64_t ws_bytes, int device, hipStream_t stream)
+{
+    if (n == 0) return MODGPU_OK;
+    if (n > kTableMaxEntries) return fail(MODGPU_ERR_INVALID, "more than 4194304 entries (the table call's limit)");
+    if (!entries || !ws) return fail(MODGPU_ERR_INVALID, "null table or workspace");
+    if ((reinterpret_cast<uintptr_t>(entries) | reinterpret_cast<uintptr_t>(ws)) & 7) return fail(MODGPU_ERR_INVALID, "table or workspace not 8-byte aligned");
+    const TableLayout L = table_layout(n);
+    if (ws_bytes < L.bytes) return fail(MODGPU_ERR_INVALID, "workspace smaller than modgpu_table_workspace_bytes(n_entries)");
+    DeviceScope scope(device);
+    if (scope.rc) return scope.rc;
+    int phys = -1;
+    HIP_TRY(hipGetDevice(&phys));
+    if (modgpu_xfer_device_of(entries, n * sizeof(modgpu_table_entry_t)) != phys || modgpu_xfer_device_of(ws, L.bytes) != phys)
+        return fail(MODGPU_ERR_INVALID, "the table or the workspace is not device memory of the call's device");
+    uint8_t *const w = static_cast<uint8_t *>(ws);
+    CycleTableArgs a{};
+    a.entries = reinterpret_cast<const CycleTableEntry *>(entries);
+    a.n = n;
+    a.hdr = reinterpret_cast<CycleTableHdr *>(w);
+    a.blk = reinterpret_cast<CycleTableBlk *>(w + L.blk);
+    a.plan = reinterpret_cast<CycleTablePlan *>(w + L.plan);
+    for (uint32_t k = 0; k <= L.top; ++k) {
+        a.level[k] = reinterpret_cast<uint32_t *>(w + L.level[k]);
+        a.level_n[k] = L.level_n[k];
+    }
+    a.top = L.top;
+    a.n_blk = L.n_blk;
+    uint64_t cap = 0, helpers = 0;
+    queue_grid(0, large_grid(), &cap, &helpers);
+    if (table_grid_forced()) cap = table_grid_forced();
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, cap);
+    (void)hipGetLastError(); // (the launches report hipGetLastError: an earlier call's error must not be taken for theirs)
+    hipError_t e = modgpu_launch_table_plan(a, stream);
+    if (e != hipSuccess) return fail_hip(e, "table plan launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    e = modgpu_launch_table_finish(a, stream);
+    if (e != hipSuccess) return fail_hip(e, "table finish launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    e = modgpu_launch_table_stream(a, grid, stream);
+    if (e != hipSuccess) return fail_hip(e, "table stream launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    t_last_launch = {modgpu_table_kernel_name(), CYCLE_TABLE, grid, modgpu_table_block(), modgpu_table_chunk_bytes(), 0, grid, MODGPU_TABLE_KERNEL_SOURCE_HASH};
+    return MODGPU_OK;
+}
+
+// The overlap rule of modgpu_cycle_batch_device_to over a host copy, in O(n log n): destinations sorted by start must not meet each
+// other (a running maximum of ends), and a destination must not meet the source of another entry -- among the sources that start
+// before it ends, the one reaching furthest, or the furthest of another entry when that one is its own.
+int table_validate_impl(const modgpu_table_entry_t *t, uint64_t n)
+{
+    if (n > kTableMaxEntries) return fail(MODGPU_ERR_INVALID, "more than 4194304 entries (the table call's limit)");
+    if (n && !t) return fail(MODGPU_ERR_INVALID, "null table");
+    auto at = [](const void *p) { return (uint64_t)reinterpret_cast<uintptr_t>(p); };
+    auto entry = [](uint64_t i, const char *what) { return fail(MODGPU_ERR_INVALID, "entry " + std::to_string(i) + ": " + what); };
+    struct Range {
+        uint64_t lo, hi, i;
+    };
+    std::vector<Range> d, s;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (t[i].flags) return entry(i, "nonzero flags");
+        if (!t[i].n) continue;
+        if (!t[i].dst || !t[i].src) return entry(i, "null buffer");
+        const uint64_t dl = at(t[i].dst), sl = at(t[i].src);
+        if (dl + t[i].n < dl || sl + t[i].n < sl) return entry(i, "range wraps the address space");
+        if (dl != sl && dl < sl + t[i].n && sl < dl + t[i].n) return entry(i, "destination partly overlaps its source (only dst == src may alias)");
+        d.push_back({dl, dl + t[i].n, i});
+        s.push_back({sl, sl + t[i].n, i});
+    }
+    auto by_lo = [](const Range &x, const Range &y) { return x.lo < y.lo || (x.lo == y.lo && x.i < y.i); };
+    std::sort(d.begin(), d.end(), by_lo);
+    std::sort(s.begin(), s.end(), by_lo);
+    uint64_t bad = UINT64_MAX;
+    for (size_t k = 1, far = 0; k < d.size(); ++k) {
+        if (d[k].lo < d[far].hi) bad = std::min(bad, std::min(d[k].i, d[far].i));
+        if (d[k].hi > d[far].hi) far = k;
+    }
+    // prefix over the sources by start: the furthest end (and its entry) and the furthest end of any OTHER entry
+    std::vector<uint64_t> end1(s.size()), id1(s.size()), end2(s.size());
+    for (size_t k = 0; k < s.size(); ++k) {
+        uint64_t e1 = k ? end1[k - 1] : 0, i1 = k ? id1[k - 1] : UINT64_MAX, e2 = k ? end2[k - 1] : 0;
+        if (s[k].hi > e1) {
+            if (s[k].i != i1) e2 = e1;
+            e1 = s[k].hi;
+            i1 = s[k].i;
+        } else if (s[k].i != i1 && s[k].hi > e2) {
+            e2 = s[k].hi;
+        }
+        end1[k] = e1;
+        id1[k] = i1;
+        end2[k] = e2;
+    }
+    for (const Range &r : d) {
+        const size_t c = std::lower_bound(s.begin(), s.end(), r.hi, [](const Range &x, uint64_t v) { return x.lo < v; }) - s.begin();
+        if (!c) continue;
+        if ((id1[c - 1] != r.i && end1[c - 1] > r.lo) || end2[c - 1] > r.lo) bad = std::min(bad, r.i);
+    }
+    if (bad != UINT64_MAX) return entry(bad, "destination meets another entry's source or destination");
+    return MODGPU_OK;
+}
+} // namespace
+
 } // namespace modgpu
 
 using namespace modgpu;
@@ -1137,6 +1285,43 @@ int modgpu_rekey_batch_device_to(void *const *dst_parts, const void *const *src_
         if (scope.rc) return scope.rc;
         return rekey_impl(dst_parts, src_parts, sizes, offs_from, offs_to, n_parts, key_from, key_to, static_cast<hipStream_t>(hip_stream));
     });
+}
+
+uint64_t modgpu_table_workspace_bytes(uint64_t n_entries)
+{
+    return n_entries == 0 || n_entries > kTableMaxEntries ? 0 : table_layout(n_entries).bytes;
+}
+
+int modgpu_cycle_table_device(const modgpu_table_entry_t *dev_entries, uint64_t n_entries, void *dev_workspace, uint64_t workspace_bytes,
+                              int device, void *hip_stream)
+{
+    return guarded([&]() -> int {
+        return table_impl(dev_entries, n_entries, dev_workspace, workspace_bytes, device, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int modgpu_table_status(const void *dev_workspace, int device, uint64_t *first_bad_entry)
+{
+    return guarded([&]() -> int {
+        if (!dev_workspace || !first_bad_entry) return fail(MODGPU_ERR_INVALID, "null workspace or out pointer");
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        int phys = -1;
+        HIP_TRY(hipGetDevice(&phys));
+        if (modgpu_xfer_device_of(dev_workspace, sizeof(CycleTableHdr)) != phys)
+            return fail(MODGPU_ERR_INVALID, "the workspace is not device memory of the call's device");
+        CycleTableHdr h;
+        HIP_TRY(hipMemcpy(&h, dev_workspace, sizeof h, hipMemcpyDeviceToHost));
+        *first_bad_entry = h.first_bad;
+        if (h.first_bad != kTableNoBad)
+            return fail(MODGPU_ERR_INVALID, "the device refused entry " + std::to_string(h.first_bad) + " (the call wrote nothing)");
+        return MODGPU_OK;
+    });
+}
+
+int modgpu_table_validate(const modgpu_table_entry_t *host_entries, uint64_t n_entries)
+{
+    return guarded([&]() -> int { return table_validate_impl(host_entries, n_entries); });
 }
 
 int modgpu_cycle_host(uint8_t *host_buf, uint64_t n, int32_t key, uint64_t stream_off, int device)
@@ -1840,6 +2025,34 @@ const char *modgpu_feed_kernel_source_hash(void) { return MODGPU_FEED_KERNEL_SOU
 const char *modgpu_to_kernel_source_hash(void) { return MODGPU_TO_KERNEL_SOURCE_HASH; }
 const char *modgpu_xfer_kernel_source_hash(void) { return MODGPU_XFER_KERNEL_SOURCE_HASH; }
 const char *modgpu_rekey_kernel_source_hash(void) { return MODGPU_REKEY_KERNEL_SOURCE_HASH; }
+const char *modgpu_table_kernel_source_hash(void) { return MODGPU_TABLE_KERNEL_SOURCE_HASH; }
+
+int modgpu_time_cycle_table_device(const void *dev_entries, uint64_t n_entries, void *dev_workspace, uint64_t workspace_bytes,
+                                   int device, void *hip_stream, int iters, float *ms_per_call)
+{
+    return guarded([&]() -> int {
+        if (iters <= 0 || !ms_per_call) return fail(MODGPU_ERR_INVALID, "bad timing arguments");
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        int rc = MODGPU_OK;
+        hipStream_t st = static_cast<hipStream_t>(hip_stream);
+        hipEvent_t e0, e1;
+        HIP_TRY(hipEventCreate(&e0));
+        HIP_TRY(hipEventCreate(&e1));
+        HIP_TRY(hipEventRecord(e0, st));
+        for (int i = 0; i < iters && rc == MODGPU_OK; ++i) rc = table_impl(static_cast<const modgpu_table_entry_t *>(dev_entries), n_entries, dev_workspace, workspace_bytes, -1, st);
+        hipError_t e = hipEventRecord(e1, st);
+        if (e == hipSuccess) e = hipEventSynchronize(e1);
+        float ms = 0.f;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        if (rc) return rc;
+        if (e != hipSuccess) return fail_hip(e, "event timing");
+        *ms_per_call = ms / (float)iters;
+        return MODGPU_OK;
+    });
+}
 
 int modgpu_testing_hooks(void)
 {
@@ -1873,6 +2086,8 @@ void modgpu_debug_set_rekey_form(int shape)
     g_rekey_shape.store(shape < 0 ? kRekeyShapeShipped : shape == CYCLE_REKEY_SHAPE_ALL ? CYCLE_REKEY_SHAPE_ALL : CYCLE_REKEY_SHAPE_QUEUE,
                         std::memory_order_relaxed);
 }
+
+void modgpu_debug_set_table_grid(uint32_t grid) { g_table_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
 
 void modgpu_debug_set_queue_ring(uint32_t lines)
 {
