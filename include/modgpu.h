@@ -94,7 +94,8 @@ extern "C" {
 
 /* ABI version of this header (bumped on any signature change; ABI 8 also gained modgpu_cycle_device_to and
  * modgpu_cycle_batch_device_to, the four transfer calls modgpu_cycle_host_to_device & co., and modgpu_rekey_device_to and
- * modgpu_rekey_batch_device_to, and the table calls modgpu_cycle_table_device & co., additions that change no existing signature). */
+ * modgpu_rekey_batch_device_to, and the table calls modgpu_cycle_table_device & co., and the rekey table calls
+ * modgpu_rekey_table_device & co., additions that change no existing signature). */
 #define MODGPU_ABI_VERSION 8
 int modgpu_abi_version(void);
 
@@ -189,7 +190,8 @@ int modgpu_rekey_device_to(void *dev_dst, const void *dev_src, uint64_t n, int32
  * src = old part + o_old_i, dst = new part + o_new_i, offs_from = o_old, offs_to = o_new.  Everything modgpu_rekey_device_to says holds
  * per entry; as in modgpu_cycle_batch_device_to SOURCE ranges may overlap each other, a destination that meets any other entry's
  * source or destination makes the whole call MODGPU_ERR_INVALID, any n_parts is taken with up to 16 non-empty entries per launch, in
- * order, on the same stream, and empty entries are skipped. */
+ * order, on the same stream, and empty entries are skipped.  For more than a handful of entries -- the files of a part --
+ * modgpu_rekey_table_device takes a table of any length in three launches, each entry with its own pair of keys. */
 int modgpu_rekey_batch_device_to(void *const *dst_parts, const void *const *src_parts, const uint64_t *sizes,
                                  const uint64_t *offs_from, const uint64_t *offs_to, int n_parts, int32_t key_from,
                                  int32_t key_to, int device, void *hip_stream);
@@ -235,7 +237,7 @@ uint64_t modgpu_table_workspace_bytes(uint64_t n_entries);
 int modgpu_cycle_table_device(const modgpu_table_entry_t *dev_entries, uint64_t n_entries, void *dev_workspace,
                               uint64_t workspace_bytes, int device, void *hip_stream);
 
-/* Status of the last call that ran on dev_workspace (read after the caller has synchronised): MODGPU_OK with *first_bad_entry =
+/* Status of the last call that ran on dev_workspace (read after the caller has synchronised; a modgpu_rekey_table_device workspace too): MODGPU_OK with *first_bad_entry =
  * UINT64_MAX if it ran clean, MODGPU_ERR_INVALID with *first_bad_entry = the lowest entry the device refused (the call wrote
  * nothing).  Synchronous (a small copy from the device). */
 int modgpu_table_status(const void *dev_workspace, int device, uint64_t *first_bad_entry);
@@ -244,6 +246,53 @@ int modgpu_table_status(const void *dev_workspace, int device, uint64_t *first_b
  * an entry at fault (a NULL pointer with n > 0, nonzero flags, a destination partly overlapping its own source, a destination
  * meeting another entry's source or destination).  No device is touched. */
 int modgpu_table_validate(const modgpu_table_entry_t *host_entries, uint64_t n_entries);
+
+/* ---- a TABLE of rekey entries in device memory: any length, three launches -------------------------------------------------------
+ * One entry: dst[j] = src[j] ^ ks(key_from)[off_from + j] ^ ks(key_to)[off_to + j], j = 0 .. n-1 -- exactly what
+ * modgpu_rekey_device_to computes for it (any byte alignment on either side, each offset with its own phase, dst == src rekeys in
+ * place, n == 0 is skipped, 64-bit offsets; a key == 0 mod 2^31-1 is the identity keystream, so one such key applies or removes only
+ * the other, two copy, and the same reduced key at offsets equal mod 2^31-2 copies).  What relocating the files of an encrypted part
+ * is (src = old part + o_old, dst = new part + o_new, off_from = o_old, off_to = o_new), converting them between platforms in the
+ * same step if the keys differ.  The plaintext never reaches memory.  The layout is pinned (56 bytes, 8-byte aligned). */
+typedef struct modgpu_rekey_table_entry {
+    void *dst;
+    const void *src;
+    uint64_t n;
+    uint64_t off_from; /* stream offset of src[0] under key_from */
+    uint64_t off_to;   /* stream offset of dst[0] under key_to */
+    int32_t key_from;
+    int32_t key_to;
+    uint32_t flags;    /* must be 0 (reserved) */
+    uint32_t reserved; /* must be 0 */
+} modgpu_rekey_table_entry_t;
+
+/* Bytes of device workspace a rekey table call over n_entries needs: about 84 per entry plus a few lines (0 above
+ * MODGPU_TABLE_MAX_ENTRIES). */
+uint64_t modgpu_rekey_table_workspace_bytes(uint64_t n_entries);
+
+/* Rekeys the n_entries entries at dev_entries, a table in device memory of `device`, in THREE kernel launches whatever n_entries is
+ * (plan, finish, stream; path_stats().gpu_launches counts them, modgpu_last_launch reports the stream launch as variant 9).  The
+ * contract is modgpu_cycle_table_device's, word for word where it applies: asynchronous on `hip_stream`, `device` -1 = the current
+ * device, allocation-free, capturable into a hipGraph; THE TABLE IS READ WHEN THE CALL RUNS ON THE DEVICE, so a replayed graph picks
+ * up entries rewritten between replays; up to MODGPU_TABLE_MAX_ENTRIES entries; the WORKSPACE is the caller's (at least
+ * modgpu_rekey_table_workspace_bytes(n_entries) bytes of device memory of `device`, 8-byte aligned, reset by the call's first kernel
+ * in stream order), and two calls on one workspace must not overlap in time.
+ * Checks, in three tiers:
+ *   1. on the host, before anything is queued -- MODGPU_ERR_INVALID: the table call's tier 1, with this call's workspace size.
+ *   2. on the device, by the plan: an entry with a NULL dst or src and n > 0, an entry with nonzero flags or reserved, an entry of
+ *      1 TiB or more, or entries of more than 2^31 chunks of 64 KiB together.  Any of these makes the WHOLE CALL WRITE NOTHING.
+ *   3. not checked on the device: overlaps, under modgpu_rekey_batch_device_to's rule (sources may overlap each other, an entry may
+ *      alias itself exactly, a destination may meet no other entry's source or destination range).  Bytes in ranges that break it
+ *      are unspecified, but nothing outside the entries' [dst, dst+n) is ever written.  modgpu_rekey_table_validate checks a host copy.
+ * The workspace starts with the table call's header, so modgpu_table_status reports this call too: once the caller has
+ * synchronised it names the lowest entry the device refused, whichever kind of table call ran last on the workspace. */
+int modgpu_rekey_table_device(const modgpu_rekey_table_entry_t *dev_entries, uint64_t n_entries, void *dev_workspace,
+                              uint64_t workspace_bytes, int device, void *hip_stream);
+
+/* A host copy of a rekey table against tiers 1-3 above, in O(n log n): MODGPU_OK, or MODGPU_ERR_INVALID with modgpu_last_error()
+ * naming an entry at fault (a NULL pointer with n > 0, nonzero flags or reserved, a destination partly overlapping its own source,
+ * a destination meeting another entry's source or destination).  No device is touched. */
+int modgpu_rekey_table_validate(const modgpu_rekey_table_entry_t *host_entries, uint64_t n_entries);
 
 /* Replaces CEncryptionCycler::Cycle (CEncryptionCycler.cpp:4-14) for a caller-owned HOST buffer,
  * on the GPU.  Pageable memory is staged through page-locked slots owned by this library (memcpy ->

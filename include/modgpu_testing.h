@@ -38,6 +38,9 @@ int modgpu_time_rekey_device_to(void *dev_dst, const void *dev_src, uint64_t n, 
 /* The same for modgpu_cycle_table_device: `iters` back-to-back table calls (three launches each) on one workspace. */
 int modgpu_time_cycle_table_device(const void *dev_entries, uint64_t n_entries, void *dev_workspace,
                                    uint64_t workspace_bytes, int device, void *hip_stream, int iters, float *ms_per_call);
+/* The same for modgpu_rekey_table_device: `iters` back-to-back rekey table calls (three launches each) on one workspace. */
+int modgpu_time_rekey_table_device(const void *dev_entries, uint64_t n_entries, void *dev_workspace,
+                                   uint64_t workspace_bytes, int device, void *hip_stream, int iters, float *ms_per_call);
 
 /* The launch the calling thread made last (any entry point), as the library planned it. */
 typedef struct modgpu_launch_info {
@@ -50,7 +53,8 @@ typedef struct modgpu_launch_info {
                              6 = a transfer kernel (modgpu_cycle_host_to_device & co.; one launch for the whole call; `bytes` = the call's),
                              7 = the rekey kernel (modgpu_rekey_device_to / _batch_device_to; `bytes` = all entries of the launch),
                              8 = the table call's stream kernel (modgpu_cycle_table_device; `bytes` = 0: the table is only read on
-                                 the device) */
+                                 the device),
+                             9 = the rekey table call's stream kernel (modgpu_rekey_table_device; `bytes` = 0, as for 8) */
     uint32_t grid;        /* workgroups launched                                                  */
     uint32_t block;       /* threads per workgroup                                                */
     uint32_t chunk_bytes; /* bytes one workgroup trip covers                                      */
@@ -62,7 +66,8 @@ typedef struct modgpu_launch_info {
                                 modgpu_to_kernel_source_hash() for variant 5,
                                 modgpu_xfer_kernel_source_hash() for variant 6,
                                 modgpu_rekey_kernel_source_hash() for variant 7,
-                                modgpu_table_kernel_source_hash() for variant 8; static storage */
+                                modgpu_table_kernel_source_hash() for variant 8,
+                                modgpu_rekey_table_kernel_source_hash() for variant 9; static storage */
 } modgpu_launch_info_t;
 int modgpu_last_launch(modgpu_launch_info_t *out);
 
@@ -150,6 +155,9 @@ const char *modgpu_xfer_kernel_source_hash(void);
 const char *modgpu_rekey_kernel_source_hash(void);
 /* The same for the table kernels' TU (cycle_table_kernel.hip, cycle_table_kernel.h, cycle_kernel_impl.h, cycle_kernel.h, lcg.h). */
 const char *modgpu_table_kernel_source_hash(void);
+/* The same for the rekey table kernels' TU (cycle_rekey_table_kernel.hip, cycle_rekey_table_kernel.h, cycle_table_kernel.h,
+ * cycle_rekey_impl.h, cycle_kernel_impl.h, cycle_kernel.h, lcg.h). */
+const char *modgpu_rekey_table_kernel_source_hash(void);
 
 /* 1 in libmodgpu_testing.so, 0 in libmodgpu.so. */
 int modgpu_testing_hooks(void);
@@ -173,6 +181,10 @@ void modgpu_debug_set_rekey_form(int shape);
 /* The table call's stream launch: `grid` workgroups (1..4096), 0 = the shipped grid (the out-of-place kernel's, 25 per 32 CUs).
  * Measurement (tools/bench_table.py). */
 void modgpu_debug_set_table_grid(uint32_t grid);
+
+/* The rekey table call's stream launch: `grid` workgroups (1..4096), 0 = the shipped grid.  Measurement
+ * (tools/bench_rekey_table.py) and parity tests of both grids. */
+void modgpu_debug_set_rekey_table_grid(uint32_t grid);
 
 /* How the transfer calls (modgpu_cycle_host_to_device & co.) move their bytes: 0 = the transfer kernels (shipped), 1 = the DMA
  * reference form -- per chunk a hipMemcpyAsync into a device slot and an out-of-place launch from there (upload), or an out-of-place

@@ -18,6 +18,8 @@ from .capi import (  # noqa: F401
     rekey_device_to, rekey_batch_device_to, time_rekey_device_to, rekey_kernel_source_hash, debug_set_rekey_form, REKEY_FORMS,
     cycle_table_device, time_cycle_table_device, table, table_workspace_bytes, table_status, table_validate, table_kernel_source_hash,
     debug_set_table_grid, TableEntry, TABLE_DTYPE,
+    rekey_table_device, time_rekey_table_device, rekey_table, rekey_table_workspace_bytes, rekey_table_validate,
+    rekey_table_kernel_source_hash, debug_set_rekey_table_grid, RekeyTableEntry, REKEY_TABLE_DTYPE,
     cycle_host_to_device, cycle_device_to_host, cycle_file_to_device, cycle_device_to_file, xfer_kernel_source_hash, debug_set_xfer_form, XFER_FORMS,
     host_loop_isa, cycle_scalar_host_isa, device_numa_node, numa_probe, host_policy, host_policy_engine, host_trace, host_trace_read, host_pool_stats, host_chunking, HOST_TRACE_KINDS,
 )

@@ -75,6 +75,9 @@ EXPORTS = {
     "modgpu_cycle_table_device": (_int, [_vp, _u64, _vp, _u64, _int, _vp]),
     "modgpu_table_status": (_int, [_vp, _int, ctypes.POINTER(_u64)]),
     "modgpu_table_validate": (_int, [_vp, _u64]),
+    "modgpu_rekey_table_workspace_bytes": (_u64, [_u64]),
+    "modgpu_rekey_table_device": (_int, [_vp, _u64, _vp, _u64, _int, _vp]),
+    "modgpu_rekey_table_validate": (_int, [_vp, _u64]),
 }
 
 
@@ -86,6 +89,17 @@ class TableEntry(ctypes.Structure):
 # the same layout as a numpy structured dtype: a table built with numpy is the bytes the device reads
 TABLE_DTYPE = np.dtype([("dst", "<u8"), ("src", "<u8"), ("n", "<u8"), ("stream_off", "<u8"), ("key", "<i4"), ("flags", "<u4")])
 assert TABLE_DTYPE.itemsize == ctypes.sizeof(TableEntry) == 40
+
+
+class RekeyTableEntry(ctypes.Structure):
+    """modgpu_rekey_table_entry_t (include/modgpu.h): 56 bytes."""
+    _fields_ = [("dst", _vp), ("src", _vp), ("n", _u64), ("off_from", _u64), ("off_to", _u64), ("key_from", _i32), ("key_to", _i32),
+                ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+REKEY_TABLE_DTYPE = np.dtype([("dst", "<u8"), ("src", "<u8"), ("n", "<u8"), ("off_from", "<u8"), ("off_to", "<u8"), ("key_from", "<i4"),
+                              ("key_to", "<i4"), ("flags", "<u4"), ("reserved", "<u4")])
+assert REKEY_TABLE_DTYPE.itemsize == ctypes.sizeof(RekeyTableEntry) == 56
 
 
 class PathStats(ctypes.Structure):
@@ -136,6 +150,8 @@ TESTING_EXPORTS = {
     "modgpu_rekey_kernel_source_hash": (ctypes.c_char_p, []),
     "modgpu_time_cycle_table_device": (_int, [_vp, _u64, _vp, _u64, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
     "modgpu_table_kernel_source_hash": (ctypes.c_char_p, []),
+    "modgpu_time_rekey_table_device": (_int, [_vp, _u64, _vp, _u64, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
+    "modgpu_rekey_table_kernel_source_hash": (ctypes.c_char_p, []),
 }
 # include/modgpu_testing.h, modgpu_debug_* group: ONLY in libmodgpu_testing.so
 DEBUG_EXPORTS = {
@@ -157,6 +173,7 @@ DEBUG_EXPORTS = {
     "modgpu_debug_set_xfer_form": (None, [_int]),
     "modgpu_debug_set_rekey_form": (None, [_int]),
     "modgpu_debug_set_table_grid": (None, [ctypes.c_uint32]),
+    "modgpu_debug_set_rekey_table_grid": (None, [ctypes.c_uint32]),
 }
 
 
@@ -752,6 +769,84 @@ def table_kernel_source_hash():
 def debug_set_table_grid(grid=0):
     """Testing flavour: the table call's stream grid (0 = shipped)."""
     _debug_lib().modgpu_debug_set_table_grid(grid)
+
+
+def rekey_table(n):
+    """an all-zero host rekey table of n entries (REKEY_TABLE_DTYPE): fill dst, src, n, off_from, off_to, key_from, key_to; flags and
+    reserved stay 0"""
+    return np.zeros(n, dtype=REKEY_TABLE_DTYPE)
+
+
+def rekey_table_workspace_bytes(n_entries):
+    """bytes of device workspace a rekey table call over n_entries needs (0 for none, or above the limit)"""
+    return lib().modgpu_rekey_table_workspace_bytes(n_entries)
+
+
+def rekey_table_validate(entries):
+    """the overlap / pointer / flags rules over a host rekey table (REKEY_TABLE_DTYPE array); raises ModGpuError naming an entry at
+    fault"""
+    t = np.ascontiguousarray(entries, dtype=REKEY_TABLE_DTYPE)
+    _check(lib().modgpu_rekey_table_validate(_vp(t.ctypes.data if t.size else 0), t.size))
+
+
+def rekey_table_device(entries, workspace=None, device=-1, stream=None, check=True, *, n=None):
+    """Rekeys a TABLE of entries -- dst_i[j] = src_i[j] ^ ks(key_from_i)[off_from_i + j] ^ ks(key_to_i)[off_to_i + j] -- in three
+    launches, whatever its length.  `entries` is a host table (a REKEY_TABLE_DTYPE array: uploaded, and checked with
+    rekey_table_validate first unless check=False) or a table already in device memory (a DeviceBuffer or an address; then n, the entry
+    count, is needed).  `workspace` is a DeviceBuffer or address of at least rekey_table_workspace_bytes(n) bytes; None makes one.
+    When this function made a buffer itself it waits for the call before freeing it and raises ModGpuError if the device refused an
+    entry; otherwise the call is asynchronous on `stream` and table_status(workspace) tells the outcome after a synchronise."""
+    own = []
+    try:
+        if isinstance(entries, np.ndarray):
+            t = np.ascontiguousarray(entries, dtype=REKEY_TABLE_DTYPE)
+            n = t.size
+            if check:
+                rekey_table_validate(t)
+            if n == 0:
+                return
+            buf = DeviceBuffer(t.nbytes, device)
+            own.append(buf)
+            buf.upload(t.view(np.uint8))
+            addr = buf.ptr
+        else:
+            if n is None:
+                raise TypeError("n (the entry count) is needed for a table in device memory")
+            addr = _dev_addr(entries)
+        if workspace is None and n:
+            workspace = DeviceBuffer(rekey_table_workspace_bytes(n), device)
+            own.append(workspace)
+        ws = _dev_addr(workspace) if workspace is not None else 0
+        ws_bytes = workspace.nbytes if isinstance(workspace, DeviceBuffer) else rekey_table_workspace_bytes(n)
+        _check(lib().modgpu_rekey_table_device(_vp(addr), n, _vp(ws), ws_bytes, device, _vp(stream or 0)))
+        if own:
+            _check(lib().modgpu_sync(device, _vp(stream or 0)))
+            bad = table_status(ws, device)
+            if bad is not None:
+                raise ModGpuError(1, f"the device refused rekey table entry {bad}; nothing was written")
+    finally:
+        for b in own:
+            b.free()
+
+
+def time_rekey_table_device(entries, n, workspace, device=-1, stream=None, iters=2):
+    """Mean ms per rekey table call (three launches) over `iters` calls, HIP events on the launch stream; table and workspace
+    resident."""
+    ms = ctypes.c_float(0)
+    ws_bytes = workspace.nbytes if isinstance(workspace, DeviceBuffer) else rekey_table_workspace_bytes(n)
+    _check(lib().modgpu_time_rekey_table_device(_vp(_dev_addr(entries)), n, _vp(_dev_addr(workspace)), ws_bytes, device, _vp(stream or 0),
+                                                iters, ctypes.byref(ms)))
+    return ms.value
+
+
+def rekey_table_kernel_source_hash():
+    """identity of the rekey table kernels' TU (cycle_rekey_table_kernel.hip and what it includes)"""
+    return lib().modgpu_rekey_table_kernel_source_hash().decode()
+
+
+def debug_set_rekey_table_grid(grid=0):
+    """Testing flavour: the rekey table call's stream grid (0 = shipped)."""
+    _debug_lib().modgpu_debug_set_rekey_table_grid(grid)
 
 
 def _dev_addr(x):

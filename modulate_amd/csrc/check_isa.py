@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""check_isa.py <cycle_kernel.s> [<cycle_feed_kernel.s>] | <cycle_to_kernel.s> | <cycle_xfer_kernel.s> | <cycle_rekey_kernel.s> | <cycle_table_kernel.s> -- build-time guard over the gfx950 assembly of the kernel TUs (run by the
+"""check_isa.py <cycle_kernel.s> [<cycle_feed_kernel.s>] | <cycle_to_kernel.s> | <cycle_xfer_kernel.s> | <cycle_rekey_kernel.s> | <cycle_table_kernel.s> | <cycle_rekey_table_kernel.s> -- build-time guard over the gfx950 assembly of the kernel TUs (run by the
 Makefile right after the TUs are compiled and before either object exists; tests/test_capi_cpu.py runs it again and feeds it
 deliberately broken builds).
 
@@ -41,6 +41,10 @@ in any of them (their atomics stay plain); the stream kernel carries the keystre
 2 unrolled trips), its data loads are nt and its stores nt sc1, and it finds a chunk's entry with scalar loads only (s_load_dwordx16 of
 the search levels and of the entry's plan; no vector load besides the lane's two start-up table lookups -- a vector-memory search
 would wait for the chunk loads in flight); the plan and finish kernels carry no keystream block.
+The rekey table kernels (cycle_rekey_table_kernel.s: plan, finish, stream): the register budget, no spills / scratch / private segment,
+no v_mbcnt; the stream kernel carries the two-keystream blocks under the rekey kernel's rules (fixed temporaries, 60 mads + 30 addc,
+trailing s_nop 0, one v_bitop3_b32 0x96 per dword; 8 blocks: 4 words x 2 unrolled trips), data loads nt and stores nt sc1, and the
+table call's scalar-only entry search; the plan and finish kernels carry no keystream block of either kind.
 Exit status 0 = all of it holds; 1 = findings on stdout."""
 import re
 import sys
@@ -351,6 +355,49 @@ def check_table(asm, bodies):
     return bad
 
 
+REKEY_TABLE_KERNELS = ("modgpu_cycle_rekey_table_plan", "modgpu_cycle_rekey_table_finish", "modgpu_cycle_rekey_table_kernel")
+
+
+def check_rekey_table(asm, bodies):
+    """the rekey table kernels' TU (cycle_rekey_table_kernel.s): the plan and finish kernels and the stream kernel"""
+    bad = []
+    kinds = {}
+    for name, fn in bodies.items():
+        kind = next((k for k in REKEY_TABLE_KERNELS if k in name), None)
+        if kind is None:
+            bad.append("%s: the rekey table kernels' TU holds another kernel" % name)
+            continue
+        kinds[kind] = kinds.get(kind, 0) + 1
+        md = metadata(asm, name)
+        if md.get("vgpr_count", 999) > 128 or md.get("sgpr_count", 999) > 102:
+            bad.append("%s: register counts beyond the budget: %s" % (name, md))
+        if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0) or "scratch_" in fn:
+            bad.append("%s: spills, scratch or a private segment: %s" % (name, md))
+        if "v_mbcnt" in fn:
+            bad.append("%s: the atomic optimizer rewrote an atomic (build the TU with -mllvm -amdgpu-atomic-optimizer-strategy=None)" % name)
+        blocks = len([b for b in BLOCK.findall(fn) if "s[94:95]" in b])
+        if kind != "modgpu_cycle_rekey_table_kernel":
+            if blocks:
+                bad.append("%s: a planning kernel carries a keystream block" % name)
+            continue
+        bad += rekey_blocks(name, fn)
+        if blocks != 8:
+            bad.append("%s: %d two-keystream blocks, expected 8 (4 words x 2 unrolled trips)" % (name, blocks))
+        loads = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_load_dword", ln)]
+        stores = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_store_dword", ln)]
+        if not loads or not all(ln.endswith(" nt") for ln in loads):
+            bad.append("%s: a data load is not nt" % name)
+        if not stores or not all(ln.endswith(" nt sc1") for ln in stores):
+            bad.append("%s: a data store is not nt sc1" % name)
+        vec = len(re.findall(r"^\s+(?:global|flat)_load", fn, re.M))
+        if fn.count("s_load_dwordx16") < 2 or vec > 2:
+            bad.append("%s: the entry search is not scalar (%d s_load_dwordx16, %d vector loads besides the data)" % (name, fn.count("s_load_dwordx16"), vec))
+    for k in REKEY_TABLE_KERNELS:
+        if kinds.get(k, 0) != 1:
+            bad.append("the rekey table kernels' TU holds %d %s, expected 1" % (kinds.get(k, 0), k))
+    return bad
+
+
 def check_xfer(asm, bodies):
     """the transfer kernels' TU (cycle_xfer_kernel.s): the upload (ILb1) and the download (ILb0), each plain and funnel"""
     bad = []
@@ -400,6 +447,8 @@ def check(asm):
         if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0) or "scratch_" in bodies[feed[0]]:
             bad.append("%s: spills, scratch or a private segment: %s" % (feed[0], md))
         return bad + check_feed(asm, feed[0], bodies[feed[0]])
+    if any("modgpu_cycle_rekey_table" in n for n in bodies):
+        return bad + check_rekey_table(asm, bodies)
     if any("modgpu_cycle_table" in n for n in bodies):
         return bad + check_table(asm, bodies)
     if any("modgpu_cycle_to_kernel" in n for n in bodies):

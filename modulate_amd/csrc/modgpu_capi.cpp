@@ -20,6 +20,7 @@
 #include "cycle_feed_kernel.h"
 #include "cycle_kernel.h"
 #include "cycle_rekey_kernel.h"
+#include "cycle_rekey_table_kernel.h"
 #include "cycle_table_kernel.h"
 #include "cycle_to_kernel.h"
 #include "cycle_xfer_kernel.h"
@@ -1156,7 +1157,9 @@ int table_impl(const modgpu_table_entry_t *entries, uint64_t n, void *ws, uint64
 // The overlap rule of modgpu_cycle_batch_device_to over a host copy, in O(n log n): destinations sorted by start must not meet each
 // other (a running maximum of ends), and a destination must not meet the source of another entry -- among the sources that start
 // before it ends, the one reaching furthest, or the furthest of another entry when that one is its own.
-int table_validate_impl(const modgpu_table_entry_t *t, uint64_t n)
+uint32_t entry_reserved(const modgpu_table_entry_t &e) { return e.flags; }
+uint32_t entry_reserved(const modgpu_rekey_table_entry_t &e) { return e.flags | e.reserved; }
+template <class Entry> int table_validate_impl(const Entry *t, uint64_t n)
 {
     if (n > kTableMaxEntries) return fail(MODGPU_ERR_INVALID, "more than 4194304 entries (the table call's limit)");
     if (n && !t) return fail(MODGPU_ERR_INVALID, "null table");
@@ -1167,7 +1170,7 @@ int table_validate_impl(const modgpu_table_entry_t *t, uint64_t n)
     };
     std::vector<Range> d, s;
     for (uint64_t i = 0; i < n; ++i) {
-        if (t[i].flags) return entry(i, "nonzero flags");
+        if (entry_reserved(t[i])) return entry(i, sizeof(Entry) == sizeof(modgpu_table_entry_t) ? "nonzero flags" : "nonzero flags or reserved");
         if (!t[i].n) continue;
         if (!t[i].dst || !t[i].src) return entry(i, "null buffer");
         const uint64_t dl = at(t[i].dst), sl = at(t[i].src);
@@ -1205,6 +1208,88 @@ int table_validate_impl(const modgpu_table_entry_t *t, uint64_t n)
         if ((id1[c - 1] != r.i && end1[c - 1] > r.lo) || end2[c - 1] > r.lo) bad = std::min(bad, r.i);
     }
     if (bad != UINT64_MAX) return entry(bad, "destination meets another entry's source or destination");
+    return MODGPU_OK;
+}
+
+// ---- a table of rekey entries in device memory (modgpu_rekey_table_device) ----------------------------------------------------------
+static_assert(sizeof(modgpu_rekey_table_entry_t) == sizeof(RekeyTableEntry) && offsetof(modgpu_rekey_table_entry_t, off_to) == offsetof(RekeyTableEntry, off_to) &&
+                  offsetof(modgpu_rekey_table_entry_t, key_from) == offsetof(RekeyTableEntry, key_from) &&
+                  offsetof(modgpu_rekey_table_entry_t, key_to) == offsetof(RekeyTableEntry, key_to) &&
+                  offsetof(modgpu_rekey_table_entry_t, flags) == offsetof(RekeyTableEntry, flags) &&
+                  offsetof(modgpu_rekey_table_entry_t, reserved) == offsetof(RekeyTableEntry, reserved) && sizeof(modgpu_rekey_table_entry_t) == 56,
+              "the kernels read the public entry layout");
+static_assert(sizeof(RekeyTablePlan) == sizeof(CycleTablePlan), "the table call's layout holds the rekey plan records");
+
+// The table call's layout (header, 1024-entry records, plan records, search levels) with the edge states behind it, on a line of
+// their own: the header comes first in both, so modgpu_table_status reads either kind of workspace.
+struct RekeyTableLayout {
+    TableLayout t;
+    uint64_t edge, bytes;
+};
+RekeyTableLayout rekey_table_layout(uint64_t n)
+{
+    RekeyTableLayout L{table_layout(n), 0, 0};
+    L.edge = L.t.bytes;
+    L.bytes = (L.edge + n * sizeof(RekeyTableEdge) + 63) & ~63ull;
+    return L;
+}
+
+// The stream launch's grid: one workgroup per CU on every CU, as the rekey kernel (DESIGN.md 4.9 has the A/B against the table
+// call's 25 per 32 CUs, and the rule that picked it)
+#ifdef MODGPU_TESTING_HOOKS
+std::atomic<uint32_t> g_rekey_table_grid{0}; // modgpu_debug_set_rekey_table_grid
+uint32_t rekey_table_grid_forced() { return g_rekey_table_grid.load(std::memory_order_relaxed); }
+#else
+constexpr uint32_t rekey_table_grid_forced() { return 0; }
+#endif
+uint32_t rekey_table_grid()
+{
+    if (rekey_table_grid_forced()) return rekey_table_grid_forced();
+    return std::max<uint32_t>(1, large_grid());
+}
+
+// Tier 1 (include/modgpu.h): everything checked before anything is queued; then the three launches on `stream`.
+int rekey_table_impl(const modgpu_rekey_table_entry_t *entries, uint64_t n, void *ws, uint64_t ws_bytes, int device, hipStream_t stream)
+{
+    if (n == 0) return MODGPU_OK;
+    if (n > kTableMaxEntries) return fail(MODGPU_ERR_INVALID, "more than 4194304 entries (the table call's limit)");
+    if (!entries || !ws) return fail(MODGPU_ERR_INVALID, "null table or workspace");
+    if ((reinterpret_cast<uintptr_t>(entries) | reinterpret_cast<uintptr_t>(ws)) & 7) return fail(MODGPU_ERR_INVALID, "table or workspace not 8-byte aligned");
+    const RekeyTableLayout L = rekey_table_layout(n);
+    if (ws_bytes < L.bytes) return fail(MODGPU_ERR_INVALID, "workspace smaller than modgpu_rekey_table_workspace_bytes(n_entries)");
+    DeviceScope scope(device);
+    if (scope.rc) return scope.rc;
+    int phys = -1;
+    HIP_TRY(hipGetDevice(&phys));
+    if (modgpu_xfer_device_of(entries, n * sizeof(modgpu_rekey_table_entry_t)) != phys || modgpu_xfer_device_of(ws, L.bytes) != phys)
+        return fail(MODGPU_ERR_INVALID, "the table or the workspace is not device memory of the call's device");
+    uint8_t *const w = static_cast<uint8_t *>(ws);
+    RekeyTableArgs a{};
+    a.entries = reinterpret_cast<const RekeyTableEntry *>(entries);
+    a.n = n;
+    a.hdr = reinterpret_cast<CycleTableHdr *>(w);
+    a.blk = reinterpret_cast<CycleTableBlk *>(w + L.t.blk);
+    a.plan = reinterpret_cast<RekeyTablePlan *>(w + L.t.plan);
+    a.edge = reinterpret_cast<RekeyTableEdge *>(w + L.edge);
+    for (uint32_t k = 0; k <= L.t.top; ++k) {
+        a.level[k] = reinterpret_cast<uint32_t *>(w + L.t.level[k]);
+        a.level_n[k] = L.t.level_n[k];
+    }
+    a.top = L.t.top;
+    a.n_blk = L.t.n_blk;
+    const uint32_t grid = rekey_table_grid();
+    (void)hipGetLastError(); // (the launches report hipGetLastError: an earlier call's error must not be taken for theirs)
+    hipError_t e = modgpu_launch_rekey_table_plan(a, stream);
+    if (e != hipSuccess) return fail_hip(e, "rekey table plan launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    e = modgpu_launch_rekey_table_finish(a, stream);
+    if (e != hipSuccess) return fail_hip(e, "rekey table finish launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    e = modgpu_launch_rekey_table_stream(a, grid, stream);
+    if (e != hipSuccess) return fail_hip(e, "rekey table stream launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    t_last_launch = {modgpu_rekey_table_kernel_name(), CYCLE_REKEY_TABLE, grid, modgpu_rekey_table_block(), modgpu_rekey_table_chunk_bytes(), 0, grid,
+                     MODGPU_REKEY_TABLE_KERNEL_SOURCE_HASH};
     return MODGPU_OK;
 }
 } // namespace
@@ -1320,6 +1405,24 @@ int modgpu_table_status(const void *dev_workspace, int device, uint64_t *first_b
 }
 
 int modgpu_table_validate(const modgpu_table_entry_t *host_entries, uint64_t n_entries)
+{
+    return guarded([&]() -> int { return table_validate_impl(host_entries, n_entries); });
+}
+
+uint64_t modgpu_rekey_table_workspace_bytes(uint64_t n_entries)
+{
+    return n_entries == 0 || n_entries > kTableMaxEntries ? 0 : rekey_table_layout(n_entries).bytes;
+}
+
+int modgpu_rekey_table_device(const modgpu_rekey_table_entry_t *dev_entries, uint64_t n_entries, void *dev_workspace, uint64_t workspace_bytes,
+                              int device, void *hip_stream)
+{
+    return guarded([&]() -> int {
+        return rekey_table_impl(dev_entries, n_entries, dev_workspace, workspace_bytes, device, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int modgpu_rekey_table_validate(const modgpu_rekey_table_entry_t *host_entries, uint64_t n_entries)
 {
     return guarded([&]() -> int { return table_validate_impl(host_entries, n_entries); });
 }
@@ -2026,6 +2129,7 @@ const char *modgpu_to_kernel_source_hash(void) { return MODGPU_TO_KERNEL_SOURCE_
 const char *modgpu_xfer_kernel_source_hash(void) { return MODGPU_XFER_KERNEL_SOURCE_HASH; }
 const char *modgpu_rekey_kernel_source_hash(void) { return MODGPU_REKEY_KERNEL_SOURCE_HASH; }
 const char *modgpu_table_kernel_source_hash(void) { return MODGPU_TABLE_KERNEL_SOURCE_HASH; }
+const char *modgpu_rekey_table_kernel_source_hash(void) { return MODGPU_REKEY_TABLE_KERNEL_SOURCE_HASH; }
 
 int modgpu_time_cycle_table_device(const void *dev_entries, uint64_t n_entries, void *dev_workspace, uint64_t workspace_bytes,
                                    int device, void *hip_stream, int iters, float *ms_per_call)
@@ -2041,6 +2145,33 @@ int modgpu_time_cycle_table_device(const void *dev_entries, uint64_t n_entries, 
         HIP_TRY(hipEventCreate(&e1));
         HIP_TRY(hipEventRecord(e0, st));
         for (int i = 0; i < iters && rc == MODGPU_OK; ++i) rc = table_impl(static_cast<const modgpu_table_entry_t *>(dev_entries), n_entries, dev_workspace, workspace_bytes, -1, st);
+        hipError_t e = hipEventRecord(e1, st);
+        if (e == hipSuccess) e = hipEventSynchronize(e1);
+        float ms = 0.f;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        if (rc) return rc;
+        if (e != hipSuccess) return fail_hip(e, "event timing");
+        *ms_per_call = ms / (float)iters;
+        return MODGPU_OK;
+    });
+}
+
+int modgpu_time_rekey_table_device(const void *dev_entries, uint64_t n_entries, void *dev_workspace, uint64_t workspace_bytes,
+                                   int device, void *hip_stream, int iters, float *ms_per_call)
+{
+    return guarded([&]() -> int {
+        if (iters <= 0 || !ms_per_call) return fail(MODGPU_ERR_INVALID, "bad timing arguments");
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        int rc = MODGPU_OK;
+        hipStream_t st = static_cast<hipStream_t>(hip_stream);
+        hipEvent_t e0, e1;
+        HIP_TRY(hipEventCreate(&e0));
+        HIP_TRY(hipEventCreate(&e1));
+        HIP_TRY(hipEventRecord(e0, st));
+        for (int i = 0; i < iters && rc == MODGPU_OK; ++i) rc = rekey_table_impl(static_cast<const modgpu_rekey_table_entry_t *>(dev_entries), n_entries, dev_workspace, workspace_bytes, -1, st);
         hipError_t e = hipEventRecord(e1, st);
         if (e == hipSuccess) e = hipEventSynchronize(e1);
         float ms = 0.f;
@@ -2088,6 +2219,7 @@ void modgpu_debug_set_rekey_form(int shape)
 }
 
 void modgpu_debug_set_table_grid(uint32_t grid) { g_table_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
+void modgpu_debug_set_rekey_table_grid(uint32_t grid) { g_rekey_table_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
 
 void modgpu_debug_set_queue_ring(uint32_t lines)
 {
