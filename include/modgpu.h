@@ -95,7 +95,7 @@ extern "C" {
 /* ABI version of this header (bumped on any signature change; ABI 8 also gained modgpu_cycle_device_to and
  * modgpu_cycle_batch_device_to, the four transfer calls modgpu_cycle_host_to_device & co., and modgpu_rekey_device_to and
  * modgpu_rekey_batch_device_to, and the table calls modgpu_cycle_table_device & co., and the rekey table calls
- * modgpu_rekey_table_device & co., additions that change no existing signature). */
+ * modgpu_rekey_table_device & co., and the verify calls modgpu_verify_device & co., additions that change no existing signature). */
 #define MODGPU_ABI_VERSION 8
 int modgpu_abi_version(void);
 
@@ -293,6 +293,55 @@ int modgpu_rekey_table_device(const modgpu_rekey_table_entry_t *dev_entries, uin
  * naming an entry at fault (a NULL pointer with n > 0, nonzero flags or reserved, a destination partly overlapping its own source,
  * a destination meeting another entry's source or destination).  No device is touched. */
 int modgpu_rekey_table_validate(const modgpu_rekey_table_entry_t *host_entries, uint64_t n_entries);
+
+/* ---- VERIFY: is this buffer what the cipher would have produced from that one?  One read-only pass, two numbers -------------------
+ * The result of one entry, in device memory.  The layout is pinned (32 bytes, 8-byte aligned). */
+typedef struct modgpu_verify_result {
+    uint64_t mismatches;     /* number of j in [0, n) with expect[j] != (src[j] ^ ks(key)[stream_off + j]) -- BYTES, not words */
+    uint64_t first_mismatch; /* the lowest such j, counted from the entry's own first byte; UINT64_MAX if there is none */
+    uint64_t n;              /* bytes compared = the entry's n (lets a reader tell "ran clean" from "never ran") */
+    uint64_t reserved;       /* 0 */
+} modgpu_verify_result_t;
+
+/* Compares dev_expect[j] with dev_src[j] ^ ks(key)[stream_off + j] for j = 0 .. n-1 -- the bytes modgpu_cycle_device_to would have
+ * written -- where the data lies, in one pass that READS 2n bytes and writes the 32 bytes of *dev_result.  Same keystream, 64-bit
+ * offsets and key reduction as modgpu_cycle_device.  The contract is modgpu_cycle_device_to's, word for word where it applies:
+ * asynchronous on `hip_stream`; `device` -1 = the current device, an explicit device leaves the thread's current device as it was;
+ * allocation-free; capturable into a hipGraph; any number of calls may be in flight on any streams as long as their RESULT ranges
+ * differ.  Kernel entry point: no host loop, MODGPU_ERR_NO_DEVICE / MODGPU_ERR_HIP as usual.
+ *   * NOTHING BUT THE RESULT IS WRITTEN.  `expect` and `src` are read-only, so there is no overlap rule at all: they may be the same
+ *     pointer or overlap partly (and in the batch any entry may overlap any other).  Either may be page-locked host memory
+ *     (supported, not tuned).  Each may have any byte alignment; their phases mod 16 are independent.
+ *   * The result lives in device memory of `device`, 8-byte aligned, the caller's.  A result pointer that the runtime does not report
+ *     as device memory of the call's device (both ends of the range are asked about, as the transfer calls do), or that is misaligned,
+ *     is MODGPU_ERR_INVALID before anything is queued; so is a NULL expect or src with n > 0, a NULL result, and an entry that spans
+ *     2^24 chunks of 64 KiB or more (1 TiB; the table calls' limit).
+ *   * THE CALL INITIALISES ITS RESULT ITSELF, IN STREAM ORDER, with a small kernel in front of the compare.  Nothing needs clearing
+ *     beforehand, and a replayed graph starts from a clean result on every replay.  Once the call has completed on its stream the
+ *     fields are as documented above.
+ *   * n == 0 still produces a result: {0, UINT64_MAX, 0, 0}.
+ *   * key == 0 mod 2^31-1 (the identity keystream) is a plain device memcmp with a count: same result fields.
+ *   * The call never fails or degrades for lack of scheduling scratch: its chunks are assigned to workgroups statically, it draws no
+ *     ticket line (modgpu_cycle_device_to does, and copies + cycles in place when none is free; a read-only call has nothing to fall
+ *     back to, and measured against that call it does not need the ticket queue: DESIGN.md 4.10).
+ *   * Launches (path_stats().gpu_launches counts them): ONE to initialise the results of the call, then ONE per started group of 16
+ *     non-empty entries -- 2 for this call with n > 0, 1 with n == 0.  modgpu_last_launch reports the compare launch as variant 10
+ *     (the initialising launch alone, `bytes` = 0, if the call had no non-empty entry). */
+int modgpu_verify_device(const void *dev_expect, const void *dev_src, uint64_t n, int32_t key, uint64_t stream_off,
+                         modgpu_verify_result_t *dev_result, int device, void *hip_stream);
+
+/* n_parts entries of ONE device, dev_results[i] the result of entry i: everything modgpu_verify_device says holds per entry.
+ * stream_offs NULL = 0 for every entry.  Any n_parts is taken: one launch initialises all n_parts results (empty entries get
+ * {0, UINT64_MAX, 0, 0}), then up to 16 non-empty entries share a compare launch and further launches follow in order on the same
+ * stream -- 1 + ceil(non_empty / 16) launches.  A negative n_parts, or NULL arrays or a NULL dev_results with n_parts > 0, is
+ * MODGPU_ERR_INVALID; n_parts == 0 queues nothing. */
+int modgpu_verify_batch_device(const void *const *expect_parts, const void *const *src_parts, const uint64_t *sizes,
+                               const uint64_t *stream_offs, int n_parts, int32_t key, modgpu_verify_result_t *dev_results,
+                               int device, void *hip_stream);
+
+/* `count` results from device memory of `device` into host_out.  Synchronous (a small copy from the device, like
+ * modgpu_table_status): call it after the caller has synchronised the stream the verify calls ran on. */
+int modgpu_verify_results(const modgpu_verify_result_t *dev_results, uint64_t count, int device, modgpu_verify_result_t *host_out);
 
 /* Replaces CEncryptionCycler::Cycle (CEncryptionCycler.cpp:4-14) for a caller-owned HOST buffer,
  * on the GPU.  Pageable memory is staged through page-locked slots owned by this library (memcpy ->

@@ -78,6 +78,10 @@ EXPORTS = {
     "modgpu_rekey_table_workspace_bytes": (_u64, [_u64]),
     "modgpu_rekey_table_device": (_int, [_vp, _u64, _vp, _u64, _int, _vp]),
     "modgpu_rekey_table_validate": (_int, [_vp, _u64]),
+    "modgpu_verify_device": (_int, [_vp, _vp, _u64, _i32, _u64, _vp, _int, _vp]),
+    "modgpu_verify_batch_device": (_int, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64), ctypes.POINTER(_u64), _int, _i32,
+                                          _vp, _int, _vp]),
+    "modgpu_verify_results": (_int, [_vp, _u64, _int, _vp]),
 }
 
 
@@ -100,6 +104,11 @@ class RekeyTableEntry(ctypes.Structure):
 REKEY_TABLE_DTYPE = np.dtype([("dst", "<u8"), ("src", "<u8"), ("n", "<u8"), ("off_from", "<u8"), ("off_to", "<u8"), ("key_from", "<i4"),
                               ("key_to", "<i4"), ("flags", "<u4"), ("reserved", "<u4")])
 assert REKEY_TABLE_DTYPE.itemsize == ctypes.sizeof(RekeyTableEntry) == 56
+
+
+# modgpu_verify_result_t (include/modgpu.h): 32 bytes
+VERIFY_RESULT_DTYPE = np.dtype([("mismatches", "<u8"), ("first_mismatch", "<u8"), ("n", "<u8"), ("reserved", "<u8")])
+VERIFY_NONE = 0xFFFFFFFFFFFFFFFF  # first_mismatch of a clean entry
 
 
 class PathStats(ctypes.Structure):
@@ -152,6 +161,8 @@ TESTING_EXPORTS = {
     "modgpu_table_kernel_source_hash": (ctypes.c_char_p, []),
     "modgpu_time_rekey_table_device": (_int, [_vp, _u64, _vp, _u64, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
     "modgpu_rekey_table_kernel_source_hash": (ctypes.c_char_p, []),
+    "modgpu_time_verify_device": (_int, [_vp, _vp, _u64, _i32, _u64, _vp, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
+    "modgpu_verify_kernel_source_hash": (ctypes.c_char_p, []),
 }
 # include/modgpu_testing.h, modgpu_debug_* group: ONLY in libmodgpu_testing.so
 DEBUG_EXPORTS = {
@@ -174,6 +185,7 @@ DEBUG_EXPORTS = {
     "modgpu_debug_set_rekey_form": (None, [_int]),
     "modgpu_debug_set_table_grid": (None, [ctypes.c_uint32]),
     "modgpu_debug_set_rekey_table_grid": (None, [ctypes.c_uint32]),
+    "modgpu_debug_set_verify_form": (None, [_int]),
 }
 
 
@@ -847,6 +859,66 @@ def rekey_table_kernel_source_hash():
 def debug_set_rekey_table_grid(grid=0):
     """Testing flavour: the rekey table call's stream grid (0 = shipped)."""
     _debug_lib().modgpu_debug_set_rekey_table_grid(grid)
+
+
+def verify_device(expect, src, key, stream_off=0, result=None, device=-1, stream=None, *, n=None):
+    """Asynchronous VERIFY of n bytes at raw device addresses: counts the j with expect[j] != (src[j] ^ ks(key)[stream_off + j]) and
+    finds the lowest, in one read-only pass; only the 32-byte result (device memory: a DeviceBuffer or an address) is written.
+    `expect` / `src` are addresses or DeviceBuffer; n defaults to the smaller buffer's size when both are DeviceBuffer.  With
+    result=None a result buffer is made, the stream synchronised and the result returned as a VERIFY_RESULT_DTYPE record."""
+    if n is None:
+        if not (isinstance(expect, DeviceBuffer) and isinstance(src, DeviceBuffer)):
+            raise TypeError("n is needed unless both sides are DeviceBuffer")
+        n = min(expect.nbytes, src.nbytes)
+    own = DeviceBuffer(VERIFY_RESULT_DTYPE.itemsize, device) if result is None else None
+    try:
+        _check(lib().modgpu_verify_device(_vp(_dev_addr(expect)), _vp(_dev_addr(src)), n, as_int32(key), stream_off,
+                                          _vp(_dev_addr(own if own is not None else result)), device, _vp(stream or 0)))
+        if own is None:
+            return None
+        _check(lib().modgpu_sync(device, _vp(stream or 0)))
+        return verify_results(own, 1, device)[0]
+    finally:
+        if own is not None:
+            own.free()
+
+
+def verify_batch_device(expect_ptrs, src_ptrs, sizes, key, results, stream_offs=None, device=-1, stream=None):
+    """Several verify entries of ONE device (entry i from stream_offs[i] or 0, its result at results + 32 * i); every range is only
+    read, so anything may overlap anything.  One launch initialises the results, up to 16 non-empty entries share a compare launch."""
+    n = len(expect_ptrs)
+    assert len(src_ptrs) == n and len(sizes) == n
+    e = (_vp * n)(*[_dev_addr(x) for x in expect_ptrs])
+    s = (_vp * n)(*[_dev_addr(x) for x in src_ptrs])
+    z = (_u64 * n)(*sizes)
+    o = (_u64 * n)(*stream_offs) if stream_offs is not None else None
+    _check(lib().modgpu_verify_batch_device(e, s, z, o, n, as_int32(key), _vp(_dev_addr(results)), device, _vp(stream or 0)))
+
+
+def verify_results(results, count=1, device=-1):
+    """`count` results from device memory (a DeviceBuffer or an address) as a VERIFY_RESULT_DTYPE array; synchronous small copy --
+    synchronise the stream the verify calls ran on first."""
+    out = np.zeros(count, dtype=VERIFY_RESULT_DTYPE)
+    _check(lib().modgpu_verify_results(_vp(_dev_addr(results)), count, device, _vp(out.ctypes.data if count else 0)))
+    return out
+
+
+def time_verify_device(expect, src, n, key, result, stream_off=0, device=-1, stream=None, iters=2):
+    """Mean ms per verify call (two launches) over `iters` calls, HIP events on the launch stream."""
+    ms = ctypes.c_float(0)
+    _check(lib().modgpu_time_verify_device(_vp(_dev_addr(expect)), _vp(_dev_addr(src)), n, as_int32(key), stream_off, _vp(_dev_addr(result)),
+                                           device, _vp(stream or 0), iters, ctypes.byref(ms)))
+    return ms.value
+
+
+def verify_kernel_source_hash():
+    """identity of the verify kernels' TU (cycle_verify_kernel.hip and what it includes)"""
+    return lib().modgpu_verify_kernel_source_hash().decode()
+
+
+def debug_set_verify_form(grid=0):
+    """Testing flavour: the most workgroups a verify compare launch takes (0 = shipped: one per CU)."""
+    _debug_lib().modgpu_debug_set_verify_form(grid)
 
 
 def _dev_addr(x):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""check_isa.py <cycle_kernel.s> [<cycle_feed_kernel.s>] | <cycle_to_kernel.s> | <cycle_xfer_kernel.s> | <cycle_rekey_kernel.s> | <cycle_table_kernel.s> | <cycle_rekey_table_kernel.s> -- build-time guard over the gfx950 assembly of the kernel TUs (run by the
+"""check_isa.py <cycle_kernel.s> [<cycle_feed_kernel.s>] | <cycle_to_kernel.s> | <cycle_xfer_kernel.s> | <cycle_rekey_kernel.s> | <cycle_table_kernel.s> | <cycle_rekey_table_kernel.s> | <cycle_verify_kernel.s> -- build-time guard over the gfx950 assembly of the kernel TUs (run by the
 Makefile right after the TUs are compiled and before either object exists; tests/test_capi_cpu.py runs it again and feeds it
 deliberately broken builds).
 
@@ -45,6 +45,12 @@ The rekey table kernels (cycle_rekey_table_kernel.s: plan, finish, stream): the 
 no v_mbcnt; the stream kernel carries the two-keystream blocks under the rekey kernel's rules (fixed temporaries, 60 mads + 30 addc,
 trailing s_nop 0, one v_bitop3_b32 0x96 per dword; 8 blocks: 4 words x 2 unrolled trips), data loads nt and stores nt sc1, and the
 table call's scalar-only entry search; the plan and finish kernels carry no keystream block of either kind.
+The verify kernels (cycle_verify_kernel.s: the init kernel and four forms of the stream kernel -- plain / funnel x keyed / identity): the
+register budget, no spills / scratch / private segment; the keyed forms carry the keystream blocks under the rules above (9 of them: 4
+words x 2 unrolled trips + the cut first chunk's loop), the identity forms and the init kernel none; every data load nt; NO buffer store
+and no buffer atomic anywhere in a stream kernel (it reads its inputs and nothing else), no flat access, its only global store the
+8 bytes of the entry's n, its only atomics 64-bit adds and unsigned mins, as many of the one as of the other; 16 bytes of LDS (the
+workgroup's count and lowest index); the init kernel loads nothing and stores with global_store only.
 Exit status 0 = all of it holds; 1 = findings on stdout."""
 import re
 import sys
@@ -398,6 +404,59 @@ def check_rekey_table(asm, bodies):
     return bad
 
 
+VERIFY_KERNELS = ("modgpu_cycle_verify_init", "modgpu_cycle_verify_kernel")
+
+
+def check_verify(asm, bodies):
+    """the verify kernels' TU (cycle_verify_kernel.s): the init kernel and the stream kernel's four forms"""
+    bad = []
+    kinds = {}
+    for name, fn in bodies.items():
+        kind = next((k for k in VERIFY_KERNELS if k in name), None)
+        if kind is None:
+            bad.append("%s: the verify kernels' TU holds another kernel" % name)
+            continue
+        kinds[kind] = kinds.get(kind, 0) + 1
+        md = metadata(asm, name)
+        if md.get("vgpr_count", 999) > 128 or md.get("sgpr_count", 999) > 102:
+            bad.append("%s: register counts beyond the budget: %s" % (name, md))
+        if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0) or "scratch_" in fn:
+            bad.append("%s: spills, scratch or a private segment: %s" % (name, md))
+        found, findings = keystream_blocks(name, fn)
+        bad += findings
+        if re.search(r"^\s+buffer_(store|atomic)", fn, re.M):
+            bad.append("%s: a verify kernel stores through a buffer descriptor (its inputs are read-only; the stream has no store at all)" % name)
+        if re.search(r"^\s+flat_", fn, re.M):
+            bad.append("%s: flat_ accesses (LDS must be ds_ instructions, results global_)" % name)
+        if kind == "modgpu_cycle_verify_init":
+            if found:
+                bad.append("%s: the init kernel carries a keystream block" % name)
+            if re.search(r"^\s+(buffer|global)_load", fn, re.M) or not re.search(r"^\s+global_store_dword", fn, re.M) or "global_atomic" in fn:
+                bad.append("%s: the init kernel does something other than store its results" % name)
+            continue
+        keyed = name.endswith("Lb1EEv15CycleVerifyArgs")
+        blocks = len([b for b in BLOCK.findall(fn) if "s[94:95]" in b])
+        if keyed and blocks != 9:
+            bad.append("%s: %d keystream blocks, expected 9 (4 words x 2 unrolled trips + the cut first chunk)" % (name, blocks))
+        if not keyed and blocks:
+            bad.append("%s: an identity form carries a keystream block" % name)
+        loads = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_load_dword", ln)]
+        if not loads or not all(ln.endswith(" nt") for ln in loads):
+            bad.append("%s: a data load is not nt" % name)
+        stores = re.findall(r"^\s+(global_store_\w+)", fn, re.M)
+        if stores != ["global_store_dwordx2"]:
+            bad.append("%s: global stores %s, expected the one global_store_dwordx2 of the entry's n" % (name, stores))
+        atomics = re.findall(r"^\s+(global_atomic_\w+)", fn, re.M)
+        adds, mins = atomics.count("global_atomic_add_x2"), atomics.count("global_atomic_umin_x2")
+        if not adds or adds != mins or adds + mins != len(atomics):
+            bad.append("%s: result atomics %s, expected 64-bit adds and unsigned mins in equal numbers and nothing else" % (name, sorted(set(atomics))))
+        if md.get("group_segment_fixed_size", -1) != 16:
+            bad.append("%s: LDS is %s bytes, expected the 16 of the workgroup's count and lowest index" % (name, md.get("group_segment_fixed_size")))
+    if kinds.get("modgpu_cycle_verify_init", 0) != 1 or kinds.get("modgpu_cycle_verify_kernel", 0) != 4:
+        bad.append("the verify kernels' TU holds %d init and %d stream kernels, expected 1 and 4" % (kinds.get("modgpu_cycle_verify_init", 0), kinds.get("modgpu_cycle_verify_kernel", 0)))
+    return bad
+
+
 def check_xfer(asm, bodies):
     """the transfer kernels' TU (cycle_xfer_kernel.s): the upload (ILb1) and the download (ILb0), each plain and funnel"""
     bad = []
@@ -447,6 +506,8 @@ def check(asm):
         if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0) or "scratch_" in bodies[feed[0]]:
             bad.append("%s: spills, scratch or a private segment: %s" % (feed[0], md))
         return bad + check_feed(asm, feed[0], bodies[feed[0]])
+    if any("modgpu_cycle_verify" in n for n in bodies):
+        return bad + check_verify(asm, bodies)
     if any("modgpu_cycle_rekey_table" in n for n in bodies):
         return bad + check_rekey_table(asm, bodies)
     if any("modgpu_cycle_table" in n for n in bodies):

@@ -21,6 +21,7 @@
 #include "cycle_kernel.h"
 #include "cycle_rekey_kernel.h"
 #include "cycle_rekey_table_kernel.h"
+#include "cycle_verify_kernel.h"
 #include "cycle_table_kernel.h"
 #include "cycle_to_kernel.h"
 #include "cycle_xfer_kernel.h"
@@ -929,6 +930,107 @@ int rekey_impl(void *const *dst, const void *const *src, const uint64_t *sizes, 
     }
     return MODGPU_OK;
 }
+
+// ---- verify: count and locate the j with expect[j] != (src[j] ^ ks(key)[off + j]) (modgpu_verify_device / modgpu_verify_batch_device) ----
+// Launch shape (cycle_verify_kernel.h): static chunk assignment on one workgroup per CU.  No ticket pair is drawn, so there is nothing
+// to run out of and no second route -- DESIGN.md 4.10, profiles/r11_verify.json.
+static_assert(sizeof(modgpu_verify_result_t) == sizeof(CycleVerifyResult) && sizeof(modgpu_verify_result_t) == 32 &&
+                  offsetof(modgpu_verify_result_t, first_mismatch) == offsetof(CycleVerifyResult, first_mismatch) &&
+                  offsetof(modgpu_verify_result_t, n) == offsetof(CycleVerifyResult, n) &&
+                  offsetof(modgpu_verify_result_t, reserved) == offsetof(CycleVerifyResult, reserved),
+              "the kernels' result record is the public one");
+#ifdef MODGPU_TESTING_HOOKS
+std::atomic<uint32_t> g_verify_grid{0}; // modgpu_debug_set_verify_form
+uint32_t verify_grid_forced() { return g_verify_grid.load(std::memory_order_relaxed); }
+#else
+constexpr uint32_t verify_grid_forced() { return 0; }
+#endif
+
+// One compare launch over 1..kCycleBatchMax non-empty entries of the current device (key_res == 0: the identity forms).
+int launch_verify(const uint8_t *const *expect, const uint8_t *const *src, const uint64_t *sizes, const uint64_t *offs,
+                  modgpu_verify_result_t *const *results, int n, uint32_t key_res, hipStream_t stream)
+{
+    CycleVerifyArgs a{};
+    const uint64_t chunk = modgpu_verify_chunk_bytes();
+    uint64_t total = 0, bytes = 0;
+    bool misaligned = false;
+    for (int k = 0; k < n; ++k) {
+        CycleVerifyPart &P = a.part[k];
+        const EntryGeom g = entry_geom(expect[k], sizes[k], chunk);
+        P.expect_body = expect[k] + g.head;
+        P.src_body = src[k] + g.head;
+        P.result = reinterpret_cast<CycleVerifyResult *>(results[k]);
+        P.n = sizes[k];
+        P.head_n = (uint32_t)g.head;
+        P.tail_n = (uint32_t)g.tail;
+        P.lead = g.lead;
+        P.end = g.end;
+        if (key_res) entry_bases(g, key_res, offs[k] % lcg::PERIOD, P.base_head, P.base_body, P.base_tail);
+        a.start[k] = (uint32_t)total;
+        total += g.n_chunks > g.first ? g.n_chunks - g.first : 0;
+        bytes += sizes[k];
+        misaligned |= g.words != 0 && ((reinterpret_cast<uintptr_t>(src[k]) - reinterpret_cast<uintptr_t>(expect[k])) & 3) != 0;
+    }
+    for (int k = n; k <= kCycleBatchMax; ++k) a.start[k] = (uint32_t)total;
+    a.n_parts = (uint32_t)n;
+    const uint64_t cap = verify_grid_forced() ? verify_grid_forced() : large_grid();
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(total, cap));
+    const int form = (misaligned ? CYCLE_VERIFY_FUNNEL : CYCLE_VERIFY_PLAIN) | (key_res ? 0 : CYCLE_VERIFY_IDENTITY);
+    const hipError_t e = modgpu_launch_cycle_verify(a, form, grid, stream);
+    if (e != hipSuccess) return fail_hip(e, "verify kernel launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    t_last_launch = {modgpu_verify_kernel_name(form), CYCLE_VERIFY, grid, modgpu_verify_block(), (uint32_t)chunk, bytes, grid, MODGPU_VERIFY_KERNEL_SOURCE_HASH};
+    return MODGPU_OK;
+}
+
+// Everything that is checked before a device is looked at.
+int check_verify_entries(const void *const *expect, const void *const *src, const uint64_t *sizes, int n, const modgpu_verify_result_t *results)
+{
+    if (n < 0 || (n > 0 && (!expect || !src || !sizes))) return fail(MODGPU_ERR_INVALID, "bad entry list");
+    if (n > 0 && !results) return fail(MODGPU_ERR_INVALID, "null result");
+    if (reinterpret_cast<uintptr_t>(results) & 7) return fail(MODGPU_ERR_INVALID, "result not 8-byte aligned");
+    for (int i = 0; i < n; ++i) {
+        if (!sizes[i]) continue;
+        if (!expect[i] || !src[i]) return fail(MODGPU_ERR_INVALID, "null buffer");
+        // (the kernel jumps to a chunk's keystream state by the three bytes of its index in the entry)
+        if (sizes[i] >= (1ull << 41) || entry_geom(static_cast<const uint8_t *>(expect[i]), sizes[i], modgpu_verify_chunk_bytes()).n_chunks >= (1ull << 24))
+            return fail(MODGPU_ERR_INVALID, "an entry that spans 2^24 chunks of 64 KiB or more (1 TiB)");
+    }
+    return MODGPU_OK;
+}
+
+// Entries already checked (check_verify_entries), on the current device, asynchronous on `stream`: one launch initialises all n results,
+// then runs of up to kCycleBatchMax non-empty entries share a compare launch.
+int verify_impl(const void *const *expect, const void *const *src, const uint64_t *sizes, const uint64_t *offs, int n, int32_t key,
+                modgpu_verify_result_t *results, hipStream_t stream)
+{
+    if (n == 0) return MODGPU_OK;
+    int phys = -1;
+    HIP_TRY(hipGetDevice(&phys));
+    if (modgpu_xfer_device_of(results, (uint64_t)n * sizeof(modgpu_verify_result_t)) != phys)
+        return fail(MODGPU_ERR_INVALID, "the result is not device memory of the call's device");
+    const uint32_t key_res = lcg::key_residue(key);
+    (void)hipGetLastError(); // (the launches report hipGetLastError: an earlier call's error must not be taken for theirs)
+    const hipError_t e = modgpu_launch_verify_init(reinterpret_cast<CycleVerifyResult *>(results), (uint64_t)n, stream);
+    if (e != hipSuccess) return fail_hip(e, "verify init launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    t_last_launch = {"modgpu_cycle_verify_init", CYCLE_VERIFY, (uint32_t)(((uint64_t)n + 255) / 256), 256u, 0u, 0, 0u, MODGPU_VERIFY_KERNEL_SOURCE_HASH};
+    int i = 0, idx[kCycleBatchMax];
+    while (const int g = next_run(sizes, n, i, idx, [](int) { return true; })) {
+        const uint8_t *ge[kCycleBatchMax], *gs[kCycleBatchMax];
+        uint64_t gn[kCycleBatchMax], go[kCycleBatchMax];
+        modgpu_verify_result_t *gr[kCycleBatchMax];
+        for (int k = 0; k < g; ++k) {
+            ge[k] = static_cast<const uint8_t *>(expect[idx[k]]);
+            gs[k] = static_cast<const uint8_t *>(src[idx[k]]);
+            gn[k] = sizes[idx[k]];
+            go[k] = offs ? offs[idx[k]] : 0;
+            gr[k] = results + idx[k];
+        }
+        if (const int rc = launch_verify(ge, gs, gn, go, gr, g, key_res, stream)) return rc;
+    }
+    return MODGPU_OK;
+}
 } // namespace
 
 int cycle_to_device_impl(void *dst, const void *src, uint64_t n, int32_t key, uint64_t stream_off, hipStream_t stream)
@@ -1369,6 +1471,46 @@ int modgpu_rekey_batch_device_to(void *const *dst_parts, const void *const *src_
         DeviceScope scope(device);
         if (scope.rc) return scope.rc;
         return rekey_impl(dst_parts, src_parts, sizes, offs_from, offs_to, n_parts, key_from, key_to, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int modgpu_verify_device(const void *dev_expect, const void *dev_src, uint64_t n, int32_t key, uint64_t stream_off,
+                         modgpu_verify_result_t *dev_result, int device, void *hip_stream)
+{
+    return guarded([&]() -> int {
+        if (int rc = check_verify_entries(&dev_expect, &dev_src, &n, 1, dev_result)) return rc;
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        return verify_impl(&dev_expect, &dev_src, &n, &stream_off, 1, key, dev_result, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int modgpu_verify_batch_device(const void *const *expect_parts, const void *const *src_parts, const uint64_t *sizes, const uint64_t *stream_offs,
+                               int n_parts, int32_t key, modgpu_verify_result_t *dev_results, int device, void *hip_stream)
+{
+    return guarded([&]() -> int {
+        if (int rc = check_verify_entries(expect_parts, src_parts, sizes, n_parts, dev_results)) return rc;
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        return verify_impl(expect_parts, src_parts, sizes, stream_offs, n_parts, key, dev_results, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int modgpu_verify_results(const modgpu_verify_result_t *dev_results, uint64_t count, int device, modgpu_verify_result_t *host_out)
+{
+    return guarded([&]() -> int {
+        if (count > 0 && (!dev_results || !host_out)) return fail(MODGPU_ERR_INVALID, "null results or out pointer");
+        if (reinterpret_cast<uintptr_t>(dev_results) & 7) return fail(MODGPU_ERR_INVALID, "results not 8-byte aligned");
+        if (count > (1ull << 40)) return fail(MODGPU_ERR_INVALID, "too many results");
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        if (count == 0) return MODGPU_OK;
+        int phys = -1;
+        HIP_TRY(hipGetDevice(&phys));
+        if (modgpu_xfer_device_of(dev_results, count * sizeof(modgpu_verify_result_t)) != phys)
+            return fail(MODGPU_ERR_INVALID, "the results are not device memory of the call's device");
+        HIP_TRY(hipMemcpy(host_out, dev_results, count * sizeof(modgpu_verify_result_t), hipMemcpyDeviceToHost));
+        return MODGPU_OK;
     });
 }
 
@@ -2086,6 +2228,35 @@ int modgpu_time_rekey_device_to(void *dev_dst, const void *dev_src, uint64_t n, 
     });
 }
 
+int modgpu_time_verify_device(const void *dev_expect, const void *dev_src, uint64_t n, int32_t key, uint64_t stream_off, void *dev_result,
+                              int device, void *hip_stream, int iters, float *ms_per_call)
+{
+    return guarded([&]() -> int {
+        if (iters <= 0 || !ms_per_call) return fail(MODGPU_ERR_INVALID, "bad timing arguments");
+        modgpu_verify_result_t *res = static_cast<modgpu_verify_result_t *>(dev_result);
+        if (int rc = check_verify_entries(&dev_expect, &dev_src, &n, 1, res)) return rc;
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        int rc = MODGPU_OK;
+        hipStream_t st = static_cast<hipStream_t>(hip_stream);
+        hipEvent_t e0, e1;
+        HIP_TRY(hipEventCreate(&e0));
+        HIP_TRY(hipEventCreate(&e1));
+        HIP_TRY(hipEventRecord(e0, st));
+        for (int i = 0; i < iters && rc == MODGPU_OK; ++i) rc = verify_impl(&dev_expect, &dev_src, &n, &stream_off, 1, key, res, st);
+        hipError_t e = hipEventRecord(e1, st);
+        if (e == hipSuccess) e = hipEventSynchronize(e1);
+        float ms = 0.f;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        if (rc) return rc;
+        if (e != hipSuccess) return fail_hip(e, "event timing");
+        *ms_per_call = ms / (float)iters;
+        return MODGPU_OK;
+    });
+}
+
 int modgpu_last_launch(modgpu_launch_info_t *out)
 {
     if (!out) return fail(MODGPU_ERR_INVALID, "null out pointer");
@@ -2130,6 +2301,7 @@ const char *modgpu_xfer_kernel_source_hash(void) { return MODGPU_XFER_KERNEL_SOU
 const char *modgpu_rekey_kernel_source_hash(void) { return MODGPU_REKEY_KERNEL_SOURCE_HASH; }
 const char *modgpu_table_kernel_source_hash(void) { return MODGPU_TABLE_KERNEL_SOURCE_HASH; }
 const char *modgpu_rekey_table_kernel_source_hash(void) { return MODGPU_REKEY_TABLE_KERNEL_SOURCE_HASH; }
+const char *modgpu_verify_kernel_source_hash(void) { return MODGPU_VERIFY_KERNEL_SOURCE_HASH; }
 
 int modgpu_time_cycle_table_device(const void *dev_entries, uint64_t n_entries, void *dev_workspace, uint64_t workspace_bytes,
                                    int device, void *hip_stream, int iters, float *ms_per_call)
@@ -2220,6 +2392,8 @@ void modgpu_debug_set_rekey_form(int shape)
 
 void modgpu_debug_set_table_grid(uint32_t grid) { g_table_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
 void modgpu_debug_set_rekey_table_grid(uint32_t grid) { g_rekey_table_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
+
+void modgpu_debug_set_verify_form(int grid) { g_verify_grid.store(grid <= 0 ? 0u : std::min<uint32_t>((uint32_t)grid, 4096u), std::memory_order_relaxed); }
 
 void modgpu_debug_set_queue_ring(uint32_t lines)
 {
