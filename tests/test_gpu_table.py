@@ -278,7 +278,7 @@ def test_entry_beyond_4_gib(gpu, oracle):
     by the runtime) and compared with the oracle over the source's known pattern."""
     n = (1 << 32) + 77
     src, dst = gpu.DeviceBuffer(n + 64), gpu.DeviceBuffer(n + 64)
-    tile = np.random.default_rng(4).integers(0, 256, size=1 << 24, dtype=np.uint8)
+    tile = np.random.default_rng(4).integers(0, 256, size=(1 << 24) + 13, dtype=np.uint8)
     for at in range(0, n + 64, tile.size):
         src.upload(tile[:min(tile.size, n + 64 - at)], offset=at)
     dst.upload(np.full(61, 0x5A, np.uint8), offset=n + 3)
