@@ -10,6 +10,8 @@ import sys
 import numpy as np
 import pytest
 
+import _csrc_build as B
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -400,33 +402,42 @@ def test_kernel_codegen_guard_passes_the_tree_and_rejects_a_broken_build():
     """The streaming kernels' keystream is a hand-scheduled assembly block in FIXED registers; the work-queue kernel's ticket
     fetch must stay one plain returning atomic.  Whether the compiler kept to that is visible only in its output, so
     modulate_amd/csrc/check_isa.py reads the gfx950 assembly of BOTH kernel TUs -- `make` runs it before it will produce either
-    object.  Here: the tree's TUs pass, and a build with an input of the block pinned into one of its fixed temporaries (round 3's
-    wrong-keystream build) is REJECTED.  hipcc is part of the build container: its absence is a failure, not a skip."""
+    object (next test).  Here: the tree's TUs pass (`make isa-check-main`, 4 kernels), and a build with an input of the block pinned
+    into one of its fixed temporaries (round 3's wrong-keystream build) is REJECTED.  hipcc is part of the build container: its
+    absence is a failure, not a skip."""
     hipcc = "/opt/rocm/bin/hipcc"
     assert os.path.exists(hipcc), "hipcc is missing: the code-generation guard cannot run, and that is not acceptable for a build box"
-    csrc = os.path.join(ROOT, "modulate_amd", "csrc")
-    flags = subprocess.run(["make", "-s", "-C", csrc, "--eval", "print-kflags: ; @echo $(KERNEL_FLAGS)", "print-kflags"],
-                           capture_output=True, text=True).stdout.split()
-    assert "-amdgpu-atomic-optimizer-strategy=None" in flags, flags
-    good = subprocess.run(["make", "-s", "-C", csrc, "isa-check"], capture_output=True, text=True, timeout=900)
-    assert good.returncode == 0 and "check_isa: ok (4 kernels)" in good.stdout, good.stdout[-3000:] + good.stderr[-2000:]
-    broken = subprocess.run(["make", "-s", "-C", csrc, "isa-check-broken"], capture_output=True, text=True, timeout=900)
+    B.isa_check_target("isa-check-main", 4)
+    broken = subprocess.run(["make", "-s", "-C", B.CSRC, "isa-check-broken"], capture_output=True, text=True, timeout=900)
     assert broken.returncode != 0, "the guard accepted a build whose keystream block reads a register the block overwrites"
     assert "the compiler gave a block operand a fixed temporary" in broken.stdout, broken.stdout[-3000:]
-    # the object file rules depend on the guard: a TU that fails it produces neither cycle_kernel.o nor cycle_feed_kernel.o
-    mk = open(os.path.join(csrc, "Makefile")).read()
-    stamp = mk[mk.index("isa_checked.stamp:"):mk.index("cycle_kernel.o:")]
-    assert "check_isa.py cycle_kernel.s cycle_feed_kernel.s" in stamp
-    for obj in ("cycle_kernel.o:", "cycle_feed_kernel.o:"):
-        assert "isa_checked.stamp" in mk[mk.index(obj):].splitlines()[0], obj
 
 
-def _check_isa():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("check_isa", os.path.join(ROOT, "modulate_amd", "csrc", "check_isa.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+def test_isa_check_covers_every_tu_and_the_plan_guards_the_main_pair():
+    """What `make` itself plans and prints, not how the Makefile spells it.  `make isa-check` passes the tree with one line per TU:
+    main first, then the order of the Makefile's table.  The TUs with a ticket
+    atomic, and only they, are assembled and compiled with the atomic-optimizer flag.  Both objects of the main pair wait for the one
+    guard run over both files, which ISA_CHECK=0 leaves out without touching a stamp; the stand-in is wired; the source lists are the
+    hashed ones (test_kernel_source_hash_matches_sources)."""
+    good = subprocess.run(["make", "-s", "-C", B.CSRC, "isa-check"], capture_output=True, text=True, timeout=900)
+    assert good.returncode == 0, good.stdout[-3000:] + good.stderr[-2000:]
+    assert [ln for ln in good.stdout.splitlines() if ln.startswith("check_isa:")] == [
+        "check_isa: ok (4 kernels)", "check_isa: ok (2 kernels)", "check_isa: ok (4 kernels)", "check_isa: ok (2 kernels)",
+        "check_isa: ok (3 kernels)", "check_isa: ok (3 kernels)", "check_isa: ok (5 kernels)"], good.stdout
+    flag = "-amdgpu-atomic-optimizer-strategy=None"
+    assert flag in B.make_var("KERNEL_FLAGS").split()
+    plan = B.dry_run("all")
+    ticket = {"cycle_kernel", "cycle_to_kernel", "cycle_rekey_kernel", "cycle_table_kernel", "cycle_rekey_table_kernel"}
+    for tu in sorted(ticket | {"cycle_feed_kernel", "cycle_xfer_kernel", "cycle_verify_kernel"}):
+        for step in ("-S --cuda-device-only", "-c"):
+            lines = [ln for ln in plan if f" {step} {tu}.hip " in ln]
+            assert len(lines) == 1 and (f" -mllvm {flag} " in lines[0]) == (tu in ticket), (tu, step, lines)
+    for tu in ("cycle_kernel", "cycle_feed_kernel"):
+        B.guard_then_compile(tu, asm="cycle_kernel.s cycle_feed_kernel.s")
+        B.unguarded_plan(tu)
+    B.standin_is_wired("standin_launch.cpp")
+    assert B.make_var("KERNEL_SRC").split() == ["cycle_kernel_impl.h", "cycle_kernel.hip", "cycle_kernel.h", "lcg.h"]
+    assert B.make_var("FEED_SRC").split() == ["cycle_feed_kernel.hip", "cycle_feed_kernel.h", "cycle_kernel_impl.h", "lcg.h"]
 
 
 def test_codegen_guard_sdwa_forwarding_rule():
@@ -441,7 +452,7 @@ def test_codegen_guard_sdwa_forwarding_rule():
     assert broken.returncode != 0, "the guard accepted a read directly behind an SDWA partial write"
     out = broken.stdout
     assert "dst_sel forwarding hazard" in out and "modgpu_cycle_feed_kernel" in out and "modgpu_cycle_kernelILi1ELi256E" in out, out[-3000:]
-    ci = _check_isa()
+    ci = B.load_check_isa()
     subprocess.check_call(["make", "-s", "-C", csrc, "cycle_feed_kernel.s"])
     asm = open(os.path.join(csrc, "cycle_feed_kernel.s")).read()
     assert ci.check(asm) == []
@@ -465,7 +476,7 @@ def test_codegen_guard_barriers_need_the_whole_wave():
     is rejected; so are nt stores and a third barrier."""
     import re
     csrc = os.path.join(ROOT, "modulate_amd", "csrc")
-    ci = _check_isa()
+    ci = B.load_check_isa()
     subprocess.check_call(["make", "-s", "-C", csrc, "cycle_kernel.s", "cycle_feed_kernel.s"])
     main = open(os.path.join(csrc, "cycle_kernel.s")).read()
     feed = open(os.path.join(csrc, "cycle_feed_kernel.s")).read()
@@ -501,7 +512,7 @@ def test_lab_kernel_at_the_products_settings_is_the_products_loop():
     assert os.path.exists(hipcc), "hipcc is missing"
     tools, csrc = os.path.join(ROOT, "tools"), os.path.join(ROOT, "modulate_amd", "csrc")
     subprocess.check_call(["make", "-s", "-C", tools, "golden_kat.inc"])
-    flags = subprocess.run(["make", "-s", "-C", csrc, "--eval", "print-kflags: ; @echo $(KERNEL_FLAGS)", "print-kflags"], capture_output=True, text=True).stdout.split()
+    flags = B.make_var("KERNEL_FLAGS").split()
     r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", *flags, "-I" + csrc, "-I" + os.path.join(ROOT, "include"), "-S", "--cuda-device-only",
                         os.path.join(tools, "tune_cycle.hip"), "-o", "-"], capture_output=True, text=True, timeout=900, cwd=tools)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -620,7 +631,7 @@ def test_codegen_guard_exec_tracking_on_hand_written_snippets():
     """The barrier rule's control-flow walk on assembly small enough to read: a barrier behind the EXEC restore passes; inside a
     saveexec region, inside a loop whose lanes leave one by one (s_andn2 exec), or reachable through a branch that skips the restore,
     it is refused; a region that is closed on both paths of an if / else passes."""
-    ci = _check_isa()
+    ci = B.load_check_isa()
     ok = """
         s_and_saveexec_b64 s[4:5], vcc
         s_cbranch_execz .LBB0_2

@@ -3,12 +3,12 @@ symbols are in both library flavours, argument validation happens before any dev
 passes the tree and rejects a broken build and hand-made faults, and the host code runs clean under ASan/UBSan and TSan against
 the CPU stand-in of the HIP runtime."""
 import os
-import re
 import subprocess
-import sys
 
 import numpy as np
 import pytest
+
+import _csrc_build as B
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "modulate_amd", "csrc")
@@ -72,31 +72,21 @@ def test_validation_comes_before_the_device(modgpu):
 
 
 def test_codegen_guard_of_the_new_tu():
-    """`make isa-check` runs the guard over the old TUs (unchanged: 4 kernels) and, separately, over the out-of-place TU; the
-    same TU built without -amdgpu-atomic-optimizer-strategy=None is REJECTED; the object depends on its own stamp."""
-    good = subprocess.run(["make", "-s", "-C", CSRC, "isa-check"], capture_output=True, text=True, timeout=900)
-    assert good.returncode == 0, good.stdout[-3000:] + good.stderr[-2000:]
-    assert "check_isa: ok (4 kernels)" in good.stdout and "check_isa: ok (2 kernels)" in good.stdout, good.stdout
+    """`make isa-check-to` is the guard's pass over the out-of-place TU (2 kernels); the same TU built without
+    -amdgpu-atomic-optimizer-strategy=None is REJECTED; the object waits for its own guard run, which ISA_CHECK=0 leaves out.
+    (`make isa-check` as a whole: tests/test_capi_cpu.py.)"""
+    B.isa_check_target("isa-check-to", 2)
     broken = subprocess.run(["make", "-s", "-C", CSRC, "isa-check-broken-to"], capture_output=True, text=True, timeout=900)
     assert broken.returncode != 0, "the guard accepted an out-of-place kernel whose ticket atomic is wave-aggregated"
     assert "the atomic optimizer rewrote the ticket atomic" in broken.stdout, broken.stdout[-3000:]
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert re.search(r"^cycle_to_kernel\.o: .*\$\(TO_GUARD\)", mk, re.M) and "TO_GUARD = isa_to_checked.stamp" in mk
-    assert re.search(r"^isa_to_checked\.stamp: .*\n\tpython3 check_isa\.py cycle_to_kernel\.s\n", mk, re.M)
-
-
-def _check_isa():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("check_isa", os.path.join(CSRC, "check_isa.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+    B.guard_then_compile("cycle_to_kernel")
+    B.unguarded_plan("cycle_to_kernel")
 
 
 def test_codegen_guard_rules_on_altered_assembly():
     """Each rule of the out-of-place branch of check_isa.check() on the tree's own assembly with one fault put in by hand."""
     subprocess.check_call(["make", "-s", "-C", CSRC, "cycle_to_kernel.s"])
-    ci = _check_isa()
+    ci = B.load_check_isa()
     asm = open(os.path.join(CSRC, "cycle_to_kernel.s")).read()
     assert ci.check(asm) == []
     names = list(ci.kernel_bodies(asm))
@@ -132,35 +122,9 @@ def test_codegen_guard_rules_on_altered_assembly():
         assert any(want in f for f in got), (want, got[:5])
 
 
-def _runtime(name):
-    p = subprocess.run(["gcc", f"-print-file-name={name}"], capture_output=True, text=True).stdout.strip()
-    return p if os.path.isabs(p) and os.path.exists(p) else None
-
-
-def _san_to_cases(preload, lib, extra_env):
-    from oracle import oracle as O
-    O.build(ref=False)  # here, not in the child: the compiler must not run under a preloaded sanitizer runtime
-    subprocess.check_call(["make", "-s", "-C", CSRC, "sanitize-lib"])
-    env = dict(os.environ, LD_PRELOAD=preload, MODGPU_LIB=os.path.join(ROOT, "modulate_amd", "_san", lib), MODGPU_SHIM_DEVICES="8",
-               MODGPU_REQUIRE_GPU="0", **extra_env)
-    for k in ("MODGPU_DEVICE_ALIAS", "MODGPU_SHIM_SLOW"):
-        env.pop(k, None)
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "san_to_cases.py"), "-x", "-q", "-p", "no:cacheprovider"],
-                       env=env, capture_output=True, text=True, cwd=ROOT, timeout=1500)
-    assert r.returncode == 0 and "6 passed" in r.stdout, r.stdout[-4000:] + r.stderr[-4000:]
-
-
 def test_out_of_place_host_code_under_asan_ubsan():
-    asan, ubsan = _runtime("libasan.so"), _runtime("libubsan.so")
-    if not asan or not ubsan:
-        pytest.skip("gcc sanitizer runtimes not installed")
-    _san_to_cases(f"{asan}:{ubsan}", "libmodgpu_asan.so",
-                  {"ASAN_OPTIONS": "detect_leaks=0:abort_on_error=1", "UBSAN_OPTIONS": "halt_on_error=1:print_stacktrace=1"})
+    B.run_sanitized_cases("san_to_cases.py", "asan", "6 passed")
 
 
 def test_out_of_place_host_code_under_tsan():
-    tsan = _runtime("libtsan.so")
-    if not tsan:
-        pytest.skip("gcc ThreadSanitizer runtime not installed")
-    _san_to_cases(tsan, "libmodgpu_tsan.so",
-                  {"TSAN_OPTIONS": f"halt_on_error=1 second_deadlock_stack=1 suppressions={os.path.join(ROOT, 'tests', 'tsan.supp')}"})
+    B.run_sanitized_cases("san_to_cases.py", "tsan", "6 passed")

@@ -6,10 +6,11 @@ import hashlib
 import os
 import re
 import subprocess
-import sys
 
 import numpy as np
 import pytest
+
+import _csrc_build as B
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "modulate_amd", "csrc")
@@ -87,34 +88,23 @@ def test_validation_comes_before_the_device(modgpu):
 
 
 def test_codegen_guard_of_the_new_tu():
-    """`make isa-check` keeps its earlier lines (two passes of 4 kernels) and adds a pass over the rekey TU (2 kernels); the TU with a
-    block operand pinned into a fixed temporary is REJECTED by name; the object depends on its own stamp; the stand-in is wired."""
-    good = subprocess.run(["make", "-s", "-C", CSRC, "isa-check"], capture_output=True, text=True, timeout=900)
-    assert good.returncode == 0, good.stdout[-3000:] + good.stderr[-2000:]
-    assert good.stdout.count("check_isa: ok (4 kernels)") == 2 and good.stdout.count("check_isa: ok (2 kernels)") == 2, good.stdout
+    """`make isa-check-rekey` is the guard's pass over the rekey TU (2 kernels); the TU with a block operand pinned into a fixed
+    temporary is REJECTED by name; the object waits for its own guard run, which ISA_CHECK=0 leaves out; the stand-in is wired.
+    (`make isa-check` as a whole: tests/test_capi_cpu.py.)"""
+    B.isa_check_target("isa-check-rekey", 2)
     broken = subprocess.run(["make", "-s", "-C", CSRC, "isa-check-broken-rekey"], capture_output=True, text=True, timeout=900)
     assert broken.returncode != 0, "the guard accepted a two-keystream block whose input sits in a fixed temporary"
     assert "the compiler gave a two-keystream block operand a fixed temporary" in broken.stdout, broken.stdout[-3000:]
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert "cycle_rekey_kernel.o: $(REKEY_SRC) $(REKEY_GUARD)" in mk and "REKEY_GUARD = isa_rekey_checked.stamp" in mk
-    assert re.search(r"^isa_rekey_checked\.stamp: .*\n\tpython3 check_isa\.py cycle_rekey_kernel\.s\n", mk, re.M)
-    assert re.search(r"^ifeq \(\$\(ISA_CHECK\),0\)\nREKEY_GUARD =\n", mk, re.M)
-    assert "$(STANDIN)/standin_launch_rekey.cpp" in mk
-    assert "REKEY_SRC = " + " ".join(REKEY_SRC) in mk
-
-
-def _check_isa():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("check_isa", os.path.join(CSRC, "check_isa.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+    B.guard_then_compile("cycle_rekey_kernel")
+    B.unguarded_plan("cycle_rekey_kernel")
+    B.standin_is_wired("standin_launch_rekey.cpp")
+    assert tuple(B.make_var("REKEY_SRC").split()) == REKEY_SRC
 
 
 def test_codegen_guard_rules_on_altered_assembly():
     """Each rule of the rekey branch of check_isa.check() on the tree's own assembly with one fault put in by hand."""
     subprocess.check_call(["make", "-s", "-C", CSRC, "cycle_rekey_kernel.s"])
-    ci = _check_isa()
+    ci = B.load_check_isa()
     asm = open(os.path.join(CSRC, "cycle_rekey_kernel.s")).read()
     assert ci.check(asm) == []
     names = list(ci.kernel_bodies(asm))
@@ -150,35 +140,9 @@ def test_codegen_guard_rules_on_altered_assembly():
         assert any(want in f for f in got), (want, got[:5])
 
 
-def _runtime(name):
-    p = subprocess.run(["gcc", f"-print-file-name={name}"], capture_output=True, text=True).stdout.strip()
-    return p if os.path.isabs(p) and os.path.exists(p) else None
-
-
-def _san_rekey_cases(preload, lib, extra_env):
-    from oracle import oracle as O
-    O.build(ref=False)  # here, not in the child: the compiler must not run under a preloaded sanitizer runtime
-    subprocess.check_call(["make", "-s", "-C", CSRC, "sanitize-lib"])
-    env = dict(os.environ, LD_PRELOAD=preload, MODGPU_LIB=os.path.join(ROOT, "modulate_amd", "_san", lib), MODGPU_SHIM_DEVICES="8",
-               MODGPU_REQUIRE_GPU="0", **extra_env)
-    for k in ("MODGPU_DEVICE_ALIAS", "MODGPU_SHIM_SLOW"):
-        env.pop(k, None)
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "san_rekey_cases.py"), "-x", "-q", "-p", "no:cacheprovider"],
-                       env=env, capture_output=True, text=True, cwd=ROOT, timeout=1500)
-    assert r.returncode == 0 and "6 passed" in r.stdout, r.stdout[-4000:] + r.stderr[-4000:]
-
-
 def test_rekey_host_code_under_asan_ubsan():
-    asan, ubsan = _runtime("libasan.so"), _runtime("libubsan.so")
-    if not asan or not ubsan:
-        pytest.skip("gcc sanitizer runtimes not installed")
-    _san_rekey_cases(f"{asan}:{ubsan}", "libmodgpu_asan.so",
-                     {"ASAN_OPTIONS": "detect_leaks=0:abort_on_error=1", "UBSAN_OPTIONS": "halt_on_error=1:print_stacktrace=1"})
+    B.run_sanitized_cases("san_rekey_cases.py", "asan", "6 passed")
 
 
 def test_rekey_host_code_under_tsan():
-    tsan = _runtime("libtsan.so")
-    if not tsan:
-        pytest.skip("gcc ThreadSanitizer runtime not installed")
-    _san_rekey_cases(tsan, "libmodgpu_tsan.so",
-                     {"TSAN_OPTIONS": f"halt_on_error=1 second_deadlock_stack=1 suppressions={os.path.join(ROOT, 'tests', 'tsan.supp')}"})
+    B.run_sanitized_cases("san_rekey_cases.py", "tsan", "6 passed")

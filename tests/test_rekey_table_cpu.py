@@ -7,10 +7,11 @@ import hashlib
 import os
 import re
 import subprocess
-import sys
 
 import numpy as np
 import pytest
+
+import _csrc_build as B
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "modulate_amd", "csrc")
@@ -181,29 +182,23 @@ def test_host_tier_refuses_before_the_device(modgpu):
 
 
 def test_codegen_guard_of_the_new_tu():
-    """`make isa-check-rekey-table` passes the tree (3 kernels); `make isa-check` prints exactly its earlier lines; the TU with the
-    two-keystream block's operand pinned into a fixed temporary is REJECTED; the object depends on its own stamp; the stand-in is
-    wired."""
-    good = subprocess.run(["make", "-s", "-C", CSRC, "isa-check-rekey-table"], capture_output=True, text=True, timeout=900)
-    assert good.returncode == 0 and "check_isa: ok (3 kernels)" in good.stdout, good.stdout[-3000:] + good.stderr[-2000:]
-    old = subprocess.run(["make", "-s", "-C", CSRC, "isa-check"], capture_output=True, text=True, timeout=900)
-    assert old.returncode == 0 and old.stdout.count("check_isa: ok") == 5, old.stdout
+    """`make isa-check-rekey-table` passes the tree (3 kernels); the TU with the two-keystream block's operand pinned into a fixed
+    temporary is REJECTED; the object waits for its own guard run, which ISA_CHECK=0 leaves out; the stand-in is wired.
+    (`make isa-check` as a whole: tests/test_capi_cpu.py.)"""
+    B.isa_check_target("isa-check-rekey-table", 3)
     broken = subprocess.run(["make", "-s", "-C", CSRC, "isa-check-broken-rekey-table"], capture_output=True, text=True, timeout=900)
     assert broken.returncode != 0, "the guard accepted a two-keystream block whose input sits in a fixed temporary"
     assert "the compiler gave a two-keystream block operand a fixed temporary" in broken.stdout, broken.stdout[-3000:]
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert "cycle_rekey_table_kernel.o: $(REKEY_TABLE_SRC) $(REKEY_TABLE_GUARD)" in mk and "REKEY_TABLE_GUARD = isa_rekey_table_checked.stamp" in mk
-    assert "$(STANDIN)/standin_launch_rekey_table.cpp" in mk
-    assert "REKEY_TABLE_SRC = " + " ".join(REKEY_TABLE_SRC) in mk
+    B.guard_then_compile("cycle_rekey_table_kernel")
+    B.unguarded_plan("cycle_rekey_table_kernel")
+    B.standin_is_wired("standin_launch_rekey_table.cpp")
+    assert tuple(B.make_var("REKEY_TABLE_SRC").split()) == REKEY_TABLE_SRC
 
 
 def test_codegen_guard_rules_on_altered_assembly():
     """Rules of the rekey table branch of check_isa.check() on the tree's own assembly with one fault put in by hand."""
-    import importlib.util
     subprocess.check_call(["make", "-s", "-C", CSRC, "cycle_rekey_table_kernel.s"])
-    spec = importlib.util.spec_from_file_location("check_isa", os.path.join(CSRC, "check_isa.py"))
-    ci = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ci)
+    ci = B.load_check_isa()
     asm = open(os.path.join(CSRC, "cycle_rekey_table_kernel.s")).read()
     assert ci.check(asm) == []
     names = list(ci.kernel_bodies(asm))
@@ -231,35 +226,9 @@ def test_codegen_guard_rules_on_altered_assembly():
         assert any(want in f for f in got), (want, got[:5])
 
 
-def _runtime(name):
-    p = subprocess.run(["gcc", f"-print-file-name={name}"], capture_output=True, text=True).stdout.strip()
-    return p if os.path.isabs(p) and os.path.exists(p) else None
-
-
-def _san_rekey_table_cases(preload, lib, extra_env):
-    from oracle import oracle as O
-    O.build(ref=False)  # here, not in the child: the compiler must not run under a preloaded sanitizer runtime
-    subprocess.check_call(["make", "-s", "-C", CSRC, "sanitize-lib"])
-    env = dict(os.environ, LD_PRELOAD=preload, MODGPU_LIB=os.path.join(ROOT, "modulate_amd", "_san", lib), MODGPU_SHIM_DEVICES="8",
-               MODGPU_REQUIRE_GPU="0", **extra_env)
-    for k in ("MODGPU_DEVICE_ALIAS", "MODGPU_SHIM_SLOW"):
-        env.pop(k, None)
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "san_rekey_table_cases.py"), "-x", "-q", "-p", "no:cacheprovider"],
-                       env=env, capture_output=True, text=True, cwd=ROOT, timeout=1500)
-    assert r.returncode == 0 and "5 passed" in r.stdout, r.stdout[-4000:] + r.stderr[-4000:]
-
-
 def test_rekey_table_host_code_under_asan_ubsan():
-    asan, ubsan = _runtime("libasan.so"), _runtime("libubsan.so")
-    if not asan or not ubsan:
-        pytest.skip("gcc sanitizer runtimes not installed")
-    _san_rekey_table_cases(f"{asan}:{ubsan}", "libmodgpu_asan.so",
-                           {"ASAN_OPTIONS": "detect_leaks=0:abort_on_error=1", "UBSAN_OPTIONS": "halt_on_error=1:print_stacktrace=1"})
+    B.run_sanitized_cases("san_rekey_table_cases.py", "asan", "5 passed")
 
 
 def test_rekey_table_host_code_under_tsan():
-    tsan = _runtime("libtsan.so")
-    if not tsan:
-        pytest.skip("gcc ThreadSanitizer runtime not installed")
-    _san_rekey_table_cases(tsan, "libmodgpu_tsan.so",
-                           {"TSAN_OPTIONS": f"halt_on_error=1 second_deadlock_stack=1 suppressions={os.path.join(ROOT, 'tests', 'tsan.supp')}"})
+    B.run_sanitized_cases("san_rekey_table_cases.py", "tsan", "5 passed")

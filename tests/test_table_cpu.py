@@ -7,10 +7,11 @@ import hashlib
 import os
 import re
 import subprocess
-import sys
 
 import numpy as np
 import pytest
+
+import _csrc_build as B
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "modulate_amd", "csrc")
@@ -165,28 +166,23 @@ def test_host_tier_refuses_before_the_device(modgpu):
 
 
 def test_codegen_guard_of_the_new_tu():
-    """`make isa-check` keeps its earlier lines and adds a fifth pass over the table TU (3 kernels); the TU with the keystream block's
-    lane state pinned into a fixed temporary is REJECTED; the object depends on its own stamp; the stand-in is wired."""
-    good = subprocess.run(["make", "-s", "-C", CSRC, "isa-check"], capture_output=True, text=True, timeout=900)
-    assert good.returncode == 0, good.stdout[-3000:] + good.stderr[-2000:]
-    assert good.stdout.count("check_isa: ok (4 kernels)") == 2 and good.stdout.count("check_isa: ok (2 kernels)") == 2, good.stdout
-    assert good.stdout.count("check_isa: ok (3 kernels)") == 1, good.stdout
+    """`make isa-check-table` is the guard's pass over the table TU (3 kernels); the TU with the keystream block's lane state pinned
+    into a fixed temporary is REJECTED; the object waits for its own guard run, which ISA_CHECK=0 leaves out; the stand-in is wired.
+    (`make isa-check` as a whole: tests/test_capi_cpu.py.)"""
+    B.isa_check_target("isa-check-table", 3)
     broken = subprocess.run(["make", "-s", "-C", CSRC, "isa-check-broken-table"], capture_output=True, text=True, timeout=900)
     assert broken.returncode != 0, "the guard accepted a keystream block whose input sits in a fixed temporary"
     assert "the compiler gave a block operand a fixed temporary" in broken.stdout, broken.stdout[-3000:]
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert "cycle_table_kernel.o: $(TABLE_SRC) $(TABLE_GUARD)" in mk and "TABLE_GUARD = isa_table_checked.stamp" in mk
-    assert "$(STANDIN)/standin_launch_table.cpp" in mk
-    assert "TABLE_SRC = " + " ".join(TABLE_SRC) in mk
+    B.guard_then_compile("cycle_table_kernel")
+    B.unguarded_plan("cycle_table_kernel")
+    B.standin_is_wired("standin_launch_table.cpp")
+    assert tuple(B.make_var("TABLE_SRC").split()) == TABLE_SRC
 
 
 def test_codegen_guard_rules_on_altered_assembly():
     """Rules of the table branch of check_isa.check() on the tree's own assembly with one fault put in by hand."""
-    import importlib.util
     subprocess.check_call(["make", "-s", "-C", CSRC, "cycle_table_kernel.s"])
-    spec = importlib.util.spec_from_file_location("check_isa", os.path.join(CSRC, "check_isa.py"))
-    ci = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ci)
+    ci = B.load_check_isa()
     asm = open(os.path.join(CSRC, "cycle_table_kernel.s")).read()
     assert ci.check(asm) == []
     names = list(ci.kernel_bodies(asm))
@@ -212,35 +208,9 @@ def test_codegen_guard_rules_on_altered_assembly():
         assert any(want in f for f in got), (want, got[:5])
 
 
-def _runtime(name):
-    p = subprocess.run(["gcc", f"-print-file-name={name}"], capture_output=True, text=True).stdout.strip()
-    return p if os.path.isabs(p) and os.path.exists(p) else None
-
-
-def _san_table_cases(preload, lib, extra_env):
-    from oracle import oracle as O
-    O.build(ref=False)  # here, not in the child: the compiler must not run under a preloaded sanitizer runtime
-    subprocess.check_call(["make", "-s", "-C", CSRC, "sanitize-lib"])
-    env = dict(os.environ, LD_PRELOAD=preload, MODGPU_LIB=os.path.join(ROOT, "modulate_amd", "_san", lib), MODGPU_SHIM_DEVICES="8",
-               MODGPU_REQUIRE_GPU="0", **extra_env)
-    for k in ("MODGPU_DEVICE_ALIAS", "MODGPU_SHIM_SLOW"):
-        env.pop(k, None)
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "san_table_cases.py"), "-x", "-q", "-p", "no:cacheprovider"],
-                       env=env, capture_output=True, text=True, cwd=ROOT, timeout=1500)
-    assert r.returncode == 0 and "5 passed" in r.stdout, r.stdout[-4000:] + r.stderr[-4000:]
-
-
 def test_table_host_code_under_asan_ubsan():
-    asan, ubsan = _runtime("libasan.so"), _runtime("libubsan.so")
-    if not asan or not ubsan:
-        pytest.skip("gcc sanitizer runtimes not installed")
-    _san_table_cases(f"{asan}:{ubsan}", "libmodgpu_asan.so",
-                     {"ASAN_OPTIONS": "detect_leaks=0:abort_on_error=1", "UBSAN_OPTIONS": "halt_on_error=1:print_stacktrace=1"})
+    B.run_sanitized_cases("san_table_cases.py", "asan", "5 passed")
 
 
 def test_table_host_code_under_tsan():
-    tsan = _runtime("libtsan.so")
-    if not tsan:
-        pytest.skip("gcc ThreadSanitizer runtime not installed")
-    _san_table_cases(tsan, "libmodgpu_tsan.so",
-                     {"TSAN_OPTIONS": f"halt_on_error=1 second_deadlock_stack=1 suppressions={os.path.join(ROOT, 'tests', 'tsan.supp')}"})
+    B.run_sanitized_cases("san_table_cases.py", "tsan", "5 passed")

@@ -1,16 +1,16 @@
 """CPU checks of the verify entry points (modgpu_verify_device / modgpu_verify_batch_device / modgpu_verify_results,
 include/modgpu.h): the symbols are declared, exported and listed, the new TU has a source hash of its own, argument validation happens
-before any device work, the TU's code-generation guard passes the tree and rejects a broken build and hand-made faults while
-`make isa-check` prints what it printed before, and the host code runs clean under ASan/UBSan and TSan against the CPU stand-in of
-the HIP runtime."""
+before any device work, the TU's code-generation guard passes the tree and rejects a broken build and hand-made faults, and the host
+code runs clean under ASan/UBSan and TSan against the CPU stand-in of the HIP runtime."""
 import hashlib
 import os
 import re
 import subprocess
-import sys
 
 import numpy as np
 import pytest
+
+import _csrc_build as B
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "modulate_amd", "csrc")
@@ -103,40 +103,23 @@ def test_validation_comes_before_the_device(modgpu):
 
 
 def test_codegen_guard_of_the_new_tu():
-    """`make isa-check` prints exactly the lines it printed before this TU existed; `make isa-check-verify` is the TU's own pass
-    (5 kernels: the init kernel and four forms); the TU with a store in its stream loop is REJECTED by name; the object depends on its
-    own stamp, which ISA_CHECK=0 leaves out; the stand-in is wired."""
-    good = subprocess.run(["make", "-s", "-C", CSRC, "isa-check"], capture_output=True, text=True, timeout=900)
-    assert good.returncode == 0, good.stdout[-3000:] + good.stderr[-2000:]
-    lines = [ln for ln in good.stdout.splitlines() if ln.startswith("check_isa:")]
-    assert lines == ["check_isa: ok (4 kernels)", "check_isa: ok (2 kernels)", "check_isa: ok (4 kernels)", "check_isa: ok (2 kernels)",
-                     "check_isa: ok (3 kernels)"], good.stdout
-    own = subprocess.run(["make", "-s", "-C", CSRC, "isa-check-verify"], capture_output=True, text=True, timeout=900)
-    assert own.returncode == 0 and own.stdout.count("check_isa: ok (5 kernels)") == 1, own.stdout[-3000:] + own.stderr[-2000:]
+    """`make isa-check-verify` is the TU's own pass (5 kernels: the init kernel and four forms); the TU with a store in its stream
+    loop is REJECTED by name; the object waits for its own guard run, which ISA_CHECK=0 leaves out; the stand-in is wired.
+    (`make isa-check` as a whole: tests/test_capi_cpu.py.)"""
+    B.isa_check_target("isa-check-verify", 5)
     broken = subprocess.run(["make", "-s", "-C", CSRC, "isa-check-broken-verify"], capture_output=True, text=True, timeout=900)
     assert broken.returncode != 0, "the guard accepted a verify kernel that stores in its stream loop"
     assert "a verify kernel stores through a buffer descriptor" in broken.stdout, broken.stdout[-3000:]
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert "cycle_verify_kernel.o: $(VERIFY_SRC) $(VERIFY_GUARD)" in mk and "VERIFY_GUARD = isa_verify_checked.stamp" in mk
-    assert re.search(r"^isa_verify_checked\.stamp: .*\n\tpython3 check_isa\.py cycle_verify_kernel\.s\n", mk, re.M)
-    assert re.search(r"^ifeq \(\$\(ISA_CHECK\),0\)\nVERIFY_GUARD =\n", mk, re.M)
-    assert not re.search(r"^isa-check:.*cycle_verify_kernel", mk, re.M)
-    assert "$(STANDIN)/standin_launch_verify.cpp" in mk
-    assert "VERIFY_SRC = " + " ".join(VERIFY_SRC) in mk
-
-
-def _check_isa():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("check_isa", os.path.join(CSRC, "check_isa.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+    B.guard_then_compile("cycle_verify_kernel")
+    B.unguarded_plan("cycle_verify_kernel")
+    B.standin_is_wired("standin_launch_verify.cpp")
+    assert tuple(B.make_var("VERIFY_SRC").split()) == VERIFY_SRC
 
 
 def test_codegen_guard_rules_on_altered_assembly():
     """Each rule of the verify branch of check_isa.check() on the tree's own assembly with one fault put in by hand."""
     subprocess.check_call(["make", "-s", "-C", CSRC, "cycle_verify_kernel.s"])
-    ci = _check_isa()
+    ci = B.load_check_isa()
     asm = open(os.path.join(CSRC, "cycle_verify_kernel.s")).read()
     assert ci.check(asm) == []
     names = list(ci.kernel_bodies(asm))
@@ -184,35 +167,9 @@ def test_codegen_guard_rules_on_altered_assembly():
         assert any(want in f for f in got), (want, got[:5])
 
 
-def _runtime(name):
-    p = subprocess.run(["gcc", f"-print-file-name={name}"], capture_output=True, text=True).stdout.strip()
-    return p if os.path.isabs(p) and os.path.exists(p) else None
-
-
-def _san_verify_cases(preload, lib, extra_env):
-    from oracle import oracle as O
-    O.build(ref=False)  # here, not in the child: the compiler must not run under a preloaded sanitizer runtime
-    subprocess.check_call(["make", "-s", "-C", CSRC, "sanitize-lib"])
-    env = dict(os.environ, LD_PRELOAD=preload, MODGPU_LIB=os.path.join(ROOT, "modulate_amd", "_san", lib), MODGPU_SHIM_DEVICES="8",
-               MODGPU_REQUIRE_GPU="0", **extra_env)
-    for k in ("MODGPU_DEVICE_ALIAS", "MODGPU_SHIM_SLOW"):
-        env.pop(k, None)
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "san_verify_cases.py"), "-x", "-q", "-p", "no:cacheprovider"],
-                       env=env, capture_output=True, text=True, cwd=ROOT, timeout=1500)
-    assert r.returncode == 0 and "5 passed" in r.stdout, r.stdout[-4000:] + r.stderr[-4000:]
-
-
 def test_verify_host_code_under_asan_ubsan():
-    asan, ubsan = _runtime("libasan.so"), _runtime("libubsan.so")
-    if not asan or not ubsan:
-        pytest.skip("gcc sanitizer runtimes not installed")
-    _san_verify_cases(f"{asan}:{ubsan}", "libmodgpu_asan.so",
-                      {"ASAN_OPTIONS": "detect_leaks=0:abort_on_error=1", "UBSAN_OPTIONS": "halt_on_error=1:print_stacktrace=1"})
+    B.run_sanitized_cases("san_verify_cases.py", "asan", "5 passed")
 
 
 def test_verify_host_code_under_tsan():
-    tsan = _runtime("libtsan.so")
-    if not tsan:
-        pytest.skip("gcc ThreadSanitizer runtime not installed")
-    _san_verify_cases(tsan, "libmodgpu_tsan.so",
-                      {"TSAN_OPTIONS": f"halt_on_error=1 second_deadlock_stack=1 suppressions={os.path.join(ROOT, 'tests', 'tsan.supp')}"})
+    B.run_sanitized_cases("san_verify_cases.py", "tsan", "5 passed")

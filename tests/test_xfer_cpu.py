@@ -5,10 +5,11 @@ device work, and the host code runs clean under ASan/UBSan and TSan against the 
 import hashlib
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
+
+import _csrc_build as B
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "modulate_amd", "csrc")
@@ -46,18 +47,16 @@ def test_xfer_kernel_source_hash_matches_its_sources(modgpu):
 
 
 def test_codegen_guard_of_the_new_tu():
-    """`make isa-check` keeps its two earlier lines and adds a third pass over the transfer TU (4 kernels); the TU with the download's
-    stores across PCIe made nt is REJECTED; the object depends on its own stamp."""
-    good = subprocess.run(["make", "-s", "-C", CSRC, "isa-check"], capture_output=True, text=True, timeout=900)
-    assert good.returncode == 0, good.stdout[-3000:] + good.stderr[-2000:]
-    assert "check_isa: ok (4 kernels)" in good.stdout and "check_isa: ok (2 kernels)" in good.stdout, good.stdout
-    assert good.stdout.count("check_isa: ok (4 kernels)") == 2, good.stdout
+    """`make isa-check-xfer` is the guard's pass over the transfer TU (4 kernels); the TU with the download's stores across PCIe made
+    nt is REJECTED; the object waits for its own guard run, which ISA_CHECK=0 leaves out; the stand-in is wired.
+    (`make isa-check` as a whole: tests/test_capi_cpu.py.)"""
+    B.isa_check_target("isa-check-xfer", 4)
     broken = subprocess.run(["make", "-s", "-C", CSRC, "isa-check-broken-xfer"], capture_output=True, text=True, timeout=900)
     assert broken.returncode != 0, "the guard accepted nt stores across PCIe in the download kernel"
     assert "a download store across PCIe is not `sc1` without nt" in broken.stdout, broken.stdout[-3000:]
-    mk = open(os.path.join(CSRC, "Makefile")).read()
-    assert "cycle_xfer_kernel.o: $(XFER_SRC) $(XFER_GUARD)" in mk and "XFER_GUARD = isa_xfer_checked.stamp" in mk
-    assert "$(STANDIN)/standin_launch_xfer.cpp" in mk
+    B.guard_then_compile("cycle_xfer_kernel")
+    B.unguarded_plan("cycle_xfer_kernel")
+    B.standin_is_wired("standin_launch_xfer.cpp")
 
 
 def test_validation_comes_before_the_device(modgpu, tmp_path):
@@ -87,35 +86,9 @@ def test_validation_comes_before_the_device(modgpu, tmp_path):
     assert st["gpu_launches"] == before["gpu_launches"] == 0 and st["scalar_calls"] == before["scalar_calls"]
 
 
-def _runtime(name):
-    p = subprocess.run(["gcc", f"-print-file-name={name}"], capture_output=True, text=True).stdout.strip()
-    return p if os.path.isabs(p) and os.path.exists(p) else None
-
-
-def _san_xfer_cases(preload, lib, extra_env):
-    from oracle import oracle as O
-    O.build(ref=False)  # here, not in the child: the compiler must not run under a preloaded sanitizer runtime
-    subprocess.check_call(["make", "-s", "-C", CSRC, "sanitize-lib"])
-    env = dict(os.environ, LD_PRELOAD=preload, MODGPU_LIB=os.path.join(ROOT, "modulate_amd", "_san", lib), MODGPU_SHIM_DEVICES="8",
-               MODGPU_REQUIRE_GPU="0", **extra_env)
-    for k in ("MODGPU_DEVICE_ALIAS", "MODGPU_SHIM_SLOW"):
-        env.pop(k, None)
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "san_xfer_cases.py"), "-x", "-q", "-p", "no:cacheprovider"],
-                       env=env, capture_output=True, text=True, cwd=ROOT, timeout=1500)
-    assert r.returncode == 0 and "14 passed" in r.stdout, r.stdout[-4000:] + r.stderr[-4000:]
-
-
 def test_transfer_host_code_under_asan_ubsan():
-    asan, ubsan = _runtime("libasan.so"), _runtime("libubsan.so")
-    if not asan or not ubsan:
-        pytest.skip("gcc sanitizer runtimes not installed")
-    _san_xfer_cases(f"{asan}:{ubsan}", "libmodgpu_asan.so",
-                    {"ASAN_OPTIONS": "detect_leaks=0:abort_on_error=1", "UBSAN_OPTIONS": "halt_on_error=1:print_stacktrace=1"})
+    B.run_sanitized_cases("san_xfer_cases.py", "asan", "14 passed")
 
 
 def test_transfer_host_code_under_tsan():
-    tsan = _runtime("libtsan.so")
-    if not tsan:
-        pytest.skip("gcc ThreadSanitizer runtime not installed")
-    _san_xfer_cases(tsan, "libmodgpu_tsan.so",
-                    {"TSAN_OPTIONS": f"halt_on_error=1 second_deadlock_stack=1 suppressions={os.path.join(ROOT, 'tests', 'tsan.supp')}"})
+    B.run_sanitized_cases("san_xfer_cases.py", "tsan", "14 passed")
