@@ -95,7 +95,8 @@ extern "C" {
 /* ABI version of this header (bumped on any signature change; ABI 8 also gained modgpu_cycle_device_to and
  * modgpu_cycle_batch_device_to, the four transfer calls modgpu_cycle_host_to_device & co., and modgpu_rekey_device_to and
  * modgpu_rekey_batch_device_to, and the table calls modgpu_cycle_table_device & co., and the rekey table calls
- * modgpu_rekey_table_device & co., and the verify calls modgpu_verify_device & co., additions that change no existing signature). */
+ * modgpu_rekey_table_device & co., and the verify calls modgpu_verify_device & co., and the verify table calls
+ * modgpu_verify_table_device & co., additions that change no existing signature). */
 #define MODGPU_ABI_VERSION 8
 int modgpu_abi_version(void);
 
@@ -342,6 +343,45 @@ int modgpu_verify_batch_device(const void *const *expect_parts, const void *cons
 /* `count` results from device memory of `device` into host_out.  Synchronous (a small copy from the device, like
  * modgpu_table_status): call it after the caller has synchronised the stream the verify calls ran on. */
 int modgpu_verify_results(const modgpu_verify_result_t *dev_results, uint64_t count, int device, modgpu_verify_result_t *host_out);
+
+/* ---- VERIFY TABLE: the verify call over a device-resident table of any length, in three launches -------------------------------------
+ * One entry is a modgpu_table_entry_t as it stands (40 bytes, flags 0) with `dst` read as the COMPARAND (`expect`; never written):
+ * dev_results[i] receives exactly what modgpu_verify_device(dst, src, n, key, stream_off, ...) would have produced for entry i --
+ * the same four fields, first_mismatch counted from the entry's own first byte; n == 0 gives {0, UINT64_MAX, 0, 0}; a key == 0 mod
+ * 2^31-1 is a plain compare.  The bytes of workspace a call over n_entries needs (0 for none, or above MODGPU_TABLE_MAX_ENTRIES): */
+uint64_t modgpu_verify_table_workspace_bytes(uint64_t n_entries);
+
+/* The contract is modgpu_cycle_table_device's, word for word where it applies: THREE launches (plan, finish, stream) whatever the
+ * count -- path_stats().gpu_launches counts 3, modgpu_last_launch reports the stream launch as variant 11 with `bytes` = 0 --;
+ * asynchronous on `hip_stream`, allocation-free, capturable into a hipGraph; the table is read when the call RUNS on the device; the
+ * workspace (modgpu_verify_table_workspace_bytes(n_entries) bytes of device memory of `device`, 8-byte aligned) is the caller's, reset
+ * by the plan launch in stream order, and two calls on one workspace must not overlap in time.  The workspace starts with the table
+ * call's header, so modgpu_table_status reports this call too.
+ *   * EVERYTHING BUT THE RESULTS AND THE WORKSPACE IS READ-ONLY.  There is no overlap rule at all -- any entry's dst or src may
+ *     overlap anything, itself included -- and no _validate function.
+ *   * dev_results: n_entries results in device memory of `device`, 8-byte aligned, the caller's.  THE CALL INITIALISES THEM ITSELF:
+ *     the finish launch stores every entry's result whole (what the < 16 ragged bytes at either end of the entry gave, and n), the
+ *     stream launch then only adds to and lowers valid results.  Nothing needs clearing beforehand; a replayed graph starts clean.
+ *   * Tier 1 (host, MODGPU_ERR_INVALID before anything is queued): modgpu_cycle_table_device's tier 1 with this call's workspace
+ *     size; dev_results NULL with n_entries > 0, not 8-byte aligned, or not reported as device memory of `device` (both ends of the
+ *     range are asked about, as modgpu_verify_device does).  n_entries == 0 queues nothing.
+ *   * Tier 2 (device, by the plan launch): a NULL dst or src with n > 0, nonzero flags, an entry of 1 TiB or more, more than 2^31
+ *     chunks of 64 KiB together.  Any of these makes the whole call write NO RESULT AT ALL -- dev_results stays as the caller left
+ *     it --, modgpu_table_status names the lowest such entry and modgpu_verify_table_summary returns MODGPU_ERR_INVALID. */
+int modgpu_verify_table_device(const modgpu_table_entry_t *dev_entries, uint64_t n_entries, modgpu_verify_result_t *dev_results,
+                               void *dev_workspace, uint64_t workspace_bytes, int device, void *hip_stream);
+
+/* The whole call in 32 bytes, for the caller that asks "is the part intact, and if not, which file first" and does not want to
+ * download n_entries results.  The layout is pinned. */
+typedef struct modgpu_verify_table_summary {
+    uint64_t mismatches;      /* sum of every entry's mismatches */
+    uint64_t first_bad_entry; /* lowest entry index with at least one mismatch; UINT64_MAX if none */
+    uint64_t entries;         /* n_entries of the call that ran */
+    uint64_t reserved;        /* 0 */
+} modgpu_verify_table_summary_t;
+/* Synchronous (a small copy from the device, like modgpu_table_status): call it after the caller has synchronised the stream the
+ * call ran on.  MODGPU_ERR_INVALID if the device refused the call (modgpu_table_status names the entry). */
+int modgpu_verify_table_summary(const void *dev_workspace, int device, modgpu_verify_table_summary_t *out);
 
 /* Replaces CEncryptionCycler::Cycle (CEncryptionCycler.cpp:4-14) for a caller-owned HOST buffer,
  * on the GPU.  Pageable memory is staged through page-locked slots owned by this library (memcpy ->

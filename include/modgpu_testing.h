@@ -45,6 +45,10 @@ int modgpu_time_rekey_table_device(const void *dev_entries, uint64_t n_entries, 
 /* The same for modgpu_verify_device: `iters` back-to-back verify calls (two launches each with n > 0) on one result. */
 int modgpu_time_verify_device(const void *dev_expect, const void *dev_src, uint64_t n, int32_t key, uint64_t stream_off,
                               void *dev_result, int device, void *hip_stream, int iters, float *ms_per_call);
+/* The same for modgpu_verify_table_device: `iters` back-to-back verify table calls (three launches each) on one workspace and one
+ * results array. */
+int modgpu_time_verify_table_device(const void *dev_entries, uint64_t n_entries, void *dev_results, void *dev_workspace,
+                                    uint64_t workspace_bytes, int device, void *hip_stream, int iters, float *ms_per_call);
 
 /* The launch the calling thread made last (any entry point), as the library planned it. */
 typedef struct modgpu_launch_info {
@@ -60,7 +64,8 @@ typedef struct modgpu_launch_info {
                                  the device),
                              9 = the rekey table call's stream kernel (modgpu_rekey_table_device; `bytes` = 0, as for 8),
                              10 = the verify call's compare kernel (modgpu_verify_device / _batch_device; `bytes` = all entries of the
-                                  launch), or its initialising kernel alone (`bytes` = 0) if the call had no non-empty entry */
+                                  launch), or its initialising kernel alone (`bytes` = 0) if the call had no non-empty entry,
+                             11 = the verify table call's stream kernel (modgpu_verify_table_device; `bytes` = 0, as for 8) */
     uint32_t grid;        /* workgroups launched                                                  */
     uint32_t block;       /* threads per workgroup                                                */
     uint32_t chunk_bytes; /* bytes one workgroup trip covers                                      */
@@ -74,7 +79,8 @@ typedef struct modgpu_launch_info {
                                 modgpu_rekey_kernel_source_hash() for variant 7,
                                 modgpu_table_kernel_source_hash() for variant 8,
                                 modgpu_rekey_table_kernel_source_hash() for variant 9,
-                                modgpu_verify_kernel_source_hash() for variant 10; static storage */
+                                modgpu_verify_kernel_source_hash() for variant 10,
+                                modgpu_verify_table_kernel_source_hash() for variant 11; static storage */
 } modgpu_launch_info_t;
 int modgpu_last_launch(modgpu_launch_info_t *out);
 
@@ -167,6 +173,9 @@ const char *modgpu_table_kernel_source_hash(void);
 const char *modgpu_rekey_table_kernel_source_hash(void);
 /* The same for the verify kernels' TU (cycle_verify_kernel.hip, cycle_verify_kernel.h, cycle_kernel_impl.h, cycle_kernel.h, lcg.h). */
 const char *modgpu_verify_kernel_source_hash(void);
+/* The same for the verify table kernels' TU (cycle_verify_table_kernel.hip, cycle_verify_table_kernel.h, cycle_table_kernel.h,
+ * cycle_verify_kernel.h, cycle_kernel_impl.h, cycle_kernel.h, lcg.h). */
+const char *modgpu_verify_table_kernel_source_hash(void);
 
 /* 1 in libmodgpu_testing.so, 0 in libmodgpu.so. */
 int modgpu_testing_hooks(void);
@@ -200,6 +209,10 @@ void modgpu_debug_set_rekey_table_grid(uint32_t grid);
  * static one; its plain / funnel and keyed / identity forms follow from the call's pointers and key.  Measurement
  * (tools/bench_verify.py) and parity tests of small grids. */
 void modgpu_debug_set_verify_form(int grid);
+
+/* The verify table call's stream launch: `grid` workgroups (1..4096), 0 = the shipped grid (one workgroup per CU).
+ * Measurement (tools/bench_verify_table.py) and parity tests of small grids, where one workgroup passes several entries. */
+void modgpu_debug_set_verify_table_grid(uint32_t grid);
 
 /* How the transfer calls (modgpu_cycle_host_to_device & co.) move their bytes: 0 = the transfer kernels (shipped), 1 = the DMA
  * reference form -- per chunk a hipMemcpyAsync into a device slot and an out-of-place launch from there (upload), or an out-of-place

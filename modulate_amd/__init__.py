@@ -22,6 +22,8 @@ from .capi import (  # noqa: F401
     rekey_table_kernel_source_hash, debug_set_rekey_table_grid, RekeyTableEntry, REKEY_TABLE_DTYPE,
     verify_device, verify_batch_device, verify_results, time_verify_device, verify_kernel_source_hash, debug_set_verify_form,
     VERIFY_RESULT_DTYPE, VERIFY_NONE,
+    verify_table_device, verify_table_summary, verify_table_workspace_bytes, time_verify_table_device, verify_table_kernel_source_hash,
+    debug_set_verify_table_grid, VERIFY_TABLE_SUMMARY_DTYPE,
     cycle_host_to_device, cycle_device_to_host, cycle_file_to_device, cycle_device_to_file, xfer_kernel_source_hash, debug_set_xfer_form, XFER_FORMS,
     host_loop_isa, cycle_scalar_host_isa, device_numa_node, numa_probe, host_policy, host_policy_engine, host_trace, host_trace_read, host_pool_stats, host_chunking, HOST_TRACE_KINDS,
 )

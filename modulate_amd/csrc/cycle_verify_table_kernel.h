@@ -1,0 +1,55 @@
+// cycle_verify_table_kernel.h -- launch interface of the VERIFY TABLE kernels (cycle_verify_table_kernel.hip): a table of verify entries
+// that lives in device memory, any number of them, in three launches whatever the count -- for entry i the count of the j with
+// dst_i[j] != (src_i[j] ^ ks(key_i)[off_i + j]) and the lowest such j, dst being the comparand.  Nothing is written but the entries'
+// results and the workspace.  Its own TU with a source hash of its own (modgpu_verify_table_kernel_source_hash); the keystream
+// arithmetic is cycle_kernel_impl.h's (ALG 2).
+//
+// The entry is the table call's (CycleTableEntry), the per-entry record the table call's (CycleTablePlan, dst_origin read as the
+// comparand's chunk origin), the result the verify call's (CycleVerifyResult).  The workspace is the table call's with one more line;
+// its layout is planned on the host (modgpu_capi.cpp: verify_table_layout) and handed to every launch in VerifyTableArgs:
+//   hdr     CycleTableHdr, the table call's own header: modgpu_table_status reads this kind of call's workspace too
+//   sum     VerifyTableSummary, the line behind the header: the whole call's count and its lowest dirty entry (plan resets it)
+//   blk     per 1024 entries: their chunk count and whether one of them is bad (plan -> finish)
+//   plan    per entry: CycleTablePlan (plan -> finish, stream)
+//   level   the 16-ary search levels of the chunk starts, as the table call's (finish -> stream)
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+#include "cycle_table_kernel.h"  // CycleTableEntry, CycleTableHdr, CycleTableBlk, CycleTablePlan and the table call's limits
+#include "cycle_verify_kernel.h" // CycleVerifyResult, kVerifyNone
+
+// reporting only (modgpu_last_launch): the stream launch of a verify table call
+constexpr int CYCLE_VERIFY_TABLE = 11;
+
+// modgpu_verify_table_summary_t (include/modgpu.h) in its first 32 bytes; one line of the workspace
+struct VerifyTableSummary {
+    unsigned long long mismatches;      // sum of every entry's mismatches (finish: the edges; stream: the bodies)
+    unsigned long long first_bad_entry; // lowest entry index with a mismatch, kVerifyNone if none
+    unsigned long long entries;         // n_entries of the call
+    unsigned long long reserved;
+    unsigned long long pad[4];
+};
+static_assert(sizeof(VerifyTableSummary) == 64, "one line");
+
+struct VerifyTableArgs {
+    const CycleTableEntry *entries;
+    uint64_t n;
+    CycleTableHdr *hdr;
+    VerifyTableSummary *sum;
+    CycleTableBlk *blk;
+    CycleTablePlan *plan;
+    CycleVerifyResult *results;    // n results in the caller's device memory: stored whole by finish, added to and lowered by stream
+    uint32_t *level[kTableLevels]; // level[k][j] = start of entry j * 16^k; unused levels nullptr
+    uint64_t level_n[kTableLevels];
+    uint32_t top;                  // highest level (<= 16 keys)
+    uint32_t n_blk;                // ceil(n / 1024)
+};
+
+uint32_t modgpu_verify_table_chunk_bytes();
+uint32_t modgpu_verify_table_block();
+const char *modgpu_verify_table_kernel_name();
+// The three launches of one call, in this order on one stream.  Each returns hipGetLastError().
+hipError_t modgpu_launch_verify_table_plan(const VerifyTableArgs &a, hipStream_t stream);
+hipError_t modgpu_launch_verify_table_finish(const VerifyTableArgs &a, hipStream_t stream);
+hipError_t modgpu_launch_verify_table_stream(const VerifyTableArgs &a, uint32_t grid, hipStream_t stream);

@@ -21,6 +21,7 @@
 #include "cycle_kernel.h"
 #include "cycle_rekey_kernel.h"
 #include "cycle_rekey_table_kernel.h"
+#include "cycle_verify_table_kernel.h"
 #include "cycle_verify_kernel.h"
 #include "cycle_table_kernel.h"
 #include "cycle_to_kernel.h"
@@ -1394,6 +1395,95 @@ int rekey_table_impl(const modgpu_rekey_table_entry_t *entries, uint64_t n, void
                      MODGPU_REKEY_TABLE_KERNEL_SOURCE_HASH};
     return MODGPU_OK;
 }
+
+// ---- a table of verify entries in device memory (modgpu_verify_table_device) --------------------------------------------------------
+static_assert(sizeof(modgpu_verify_table_summary_t) == 32 && offsetof(modgpu_verify_table_summary_t, first_bad_entry) == offsetof(VerifyTableSummary, first_bad_entry) &&
+                  offsetof(modgpu_verify_table_summary_t, entries) == offsetof(VerifyTableSummary, entries) &&
+                  offsetof(modgpu_verify_table_summary_t, reserved) == offsetof(VerifyTableSummary, reserved),
+              "the summary line starts with the public record");
+
+// The table call's layout with one line for the summary put in right behind the header (every later section 64 bytes further on): the
+// header comes first here too, so modgpu_table_status reads this kind of workspace.
+struct VerifyTableLayout {
+    TableLayout t; // offsets already moved
+    uint64_t sum, bytes;
+};
+VerifyTableLayout verify_table_layout(uint64_t n)
+{
+    VerifyTableLayout L{table_layout(n), sizeof(CycleTableHdr), 0};
+    constexpr uint64_t line = sizeof(VerifyTableSummary);
+    L.t.blk += line;
+    L.t.plan += line;
+    for (uint32_t k = 0; k <= L.t.top; ++k) L.t.level[k] += line;
+    L.t.bytes += line;
+    L.bytes = L.t.bytes;
+    return L;
+}
+
+// The stream launch's grid: one workgroup per CU on every CU, as the verify kernel (DESIGN.md 4.11 has the A/B against the table
+// call's 25 per 32 CUs)
+#ifdef MODGPU_TESTING_HOOKS
+std::atomic<uint32_t> g_verify_table_grid{0}; // modgpu_debug_set_verify_table_grid
+uint32_t verify_table_grid_forced() { return g_verify_table_grid.load(std::memory_order_relaxed); }
+#else
+constexpr uint32_t verify_table_grid_forced() { return 0; }
+#endif
+uint32_t verify_table_grid()
+{
+    if (verify_table_grid_forced()) return verify_table_grid_forced();
+    return std::max<uint32_t>(1, large_grid());
+}
+
+// Tier 1 (include/modgpu.h): everything checked before anything is queued; then the three launches on `stream`.
+int verify_table_impl(const modgpu_table_entry_t *entries, uint64_t n, modgpu_verify_result_t *results, void *ws, uint64_t ws_bytes, int device,
+                      hipStream_t stream)
+{
+    if (n == 0) return MODGPU_OK;
+    if (n > kTableMaxEntries) return fail(MODGPU_ERR_INVALID, "more than 4194304 entries (the table call's limit)");
+    if (!entries || !ws) return fail(MODGPU_ERR_INVALID, "null table or workspace");
+    if (!results) return fail(MODGPU_ERR_INVALID, "null results");
+    if ((reinterpret_cast<uintptr_t>(entries) | reinterpret_cast<uintptr_t>(ws)) & 7) return fail(MODGPU_ERR_INVALID, "table or workspace not 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(results) & 7) return fail(MODGPU_ERR_INVALID, "results not 8-byte aligned");
+    const VerifyTableLayout L = verify_table_layout(n);
+    if (ws_bytes < L.bytes) return fail(MODGPU_ERR_INVALID, "workspace smaller than modgpu_verify_table_workspace_bytes(n_entries)");
+    DeviceScope scope(device);
+    if (scope.rc) return scope.rc;
+    int phys = -1;
+    HIP_TRY(hipGetDevice(&phys));
+    if (modgpu_xfer_device_of(entries, n * sizeof(modgpu_table_entry_t)) != phys || modgpu_xfer_device_of(ws, L.bytes) != phys)
+        return fail(MODGPU_ERR_INVALID, "the table or the workspace is not device memory of the call's device");
+    if (modgpu_xfer_device_of(results, n * sizeof(modgpu_verify_result_t)) != phys)
+        return fail(MODGPU_ERR_INVALID, "the results are not device memory of the call's device");
+    uint8_t *const w = static_cast<uint8_t *>(ws);
+    VerifyTableArgs a{};
+    a.entries = reinterpret_cast<const CycleTableEntry *>(entries);
+    a.n = n;
+    a.hdr = reinterpret_cast<CycleTableHdr *>(w);
+    a.sum = reinterpret_cast<VerifyTableSummary *>(w + L.sum);
+    a.blk = reinterpret_cast<CycleTableBlk *>(w + L.t.blk);
+    a.plan = reinterpret_cast<CycleTablePlan *>(w + L.t.plan);
+    a.results = reinterpret_cast<CycleVerifyResult *>(results);
+    for (uint32_t k = 0; k <= L.t.top; ++k) {
+        a.level[k] = reinterpret_cast<uint32_t *>(w + L.t.level[k]);
+        a.level_n[k] = L.t.level_n[k];
+    }
+    a.top = L.t.top;
+    a.n_blk = L.t.n_blk;
+    const uint32_t grid = verify_table_grid();
+    (void)hipGetLastError(); // (the launches report hipGetLastError: an earlier call's error must not be taken for theirs)
+    hipError_t e = modgpu_launch_verify_table_plan(a, stream);
+    if (e != hipSuccess) return fail_hip(e, "verify table plan launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    e = modgpu_launch_verify_table_finish(a, stream);
+    if (e != hipSuccess) return fail_hip(e, "verify table finish launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    e = modgpu_launch_verify_table_stream(a, grid, stream);
+    if (e != hipSuccess) return fail_hip(e, "verify table stream launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    t_last_launch = {modgpu_verify_table_kernel_name(), CYCLE_VERIFY_TABLE, grid, modgpu_verify_table_block(), modgpu_verify_table_chunk_bytes(), 0, grid,
+                     MODGPU_VERIFY_TABLE_KERNEL_SOURCE_HASH};
+    return MODGPU_OK;
+}
 } // namespace
 
 } // namespace modgpu
@@ -1567,6 +1657,43 @@ int modgpu_rekey_table_device(const modgpu_rekey_table_entry_t *dev_entries, uin
 int modgpu_rekey_table_validate(const modgpu_rekey_table_entry_t *host_entries, uint64_t n_entries)
 {
     return guarded([&]() -> int { return table_validate_impl(host_entries, n_entries); });
+}
+
+uint64_t modgpu_verify_table_workspace_bytes(uint64_t n_entries)
+{
+    return n_entries == 0 || n_entries > kTableMaxEntries ? 0 : verify_table_layout(n_entries).bytes;
+}
+
+int modgpu_verify_table_device(const modgpu_table_entry_t *dev_entries, uint64_t n_entries, modgpu_verify_result_t *dev_results, void *dev_workspace,
+                               uint64_t workspace_bytes, int device, void *hip_stream)
+{
+    return guarded([&]() -> int {
+        return verify_table_impl(dev_entries, n_entries, dev_results, dev_workspace, workspace_bytes, device, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int modgpu_verify_table_summary(const void *dev_workspace, int device, modgpu_verify_table_summary_t *out)
+{
+    return guarded([&]() -> int {
+        if (!dev_workspace || !out) return fail(MODGPU_ERR_INVALID, "null workspace or out pointer");
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        int phys = -1;
+        HIP_TRY(hipGetDevice(&phys));
+        struct {
+            CycleTableHdr h;
+            VerifyTableSummary s;
+        } top;
+        if (modgpu_xfer_device_of(dev_workspace, sizeof top) != phys) return fail(MODGPU_ERR_INVALID, "the workspace is not device memory of the call's device");
+        HIP_TRY(hipMemcpy(&top, dev_workspace, sizeof top, hipMemcpyDeviceToHost));
+        if (top.h.first_bad != kTableNoBad)
+            return fail(MODGPU_ERR_INVALID, "the device refused entry " + std::to_string(top.h.first_bad) + " (the call wrote no result)");
+        out->mismatches = top.s.mismatches;
+        out->first_bad_entry = top.s.first_bad_entry;
+        out->entries = top.s.entries;
+        out->reserved = 0;
+        return MODGPU_OK;
+    });
 }
 
 int modgpu_cycle_host(uint8_t *host_buf, uint64_t n, int32_t key, uint64_t stream_off, int device)
@@ -2302,6 +2429,7 @@ const char *modgpu_rekey_kernel_source_hash(void) { return MODGPU_REKEY_KERNEL_S
 const char *modgpu_table_kernel_source_hash(void) { return MODGPU_TABLE_KERNEL_SOURCE_HASH; }
 const char *modgpu_rekey_table_kernel_source_hash(void) { return MODGPU_REKEY_TABLE_KERNEL_SOURCE_HASH; }
 const char *modgpu_verify_kernel_source_hash(void) { return MODGPU_VERIFY_KERNEL_SOURCE_HASH; }
+const char *modgpu_verify_table_kernel_source_hash(void) { return MODGPU_VERIFY_TABLE_KERNEL_SOURCE_HASH; }
 
 int modgpu_time_cycle_table_device(const void *dev_entries, uint64_t n_entries, void *dev_workspace, uint64_t workspace_bytes,
                                    int device, void *hip_stream, int iters, float *ms_per_call)
@@ -2357,6 +2485,35 @@ int modgpu_time_rekey_table_device(const void *dev_entries, uint64_t n_entries, 
     });
 }
 
+int modgpu_time_verify_table_device(const void *dev_entries, uint64_t n_entries, void *dev_results, void *dev_workspace, uint64_t workspace_bytes,
+                                    int device, void *hip_stream, int iters, float *ms_per_call)
+{
+    return guarded([&]() -> int {
+        if (iters <= 0 || !ms_per_call) return fail(MODGPU_ERR_INVALID, "bad timing arguments");
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        int rc = MODGPU_OK;
+        hipStream_t st = static_cast<hipStream_t>(hip_stream);
+        hipEvent_t e0, e1;
+        HIP_TRY(hipEventCreate(&e0));
+        HIP_TRY(hipEventCreate(&e1));
+        HIP_TRY(hipEventRecord(e0, st));
+        for (int i = 0; i < iters && rc == MODGPU_OK; ++i)
+            rc = verify_table_impl(static_cast<const modgpu_table_entry_t *>(dev_entries), n_entries, static_cast<modgpu_verify_result_t *>(dev_results), dev_workspace,
+                                   workspace_bytes, -1, st);
+        hipError_t e = hipEventRecord(e1, st);
+        if (e == hipSuccess) e = hipEventSynchronize(e1);
+        float ms = 0.f;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        if (rc) return rc;
+        if (e != hipSuccess) return fail_hip(e, "event timing");
+        *ms_per_call = ms / (float)iters;
+        return MODGPU_OK;
+    });
+}
+
 int modgpu_testing_hooks(void)
 {
 #ifdef MODGPU_TESTING_HOOKS
@@ -2392,6 +2549,8 @@ void modgpu_debug_set_rekey_form(int shape)
 
 void modgpu_debug_set_table_grid(uint32_t grid) { g_table_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
 void modgpu_debug_set_rekey_table_grid(uint32_t grid) { g_rekey_table_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
+
+void modgpu_debug_set_verify_table_grid(uint32_t grid) { g_verify_table_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
 
 void modgpu_debug_set_verify_form(int grid) { g_verify_grid.store(grid <= 0 ? 0u : std::min<uint32_t>((uint32_t)grid, 4096u), std::memory_order_relaxed); }
 
