@@ -96,7 +96,8 @@ extern "C" {
  * modgpu_cycle_batch_device_to, the four transfer calls modgpu_cycle_host_to_device & co., and modgpu_rekey_device_to and
  * modgpu_rekey_batch_device_to, and the table calls modgpu_cycle_table_device & co., and the rekey table calls
  * modgpu_rekey_table_device & co., and the verify calls modgpu_verify_device & co., and the verify table calls
- * modgpu_verify_table_device & co., additions that change no existing signature). */
+ * modgpu_verify_table_device & co., and the rekey verify calls modgpu_verify_rekey_device and modgpu_verify_rekey_batch_device,
+ * additions that change no existing signature). */
 #define MODGPU_ABI_VERSION 8
 int modgpu_abi_version(void);
 
@@ -343,6 +344,36 @@ int modgpu_verify_batch_device(const void *const *expect_parts, const void *cons
 /* `count` results from device memory of `device` into host_out.  Synchronous (a small copy from the device, like
  * modgpu_table_status): call it after the caller has synchronised the stream the verify calls ran on. */
 int modgpu_verify_results(const modgpu_verify_result_t *dev_results, uint64_t count, int device, modgpu_verify_result_t *host_out);
+
+/* ---- VERIFY REKEY: is this buffer what the rekey would have produced from that one?  The verify call against two keystreams ---------
+ * Compares dev_expect[j] with dev_src[j] ^ ks(key_from)[off_from + j] ^ ks(key_to)[off_to + j] for j = 0 .. n-1 -- the bytes
+ * modgpu_rekey_device_to would have written -- where the data lies, in one pass that READS 2n bytes and writes the 32 bytes of
+ * *dev_result: mismatching BYTES, the lowest mismatching index counted from the entry's first byte, n, 0.  Without it a caller that
+ * no longer has the plaintext has to rekey again into scratch memory as large as the data and compare that with the identity key.
+ * The contract is modgpu_verify_device's, word for word where it applies: asynchronous on `hip_stream`; `device` -1 = the current
+ * device, an explicit device leaves the thread's current device as it was; allocation-free; capturable into a hipGraph, a replay
+ * starts from a clean result (the call initialises its result itself, in stream order); it draws no ticket line and cannot degrade
+ * for lack of scratch; any alignment on either side, the two offsets' phases independent of each other and of the pointers'; no
+ * overlap rule at all (nothing but the result is written); page-locked host memory on either input is supported, not tuned;
+ * n == 0 gives {0, UINT64_MAX, 0, 0}.  MODGPU_ERR_INVALID before anything is queued: a NULL input with n > 0, a NULL, misaligned or
+ * non-device result, an entry that spans 2^24 chunks of 64 KiB or more.  modgpu_verify_results reads the result back.
+ *   * Degenerate keystreams follow modgpu_rekey_device_to's rules: a key == 0 mod 2^31-1 leaves only the other keystream (both: a
+ *     plain compare), and the same reduced key at offsets equal mod 2^31-2 is a plain compare (ks ^ ks = 0).  Those entries run on
+ *     modgpu_verify_device's kernels and are reported as variant 10; only entries whose two streams really differ reach the
+ *     two-keystream kernel (variant 12).
+ *   * Launches (path_stats().gpu_launches counts them): ONE to initialise the results of the call, then one per started group of 16
+ *     non-empty entries -- 2 for this call with n > 0, 1 with n == 0. */
+int modgpu_verify_rekey_device(const void *dev_expect, const void *dev_src, uint64_t n, int32_t key_from, uint64_t off_from,
+                               int32_t key_to, uint64_t off_to, modgpu_verify_result_t *dev_result, int device, void *hip_stream);
+
+/* n_parts entries of ONE device under one pair of keys, dev_results[i] the result of entry i: everything
+ * modgpu_verify_rekey_device says holds per entry.  offs_from / offs_to NULL = 0 for every entry.  Any n_parts is taken: one launch
+ * initialises all n_parts results, then one launch per started group of 16 non-empty entries whose two streams differ and one per
+ * started group of 16 non-empty entries whose streams coincide (or of which a key is the identity), in that order on the same stream.
+ * A negative n_parts, or NULL arrays or a NULL dev_results with n_parts > 0, is MODGPU_ERR_INVALID; n_parts == 0 queues nothing. */
+int modgpu_verify_rekey_batch_device(const void *const *expect_parts, const void *const *src_parts, const uint64_t *sizes,
+                                     const uint64_t *offs_from, const uint64_t *offs_to, int n_parts, int32_t key_from, int32_t key_to,
+                                     modgpu_verify_result_t *dev_results, int device, void *hip_stream);
 
 /* ---- VERIFY TABLE: the verify call over a device-resident table of any length, in three launches -------------------------------------
  * One entry is a modgpu_table_entry_t as it stands (40 bytes, flags 0) with `dst` read as the COMPARAND (`expect`; never written):

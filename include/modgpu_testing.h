@@ -45,6 +45,10 @@ int modgpu_time_rekey_table_device(const void *dev_entries, uint64_t n_entries, 
 /* The same for modgpu_verify_device: `iters` back-to-back verify calls (two launches each with n > 0) on one result. */
 int modgpu_time_verify_device(const void *dev_expect, const void *dev_src, uint64_t n, int32_t key, uint64_t stream_off,
                               void *dev_result, int device, void *hip_stream, int iters, float *ms_per_call);
+/* The same for modgpu_verify_rekey_device: `iters` back-to-back rekey verify calls (two launches each with n > 0) on one result. */
+int modgpu_time_verify_rekey_device(const void *dev_expect, const void *dev_src, uint64_t n, int32_t key_from, uint64_t off_from,
+                                    int32_t key_to, uint64_t off_to, void *dev_result, int device, void *hip_stream, int iters,
+                                    float *ms_per_call);
 /* The same for modgpu_verify_table_device: `iters` back-to-back verify table calls (three launches each) on one workspace and one
  * results array. */
 int modgpu_time_verify_table_device(const void *dev_entries, uint64_t n_entries, void *dev_results, void *dev_workspace,
@@ -65,7 +69,9 @@ typedef struct modgpu_launch_info {
                              9 = the rekey table call's stream kernel (modgpu_rekey_table_device; `bytes` = 0, as for 8),
                              10 = the verify call's compare kernel (modgpu_verify_device / _batch_device; `bytes` = all entries of the
                                   launch), or its initialising kernel alone (`bytes` = 0) if the call had no non-empty entry,
-                             11 = the verify table call's stream kernel (modgpu_verify_table_device; `bytes` = 0, as for 8) */
+                             11 = the verify table call's stream kernel (modgpu_verify_table_device; `bytes` = 0, as for 8),
+                             12 = the rekey verify call's two-keystream compare kernel (modgpu_verify_rekey_device / _batch_device;
+                                  `bytes` = all entries of the launch); its entries with coinciding streams are a variant 10 launch */
     uint32_t grid;        /* workgroups launched                                                  */
     uint32_t block;       /* threads per workgroup                                                */
     uint32_t chunk_bytes; /* bytes one workgroup trip covers                                      */
@@ -80,7 +86,8 @@ typedef struct modgpu_launch_info {
                                 modgpu_table_kernel_source_hash() for variant 8,
                                 modgpu_rekey_table_kernel_source_hash() for variant 9,
                                 modgpu_verify_kernel_source_hash() for variant 10,
-                                modgpu_verify_table_kernel_source_hash() for variant 11; static storage */
+                                modgpu_verify_table_kernel_source_hash() for variant 11,
+                                modgpu_rekey_verify_kernel_source_hash() for variant 12; static storage */
 } modgpu_launch_info_t;
 int modgpu_last_launch(modgpu_launch_info_t *out);
 
@@ -176,6 +183,9 @@ const char *modgpu_verify_kernel_source_hash(void);
 /* The same for the verify table kernels' TU (cycle_verify_table_kernel.hip, cycle_verify_table_kernel.h, cycle_table_kernel.h,
  * cycle_verify_kernel.h, cycle_kernel_impl.h, cycle_kernel.h, lcg.h). */
 const char *modgpu_verify_table_kernel_source_hash(void);
+/* The same for the rekey verify kernel's TU (cycle_rekey_verify_kernel.hip, cycle_rekey_verify_kernel.h, cycle_verify_kernel.h,
+ * cycle_rekey_impl.h, cycle_kernel_impl.h, cycle_kernel.h, lcg.h). */
+const char *modgpu_rekey_verify_kernel_source_hash(void);
 
 /* 1 in libmodgpu_testing.so, 0 in libmodgpu.so. */
 int modgpu_testing_hooks(void);
@@ -206,8 +216,9 @@ void modgpu_debug_set_rekey_table_grid(uint32_t grid);
 
 /* The verify call's compare launch: at most `grid` workgroups (1..4096), 0 or less = the shipped grid (one workgroup per CU on
  * every CU; DESIGN.md 4.10 has the A/B against the out-of-place kernel's 25 per 32 CUs).  The kernel has one chunk assignment, the
- * static one; its plain / funnel and keyed / identity forms follow from the call's pointers and key.  Measurement
- * (tools/bench_verify.py) and parity tests of small grids. */
+ * static one; its plain / funnel and keyed / identity forms follow from the call's pointers and key.  The same cap holds for the
+ * rekey verify call's compare launches (modgpu_verify_rekey_device, both kernels it may run on).  Measurement
+ * (tools/bench_verify.py, tools/bench_verify_rekey.py) and parity tests of small grids. */
 void modgpu_debug_set_verify_form(int grid);
 
 /* The verify table call's stream launch: `grid` workgroups (1..4096), 0 = the shipped grid (one workgroup per CU).

@@ -85,6 +85,9 @@ EXPORTS = {
     "modgpu_verify_table_workspace_bytes": (_u64, [_u64]),
     "modgpu_verify_table_device": (_int, [_vp, _u64, _vp, _vp, _u64, _int, _vp]),
     "modgpu_verify_table_summary": (_int, [_vp, _int, _vp]),
+    "modgpu_verify_rekey_device": (_int, [_vp, _vp, _u64, _i32, _u64, _i32, _u64, _vp, _int, _vp]),
+    "modgpu_verify_rekey_batch_device": (_int, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64), ctypes.POINTER(_u64),
+                                                ctypes.POINTER(_u64), _int, _i32, _i32, _vp, _int, _vp]),
 }
 
 
@@ -170,6 +173,8 @@ TESTING_EXPORTS = {
     "modgpu_verify_kernel_source_hash": (ctypes.c_char_p, []),
     "modgpu_time_verify_table_device": (_int, [_vp, _u64, _vp, _vp, _u64, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
     "modgpu_verify_table_kernel_source_hash": (ctypes.c_char_p, []),
+    "modgpu_time_verify_rekey_device": (_int, [_vp, _vp, _u64, _i32, _u64, _i32, _u64, _vp, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
+    "modgpu_rekey_verify_kernel_source_hash": (ctypes.c_char_p, []),
 }
 # include/modgpu_testing.h, modgpu_debug_* group: ONLY in libmodgpu_testing.so
 DEBUG_EXPORTS = {
@@ -927,6 +932,56 @@ def verify_kernel_source_hash():
 def debug_set_verify_form(grid=0):
     """Testing flavour: the most workgroups a verify compare launch takes (0 = shipped: one per CU)."""
     _debug_lib().modgpu_debug_set_verify_form(grid)
+
+
+def verify_rekey_device(expect, src, key_from, key_to, off_from=0, off_to=0, result=None, device=-1, stream=None, *, n=None):
+    """Asynchronous REKEY VERIFY of n bytes at raw device addresses: counts the j with expect[j] != (src[j] ^ ks(key_from)[off_from + j]
+    ^ ks(key_to)[off_to + j]) -- the bytes rekey_device_to would have written -- and finds the lowest, in one read-only pass; only the
+    32-byte result (device memory: a DeviceBuffer or an address) is written.  Arguments and the result=None convenience as
+    verify_device."""
+    if n is None:
+        if not (isinstance(expect, DeviceBuffer) and isinstance(src, DeviceBuffer)):
+            raise TypeError("n is needed unless both sides are DeviceBuffer")
+        n = min(expect.nbytes, src.nbytes)
+    own = DeviceBuffer(VERIFY_RESULT_DTYPE.itemsize, device) if result is None else None
+    try:
+        _check(lib().modgpu_verify_rekey_device(_vp(_dev_addr(expect)), _vp(_dev_addr(src)), n, as_int32(key_from), off_from, as_int32(key_to), off_to,
+                                                _vp(_dev_addr(own if own is not None else result)), device, _vp(stream or 0)))
+        if own is None:
+            return None
+        _check(lib().modgpu_sync(device, _vp(stream or 0)))
+        return verify_results(own, 1, device)[0]
+    finally:
+        if own is not None:
+            own.free()
+
+
+def verify_rekey_batch_device(expect_ptrs, src_ptrs, sizes, key_from, key_to, results, offs_from=None, offs_to=None, device=-1, stream=None):
+    """Several rekey verify entries of ONE device under one pair of keys (entry i at offs_from[i] / offs_to[i] or 0, its result at
+    results + 32 * i); every range is only read, so anything may overlap anything.  One launch initialises the results, up to 16
+    non-empty entries whose two streams differ share a compare launch, and so do up to 16 whose streams coincide."""
+    n = len(expect_ptrs)
+    assert len(src_ptrs) == n and len(sizes) == n
+    e = (_vp * n)(*[_dev_addr(x) for x in expect_ptrs])
+    s = (_vp * n)(*[_dev_addr(x) for x in src_ptrs])
+    z = (_u64 * n)(*sizes)
+    f = (_u64 * n)(*offs_from) if offs_from is not None else None
+    t = (_u64 * n)(*offs_to) if offs_to is not None else None
+    _check(lib().modgpu_verify_rekey_batch_device(e, s, z, f, t, n, as_int32(key_from), as_int32(key_to), _vp(_dev_addr(results)), device,
+                                                  _vp(stream or 0)))
+
+
+def time_verify_rekey_device(expect, src, n, key_from, key_to, result, off_from=0, off_to=0, device=-1, stream=None, iters=2):
+    """Mean ms per rekey verify call (two launches) over `iters` calls, HIP events on the launch stream."""
+    ms = ctypes.c_float(0)
+    _check(lib().modgpu_time_verify_rekey_device(_vp(_dev_addr(expect)), _vp(_dev_addr(src)), n, as_int32(key_from), off_from, as_int32(key_to), off_to,
+                                                 _vp(_dev_addr(result)), device, _vp(stream or 0), iters, ctypes.byref(ms)))
+    return ms.value
+
+
+def rekey_verify_kernel_source_hash():
+    """identity of the rekey verify kernel's TU (cycle_rekey_verify_kernel.hip and what it includes)"""
+    return lib().modgpu_rekey_verify_kernel_source_hash().decode()
 
 
 def verify_table_workspace_bytes(n_entries):

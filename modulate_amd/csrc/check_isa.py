@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""check_isa.py <cycle_kernel.s> [<cycle_feed_kernel.s>] | <cycle_to_kernel.s> | <cycle_xfer_kernel.s> | <cycle_rekey_kernel.s> | <cycle_table_kernel.s> | <cycle_rekey_table_kernel.s> | <cycle_verify_kernel.s> | <cycle_verify_table_kernel.s> -- build-time guard over the gfx950 assembly of the kernel TUs (run by the
+"""check_isa.py <cycle_kernel.s> [<cycle_feed_kernel.s>] | <cycle_to_kernel.s> | <cycle_xfer_kernel.s> | <cycle_rekey_kernel.s> | <cycle_table_kernel.s> | <cycle_rekey_table_kernel.s> | <cycle_verify_kernel.s> | <cycle_verify_table_kernel.s> | <cycle_rekey_verify_kernel.s> -- build-time guard over the gfx950 assembly of the kernel TUs (run by the
 Makefile right after the TUs are compiled and before either object exists; tests/test_capi_cpu.py runs it again and feeds it
 deliberately broken builds).
 
@@ -57,6 +57,12 @@ block; the stream kernel carries the keystream blocks under the rules above (8 o
 nt, the ticket fetch ONE plain returning 32-bit atomic per unrolled trip, the table call's scalar-only entry search, NO store
 instruction of any kind (buffer, global, flat or scratch: it writes through atomics and into its LDS mailbox only), no buffer atomic,
 and besides the ticket fetch only 64-bit adds and unsigned mins, as many of the one as of the other, none of them returning.
+The rekey verify kernel (cycle_rekey_verify_kernel.s: two forms, plain and funnel, and no other kernel): the register budget, no spills
+/ scratch / private segment; the two-keystream blocks under the rekey kernel's rules (fixed temporaries v[112:127] and s[94:95], 60
+mads + 30 addc, trailing s_nop 0, one v_bitop3_b32 0x96 per dword; 9 blocks: 4 words x 2 unrolled trips + the cut first chunk's
+loop); every data load nt; NO buffer store and no buffer atomic anywhere (it reads its inputs and nothing else), no flat access, its
+only global store the 8 bytes of the entry's n, its only atomics 64-bit adds and unsigned mins, as many of the one as of the other;
+16 bytes of LDS (the workgroup's count and lowest index).
 Exit status 0 = all of it holds; 1 = findings on stdout."""
 import re
 import sys
@@ -463,6 +469,43 @@ def check_verify(asm, bodies):
     return bad
 
 
+def check_rekey_verify(asm, bodies):
+    """the rekey verify kernel's TU (cycle_rekey_verify_kernel.s): the plain and the funnel form of modgpu_cycle_rekey_verify_kernel"""
+    bad = []
+    for name, fn in bodies.items():
+        if "modgpu_cycle_rekey_verify_kernel" not in name:
+            bad.append("%s: the rekey verify kernel's TU holds another kernel" % name)
+            continue
+        md = metadata(asm, name)
+        if md.get("vgpr_count", 999) > 128 or md.get("sgpr_count", 999) > 102:
+            bad.append("%s: register counts beyond the budget: %s" % (name, md))
+        if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0) or "scratch_" in fn:
+            bad.append("%s: spills, scratch or a private segment: %s" % (name, md))
+        bad += rekey_blocks(name, fn)
+        blocks = len([b for b in BLOCK.findall(fn) if "s[94:95]" in b])
+        if blocks != 9:
+            bad.append("%s: %d two-keystream blocks, expected 9 (4 words x 2 unrolled trips + the cut first chunk)" % (name, blocks))
+        if re.search(r"^\s+buffer_(store|atomic)", fn, re.M):
+            bad.append("%s: a rekey verify kernel stores through a buffer descriptor (its inputs are read-only; the stream has no store at all)" % name)
+        if re.search(r"^\s+flat_", fn, re.M):
+            bad.append("%s: flat_ accesses (LDS must be ds_ instructions, results global_)" % name)
+        loads = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_load_dword", ln)]
+        if not loads or not all(ln.endswith(" nt") for ln in loads):
+            bad.append("%s: a data load is not nt" % name)
+        stores = re.findall(r"^\s+(global_store_\w+)", fn, re.M)
+        if stores != ["global_store_dwordx2"]:
+            bad.append("%s: global stores %s, expected the one global_store_dwordx2 of the entry's n" % (name, stores))
+        atomics = re.findall(r"^\s+(global_atomic_\w+)", fn, re.M)
+        adds, mins = atomics.count("global_atomic_add_x2"), atomics.count("global_atomic_umin_x2")
+        if not adds or adds != mins or adds + mins != len(atomics):
+            bad.append("%s: result atomics %s, expected 64-bit adds and unsigned mins in equal numbers and nothing else" % (name, sorted(set(atomics))))
+        if md.get("group_segment_fixed_size", -1) != 16:
+            bad.append("%s: LDS is %s bytes, expected the 16 of the workgroup's count and lowest index" % (name, md.get("group_segment_fixed_size")))
+    if len(bodies) != 2:
+        bad.append("the rekey verify kernel's TU holds %d kernels, expected 2 (plain and funnel)" % len(bodies))
+    return bad
+
+
 VERIFY_TABLE_KERNELS = ("modgpu_cycle_verify_table_plan", "modgpu_cycle_verify_table_finish", "modgpu_cycle_verify_table_kernel")
 
 
@@ -569,6 +612,8 @@ def check(asm):
         if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0) or "scratch_" in bodies[feed[0]]:
             bad.append("%s: spills, scratch or a private segment: %s" % (feed[0], md))
         return bad + check_feed(asm, feed[0], bodies[feed[0]])
+    if any("modgpu_cycle_rekey_verify" in n for n in bodies):  # (no other branch's name is part of this one)
+        return bad + check_rekey_verify(asm, bodies)
     if any("modgpu_cycle_verify_table" in n for n in bodies):  # (before the verify kernels: their name is the start of this one)
         return bad + check_verify_table(asm, bodies)
     if any("modgpu_cycle_verify" in n for n in bodies):

@@ -23,6 +23,7 @@
 #include "cycle_rekey_table_kernel.h"
 #include "cycle_verify_table_kernel.h"
 #include "cycle_verify_kernel.h"
+#include "cycle_rekey_verify_kernel.h"
 #include "cycle_table_kernel.h"
 #include "cycle_to_kernel.h"
 #include "cycle_xfer_kernel.h"
@@ -1032,6 +1033,94 @@ int verify_impl(const void *const *expect, const void *const *src, const uint64_
     }
     return MODGPU_OK;
 }
+
+// ---- rekey verify: count and locate the j with expect[j] != (src[j] ^ ks(key_from)[off_from + j] ^ ks(key_to)[off_to + j])
+// (modgpu_verify_rekey_device / modgpu_verify_rekey_batch_device) ----
+// One two-keystream compare launch over 1..kCycleBatchMax non-empty entries of the current device, both keys non-zero residues:
+// launch_verify's geometry with two sets of bases.
+static_assert(sizeof(CycleRekeyVerifyArgs) <= 4096, "the table of entries travels in the kernel arguments");
+int launch_rekey_verify(const uint8_t *const *expect, const uint8_t *const *src, const uint64_t *sizes, const uint64_t *offs_from,
+                        const uint64_t *offs_to, modgpu_verify_result_t *const *results, int n, uint32_t key_from, uint32_t key_to,
+                        hipStream_t stream)
+{
+    CycleRekeyVerifyArgs a{};
+    const uint64_t chunk = modgpu_rekey_verify_chunk_bytes();
+    uint64_t total = 0, bytes = 0;
+    bool misaligned = false;
+    for (int k = 0; k < n; ++k) {
+        CycleRekeyVerifyPart &P = a.part[k];
+        const EntryGeom g = entry_geom(expect[k], sizes[k], chunk);
+        P.expect_body = expect[k] + g.head;
+        P.src_body = src[k] + g.head;
+        P.result = reinterpret_cast<CycleVerifyResult *>(results[k]);
+        P.n = sizes[k];
+        P.head_n = (uint32_t)g.head;
+        P.tail_n = (uint32_t)g.tail;
+        P.lead = g.lead;
+        P.end = g.end;
+        entry_bases(g, key_from, offs_from[k] % lcg::PERIOD, P.base_head[0], P.base_body[0], P.base_tail[0]);
+        entry_bases(g, key_to, offs_to[k] % lcg::PERIOD, P.base_head[1], P.base_body[1], P.base_tail[1]);
+        a.start[k] = (uint32_t)total;
+        total += g.n_chunks > g.first ? g.n_chunks - g.first : 0;
+        bytes += sizes[k];
+        misaligned |= g.words != 0 && ((reinterpret_cast<uintptr_t>(src[k]) - reinterpret_cast<uintptr_t>(expect[k])) & 3) != 0;
+    }
+    for (int k = n; k <= kCycleBatchMax; ++k) a.start[k] = (uint32_t)total;
+    a.n_parts = (uint32_t)n;
+    const uint64_t cap = verify_grid_forced() ? verify_grid_forced() : large_grid();
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(total, cap));
+    const int form = misaligned ? CYCLE_REKEY_VERIFY_FUNNEL : CYCLE_REKEY_VERIFY_PLAIN;
+    const hipError_t e = modgpu_launch_cycle_rekey_verify(a, form, grid, stream);
+    if (e != hipSuccess) return fail_hip(e, "rekey verify kernel launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    t_last_launch = {modgpu_rekey_verify_kernel_name(form), CYCLE_REKEY_VERIFY, grid, modgpu_rekey_verify_block(), (uint32_t)chunk, bytes, grid,
+                     MODGPU_REKEY_VERIFY_KERNEL_SOURCE_HASH};
+    return MODGPU_OK;
+}
+
+// Entries already checked (check_verify_entries), on the current device, asynchronous on `stream`.  One launch initialises all n
+// results.  Degenerate keystreams follow rekey_impl's rules and run on the verify kernels: a key == 0 mod m leaves only the other key
+// (both zero: the identity forms); an entry with the same reduced key at the same stream position has ks ^ ks = 0 and is compared under
+// the identity forms.  The entries whose two streams differ come first, in groups of up to kCycleBatchMax per two-keystream launch,
+// then the coinciding ones in groups of their own.
+int verify_rekey_impl(const void *const *expect, const void *const *src, const uint64_t *sizes, const uint64_t *offs_from, const uint64_t *offs_to,
+                      int n, int32_t key_from, int32_t key_to, modgpu_verify_result_t *results, hipStream_t stream)
+{
+    const uint32_t kf = lcg::key_residue(key_from), kt = lcg::key_residue(key_to);
+    if (!kf) return verify_impl(expect, src, sizes, offs_to, n, key_to, results, stream); // (key_to == 0 too: a plain compare)
+    if (!kt) return verify_impl(expect, src, sizes, offs_from, n, key_from, results, stream);
+    if (n == 0) return MODGPU_OK;
+    int phys = -1;
+    HIP_TRY(hipGetDevice(&phys));
+    if (modgpu_xfer_device_of(results, (uint64_t)n * sizeof(modgpu_verify_result_t)) != phys)
+        return fail(MODGPU_ERR_INVALID, "the result is not device memory of the call's device");
+    (void)hipGetLastError(); // (the launches report hipGetLastError: an earlier call's error must not be taken for theirs)
+    const hipError_t e = modgpu_launch_verify_init(reinterpret_cast<CycleVerifyResult *>(results), (uint64_t)n, stream);
+    if (e != hipSuccess) return fail_hip(e, "verify init launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    t_last_launch = {"modgpu_cycle_verify_init", CYCLE_VERIFY, (uint32_t)(((uint64_t)n + 255) / 256), 256u, 0u, 0, 0u, MODGPU_VERIFY_KERNEL_SOURCE_HASH};
+    auto at = [](const uint64_t *offs, int i) { return offs ? offs[i] % lcg::PERIOD : 0; };
+    auto identity = [&](int i) { return kf == kt && at(offs_from, i) == at(offs_to, i); };
+    for (int pass = 0; pass < 2; ++pass) { // 0: two streams, 1: coinciding streams
+        int i = 0, idx[kCycleBatchMax];
+        while (const int g = next_run(sizes, n, i, idx, [&](int j) { return identity(j) == (pass == 1); })) {
+            const uint8_t *ge[kCycleBatchMax], *gs[kCycleBatchMax];
+            uint64_t gn[kCycleBatchMax], gf[kCycleBatchMax], gt[kCycleBatchMax];
+            modgpu_verify_result_t *gr[kCycleBatchMax];
+            for (int k = 0; k < g; ++k) {
+                ge[k] = static_cast<const uint8_t *>(expect[idx[k]]);
+                gs[k] = static_cast<const uint8_t *>(src[idx[k]]);
+                gn[k] = sizes[idx[k]];
+                gf[k] = at(offs_from, idx[k]);
+                gt[k] = at(offs_to, idx[k]);
+                gr[k] = results + idx[k];
+            }
+            const int rc = pass == 0 ? launch_rekey_verify(ge, gs, gn, gf, gt, gr, g, kf, kt, stream) : launch_verify(ge, gs, gn, gf, gr, g, 0u, stream);
+            if (rc) return rc;
+        }
+    }
+    return MODGPU_OK;
+}
 } // namespace
 
 int cycle_to_device_impl(void *dst, const void *src, uint64_t n, int32_t key, uint64_t stream_off, hipStream_t stream)
@@ -1583,6 +1672,30 @@ int modgpu_verify_batch_device(const void *const *expect_parts, const void *cons
         DeviceScope scope(device);
         if (scope.rc) return scope.rc;
         return verify_impl(expect_parts, src_parts, sizes, stream_offs, n_parts, key, dev_results, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int modgpu_verify_rekey_device(const void *dev_expect, const void *dev_src, uint64_t n, int32_t key_from, uint64_t off_from, int32_t key_to,
+                               uint64_t off_to, modgpu_verify_result_t *dev_result, int device, void *hip_stream)
+{
+    return guarded([&]() -> int {
+        if (int rc = check_verify_entries(&dev_expect, &dev_src, &n, 1, dev_result)) return rc;
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        return verify_rekey_impl(&dev_expect, &dev_src, &n, &off_from, &off_to, 1, key_from, key_to, dev_result, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int modgpu_verify_rekey_batch_device(const void *const *expect_parts, const void *const *src_parts, const uint64_t *sizes, const uint64_t *offs_from,
+                                     const uint64_t *offs_to, int n_parts, int32_t key_from, int32_t key_to, modgpu_verify_result_t *dev_results,
+                                     int device, void *hip_stream)
+{
+    return guarded([&]() -> int {
+        if (int rc = check_verify_entries(expect_parts, src_parts, sizes, n_parts, dev_results)) return rc;
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        return verify_rekey_impl(expect_parts, src_parts, sizes, offs_from, offs_to, n_parts, key_from, key_to, dev_results,
+                                 static_cast<hipStream_t>(hip_stream));
     });
 }
 
@@ -2384,6 +2497,35 @@ int modgpu_time_verify_device(const void *dev_expect, const void *dev_src, uint6
     });
 }
 
+int modgpu_time_verify_rekey_device(const void *dev_expect, const void *dev_src, uint64_t n, int32_t key_from, uint64_t off_from, int32_t key_to,
+                                    uint64_t off_to, void *dev_result, int device, void *hip_stream, int iters, float *ms_per_call)
+{
+    return guarded([&]() -> int {
+        if (iters <= 0 || !ms_per_call) return fail(MODGPU_ERR_INVALID, "bad timing arguments");
+        modgpu_verify_result_t *res = static_cast<modgpu_verify_result_t *>(dev_result);
+        if (int rc = check_verify_entries(&dev_expect, &dev_src, &n, 1, res)) return rc;
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        int rc = MODGPU_OK;
+        hipStream_t st = static_cast<hipStream_t>(hip_stream);
+        hipEvent_t e0, e1;
+        HIP_TRY(hipEventCreate(&e0));
+        HIP_TRY(hipEventCreate(&e1));
+        HIP_TRY(hipEventRecord(e0, st));
+        for (int i = 0; i < iters && rc == MODGPU_OK; ++i) rc = verify_rekey_impl(&dev_expect, &dev_src, &n, &off_from, &off_to, 1, key_from, key_to, res, st);
+        hipError_t e = hipEventRecord(e1, st);
+        if (e == hipSuccess) e = hipEventSynchronize(e1);
+        float ms = 0.f;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        if (rc) return rc;
+        if (e != hipSuccess) return fail_hip(e, "event timing");
+        *ms_per_call = ms / (float)iters;
+        return MODGPU_OK;
+    });
+}
+
 int modgpu_last_launch(modgpu_launch_info_t *out)
 {
     if (!out) return fail(MODGPU_ERR_INVALID, "null out pointer");
@@ -2430,6 +2572,7 @@ const char *modgpu_table_kernel_source_hash(void) { return MODGPU_TABLE_KERNEL_S
 const char *modgpu_rekey_table_kernel_source_hash(void) { return MODGPU_REKEY_TABLE_KERNEL_SOURCE_HASH; }
 const char *modgpu_verify_kernel_source_hash(void) { return MODGPU_VERIFY_KERNEL_SOURCE_HASH; }
 const char *modgpu_verify_table_kernel_source_hash(void) { return MODGPU_VERIFY_TABLE_KERNEL_SOURCE_HASH; }
+const char *modgpu_rekey_verify_kernel_source_hash(void) { return MODGPU_REKEY_VERIFY_KERNEL_SOURCE_HASH; }
 
 int modgpu_time_cycle_table_device(const void *dev_entries, uint64_t n_entries, void *dev_workspace, uint64_t workspace_bytes,
                                    int device, void *hip_stream, int iters, float *ms_per_call)
@@ -2552,6 +2695,7 @@ void modgpu_debug_set_rekey_table_grid(uint32_t grid) { g_rekey_table_grid.store
 
 void modgpu_debug_set_verify_table_grid(uint32_t grid) { g_verify_table_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
 
+// (caps the compare launches of the verify call and of the rekey verify call alike)
 void modgpu_debug_set_verify_form(int grid) { g_verify_grid.store(grid <= 0 ? 0u : std::min<uint32_t>((uint32_t)grid, 4096u), std::memory_order_relaxed); }
 
 void modgpu_debug_set_queue_ring(uint32_t lines)
