@@ -58,7 +58,9 @@ int modgpu_time_verify_table_device(const void *dev_entries, uint64_t n_entries,
 typedef struct modgpu_launch_info {
     const char *kernel;   /* the instantiation's name as rocprofv3 prints it, e.g.
                              "modgpu_cycle_queue_kernel<4, 1024>"; static storage */
-    int variant;          /* 0 = small shape, 1 = streaming shape (static chunk map), 2 = streaming shape fed by the work queue,
+    int variant;          /* 0 = small shape, 1 = streaming shape (static chunk map), 2 = streaming shape fed by the work queue
+                                 (one buffer of 1 GiB or more: its copy that keeps a slice in the Infinity Cache,
+                                 "modgpu_cycle_keep_kernel<4, 1024>", with modgpu_keep_kernel_source_hash() as `source_hash`),
                              3 = the work-queue shape over several parts in one launch (modgpu_cycle_batch_device; `bytes` = all of them),
                              4 = the host-fed kernel of a host-buffer call (one launch for the whole call; `bytes` = the call's),
                              5 = the out-of-place kernel (modgpu_cycle_device_to / _batch_device_to; `bytes` = all entries of the launch),
@@ -186,6 +188,13 @@ const char *modgpu_verify_table_kernel_source_hash(void);
 /* The same for the rekey verify kernel's TU (cycle_rekey_verify_kernel.hip, cycle_rekey_verify_kernel.h, cycle_verify_kernel.h,
  * cycle_rekey_impl.h, cycle_kernel_impl.h, cycle_kernel.h, lcg.h). */
 const char *modgpu_rekey_verify_kernel_source_hash(void);
+/* The same for the keep kernel's TU -- the work-queue kernel with a resident slice, what a single in-place buffer of 1 GiB or more is
+ * launched on (cycle_keep_kernel.hip, cycle_keep_kernel.h, cycle_kernel_impl.h, cycle_kernel.h, lcg.h). */
+const char *modgpu_keep_kernel_source_hash(void);
+/* What a single in-place device buffer of `bytes` bytes is launched with: returns 1 if it takes the keep kernel (0: the main
+ * work-queue kernel, or a smaller shape), and the cache policy it would carry -- of every *mask + 1 chunks of 64 KiB, counted by
+ * absolute address, the first *run are stored so that they stay in the Infinity Cache.  Either pointer may be NULL. */
+int modgpu_keep_policy(uint64_t bytes, uint32_t *mask, uint32_t *run);
 
 /* 1 in libmodgpu_testing.so, 0 in libmodgpu.so. */
 int modgpu_testing_hooks(void);
@@ -224,6 +233,12 @@ void modgpu_debug_set_verify_form(int grid);
 /* The verify table call's stream launch: `grid` workgroups (1..4096), 0 = the shipped grid (one workgroup per CU).
  * Measurement (tools/bench_verify_table.py) and parity tests of small grids, where one workgroup passes several entries. */
 void modgpu_debug_set_verify_table_grid(uint32_t grid);
+
+/* The resident slice of a single in-place buffer's work-queue launch: every such launch of `min_bytes` bytes or more takes the keep
+ * kernel with exactly this `mask` (a power of two minus one) and `run` (run = 0: no chunk is kept; mask = 0, run = 1: every chunk),
+ * smaller ones the main kernel; min_bytes = UINT64_MAX switches the route off.  (0, 0, 0) restores the shipped rule.  Measurement
+ * (tools/bench_keep.py) and parity tests of every policy at small sizes. */
+void modgpu_debug_set_keep(uint64_t min_bytes, uint32_t mask, uint32_t run);
 
 /* How the transfer calls (modgpu_cycle_host_to_device & co.) move their bytes: 0 = the transfer kernels (shipped), 1 = the DMA
  * reference form -- per chunk a hipMemcpyAsync into a device slot and an out-of-place launch from there (upload), or an out-of-place

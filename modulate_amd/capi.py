@@ -175,6 +175,8 @@ TESTING_EXPORTS = {
     "modgpu_verify_table_kernel_source_hash": (ctypes.c_char_p, []),
     "modgpu_time_verify_rekey_device": (_int, [_vp, _vp, _u64, _i32, _u64, _i32, _u64, _vp, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
     "modgpu_rekey_verify_kernel_source_hash": (ctypes.c_char_p, []),
+    "modgpu_keep_kernel_source_hash": (ctypes.c_char_p, []),
+    "modgpu_keep_policy": (_int, [_u64, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
 }
 # include/modgpu_testing.h, modgpu_debug_* group: ONLY in libmodgpu_testing.so
 DEBUG_EXPORTS = {
@@ -199,6 +201,7 @@ DEBUG_EXPORTS = {
     "modgpu_debug_set_rekey_table_grid": (None, [ctypes.c_uint32]),
     "modgpu_debug_set_verify_form": (None, [_int]),
     "modgpu_debug_set_verify_table_grid": (None, [ctypes.c_uint32]),
+    "modgpu_debug_set_keep": (None, [_u64, ctypes.c_uint32, ctypes.c_uint32]),
 }
 
 
@@ -977,6 +980,27 @@ def time_verify_rekey_device(expect, src, n, key_from, key_to, result, off_from=
     _check(lib().modgpu_time_verify_rekey_device(_vp(_dev_addr(expect)), _vp(_dev_addr(src)), n, as_int32(key_from), off_from, as_int32(key_to), off_to,
                                                  _vp(_dev_addr(result)), device, _vp(stream or 0), iters, ctypes.byref(ms)))
     return ms.value
+
+
+def keep_kernel_source_hash():
+    """SHA-256 over the keep kernel's TU (the work-queue kernel with a resident slice; include/modgpu_testing.h)."""
+    return lib().modgpu_keep_kernel_source_hash().decode()
+
+
+KEEP_OFF = (1 << 64) - 1
+
+
+def keep_policy(nbytes):
+    """(takes the keep kernel?, mask, run) of a single in-place device buffer of `nbytes` bytes (modgpu_keep_policy)."""
+    mask, run = ctypes.c_uint32(), ctypes.c_uint32()
+    route = lib().modgpu_keep_policy(nbytes, ctypes.byref(mask), ctypes.byref(run))
+    return bool(route), mask.value, run.value
+
+
+def debug_set_keep(min_bytes=0, mask=0, run=0):
+    """Test / measurement hook: single-buffer work-queue launches of `min_bytes` or more take the keep kernel with this (mask, run);
+    KEEP_OFF switches the route off; (0, 0, 0) restores the shipped rule."""
+    _debug_lib().modgpu_debug_set_keep(min_bytes, mask, run)
 
 
 def rekey_verify_kernel_source_hash():

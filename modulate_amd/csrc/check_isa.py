@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""check_isa.py <cycle_kernel.s> [<cycle_feed_kernel.s>] | <cycle_to_kernel.s> | <cycle_xfer_kernel.s> | <cycle_rekey_kernel.s> | <cycle_table_kernel.s> | <cycle_rekey_table_kernel.s> | <cycle_verify_kernel.s> | <cycle_verify_table_kernel.s> | <cycle_rekey_verify_kernel.s> -- build-time guard over the gfx950 assembly of the kernel TUs (run by the
+"""check_isa.py <cycle_kernel.s> [<cycle_feed_kernel.s>] | <cycle_to_kernel.s> | <cycle_xfer_kernel.s> | <cycle_rekey_kernel.s> | <cycle_table_kernel.s> | <cycle_rekey_table_kernel.s> | <cycle_verify_kernel.s> | <cycle_verify_table_kernel.s> | <cycle_rekey_verify_kernel.s> | <cycle_keep_kernel.s> -- build-time guard over the gfx950 assembly of the kernel TUs (run by the
 Makefile right after the TUs are compiled and before either object exists; tests/test_capi_cpu.py runs it again and feeds it
 deliberately broken builds).
 
@@ -63,6 +63,12 @@ mads + 30 addc, trailing s_nop 0, one v_bitop3_b32 0x96 per dword; 9 blocks: 4 w
 loop); every data load nt; NO buffer store and no buffer atomic anywhere (it reads its inputs and nothing else), no flat access, its
 only global store the 8 bytes of the entry's n, its only atomics 64-bit adds and unsigned mins, as many of the one as of the other;
 16 bytes of LDS (the workgroup's count and lowest index).
+The keep kernel (cycle_keep_kernel.s: modgpu_cycle_keep_kernel and no other kernel; the work-queue kernel with a cache policy per
+chunk): the work-queue kernel's rules -- the register budget, no spills / scratch / private segment, the keystream blocks' rules above
+(9 blocks: 4 words x 2 unrolled trips + the cut first chunk), the ticket fetch ONE plain returning atomic per unrolled trip (4
+global_atomic_add in all, no v_mbcnt), the mailbox accessed with ds_ instructions (3 writes, 3 reads), no flat access, every data load
+nt -- and in the unrolled stream loop exactly as many `sc1`-only stores (the resident chunks' burst) as `nt sc1` stores (the
+streaming chunks'), 4 words x 2 trips each; the cut first chunk's one store is nt sc1.
 Exit status 0 = all of it holds; 1 = findings on stdout."""
 import re
 import sys
@@ -597,6 +603,49 @@ def check_xfer(asm, bodies):
     return bad
 
 
+def check_keep(asm, bodies):
+    """the keep kernel's TU (cycle_keep_kernel.s): modgpu_cycle_keep_kernel, the work-queue kernel with a cache policy per chunk"""
+    bad = []
+    for name, fn in bodies.items():
+        if "modgpu_cycle_keep_kernel" not in name:
+            bad.append("%s: the keep kernel's TU holds another kernel" % name)
+            continue
+        md = metadata(asm, name)
+        if md.get("vgpr_count", 999) > 128 or md.get("sgpr_count", 999) > 102:
+            bad.append("%s: register counts beyond the budget: %s" % (name, md))
+        if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0) or "scratch_" in fn:
+            bad.append("%s: spills, scratch or a private segment: %s" % (name, md))
+        found, findings = keystream_blocks(name, fn)
+        bad += findings
+        if not found:
+            bad.append("%s: no keystream block (ks_word_carry)" % name)
+        if "v_mbcnt" in fn:
+            bad.append("%s: the atomic optimizer rewrote the ticket atomic (build the TU with -mllvm -amdgpu-atomic-optimizer-strategy=None)" % name)
+        if fn.count("global_atomic_add") != 4:  # one ticket fetch per unrolled trip (2) + a helper's first tickets + the exit count
+            bad.append("%s: %d global_atomic_add, expected 4" % (name, fn.count("global_atomic_add")))
+        if "flat_" in fn:
+            bad.append("%s: flat_ accesses (the LDS mailbox must be ds_ instructions)" % name)
+        if fn.count("ds_write_b32") != 3 or fn.count("ds_read_b32") != 3:
+            bad.append("%s: ticket mailbox traffic changed: %d ds_write_b32, %d ds_read_b32" % (name, fn.count("ds_write_b32"), fn.count("ds_read_b32")))
+        if fn.count("v_addc_co_u32_sdwa") != 9 * 15 or "v_add_u32_sdwa" in fn:  # 4 words x 2 unrolled trips + the peeled first chunk
+            bad.append("%s: keystream instruction mix changed (%d addc)" % (name, fn.count("v_addc_co_u32_sdwa")))
+        loads = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_load_dword", ln)]
+        stores = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_store_dword", ln)]
+        if not loads or not all(ln.endswith(" nt") for ln in loads):
+            bad.append("%s: a data load is not nt" % name)
+        streaming = len([ln for ln in stores if ln.endswith(" nt sc1")])
+        resident = len([ln for ln in stores if ln.endswith(" sc1") and " nt" not in ln])
+        if streaming + resident != len(stores):
+            bad.append("%s: a data store is neither nt sc1 nor sc1" % name)
+        # the cut first chunk's loop (cold, not unrolled) stores once, streaming; the rest is the unrolled stream loop
+        if resident != 8 or streaming - 1 != 8:
+            bad.append("%s: %d sc1-only and %d nt sc1 stores in the stream loop, expected 8 of each (4 words x 2 unrolled trips, one burst per "
+                       "cache policy)" % (name, resident, streaming - 1))
+    if len(bodies) != 1:
+        bad.append("the keep kernel's TU holds %d kernels, expected 1" % len(bodies))
+    return bad
+
+
 def check(asm):
     """one TU's assembly: the rules for every kernel, then those of the TU it is (the streaming kernels' or the host-fed kernel's)"""
     bad = []
@@ -628,6 +677,8 @@ def check(asm):
         return bad + check_xfer(asm, bodies)
     if any("modgpu_cycle_rekey_kernel" in n for n in bodies):
         return bad + check_rekey(asm, bodies)
+    if any("modgpu_cycle_keep_kernel" in n for n in bodies):
+        return bad + check_keep(asm, bodies)
     queue = [n for n in bodies if "modgpu_cycle_queue_kernel" in n]
     if len(queue) != 1:
         return bad + ["expected exactly one work-queue kernel, found %d" % len(queue)]

@@ -18,6 +18,7 @@
 #include "../../include/modgpu_testing.h"
 #include "crossover_table.h"
 #include "cycle_feed_kernel.h"
+#include "cycle_keep_kernel.h"
 #include "cycle_kernel.h"
 #include "cycle_rekey_kernel.h"
 #include "cycle_rekey_table_kernel.h"
@@ -451,6 +452,36 @@ constexpr uint32_t kSmallGridMax = 16384u;   // 4 KiB chunks: grid * 1 tile <= 6
 // work-queue streaming kernel (64 KiB chunks handed out by tickets) does.
 constexpr uint64_t kLargeMin = (256ull << 20) + 1;
 
+// ---- a resident slice of large in-place passes (cycle_keep_kernel.hip) ----
+// A single buffer of kKeepMin bytes or more takes the work-queue kernel's copy with a cache policy per chunk: of every kKeepMask + 1
+// chunks of 64 KiB (16 MiB of addresses) the first `run` are stored so that they stay in the 256 MiB Infinity Cache, about
+// kKeepBytes of the call in all; the next pass over the same memory finds them there.  The pattern is laid on absolute addresses, so
+// it is the same for every call that touches a line.  Below kKeepMin the main kernel is launched, as for batches.
+constexpr uint64_t kKeepMin = 1ull << 30;
+constexpr uint64_t kKeepBytes = 192ull << 20; // S: resident bytes aimed at (the cache has 256 MiB); profiles/r13_keep.json
+constexpr uint32_t kKeepMask = 255u;
+struct KeepPolicy {
+    bool route;         // launch the keep kernel
+    uint32_t mask, run; // CycleKeepArgs
+};
+#ifdef MODGPU_TESTING_HOOKS
+std::mutex g_keep_mutex; // modgpu_debug_set_keep
+uint64_t g_keep_min = 0; // 0 = the product's rule
+uint32_t g_keep_mask = 0, g_keep_run = 0;
+#endif
+KeepPolicy keep_policy(uint64_t bytes)
+{
+#ifdef MODGPU_TESTING_HOOKS
+    {
+        std::lock_guard<std::mutex> lock(g_keep_mutex);
+        if (g_keep_min != 0) return {bytes >= g_keep_min, g_keep_mask, g_keep_run};
+    }
+#endif
+    if (bytes < kKeepMin) return {false, kKeepMask, 0u};
+    // run = floor(S / bytes * (mask + 1)): 0 once the call is so large that S is less than one chunk per period
+    return {true, kKeepMask, (uint32_t)std::min<uint64_t>(kKeepBytes * (kKeepMask + 1ull) / bytes, kKeepMask + 1ull)};
+}
+
 // Splits [buf, buf+n) into <16 head bytes, an aligned body of 16-byte words and <16 tail bytes,
 // and computes the states that seed each piece.  key_res != 0.
 // Over PCIe (page-locked host memory): the link, not HBM, is the bound, and it is saturated by a few
@@ -539,7 +570,8 @@ Plan plan_cycle(void *dev_buf, uint64_t n, uint32_t key_res, uint64_t stream_off
 // own keystream.  Returns MODGPU_OK, an error, or 1: not possible right now (no ticket pair free -- every ring line busy, or a
 // capture with the graph pool used up -- or a part beyond the kernel's three-byte chunk jump tables): the caller takes a shape
 // that needs no pair.
-int launch_queue(void *const *bufs, const uint64_t *sizes, const uint64_t *offs, int n, uint32_t key_res, hipStream_t stream)
+// `warm_keep` (prepare_device): a single buffer takes the keep kernel whatever its size, with no chunk kept.
+int launch_queue(void *const *bufs, const uint64_t *sizes, const uint64_t *offs, int n, uint32_t key_res, hipStream_t stream, bool warm_keep = false)
 {
     CycleQueueArgs a{};
     const uint64_t chunk = modgpu_queue_chunk_bytes();
@@ -586,7 +618,18 @@ int launch_queue(void *const *bufs, const uint64_t *sizes, const uint64_t *offs,
     a.main_groups = (uint32_t)main_groups;
     a.helper_below_mhz = helper_mode() == 1 ? 0xFFFFFFFFu : helper_below_mhz();
     const uint32_t grid = (uint32_t)(main_groups + helpers);
-    hipError_t e = modgpu_launch_cycle_queue(a, grid, stream);
+    // one large buffer: the same launch through the kernel that keeps a slice of it in the Infinity Cache
+    const KeepPolicy keep = n != 1 ? KeepPolicy{false, 0u, 0u} : warm_keep ? KeepPolicy{true, kKeepMask, 0u} : keep_policy(bytes);
+    hipError_t e;
+    if (keep.route) {
+        CycleKeepArgs ka{};
+        static_cast<CycleQueueArgs &>(ka) = a;
+        ka.keep_mask = keep.mask;
+        ka.keep_run = keep.run;
+        e = modgpu_launch_cycle_keep(ka, grid, stream);
+    } else {
+        e = modgpu_launch_cycle_queue(a, grid, stream);
+    }
     if (e != hipSuccess) {
         queue_pair_unused(q);
         return fail_hip(e, "cycle kernel launch (work queue)");
@@ -596,7 +639,8 @@ int launch_queue(void *const *bufs, const uint64_t *sizes, const uint64_t *offs,
         g_batch_launches.fetch_add(1, std::memory_order_relaxed);
         g_batch_parts.fetch_add((uint64_t)n, std::memory_order_relaxed);
     }
-    t_last_launch = {modgpu_queue_kernel_name(), n > 1 ? CYCLE_BATCH : CYCLE_QUEUE, grid, modgpu_queue_block(), (uint32_t)chunk, bytes, (uint32_t)main_groups, MODGPU_KERNEL_SOURCE_HASH};
+    if (keep.route) t_last_launch = {modgpu_keep_kernel_name(), CYCLE_QUEUE, grid, modgpu_keep_block(), (uint32_t)chunk, bytes, (uint32_t)main_groups, MODGPU_KEEP_KERNEL_SOURCE_HASH};
+    else t_last_launch = {modgpu_queue_kernel_name(), n > 1 ? CYCLE_BATCH : CYCLE_QUEUE, grid, modgpu_queue_block(), (uint32_t)chunk, bytes, (uint32_t)main_groups, MODGPU_KERNEL_SOURCE_HASH};
     return MODGPU_OK;
 }
 
@@ -1175,6 +1219,13 @@ void prepare_device()
                         g_queue_eager.fetch_sub(1, std::memory_order_relaxed);
                         g_batch_launches.fetch_sub(1, std::memory_order_relaxed);
                         g_batch_parts.fetch_sub(2, std::memory_order_relaxed);
+                    }
+                // ... and of its copy with a resident slice, which a single buffer of kKeepMin bytes or more takes: the same first-launch
+                // cost (measured 0.6 ms on a fresh process's first 4 GiB pass without this), paid here instead
+                for (int k = 0; k < 2; ++k)
+                    if (launch_queue(parts, sizes, nullptr, 1, /*key_res=*/1, st, /*warm_keep=*/true) == MODGPU_OK) {
+                        g_stats.gpu_launches.fetch_sub(1, std::memory_order_relaxed);
+                        g_queue_eager.fetch_sub(1, std::memory_order_relaxed);
                     }
                 (void)hipStreamSynchronize(st);
                 (void)hipFree(big);
@@ -2573,6 +2624,15 @@ const char *modgpu_rekey_table_kernel_source_hash(void) { return MODGPU_REKEY_TA
 const char *modgpu_verify_kernel_source_hash(void) { return MODGPU_VERIFY_KERNEL_SOURCE_HASH; }
 const char *modgpu_verify_table_kernel_source_hash(void) { return MODGPU_VERIFY_TABLE_KERNEL_SOURCE_HASH; }
 const char *modgpu_rekey_verify_kernel_source_hash(void) { return MODGPU_REKEY_VERIFY_KERNEL_SOURCE_HASH; }
+const char *modgpu_keep_kernel_source_hash(void) { return MODGPU_KEEP_KERNEL_SOURCE_HASH; }
+
+int modgpu_keep_policy(uint64_t bytes, uint32_t *mask, uint32_t *run)
+{
+    const KeepPolicy k = keep_policy(bytes);
+    if (mask) *mask = k.mask;
+    if (run) *run = k.run;
+    return k.route ? 1 : 0;
+}
 
 int modgpu_time_cycle_table_device(const void *dev_entries, uint64_t n_entries, void *dev_workspace, uint64_t workspace_bytes,
                                    int device, void *hip_stream, int iters, float *ms_per_call)
@@ -2697,6 +2757,14 @@ void modgpu_debug_set_verify_table_grid(uint32_t grid) { g_verify_table_grid.sto
 
 // (caps the compare launches of the verify call and of the rekey verify call alike)
 void modgpu_debug_set_verify_form(int grid) { g_verify_grid.store(grid <= 0 ? 0u : std::min<uint32_t>((uint32_t)grid, 4096u), std::memory_order_relaxed); }
+
+void modgpu_debug_set_keep(uint64_t min_bytes, uint32_t mask, uint32_t run)
+{
+    std::lock_guard<std::mutex> lock(g_keep_mutex);
+    g_keep_min = min_bytes;
+    g_keep_mask = min_bytes ? mask : 0u;
+    g_keep_run = min_bytes ? run : 0u;
+}
 
 void modgpu_debug_set_queue_ring(uint32_t lines)
 {

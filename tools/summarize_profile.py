@@ -42,6 +42,8 @@ def main():
     try:
         import modulate_amd as M
         out["kernel_source_hash"] = M.kernel_source_hash()
+        # (the main TU's, which bench.py compares with; a 4 GiB part is launched on the keep kernel, whose TU has a hash of its own)
+        out["keep_kernel_source_hash"] = M.keep_kernel_source_hash()
     except Exception as e:  # noqa: BLE001
         out["kernel_source_hash"] = None
         out["kernel_source_hash_error"] = str(e)
