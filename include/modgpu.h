@@ -239,7 +239,8 @@ uint64_t modgpu_table_workspace_bytes(uint64_t n_entries);
 int modgpu_cycle_table_device(const modgpu_table_entry_t *dev_entries, uint64_t n_entries, void *dev_workspace,
                               uint64_t workspace_bytes, int device, void *hip_stream);
 
-/* Status of the last call that ran on dev_workspace (read after the caller has synchronised; a modgpu_rekey_table_device workspace too): MODGPU_OK with *first_bad_entry =
+/* Status of the last call that ran on dev_workspace (read after the caller has synchronised; a modgpu_rekey_table_device workspace too,
+ * and a modgpu_verify_table_device or modgpu_verify_rekey_table_device one, read unchanged: the header comes first in all of them): MODGPU_OK with *first_bad_entry =
  * UINT64_MAX if it ran clean, MODGPU_ERR_INVALID with *first_bad_entry = the lowest entry the device refused (the call wrote
  * nothing).  Synchronous (a small copy from the device). */
 int modgpu_table_status(const void *dev_workspace, int device, uint64_t *first_bad_entry);
@@ -411,8 +412,37 @@ typedef struct modgpu_verify_table_summary {
     uint64_t reserved;        /* 0 */
 } modgpu_verify_table_summary_t;
 /* Synchronous (a small copy from the device, like modgpu_table_status): call it after the caller has synchronised the stream the
- * call ran on.  MODGPU_ERR_INVALID if the device refused the call (modgpu_table_status names the entry). */
+ * call ran on.  MODGPU_ERR_INVALID if the device refused the call (modgpu_table_status names the entry).  Reads the workspace of a
+ * modgpu_verify_rekey_table_device call unchanged: its summary line sits in the same place. */
 int modgpu_verify_table_summary(const void *dev_workspace, int device, modgpu_verify_table_summary_t *out);
+
+/* ---- VERIFY REKEY TABLE: the rekey verify call over a device-resident table of any length, in three launches -------------------------
+ * One entry is a modgpu_rekey_table_entry_t as it stands (56 bytes, flags and reserved 0) with `dst` read as the COMPARAND (never
+ * written): dev_results[i] receives exactly what modgpu_verify_rekey_device(dst, src, n, key_from, off_from, key_to, off_to, ...) would
+ * have produced for entry i -- the same four fields, first_mismatch counted from the entry's own first byte; n == 0 gives
+ * {0, UINT64_MAX, 0, 0}.  So the table modgpu_rekey_table_device was given checks its own result, each entry under its own pair of
+ * keys and offsets.  Degenerate keystreams follow modgpu_rekey_table_device's rules (a key == 0 mod 2^31-1 leaves only the other
+ * keystream, two are a plain compare, the same reduced key at offsets equal mod 2^31-2 is a plain compare); every entry runs on the
+ * same kernel.  The bytes of workspace a call over n_entries needs (0 for none, or above MODGPU_TABLE_MAX_ENTRIES): */
+uint64_t modgpu_verify_rekey_table_workspace_bytes(uint64_t n_entries);
+
+/* The contract is modgpu_verify_table_device's, word for word where it applies: THREE launches (plan, finish, stream) whatever the
+ * count -- path_stats().gpu_launches counts 3, modgpu_last_launch reports the stream launch as variant 13 with `bytes` = 0 --;
+ * asynchronous on `hip_stream`, allocation-free, capturable into a hipGraph; the table is read when the call RUNS on the device, so a
+ * replay picks up rewritten entries and starts from clean results; the workspace (modgpu_verify_rekey_table_workspace_bytes(n_entries)
+ * bytes of device memory of `device`, 8-byte aligned) is the caller's, reset by the plan launch in stream order, and two calls on one
+ * workspace must not overlap in time.  The workspace starts with the table call's header and the verify table call's summary line, so
+ * modgpu_table_status and modgpu_verify_table_summary report this call too.
+ *   * EVERYTHING BUT THE RESULTS AND THE WORKSPACE IS READ-ONLY.  There is no overlap rule at all and no _validate function.
+ *   * dev_results: n_entries results in device memory of `device`, 8-byte aligned, the caller's; the call initialises them itself (the
+ *     finish launch stores every entry's result whole, the stream launch then only adds to and lowers valid results).
+ *   * Tier 1 (host, MODGPU_ERR_INVALID before anything is queued): modgpu_verify_table_device's tier 1 with this call's entry size and
+ *     workspace size.  n_entries == 0 queues nothing.
+ *   * Tier 2 (device, by the plan launch): a NULL dst or src with n > 0, nonzero flags or reserved, an entry of 1 TiB or more, more
+ *     than 2^31 chunks of 64 KiB together.  Any of these makes the whole call write NO RESULT AT ALL -- dev_results stays as the caller
+ *     left it --, modgpu_table_status names the lowest such entry and modgpu_verify_table_summary returns MODGPU_ERR_INVALID. */
+int modgpu_verify_rekey_table_device(const modgpu_rekey_table_entry_t *dev_entries, uint64_t n_entries, modgpu_verify_result_t *dev_results,
+                                     void *dev_workspace, uint64_t workspace_bytes, int device, void *hip_stream);
 
 /* Replaces CEncryptionCycler::Cycle (CEncryptionCycler.cpp:4-14) for a caller-owned HOST buffer,
  * on the GPU.  Pageable memory is staged through page-locked slots owned by this library (memcpy ->

@@ -53,6 +53,10 @@ int modgpu_time_verify_rekey_device(const void *dev_expect, const void *dev_src,
  * results array. */
 int modgpu_time_verify_table_device(const void *dev_entries, uint64_t n_entries, void *dev_results, void *dev_workspace,
                                     uint64_t workspace_bytes, int device, void *hip_stream, int iters, float *ms_per_call);
+/* The same for modgpu_verify_rekey_table_device: `iters` back-to-back rekey verify table calls (three launches each) on one workspace
+ * and one results array. */
+int modgpu_time_verify_rekey_table_device(const void *dev_entries, uint64_t n_entries, void *dev_results, void *dev_workspace,
+                                          uint64_t workspace_bytes, int device, void *hip_stream, int iters, float *ms_per_call);
 
 /* The launch the calling thread made last (any entry point), as the library planned it. */
 typedef struct modgpu_launch_info {
@@ -73,7 +77,8 @@ typedef struct modgpu_launch_info {
                                   launch), or its initialising kernel alone (`bytes` = 0) if the call had no non-empty entry,
                              11 = the verify table call's stream kernel (modgpu_verify_table_device; `bytes` = 0, as for 8),
                              12 = the rekey verify call's two-keystream compare kernel (modgpu_verify_rekey_device / _batch_device;
-                                  `bytes` = all entries of the launch); its entries with coinciding streams are a variant 10 launch */
+                                  `bytes` = all entries of the launch); its entries with coinciding streams are a variant 10 launch,
+                             13 = the rekey verify table call's stream kernel (modgpu_verify_rekey_table_device; `bytes` = 0, as for 8) */
     uint32_t grid;        /* workgroups launched                                                  */
     uint32_t block;       /* threads per workgroup                                                */
     uint32_t chunk_bytes; /* bytes one workgroup trip covers                                      */
@@ -89,7 +94,8 @@ typedef struct modgpu_launch_info {
                                 modgpu_rekey_table_kernel_source_hash() for variant 9,
                                 modgpu_verify_kernel_source_hash() for variant 10,
                                 modgpu_verify_table_kernel_source_hash() for variant 11,
-                                modgpu_rekey_verify_kernel_source_hash() for variant 12; static storage */
+                                modgpu_rekey_verify_kernel_source_hash() for variant 12,
+                                modgpu_rekey_verify_table_kernel_source_hash() for variant 13; static storage */
 } modgpu_launch_info_t;
 int modgpu_last_launch(modgpu_launch_info_t *out);
 
@@ -191,6 +197,10 @@ const char *modgpu_rekey_verify_kernel_source_hash(void);
 /* The same for the keep kernel's TU -- the work-queue kernel with a resident slice, what a single in-place buffer of 1 GiB or more is
  * launched on (cycle_keep_kernel.hip, cycle_keep_kernel.h, cycle_kernel_impl.h, cycle_kernel.h, lcg.h). */
 const char *modgpu_keep_kernel_source_hash(void);
+/* The same for the rekey verify table kernels' TU (cycle_rekey_verify_table_kernel.hip, cycle_rekey_verify_table_kernel.h,
+ * cycle_rekey_table_kernel.h, cycle_verify_table_kernel.h, cycle_table_kernel.h, cycle_verify_kernel.h, cycle_rekey_impl.h,
+ * cycle_kernel_impl.h, cycle_kernel.h, lcg.h). */
+const char *modgpu_rekey_verify_table_kernel_source_hash(void);
 /* What a single in-place device buffer of `bytes` bytes is launched with: returns 1 if it takes the keep kernel (0: the main
  * work-queue kernel, or a smaller shape), and the cache policy it would carry -- of every *mask + 1 chunks of 64 KiB, counted by
  * absolute address, the first *run are stored so that they stay in the Infinity Cache.  Either pointer may be NULL. */
@@ -233,6 +243,10 @@ void modgpu_debug_set_verify_form(int grid);
 /* The verify table call's stream launch: `grid` workgroups (1..4096), 0 = the shipped grid (one workgroup per CU).
  * Measurement (tools/bench_verify_table.py) and parity tests of small grids, where one workgroup passes several entries. */
 void modgpu_debug_set_verify_table_grid(uint32_t grid);
+
+/* The rekey verify table call's stream launch: `grid` workgroups (1..4096), 0 = the shipped grid (one workgroup per CU; DESIGN.md
+ * 4.13).  Measurement (tools/bench_verify_rekey_table.py) and parity tests of small grids, where one workgroup passes several entries. */
+void modgpu_debug_set_rekey_verify_table_grid(uint32_t grid);
 
 /* The resident slice of a single in-place buffer's work-queue launch: every such launch of `min_bytes` bytes or more takes the keep
  * kernel with exactly this `mask` (a power of two minus one) and `run` (run = 0: no chunk is kept; mask = 0, run = 1: every chunk),

@@ -24,6 +24,8 @@ from .capi import (  # noqa: F401
     VERIFY_RESULT_DTYPE, VERIFY_NONE,
     verify_table_device, verify_table_summary, verify_table_workspace_bytes, time_verify_table_device, verify_table_kernel_source_hash,
     debug_set_verify_table_grid, VERIFY_TABLE_SUMMARY_DTYPE,
+    verify_rekey_table_device, verify_rekey_table_workspace_bytes, time_verify_rekey_table_device, rekey_verify_table_kernel_source_hash,
+    debug_set_rekey_verify_table_grid,
     verify_rekey_device, verify_rekey_batch_device, time_verify_rekey_device, rekey_verify_kernel_source_hash,
     keep_kernel_source_hash, keep_policy, debug_set_keep, KEEP_OFF,
     cycle_host_to_device, cycle_device_to_host, cycle_file_to_device, cycle_device_to_file, xfer_kernel_source_hash, debug_set_xfer_form, XFER_FORMS,

@@ -85,6 +85,8 @@ EXPORTS = {
     "modgpu_verify_table_workspace_bytes": (_u64, [_u64]),
     "modgpu_verify_table_device": (_int, [_vp, _u64, _vp, _vp, _u64, _int, _vp]),
     "modgpu_verify_table_summary": (_int, [_vp, _int, _vp]),
+    "modgpu_verify_rekey_table_workspace_bytes": (_u64, [_u64]),
+    "modgpu_verify_rekey_table_device": (_int, [_vp, _u64, _vp, _vp, _u64, _int, _vp]),
     "modgpu_verify_rekey_device": (_int, [_vp, _vp, _u64, _i32, _u64, _i32, _u64, _vp, _int, _vp]),
     "modgpu_verify_rekey_batch_device": (_int, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64), ctypes.POINTER(_u64),
                                                 ctypes.POINTER(_u64), _int, _i32, _i32, _vp, _int, _vp]),
@@ -176,6 +178,8 @@ TESTING_EXPORTS = {
     "modgpu_time_verify_rekey_device": (_int, [_vp, _vp, _u64, _i32, _u64, _i32, _u64, _vp, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
     "modgpu_rekey_verify_kernel_source_hash": (ctypes.c_char_p, []),
     "modgpu_keep_kernel_source_hash": (ctypes.c_char_p, []),
+    "modgpu_time_verify_rekey_table_device": (_int, [_vp, _u64, _vp, _vp, _u64, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
+    "modgpu_rekey_verify_table_kernel_source_hash": (ctypes.c_char_p, []),
     "modgpu_keep_policy": (_int, [_u64, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
 }
 # include/modgpu_testing.h, modgpu_debug_* group: ONLY in libmodgpu_testing.so
@@ -201,6 +205,7 @@ DEBUG_EXPORTS = {
     "modgpu_debug_set_rekey_table_grid": (None, [ctypes.c_uint32]),
     "modgpu_debug_set_verify_form": (None, [_int]),
     "modgpu_debug_set_verify_table_grid": (None, [ctypes.c_uint32]),
+    "modgpu_debug_set_rekey_verify_table_grid": (None, [ctypes.c_uint32]),
     "modgpu_debug_set_keep": (None, [_u64, ctypes.c_uint32, ctypes.c_uint32]),
 }
 
@@ -1087,6 +1092,78 @@ def verify_table_kernel_source_hash():
 def debug_set_verify_table_grid(grid=0):
     """Testing flavour: the verify table call's stream grid (0 = shipped)."""
     _debug_lib().modgpu_debug_set_verify_table_grid(grid)
+
+
+def verify_rekey_table_workspace_bytes(n_entries):
+    """bytes of device workspace a rekey verify table call over n_entries needs (0 for none, or above the limit)"""
+    return lib().modgpu_verify_rekey_table_workspace_bytes(n_entries)
+
+
+def verify_rekey_table_device(entries, results=None, workspace=None, device=-1, stream=None, *, n=None):
+    """VERIFIES a TABLE of rekey entries in three launches, whatever its length: for entry i the count of the j with dst_i[j] !=
+    (src_i[j] ^ ks(key_from_i)[off_from_i + j] ^ ks(key_to_i)[off_to_i + j]) and the lowest such j -- `dst` is the comparand, nothing
+    but the results and the workspace is written, anything may overlap anything.  `entries` is a host table (a REKEY_TABLE_DTYPE array
+    from rekey_table(n): uploaded) or a table already in device memory (a DeviceBuffer or an address; then n, the entry count, is
+    needed).  `results` is a DeviceBuffer or address of 32 * n bytes, `workspace` one of at least verify_rekey_table_workspace_bytes(n)
+    bytes; None makes one.  When this function made a buffer itself it waits for the call, raises ModGpuError if the device refused an
+    entry (no result was written) and returns the results as a VERIFY_RESULT_DTYPE array; otherwise the call is asynchronous on
+    `stream`, returns None, and table_status(workspace), verify_table_summary(workspace) and verify_results(results, n) tell the
+    outcome after a synchronise."""
+    own = []
+    try:
+        if isinstance(entries, np.ndarray):
+            t = np.ascontiguousarray(entries, dtype=REKEY_TABLE_DTYPE)
+            n = t.size
+            if n == 0:
+                return np.zeros(0, dtype=VERIFY_RESULT_DTYPE)
+            buf = DeviceBuffer(t.nbytes, device)
+            own.append(buf)
+            buf.upload(t.view(np.uint8))
+            addr = buf.ptr
+        else:
+            if n is None:
+                raise TypeError("n (the entry count) is needed for a table in device memory")
+            addr = _dev_addr(entries)
+        if results is None and n:
+            results = DeviceBuffer(n * VERIFY_RESULT_DTYPE.itemsize, device)
+            own.append(results)
+        if workspace is None and n:
+            workspace = DeviceBuffer(verify_rekey_table_workspace_bytes(n), device)
+            own.append(workspace)
+        ws = _dev_addr(workspace) if workspace is not None else 0
+        ws_bytes = workspace.nbytes if isinstance(workspace, DeviceBuffer) else verify_rekey_table_workspace_bytes(n)
+        res = _dev_addr(results) if results is not None else 0
+        _check(lib().modgpu_verify_rekey_table_device(_vp(addr), n, _vp(res), _vp(ws), ws_bytes, device, _vp(stream or 0)))
+        if not own:
+            return None
+        _check(lib().modgpu_sync(device, _vp(stream or 0)))
+        bad = table_status(ws, device) if n else None
+        if bad is not None:
+            raise ModGpuError(1, f"the device refused rekey verify table entry {bad}; no result was written")
+        return verify_results(res, n, device)
+    finally:
+        for b in own:
+            b.free()
+
+
+def time_verify_rekey_table_device(entries, n, results, workspace, device=-1, stream=None, iters=2):
+    """Mean ms per rekey verify table call (three launches) over `iters` calls, HIP events on the launch stream; table, results and
+    workspace resident."""
+    ms = ctypes.c_float(0)
+    ws_bytes = workspace.nbytes if isinstance(workspace, DeviceBuffer) else verify_rekey_table_workspace_bytes(n)
+    _check(lib().modgpu_time_verify_rekey_table_device(_vp(_dev_addr(entries)), n, _vp(_dev_addr(results)), _vp(_dev_addr(workspace)), ws_bytes,
+                                                       device, _vp(stream or 0), iters, ctypes.byref(ms)))
+    return ms.value
+
+
+def rekey_verify_table_kernel_source_hash():
+    """identity of the rekey verify table kernels' TU (cycle_rekey_verify_table_kernel.hip and what it includes)"""
+    return lib().modgpu_rekey_verify_table_kernel_source_hash().decode()
+
+
+def debug_set_rekey_verify_table_grid(grid=0):
+    """Testing flavour: the rekey verify table call's stream grid (0 = shipped)."""
+    _debug_lib().modgpu_debug_set_rekey_verify_table_grid(grid)
 
 
 def _dev_addr(x):

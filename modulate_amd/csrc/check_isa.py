@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""check_isa.py <cycle_kernel.s> [<cycle_feed_kernel.s>] | <cycle_to_kernel.s> | <cycle_xfer_kernel.s> | <cycle_rekey_kernel.s> | <cycle_table_kernel.s> | <cycle_rekey_table_kernel.s> | <cycle_verify_kernel.s> | <cycle_verify_table_kernel.s> | <cycle_rekey_verify_kernel.s> | <cycle_keep_kernel.s> -- build-time guard over the gfx950 assembly of the kernel TUs (run by the
+"""check_isa.py <cycle_kernel.s> [<cycle_feed_kernel.s>] | <cycle_to_kernel.s> | <cycle_xfer_kernel.s> | <cycle_rekey_kernel.s> | <cycle_table_kernel.s> | <cycle_rekey_table_kernel.s> | <cycle_verify_kernel.s> | <cycle_verify_table_kernel.s> | <cycle_rekey_verify_kernel.s> | <cycle_keep_kernel.s> | <cycle_rekey_verify_table_kernel.s> -- build-time guard over the gfx950 assembly of the kernel TUs (run by the
 Makefile right after the TUs are compiled and before either object exists; tests/test_capi_cpu.py runs it again and feeds it
 deliberately broken builds).
 
@@ -63,6 +63,13 @@ mads + 30 addc, trailing s_nop 0, one v_bitop3_b32 0x96 per dword; 9 blocks: 4 w
 loop); every data load nt; NO buffer store and no buffer atomic anywhere (it reads its inputs and nothing else), no flat access, its
 only global store the 8 bytes of the entry's n, its only atomics 64-bit adds and unsigned mins, as many of the one as of the other;
 16 bytes of LDS (the workgroup's count and lowest index).
+The rekey verify table kernels (cycle_rekey_verify_table_kernel.s: plan, finish, stream; looked for BEFORE the rekey verify kernel, whose
+name theirs begins with): the rules of both parents' branches -- the register budget, no spills / scratch / private segment, no
+v_mbcnt; the plan and finish kernels carry no keystream block; the stream kernel carries the two-keystream blocks under the rekey
+kernel's rules (fixed temporaries v[112:127] and s[94:95], 60 mads + 30 addc, trailing s_nop 0, one v_bitop3_b32 0x96 per dword; 8
+blocks: 4 words x 2 unrolled trips), every data load nt, the ticket fetch ONE plain returning 32-bit atomic per unrolled trip, the table
+call's scalar-only entry search, NO store instruction of any kind, no buffer atomic, no flat access, and besides the ticket fetch only
+64-bit adds and unsigned mins, as many of the one as of the other, none of them returning.
 The keep kernel (cycle_keep_kernel.s: modgpu_cycle_keep_kernel and no other kernel; the work-queue kernel with a cache policy per
 chunk): the work-queue kernel's rules -- the register budget, no spills / scratch / private segment, the keystream blocks' rules above
 (9 blocks: 4 words x 2 unrolled trips + the cut first chunk), the ticket fetch ONE plain returning atomic per unrolled trip (4
@@ -569,6 +576,60 @@ def check_verify_table(asm, bodies):
     return bad
 
 
+REKEY_VERIFY_TABLE_KERNELS = ("modgpu_cycle_rekey_verify_table_plan", "modgpu_cycle_rekey_verify_table_finish", "modgpu_cycle_rekey_verify_table_kernel")
+
+
+def check_rekey_verify_table(asm, bodies):
+    """the rekey verify table kernels' TU (cycle_rekey_verify_table_kernel.s): the plan and finish kernels and the stream kernel"""
+    bad = []
+    kinds = {}
+    for name, fn in bodies.items():
+        kind = next((k for k in REKEY_VERIFY_TABLE_KERNELS if k in name), None)
+        if kind is None:
+            bad.append("%s: the rekey verify table kernels' TU holds another kernel" % name)
+            continue
+        kinds[kind] = kinds.get(kind, 0) + 1
+        md = metadata(asm, name)
+        if md.get("vgpr_count", 999) > 128 or md.get("sgpr_count", 999) > 102:
+            bad.append("%s: register counts beyond the budget: %s" % (name, md))
+        if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0) or "scratch_" in fn:
+            bad.append("%s: spills, scratch or a private segment: %s" % (name, md))
+        if "v_mbcnt" in fn:
+            bad.append("%s: the atomic optimizer rewrote an atomic (build the TU with -mllvm -amdgpu-atomic-optimizer-strategy=None)" % name)
+        blocks = len([b for b in BLOCK.findall(fn) if "s[94:95]" in b])
+        if kind != "modgpu_cycle_rekey_verify_table_kernel":
+            if blocks:
+                bad.append("%s: a planning kernel carries a keystream block" % name)
+            continue
+        bad += rekey_blocks(name, fn)
+        if blocks != 8:
+            bad.append("%s: %d two-keystream blocks, expected 8 (4 words x 2 unrolled trips)" % (name, blocks))
+        loads = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_load_dword", ln)]
+        if not loads or not all(ln.endswith(" nt") for ln in loads):
+            bad.append("%s: a data load is not nt" % name)
+        if re.search(r"^\s+(buffer|global|flat|scratch)_store", fn, re.M):
+            bad.append("%s: a rekey verify kernel stores through a buffer descriptor or a pointer (its inputs are read-only; the stream has no store at all)" % name)
+        if re.search(r"^\s+(buffer|flat)_atomic", fn, re.M) or re.search(r"^\s+flat_", fn, re.M):
+            bad.append("%s: buffer atomics or flat_ accesses (LDS must be ds_ instructions, results global_ atomics)" % name)
+        atomics = [(m.group(1), m.group(2)) for m in re.finditer(r"^\s+(global_atomic_\w+)\b([^;\n]*)", fn, re.M)]
+        tickets = [args for op, args in atomics if op == "global_atomic_add"]
+        if len(tickets) != 2 or not all(args.rstrip().endswith(" sc0") for args in tickets):
+            bad.append("%s: %d 32-bit global_atomic_add, expected the ticket fetch of each unrolled trip (2), each returning (sc0)" % (name, len(tickets)))
+        rest = [(op, args) for op, args in atomics if op != "global_atomic_add"]
+        adds = sum(1 for op, _ in rest if op == "global_atomic_add_x2")
+        mins = sum(1 for op, _ in rest if op == "global_atomic_umin_x2")
+        if not adds or adds != mins or adds + mins != len(rest) or any(" sc0" in args for _, args in rest):
+            bad.append("%s: result atomics %s, expected non-returning 64-bit adds and unsigned mins in equal numbers and nothing else"
+                       % (name, sorted(set(op for op, _ in rest))))
+        vec = len(re.findall(r"^\s+(?:global|flat)_load", fn, re.M))
+        if fn.count("s_load_dwordx16") < 2 or vec > 2:
+            bad.append("%s: the entry search is not scalar (%d s_load_dwordx16, %d vector loads besides the data)" % (name, fn.count("s_load_dwordx16"), vec))
+    for k in REKEY_VERIFY_TABLE_KERNELS:
+        if kinds.get(k, 0) != 1:
+            bad.append("the rekey verify table kernels' TU holds %d %s, expected 1" % (kinds.get(k, 0), k))
+    return bad
+
+
 def check_xfer(asm, bodies):
     """the transfer kernels' TU (cycle_xfer_kernel.s): the upload (ILb1) and the download (ILb0), each plain and funnel"""
     bad = []
@@ -661,7 +722,9 @@ def check(asm):
         if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0) or "scratch_" in bodies[feed[0]]:
             bad.append("%s: spills, scratch or a private segment: %s" % (feed[0], md))
         return bad + check_feed(asm, feed[0], bodies[feed[0]])
-    if any("modgpu_cycle_rekey_verify" in n for n in bodies):  # (no other branch's name is part of this one)
+    if any("modgpu_cycle_rekey_verify_table" in n for n in bodies):  # (before the rekey verify kernel: its name is the start of this one)
+        return bad + check_rekey_verify_table(asm, bodies)
+    if any("modgpu_cycle_rekey_verify" in n for n in bodies):  # (no other branch's name is part of this one but the one above)
         return bad + check_rekey_verify(asm, bodies)
     if any("modgpu_cycle_verify_table" in n for n in bodies):  # (before the verify kernels: their name is the start of this one)
         return bad + check_verify_table(asm, bodies)

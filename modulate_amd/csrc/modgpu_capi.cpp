@@ -23,6 +23,7 @@
 #include "cycle_rekey_kernel.h"
 #include "cycle_rekey_table_kernel.h"
 #include "cycle_verify_table_kernel.h"
+#include "cycle_rekey_verify_table_kernel.h"
 #include "cycle_verify_kernel.h"
 #include "cycle_rekey_verify_kernel.h"
 #include "cycle_table_kernel.h"
@@ -1624,6 +1625,93 @@ int verify_table_impl(const modgpu_table_entry_t *entries, uint64_t n, modgpu_ve
                      MODGPU_VERIFY_TABLE_KERNEL_SOURCE_HASH};
     return MODGPU_OK;
 }
+
+// ---- a table of rekey entries in device memory, verified (modgpu_verify_rekey_table_device) -----------------------------------------
+// The rekey table call's layout with one line for the summary put in right behind the header (every later section 64 bytes further on),
+// as verify_table_layout does to table_layout: header and summary sit where the verify table call has them, so modgpu_table_status and
+// modgpu_verify_table_summary read this kind of workspace unchanged.
+struct RekeyVerifyTableLayout {
+    RekeyTableLayout r; // offsets already moved
+    uint64_t sum, bytes;
+};
+RekeyVerifyTableLayout rekey_verify_table_layout(uint64_t n)
+{
+    RekeyVerifyTableLayout L{rekey_table_layout(n), sizeof(CycleTableHdr), 0};
+    constexpr uint64_t line = sizeof(VerifyTableSummary);
+    L.r.t.blk += line;
+    L.r.t.plan += line;
+    for (uint32_t k = 0; k <= L.r.t.top; ++k) L.r.t.level[k] += line;
+    L.r.t.bytes += line;
+    L.r.edge += line;
+    L.r.bytes += line;
+    L.bytes = L.r.bytes;
+    return L;
+}
+
+// The stream launch's grid: one workgroup per CU on every CU, the verify table call's rule
+#ifdef MODGPU_TESTING_HOOKS
+std::atomic<uint32_t> g_rekey_verify_table_grid{0}; // modgpu_debug_set_rekey_verify_table_grid
+uint32_t rekey_verify_table_grid_forced() { return g_rekey_verify_table_grid.load(std::memory_order_relaxed); }
+#else
+constexpr uint32_t rekey_verify_table_grid_forced() { return 0; }
+#endif
+uint32_t rekey_verify_table_grid()
+{
+    if (rekey_verify_table_grid_forced()) return rekey_verify_table_grid_forced();
+    return std::max<uint32_t>(1, large_grid());
+}
+
+// Tier 1 (include/modgpu.h): everything checked before anything is queued; then the three launches on `stream`.
+int verify_rekey_table_impl(const modgpu_rekey_table_entry_t *entries, uint64_t n, modgpu_verify_result_t *results, void *ws, uint64_t ws_bytes,
+                            int device, hipStream_t stream)
+{
+    if (n == 0) return MODGPU_OK;
+    if (n > kTableMaxEntries) return fail(MODGPU_ERR_INVALID, "more than 4194304 entries (the table call's limit)");
+    if (!entries || !ws) return fail(MODGPU_ERR_INVALID, "null table or workspace");
+    if (!results) return fail(MODGPU_ERR_INVALID, "null results");
+    if ((reinterpret_cast<uintptr_t>(entries) | reinterpret_cast<uintptr_t>(ws)) & 7) return fail(MODGPU_ERR_INVALID, "table or workspace not 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(results) & 7) return fail(MODGPU_ERR_INVALID, "results not 8-byte aligned");
+    const RekeyVerifyTableLayout L = rekey_verify_table_layout(n);
+    if (ws_bytes < L.bytes) return fail(MODGPU_ERR_INVALID, "workspace smaller than modgpu_verify_rekey_table_workspace_bytes(n_entries)");
+    DeviceScope scope(device);
+    if (scope.rc) return scope.rc;
+    int phys = -1;
+    HIP_TRY(hipGetDevice(&phys));
+    if (modgpu_xfer_device_of(entries, n * sizeof(modgpu_rekey_table_entry_t)) != phys || modgpu_xfer_device_of(ws, L.bytes) != phys)
+        return fail(MODGPU_ERR_INVALID, "the table or the workspace is not device memory of the call's device");
+    if (modgpu_xfer_device_of(results, n * sizeof(modgpu_verify_result_t)) != phys)
+        return fail(MODGPU_ERR_INVALID, "the results are not device memory of the call's device");
+    uint8_t *const w = static_cast<uint8_t *>(ws);
+    RekeyVerifyTableArgs a{};
+    a.entries = reinterpret_cast<const RekeyTableEntry *>(entries);
+    a.n = n;
+    a.hdr = reinterpret_cast<CycleTableHdr *>(w);
+    a.sum = reinterpret_cast<VerifyTableSummary *>(w + L.sum);
+    a.blk = reinterpret_cast<CycleTableBlk *>(w + L.r.t.blk);
+    a.plan = reinterpret_cast<RekeyTablePlan *>(w + L.r.t.plan);
+    a.edge = reinterpret_cast<RekeyTableEdge *>(w + L.r.edge);
+    a.results = reinterpret_cast<CycleVerifyResult *>(results);
+    for (uint32_t k = 0; k <= L.r.t.top; ++k) {
+        a.level[k] = reinterpret_cast<uint32_t *>(w + L.r.t.level[k]);
+        a.level_n[k] = L.r.t.level_n[k];
+    }
+    a.top = L.r.t.top;
+    a.n_blk = L.r.t.n_blk;
+    const uint32_t grid = rekey_verify_table_grid();
+    (void)hipGetLastError(); // (the launches report hipGetLastError: an earlier call's error must not be taken for theirs)
+    hipError_t e = modgpu_launch_rekey_verify_table_plan(a, stream);
+    if (e != hipSuccess) return fail_hip(e, "verify rekey table plan launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    e = modgpu_launch_rekey_verify_table_finish(a, stream);
+    if (e != hipSuccess) return fail_hip(e, "verify rekey table finish launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    e = modgpu_launch_rekey_verify_table_stream(a, grid, stream);
+    if (e != hipSuccess) return fail_hip(e, "verify rekey table stream launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    t_last_launch = {modgpu_rekey_verify_table_kernel_name(), CYCLE_REKEY_VERIFY_TABLE, grid, modgpu_rekey_verify_table_block(),
+                     modgpu_rekey_verify_table_chunk_bytes(), 0, grid, MODGPU_REKEY_VERIFY_TABLE_KERNEL_SOURCE_HASH};
+    return MODGPU_OK;
+}
 } // namespace
 
 } // namespace modgpu
@@ -1833,6 +1921,19 @@ int modgpu_verify_table_device(const modgpu_table_entry_t *dev_entries, uint64_t
 {
     return guarded([&]() -> int {
         return verify_table_impl(dev_entries, n_entries, dev_results, dev_workspace, workspace_bytes, device, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+uint64_t modgpu_verify_rekey_table_workspace_bytes(uint64_t n_entries)
+{
+    return n_entries == 0 || n_entries > kTableMaxEntries ? 0 : rekey_verify_table_layout(n_entries).bytes;
+}
+
+int modgpu_verify_rekey_table_device(const modgpu_rekey_table_entry_t *dev_entries, uint64_t n_entries, modgpu_verify_result_t *dev_results,
+                                     void *dev_workspace, uint64_t workspace_bytes, int device, void *hip_stream)
+{
+    return guarded([&]() -> int {
+        return verify_rekey_table_impl(dev_entries, n_entries, dev_results, dev_workspace, workspace_bytes, device, static_cast<hipStream_t>(hip_stream));
     });
 }
 
@@ -2625,6 +2726,7 @@ const char *modgpu_verify_kernel_source_hash(void) { return MODGPU_VERIFY_KERNEL
 const char *modgpu_verify_table_kernel_source_hash(void) { return MODGPU_VERIFY_TABLE_KERNEL_SOURCE_HASH; }
 const char *modgpu_rekey_verify_kernel_source_hash(void) { return MODGPU_REKEY_VERIFY_KERNEL_SOURCE_HASH; }
 const char *modgpu_keep_kernel_source_hash(void) { return MODGPU_KEEP_KERNEL_SOURCE_HASH; }
+const char *modgpu_rekey_verify_table_kernel_source_hash(void) { return MODGPU_REKEY_VERIFY_TABLE_KERNEL_SOURCE_HASH; }
 
 int modgpu_keep_policy(uint64_t bytes, uint32_t *mask, uint32_t *run)
 {
@@ -2717,6 +2819,35 @@ int modgpu_time_verify_table_device(const void *dev_entries, uint64_t n_entries,
     });
 }
 
+int modgpu_time_verify_rekey_table_device(const void *dev_entries, uint64_t n_entries, void *dev_results, void *dev_workspace, uint64_t workspace_bytes,
+                                          int device, void *hip_stream, int iters, float *ms_per_call)
+{
+    return guarded([&]() -> int {
+        if (iters <= 0 || !ms_per_call) return fail(MODGPU_ERR_INVALID, "bad timing arguments");
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        int rc = MODGPU_OK;
+        hipStream_t st = static_cast<hipStream_t>(hip_stream);
+        hipEvent_t e0, e1;
+        HIP_TRY(hipEventCreate(&e0));
+        HIP_TRY(hipEventCreate(&e1));
+        HIP_TRY(hipEventRecord(e0, st));
+        for (int i = 0; i < iters && rc == MODGPU_OK; ++i)
+            rc = verify_rekey_table_impl(static_cast<const modgpu_rekey_table_entry_t *>(dev_entries), n_entries, static_cast<modgpu_verify_result_t *>(dev_results),
+                                         dev_workspace, workspace_bytes, -1, st);
+        hipError_t e = hipEventRecord(e1, st);
+        if (e == hipSuccess) e = hipEventSynchronize(e1);
+        float ms = 0.f;
+        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+        (void)hipEventDestroy(e0);
+        (void)hipEventDestroy(e1);
+        if (rc) return rc;
+        if (e != hipSuccess) return fail_hip(e, "event timing");
+        *ms_per_call = ms / (float)iters;
+        return MODGPU_OK;
+    });
+}
+
 int modgpu_testing_hooks(void)
 {
 #ifdef MODGPU_TESTING_HOOKS
@@ -2754,6 +2885,7 @@ void modgpu_debug_set_table_grid(uint32_t grid) { g_table_grid.store(std::min<ui
 void modgpu_debug_set_rekey_table_grid(uint32_t grid) { g_rekey_table_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
 
 void modgpu_debug_set_verify_table_grid(uint32_t grid) { g_verify_table_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
+void modgpu_debug_set_rekey_verify_table_grid(uint32_t grid) { g_rekey_verify_table_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
 
 // (caps the compare launches of the verify call and of the rekey verify call alike)
 void modgpu_debug_set_verify_form(int grid) { g_verify_grid.store(grid <= 0 ? 0u : std::min<uint32_t>((uint32_t)grid, 4096u), std::memory_order_relaxed); }
