@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
-"""check_isa.py <cycle_kernel.s> [<cycle_feed_kernel.s>] | <cycle_to_kernel.s> | <cycle_xfer_kernel.s> | <cycle_rekey_kernel.s> | <cycle_table_kernel.s> | <cycle_rekey_table_kernel.s> | <cycle_verify_kernel.s> | <cycle_verify_table_kernel.s> | <cycle_rekey_verify_kernel.s> | <cycle_keep_kernel.s> | <cycle_rekey_verify_table_kernel.s> -- build-time guard over the gfx950 assembly of the kernel TUs (run by the
-Makefile right after the TUs are compiled and before either object exists; tests/test_capi_cpu.py runs it again and feeds it
-deliberately broken builds).
+""" -- build-time guard over the gfx950 assembly of the kernel TUs (run by the Makefile right after a TU is
+compiled to assembly and before its object exists; the TUs' CPU test files run it again and feed it deliberately broken builds).
 
 The streaming kernels' keystream is one hand-scheduled assembly block per 16-byte word (cycle_kernel_impl.h,
 ks_word_carry) that works in FIXED registers, v[120:127] and s[94:95], which the kernels keep out of the register
@@ -10,11 +9,10 @@ its output, so the output is what is checked:
   * nothing outside the blocks touches the fixed registers, and no operand the compiler chose for a block lies in them
     (round 3: as plain clobbers the allocator handed them to inputs of the block -- wrong keystream, no error);
   * every block ends with the s_nop 0 that covers the SDWA dst_sel forwarding hazard towards the compiler's next instruction;
-  * register counts stay inside the budget (the small shape: <= 64 VGPRs, 8 waves per SIMD), nothing spills, no scratch;
-  * the work-queue kernel's ticket fetch is still ONE plain returning atomic per trip (LLVM's atomic optimizer would turn it
-    into a wave-aggregated atomic followed at once by s_waitcnt vmcnt(0)), its mailbox is accessed with ds_ instructions,
-    loads are nt, stores nt sc1, and the part table is read from the kernel arguments (no private segment).
-For EVERY kernel of either TU, whatever its arithmetic (round 6):
+  * register counts stay inside the budget, nothing spills, no scratch;
+  * what each TU needs beyond that -- the form of its atomics, its cache policies, its barriers -- is in the table of TUs below
+    (TUS), one entry per TU, each rule once (the functions above the table), the reason for a rule or a parameter next to it.
+For EVERY kernel of every TU, whatever its arithmetic (round 6):
   * no instruction directly behind an SDWA write with dst_sel BYTE_n / WORD_n reads the register that write touched (gfx940+:
     such a partial write needs one wait state before a VALU reads the register; LLVM's hazard recognizer does not look into
     inline assembly, and the small shape's put_byte is one such instruction per asm statement -- whether something else ended up
@@ -23,65 +21,11 @@ For EVERY kernel of either TU, whatever its arithmetic (round 6):
     followed with a stack of the masks saved by s_*_saveexec / narrowed by s_andn2 exec, and the stack must be EMPTY at a
     barrier on every path.  (The host-fed kernel's lab form hung a workgroup because lanes 1..63 of one wave went round the
     trip loop's back edge without lane 0 and met the barrier a second time; tools/archive/ubench_pcie_persist.hip.)
-The host-fed kernel (cycle_feed_kernel.s) in particular: <= 64 VGPRs, no spills, no scratch, 8 bytes of LDS, exactly two
-s_barrier, data loads nt, data stores sc1 and NOT nt (nt stores across PCIe measured 15-20 % slower), the trip's ticket and ok
-word read into scalar registers (v_readfirstlane) behind the first barrier.
-The out-of-place kernel (cycle_to_kernel.s, both forms): the register budget, no spills / scratch / private segment, the keystream
-blocks' rules above, the ticket fetch not wave-aggregated (no v_mbcnt), data loads nt, data stores nt sc1.
-The transfer kernels (cycle_xfer_kernel.s, four forms): the host-fed kernel's rules -- <= 64 VGPRs, no spills / scratch, 8 bytes of
-LDS, exactly two s_barrier, the ticket and ok word in scalar registers behind the first barrier, ALG 1 --, every data load nt, the
-upload's stores into HBM nt sc1, the download's stores across PCIe sc1 and NOT nt.
-The rekey kernel (cycle_rekey_kernel.s, both forms): the register budget, no spills / scratch / private segment, the ticket fetch not
-wave-aggregated, data loads nt, data stores nt sc1, and the two-keystream blocks' own discipline (cycle_rekey_impl.h): fixed
-temporaries v[112:127] and s[94:95] touched by nothing outside the blocks and given to no operand the compiler chose, every block
-60 mads + 30 addc ending with s_nop 0, and one three-input XOR (v_bitop3_b32 bitop3:0x96; gfx950 has no v_xor3_b32) per dword of
-every block.
-The table kernels (cycle_table_kernel.s: plan, finish, stream): the register budget, no spills / scratch / private segment, no v_mbcnt
-in any of them (their atomics stay plain); the stream kernel carries the keystream blocks under the rules above (8 of them: 4 words x
-2 unrolled trips), its data loads are nt and its stores nt sc1, and it finds a chunk's entry with scalar loads only (s_load_dwordx16 of
-the search levels and of the entry's plan; no vector load besides the lane's two start-up table lookups -- a vector-memory search
-would wait for the chunk loads in flight); the plan and finish kernels carry no keystream block.
-The rekey table kernels (cycle_rekey_table_kernel.s: plan, finish, stream): the register budget, no spills / scratch / private segment,
-no v_mbcnt; the stream kernel carries the two-keystream blocks under the rekey kernel's rules (fixed temporaries, 60 mads + 30 addc,
-trailing s_nop 0, one v_bitop3_b32 0x96 per dword; 8 blocks: 4 words x 2 unrolled trips), data loads nt and stores nt sc1, and the
-table call's scalar-only entry search; the plan and finish kernels carry no keystream block of either kind.
-The verify kernels (cycle_verify_kernel.s: the init kernel and four forms of the stream kernel -- plain / funnel x keyed / identity): the
-register budget, no spills / scratch / private segment; the keyed forms carry the keystream blocks under the rules above (9 of them: 4
-words x 2 unrolled trips + the cut first chunk's loop), the identity forms and the init kernel none; every data load nt; NO buffer store
-and no buffer atomic anywhere in a stream kernel (it reads its inputs and nothing else), no flat access, its only global store the
-8 bytes of the entry's n, its only atomics 64-bit adds and unsigned mins, as many of the one as of the other; 16 bytes of LDS (the
-workgroup's count and lowest index); the init kernel loads nothing and stores with global_store only.
-The verify table kernels (cycle_verify_table_kernel.s: plan, finish, stream; looked for BEFORE the verify kernels, whose name theirs
-begins with): the register budget, no spills / scratch / private segment, no v_mbcnt; the plan and finish kernels carry no keystream
-block; the stream kernel carries the keystream blocks under the rules above (8 of them: 4 words x 2 unrolled trips), every data load
-nt, the ticket fetch ONE plain returning 32-bit atomic per unrolled trip, the table call's scalar-only entry search, NO store
-instruction of any kind (buffer, global, flat or scratch: it writes through atomics and into its LDS mailbox only), no buffer atomic,
-and besides the ticket fetch only 64-bit adds and unsigned mins, as many of the one as of the other, none of them returning.
-The rekey verify kernel (cycle_rekey_verify_kernel.s: two forms, plain and funnel, and no other kernel): the register budget, no spills
-/ scratch / private segment; the two-keystream blocks under the rekey kernel's rules (fixed temporaries v[112:127] and s[94:95], 60
-mads + 30 addc, trailing s_nop 0, one v_bitop3_b32 0x96 per dword; 9 blocks: 4 words x 2 unrolled trips + the cut first chunk's
-loop); every data load nt; NO buffer store and no buffer atomic anywhere (it reads its inputs and nothing else), no flat access, its
-only global store the 8 bytes of the entry's n, its only atomics 64-bit adds and unsigned mins, as many of the one as of the other;
-16 bytes of LDS (the workgroup's count and lowest index).
-The rekey verify table kernels (cycle_rekey_verify_table_kernel.s: plan, finish, stream; looked for BEFORE the rekey verify kernel, whose
-name theirs begins with): the rules of both parents' branches -- the register budget, no spills / scratch / private segment, no
-v_mbcnt; the plan and finish kernels carry no keystream block; the stream kernel carries the two-keystream blocks under the rekey
-kernel's rules (fixed temporaries v[112:127] and s[94:95], 60 mads + 30 addc, trailing s_nop 0, one v_bitop3_b32 0x96 per dword; 8
-blocks: 4 words x 2 unrolled trips), every data load nt, the ticket fetch ONE plain returning 32-bit atomic per unrolled trip, the table
-call's scalar-only entry search, NO store instruction of any kind, no buffer atomic, no flat access, and besides the ticket fetch only
-64-bit adds and unsigned mins, as many of the one as of the other, none of them returning.
-The keep kernel (cycle_keep_kernel.s: modgpu_cycle_keep_kernel and no other kernel; the work-queue kernel with a cache policy per
-chunk): the work-queue kernel's rules -- the register budget, no spills / scratch / private segment, the keystream blocks' rules above
-(9 blocks: 4 words x 2 unrolled trips + the cut first chunk), the ticket fetch ONE plain returning atomic per unrolled trip (4
-global_atomic_add in all, no v_mbcnt), the mailbox accessed with ds_ instructions (3 writes, 3 reads), no flat access, every data load
-nt -- and in the unrolled stream loop exactly as many `sc1`-only stores (the resident chunks' burst) as `nt sc1` stores (the
-streaming chunks'), 4 words x 2 trips each; the cut first chunk's one store is nt sc1.
 Exit status 0 = all of it holds; 1 = findings on stdout."""
 import re
 import sys
+from collections import namedtuple
 
-FIXED = re.compile(r"\bv12[0-7]\b|v\[\d+:12[0-7]\]|\bs9[45]\b|s\[\d+:9[45]\]")
-OWN = re.compile(r"v\[12[0246]:12[1357]\]|s\[94:95\]|\bv12[0246]\b|\bv127\b")  # the block's own uses of them
 BLOCK = re.compile(r";;#ASMSTART\n(.*?);;#ASMEND", re.S)
 
 
@@ -110,6 +54,13 @@ def metadata(asm, name):
     end = meta.find("  - .agpr_count", at)
     rec = meta[start:end if end > 0 else len(meta)]
     return {k: int(v) for k, v in re.findall(r"^\s+(?:- )?\.(\w+):\s+(\d+)\s*$", rec, re.M) if k not in ("offset", "size")}
+
+
+def source_name(mangled):
+    """_Z<length><name><template arguments, parameter types> -> (the kernel's name in the source, the rest)"""
+    m = re.match(r"_Z(\d+)", mangled)
+    end = m.end() + int(m.group(1))
+    return mangled[m.end():end], mangled[end:]
 
 
 # ---- rules for every kernel ------------------------------------------------------------------------------------------------------
@@ -209,578 +160,407 @@ def barriers_at_full_exec(name, fn):
     return sorted(set(bad))
 
 
-def check_feed(asm, name, fn):
-    """the host-fed kernel of cycle_feed_kernel.hip"""
-    bad = []
-    md = metadata(asm, name)
-    if md.get("vgpr_count", 999) > 64:
-        bad.append("%s: %d VGPRs -- more than 64, fewer than 8 waves per SIMD" % (name, md.get("vgpr_count", 999)))
-    if md.get("group_segment_fixed_size", -1) != 8:
-        bad.append("%s: LDS is %s bytes, expected the 8 of the ticket / ok mailbox" % (name, md.get("group_segment_fixed_size")))
-    if fn.count("s_barrier") != 2:
-        bad.append("%s: %d s_barrier, expected 2 (one behind thread 0's region, one at the end of the trip)" % (name, fn.count("s_barrier")))
-    loads = [ln for ln in fn.splitlines() if "buffer_load_dwordx4" in ln]
-    stores = [ln for ln in fn.splitlines() if "buffer_store_dwordx4" in ln]
-    if not loads or not all(ln.split(";")[0].rstrip().endswith(" nt") for ln in loads):
-        bad.append("%s: a data load is not nt" % name)
-    if not stores or not all(ln.split(";")[0].rstrip().endswith(" sc1") and " nt" not in ln.split(";")[0] for ln in stores):
-        bad.append("%s: a data store is not `sc1` without nt (nt stores across PCIe: -15..20 %%)" % name)
-    ins = instructions(fn)
-    first_barrier = next((k for k, (_, op, _) in enumerate(ins) if op == "s_barrier"), None)
-    if first_barrier is not None:
-        # text order is not execution order: the trip's first barrier is the one followed by the LDS read of the mailbox
-        follows = [k for k, (_, op, _) in enumerate(ins) if op == "s_barrier" and any(o.startswith("ds_read") for _, o, _ in ins[k + 1:k + 3])]
-        if len(follows) != 1 or sum(1 for _, o, _ in ins[follows[0] + 1:follows[0] + 8] if o == "v_readfirstlane_b32") < 2:
-            bad.append("%s: the ticket and the ok word are not read into scalar registers right behind the trip's first barrier" % name)
-    if fn.count("v_add_u32_sdwa") != 15:
-        bad.append("%s: keystream instruction mix changed (%d v_add_u32_sdwa, expected 15: ALG 1)" % (name, fn.count("v_add_u32_sdwa")))
-    return bad
+# ---- the rules of the TUs, each once.  A kernel rule takes a Kernel (and the parameters its entry in TUS gives it) and returns its
+# findings; `name` is what the findings call the kernel (its mangled name), `source` its name in the source, `fn` its body up to
+# s_endpgm, `md` its metadata record. ----
+Kernel = namedtuple("Kernel", "name source fn md")
 
 
-def keystream_blocks(name, fn):
-    """(does the kernel carry ks_word_carry's block, findings): the fixed-temporary discipline, the trailing s_nop 0 and the
-    30 mad + 15 addc of every block"""
+def code_lines(fn, mnemonic):
+    """the instructions of a body whose mnemonic starts with `mnemonic`, without their comments"""
+    return [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+" + mnemonic, ln)]
+
+
+def register_budget(k, vgprs=128, who=""):
+    """128 VGPRs / 102 SGPRs: 4 waves per SIMD and the keystream blocks' fixed registers above the allocator's.  64 VGPRs for a kernel
+    that lives on occupancy (512 per SIMD lane / 8 waves); `who` is how its finding begins"""
+    if vgprs == 128:
+        if k.md.get("vgpr_count", 999) > 128 or k.md.get("sgpr_count", 999) > 102:
+            return ["%s: register counts beyond the budget: %s" % (k.name, k.md)]
+    elif k.md.get("vgpr_count", 999) > vgprs:
+        return ["%s: %s%d VGPRs -- more than %d, fewer than %d waves per SIMD" % (k.name, who, k.md.get("vgpr_count", 999), vgprs, 512 // vgprs)]
+    return []
+
+
+def no_spills(k, apart=False):
+    """no spills, no scratch instruction, no private segment (`apart`: the main TU's wording, scratch reported on its own)"""
+    spills = k.md.get("vgpr_spill_count", 0) or k.md.get("sgpr_spill_count", 0) or k.md.get("private_segment_fixed_size", 0)
+    scratch = "scratch_" in k.fn
+    if apart:
+        return (["%s: spills or a private segment: %s" % (k.name, k.md)] if spills else []) + (["%s: scratch instructions" % k.name] if scratch else [])
+    return ["%s: spills, scratch or a private segment: %s" % (k.name, k.md)] if spills or scratch else []
+
+
+def atomic_optimizer_off(k, what):
+    """LLVM's atomic optimizer turns an atomic into a wave-aggregated one (v_mbcnt ...) followed at once by s_waitcnt vmcnt(0); `what` it
+    would have rewritten: a ticket fetch must stay ONE plain returning atomic whose value is waited for a trip later"""
+    if "v_mbcnt" in k.fn:
+        return ["%s: the atomic optimizer rewrote %s (build the TU with -mllvm -amdgpu-atomic-optimizer-strategy=None)" % (k.name, what)]
+    return []
+
+
+# a block family: its words in findings, its fixed registers, the block's own uses of them, its instruction mix
+Blocks = namedtuple("Blocks", "a outside operand fixed own mads addc")
+KEYSTREAM = Blocks("keystream", "a fixed temporary is touched OUTSIDE the keystream blocks", "the compiler gave a block operand a fixed temporary",
+                   re.compile(r"\bv12[0-7]\b|v\[\d+:12[0-7]\]|\bs9[45]\b|s\[\d+:9[45]\]"),
+                   re.compile(r"v\[12[0246]:12[1357]\]|s\[94:95\]|\bv12[0246]\b|\bv127\b"), 30, 15)
+# cycle_rekey_impl.h, ks_word2_carry: both streams' words in one block, fixed temporaries v[112:127] and s[94:95]
+TWO_KEYSTREAM = Blocks("two-keystream", "a fixed temporary of the two-keystream block is touched OUTSIDE the blocks",
+                       "the compiler gave a two-keystream block operand a fixed temporary",
+                       re.compile(r"\bv11[2-9]\b|\bv12[0-7]\b|v\[\d+:(?:11[2-9]|12[0-7])\]|\bs9[45]\b|s\[\d+:9[45]\]"),
+                       re.compile(r"v\[(?:11[2468]|12[0246]):(?:11[3579]|12[1357])\]|s\[94:95\]|\bv(?:11[2468]|12[0246])\b|\bv12[57]\b"), 60, 30)
+
+
+def carry_blocks(fn):
+    return [b for b in BLOCK.findall(fn) if "s[94:95]" in b]
+
+
+def block_discipline(k, family):
+    """the fixed-temporary discipline, the trailing s_nop 0 and the instruction mix of every block of the kernel"""
     bad = []
-    carry = [b for b in BLOCK.findall(fn) if "s[94:95]" in b]
-    if not carry:
-        return False, bad  # (a kernel without the block may use any register)
-    outside = BLOCK.sub("", fn)
-    for ln in outside.splitlines():
-        if FIXED.search(ln) and not ln.strip().startswith(";"):
-            bad.append("%s: a fixed temporary is touched OUTSIDE the keystream blocks: %s" % (name, ln.strip()))
-    for b in carry:
+    for ln in BLOCK.sub("", k.fn).splitlines():
+        if family.fixed.search(ln) and not ln.strip().startswith(";"):
+            bad.append("%s: %s: %s" % (k.name, family.outside, ln.strip()))
+    for b in carry_blocks(k.fn):
         lines = [ln for ln in b.splitlines() if ln.strip()]
         for ln in lines:
-            if FIXED.search(OWN.sub("", ln)):
-                bad.append("%s: the compiler gave a block operand a fixed temporary: %s" % (name, ln.strip()))
+            if family.fixed.search(family.own.sub("", ln)):
+                bad.append("%s: %s: %s" % (k.name, family.operand, ln.strip()))
         if not lines or lines[-1].split(";")[0].strip() != "s_nop 0":
-            bad.append("%s: a keystream block does not end with s_nop 0 (dst_sel forwarding hazard)" % name)
-        if len([ln for ln in lines if "v_addc_co_u32_sdwa" in ln]) != 15 or len([ln for ln in lines if "v_mad_u64_u32" in ln]) != 30:
-            bad.append("%s: a keystream block is not 30 mads + 15 addc" % name)
-    return True, bad
-
-
-def check_to(asm, bodies):
-    """the out-of-place kernel's TU (cycle_to_kernel.s): every kernel in it is a form of modgpu_cycle_to_kernel"""
-    bad = []
-    for name, fn in bodies.items():
-        if "modgpu_cycle_to_kernel" not in name:
-            bad.append("%s: the out-of-place kernel's TU holds another kernel" % name)
-            continue
-        md = metadata(asm, name)
-        if md.get("vgpr_count", 999) > 128 or md.get("sgpr_count", 999) > 102:
-            bad.append("%s: register counts beyond the budget: %s" % (name, md))
-        if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0) or "scratch_" in fn:
-            bad.append("%s: spills, scratch or a private segment: %s" % (name, md))
-        found, findings = keystream_blocks(name, fn)
-        bad += findings
-        if not found:
-            bad.append("%s: no keystream block (ks_word_carry)" % name)
-        if "v_mbcnt" in fn:
-            bad.append("%s: the atomic optimizer rewrote the ticket atomic (build the TU with -mllvm -amdgpu-atomic-optimizer-strategy=None)" % name)
-        loads = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_load_dword", ln)]
-        stores = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_store_dword", ln)]
-        if not loads or not all(ln.endswith(" nt") for ln in loads):
-            bad.append("%s: a data load is not nt" % name)
-        if not stores or not all(ln.endswith(" nt sc1") for ln in stores):
-            bad.append("%s: a data store is not nt sc1" % name)
+            bad.append("%s: a %s block does not end with s_nop 0 (dst_sel forwarding hazard)" % (k.name, family.a))
+        if len([ln for ln in lines if "v_addc_co_u32_sdwa" in ln]) != family.addc or len([ln for ln in lines if "v_mad_u64_u32" in ln]) != family.mads:
+            bad.append("%s: a %s block is not %d mads + %d addc" % (k.name, family.a, family.mads, family.addc))
     return bad
 
 
-REKEY_FIXED = re.compile(r"\bv11[2-9]\b|\bv12[0-7]\b|v\[\d+:(?:11[2-9]|12[0-7])\]|\bs9[45]\b|s\[\d+:9[45]\]")
-REKEY_OWN = re.compile(r"v\[(?:11[2468]|12[0246]):(?:11[3579]|12[1357])\]|s\[94:95\]|\bv(?:11[2468]|12[0246])\b|\bv12[57]\b")
+def keystream_blocks(k, required=True):
+    """ks_word_carry's blocks (30 mads + 15 addc).  A kernel without the block may use any register; `required`: it must carry one"""
+    if not carry_blocks(k.fn):
+        return ["%s: no keystream block (ks_word_carry)" % k.name] if required else []
+    return block_discipline(k, KEYSTREAM)
 
 
-def rekey_blocks(name, fn):
-    """the two-keystream blocks of cycle_rekey_impl.h (ks_word2_carry): fixed temporaries, trailing s_nop 0, 60 mad + 30 addc each"""
-    bad = []
-    blocks = [b for b in BLOCK.findall(fn) if "s[94:95]" in b]
+def rekey_blocks(k):
+    """ks_word2_carry's blocks (60 mads + 30 addc), and one three-input XOR (v_bitop3_b32 bitop3:0x96; gfx950 has no v_xor3_b32) per
+    dword of every block"""
+    blocks = carry_blocks(k.fn)
     if not blocks:
-        return ["%s: no two-keystream block (ks_word2_carry)" % name]
-    outside = BLOCK.sub("", fn)
-    for ln in outside.splitlines():
-        if REKEY_FIXED.search(ln) and not ln.strip().startswith(";"):
-            bad.append("%s: a fixed temporary of the two-keystream block is touched OUTSIDE the blocks: %s" % (name, ln.strip()))
-    for b in blocks:
-        lines = [ln for ln in b.splitlines() if ln.strip()]
-        for ln in lines:
-            if REKEY_FIXED.search(REKEY_OWN.sub("", ln)):
-                bad.append("%s: the compiler gave a two-keystream block operand a fixed temporary: %s" % (name, ln.strip()))
-        if not lines or lines[-1].split(";")[0].strip() != "s_nop 0":
-            bad.append("%s: a two-keystream block does not end with s_nop 0 (dst_sel forwarding hazard)" % name)
-        if len([ln for ln in lines if "v_addc_co_u32_sdwa" in ln]) != 30 or len([ln for ln in lines if "v_mad_u64_u32" in ln]) != 60:
-            bad.append("%s: a two-keystream block is not 60 mads + 30 addc" % name)
-    xor3 = len(re.findall(r"v_bitop3_b32 .*bitop3:0x96", fn))
+        return ["%s: no two-keystream block (ks_word2_carry)" % k.name]
+    bad = block_discipline(k, TWO_KEYSTREAM)
+    xor3 = len(re.findall(r"v_bitop3_b32 .*bitop3:0x96", k.fn))
     if xor3 != 4 * len(blocks):
-        bad.append("%s: %d three-input XORs (v_bitop3_b32 0x96) for %d two-keystream blocks, expected one per dword (4 per block)" % (name, xor3, len(blocks)))
+        bad.append("%s: %d three-input XORs (v_bitop3_b32 0x96) for %d two-keystream blocks, expected one per dword (4 per block)" % (k.name, xor3, len(blocks)))
     return bad
 
 
-def check_rekey(asm, bodies):
-    """the rekey kernel's TU (cycle_rekey_kernel.s): every kernel in it is a form of modgpu_cycle_rekey_kernel"""
+def block_count(k, family, expected, made_of):
+    blocks = len(carry_blocks(k.fn))
+    return ["%s: %d %s blocks, expected %d (%s)" % (k.name, blocks, family.a, expected, made_of)] if blocks != expected else []
+
+
+def no_block(k, who):
+    return ["%s: %s carries a keystream block" % (k.name, who)] if carry_blocks(k.fn) else []
+
+
+def loads_nt(k):
+    """every chunk is read once: data loads (the buffer loads) are non-temporal"""
+    loads = code_lines(k.fn, "buffer_load_dword")
+    return [] if loads and all(ln.endswith(" nt") for ln in loads) else ["%s: a data load is not nt" % k.name]
+
+
+def stores(k, policy, what="a data store"):
+    """data stores (the buffer stores) by cache policy: "nt sc1" into HBM, "sc1" without nt across PCIe (nt measured 15-20 % slower there)"""
+    lines = code_lines(k.fn, "buffer_store_dword")
+    if policy == "nt sc1":
+        return [] if lines and all(ln.endswith(" nt sc1") for ln in lines) else ["%s: %s is not nt sc1" % (k.name, what)]
+    if lines and all(ln.endswith(" sc1") and " nt" not in ln for ln in lines):
+        return []
+    return ["%s: %s is not `sc1` without nt (nt stores across PCIe: -15..20 %%)" % (k.name, what)]
+
+
+def stores_nt_sc1_at_least(k, n):
+    return ["%s: fewer than %d nt sc1 stores" % (k.name, n)] if len([ln for ln in code_lines(k.fn, "buffer_store_dword") if ln.endswith("nt sc1")]) < n else []
+
+
+def keep_store_bursts(k):
+    """the keep kernel's two bursts in the unrolled stream loop: as many `sc1`-only stores (the resident chunks') as `nt sc1` stores (the
+    streaming chunks'), 4 words x 2 trips each; the cut first chunk's loop (cold, not unrolled) stores once, streaming"""
+    lines = code_lines(k.fn, "buffer_store_dword")
+    streaming = len([ln for ln in lines if ln.endswith(" nt sc1")])
+    resident = len([ln for ln in lines if ln.endswith(" sc1") and " nt" not in ln])
     bad = []
-    for name, fn in bodies.items():
-        if "modgpu_cycle_rekey_kernel" not in name:
-            bad.append("%s: the rekey kernel's TU holds another kernel" % name)
-            continue
-        md = metadata(asm, name)
-        if md.get("vgpr_count", 999) > 128 or md.get("sgpr_count", 999) > 102:
-            bad.append("%s: register counts beyond the budget: %s" % (name, md))
-        if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0) or "scratch_" in fn:
-            bad.append("%s: spills, scratch or a private segment: %s" % (name, md))
-        bad += rekey_blocks(name, fn)
-        if "v_mbcnt" in fn:
-            bad.append("%s: the atomic optimizer rewrote the ticket atomic (build the TU with -mllvm -amdgpu-atomic-optimizer-strategy=None)" % name)
-        loads = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_load_dword", ln)]
-        stores = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_store_dword", ln)]
-        if not loads or not all(ln.endswith(" nt") for ln in loads):
-            bad.append("%s: a data load is not nt" % name)
-        if not stores or not all(ln.endswith(" nt sc1") for ln in stores):
-            bad.append("%s: a data store is not nt sc1" % name)
+    if streaming + resident != len(lines):
+        bad.append("%s: a data store is neither nt sc1 nor sc1" % k.name)
+    if resident != 8 or streaming - 1 != 8:
+        bad.append("%s: %d sc1-only and %d nt sc1 stores in the stream loop, expected 8 of each (4 words x 2 unrolled trips, one burst per "
+                   "cache policy)" % (k.name, resident, streaming - 1))
     return bad
 
 
-TABLE_KERNELS = ("modgpu_cycle_table_plan", "modgpu_cycle_table_finish", "modgpu_cycle_table_kernel")
+def scalar_entry_search(k):
+    """a table call's stream kernel finds a chunk's entry with scalar loads only (s_load_dwordx16 of the search levels and of the entry's
+    plan; no vector load besides the lane's two start-up table lookups): a vector-memory search would wait for the chunk loads in flight"""
+    vec = len(re.findall(r"^\s+(?:global|flat)_load", k.fn, re.M))
+    if k.fn.count("s_load_dwordx16") < 2 or vec > 2:
+        return ["%s: the entry search is not scalar (%d s_load_dwordx16, %d vector loads besides the data)" % (k.name, k.fn.count("s_load_dwordx16"), vec)]
+    return []
 
 
-def check_table(asm, bodies):
-    """the table kernels' TU (cycle_table_kernel.s): the plan and finish kernels and the stream kernel"""
+def read_only_stream(k, who, no_store_at_all=False):
+    """a verify kernel reads its inputs and nothing else: no buffer store or atomic, no flat access.  `no_store_at_all`: the table forms
+    write through atomics and into their LDS mailbox only, so no store instruction of any kind"""
     bad = []
-    kinds = {}
-    for name, fn in bodies.items():
-        kind = next((k for k in TABLE_KERNELS if k in name), None)
-        if kind is None:
-            bad.append("%s: the table kernels' TU holds another kernel" % name)
-            continue
-        kinds[kind] = kinds.get(kind, 0) + 1
-        md = metadata(asm, name)
-        if md.get("vgpr_count", 999) > 128 or md.get("sgpr_count", 999) > 102:
-            bad.append("%s: register counts beyond the budget: %s" % (name, md))
-        if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0) or "scratch_" in fn:
-            bad.append("%s: spills, scratch or a private segment: %s" % (name, md))
-        if "v_mbcnt" in fn:
-            bad.append("%s: the atomic optimizer rewrote an atomic (build the TU with -mllvm -amdgpu-atomic-optimizer-strategy=None)" % name)
-        found, findings = keystream_blocks(name, fn)
-        bad += findings
-        if kind != "modgpu_cycle_table_kernel":
-            if found:
-                bad.append("%s: a planning kernel carries a keystream block" % name)
-            continue
-        if not found:
-            bad.append("%s: no keystream block (ks_word_carry)" % name)
-        blocks = len([b for b in BLOCK.findall(fn) if "s[94:95]" in b])
-        if blocks != 8:
-            bad.append("%s: %d keystream blocks, expected 8 (4 words x 2 unrolled trips)" % (name, blocks))
-        loads = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_load_dword", ln)]
-        stores = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_store_dword", ln)]
-        if not loads or not all(ln.endswith(" nt") for ln in loads):
-            bad.append("%s: a data load is not nt" % name)
-        if not stores or not all(ln.endswith(" nt sc1") for ln in stores):
-            bad.append("%s: a data store is not nt sc1" % name)
-        vec = len(re.findall(r"^\s+(?:global|flat)_load", fn, re.M))
-        if fn.count("s_load_dwordx16") < 2 or vec > 2:
-            bad.append("%s: the entry search is not scalar (%d s_load_dwordx16, %d vector loads besides the data)" % (name, fn.count("s_load_dwordx16"), vec))
-    for k in TABLE_KERNELS:
-        if kinds.get(k, 0) != 1:
-            bad.append("the table kernels' TU holds %d %s, expected 1" % (kinds.get(k, 0), k))
+    if no_store_at_all:
+        if re.search(r"^\s+(buffer|global|flat|scratch)_store", k.fn, re.M):
+            bad.append("%s: %s stores through a buffer descriptor or a pointer (its inputs are read-only; the stream has no store at all)" % (k.name, who))
+        if re.search(r"^\s+(buffer|flat)_atomic", k.fn, re.M) or re.search(r"^\s+flat_", k.fn, re.M):
+            bad.append("%s: buffer atomics or flat_ accesses (LDS must be ds_ instructions, results global_ atomics)" % k.name)
+        return bad
+    if re.search(r"^\s+buffer_(store|atomic)", k.fn, re.M):
+        bad.append("%s: %s stores through a buffer descriptor (its inputs are read-only; the stream has no store at all)" % (k.name, who))
+    if re.search(r"^\s+flat_", k.fn, re.M):
+        bad.append("%s: flat_ accesses (LDS must be ds_ instructions, results global_)" % k.name)
     return bad
 
 
-REKEY_TABLE_KERNELS = ("modgpu_cycle_rekey_table_plan", "modgpu_cycle_rekey_table_finish", "modgpu_cycle_rekey_table_kernel")
+def one_global_store(k):
+    found = re.findall(r"^\s+(global_store_\w+)", k.fn, re.M)
+    return ["%s: global stores %s, expected the one global_store_dwordx2 of the entry's n" % (k.name, found)] if found != ["global_store_dwordx2"] else []
 
 
-def check_rekey_table(asm, bodies):
-    """the rekey table kernels' TU (cycle_rekey_table_kernel.s): the plan and finish kernels and the stream kernel"""
+def result_atomics(k, tickets=0):
+    """a verify kernel's results: 64-bit adds (the count) and unsigned mins (the lowest index), as many of the one as of the other, and
+    nothing else.  `tickets`: the returning 32-bit ticket fetches that come on top (one per unrolled trip), the results then not returning"""
     bad = []
-    kinds = {}
-    for name, fn in bodies.items():
-        kind = next((k for k in REKEY_TABLE_KERNELS if k in name), None)
-        if kind is None:
-            bad.append("%s: the rekey table kernels' TU holds another kernel" % name)
-            continue
-        kinds[kind] = kinds.get(kind, 0) + 1
-        md = metadata(asm, name)
-        if md.get("vgpr_count", 999) > 128 or md.get("sgpr_count", 999) > 102:
-            bad.append("%s: register counts beyond the budget: %s" % (name, md))
-        if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0) or "scratch_" in fn:
-            bad.append("%s: spills, scratch or a private segment: %s" % (name, md))
-        if "v_mbcnt" in fn:
-            bad.append("%s: the atomic optimizer rewrote an atomic (build the TU with -mllvm -amdgpu-atomic-optimizer-strategy=None)" % name)
-        blocks = len([b for b in BLOCK.findall(fn) if "s[94:95]" in b])
-        if kind != "modgpu_cycle_rekey_table_kernel":
-            if blocks:
-                bad.append("%s: a planning kernel carries a keystream block" % name)
-            continue
-        bad += rekey_blocks(name, fn)
-        if blocks != 8:
-            bad.append("%s: %d two-keystream blocks, expected 8 (4 words x 2 unrolled trips)" % (name, blocks))
-        loads = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_load_dword", ln)]
-        stores = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_store_dword", ln)]
-        if not loads or not all(ln.endswith(" nt") for ln in loads):
-            bad.append("%s: a data load is not nt" % name)
-        if not stores or not all(ln.endswith(" nt sc1") for ln in stores):
-            bad.append("%s: a data store is not nt sc1" % name)
-        vec = len(re.findall(r"^\s+(?:global|flat)_load", fn, re.M))
-        if fn.count("s_load_dwordx16") < 2 or vec > 2:
-            bad.append("%s: the entry search is not scalar (%d s_load_dwordx16, %d vector loads besides the data)" % (name, fn.count("s_load_dwordx16"), vec))
-    for k in REKEY_TABLE_KERNELS:
-        if kinds.get(k, 0) != 1:
-            bad.append("the rekey table kernels' TU holds %d %s, expected 1" % (kinds.get(k, 0), k))
+    atomics = [(m.group(1), m.group(2)) for m in re.finditer(r"^\s+(global_atomic_\w+)\b([^;\n]*)", k.fn, re.M)]
+    if tickets:
+        fetches = [args for op, args in atomics if op == "global_atomic_add"]
+        if len(fetches) != tickets or not all(args.rstrip().endswith(" sc0") for args in fetches):
+            bad.append("%s: %d 32-bit global_atomic_add, expected the ticket fetch of each unrolled trip (%d), each returning (sc0)" % (k.name, len(fetches), tickets))
+        atomics = [(op, args) for op, args in atomics if op != "global_atomic_add"]
+    ops = [op for op, _ in atomics]
+    adds, mins = ops.count("global_atomic_add_x2"), ops.count("global_atomic_umin_x2")
+    if not adds or adds != mins or adds + mins != len(ops) or (tickets and any(" sc0" in args for _, args in atomics)):
+        bad.append("%s: result atomics %s, expected %s64-bit adds and unsigned mins in equal numbers and nothing else"
+                   % (k.name, sorted(set(ops)), "non-returning " if tickets else ""))
     return bad
 
 
-VERIFY_KERNELS = ("modgpu_cycle_verify_init", "modgpu_cycle_verify_kernel")
+def lds_bytes(k, n, of):
+    if k.md.get("group_segment_fixed_size", -1) != n:
+        return ["%s: LDS is %s bytes, expected the %d of %s" % (k.name, k.md.get("group_segment_fixed_size"), n, of)]
+    return []
 
 
-def check_verify(asm, bodies):
-    """the verify kernels' TU (cycle_verify_kernel.s): the init kernel and the stream kernel's four forms"""
+def two_barriers(k):
+    if k.fn.count("s_barrier") != 2:
+        return ["%s: %d s_barrier, expected 2 (one behind thread 0's region, one at the end of the trip)" % (k.name, k.fn.count("s_barrier"))]
+    return []
+
+
+def mailbox_read_scalar(k):
+    """a host-fed trip's ticket and ok word go from the LDS mailbox into scalar registers (v_readfirstlane) behind the first barrier.
+    Text order is not execution order: the trip's first barrier is the one followed by the LDS read of the mailbox"""
+    ins = instructions(k.fn)
+    follows = [i for i, (_, op, _) in enumerate(ins) if op == "s_barrier" and any(o.startswith("ds_read") for _, o, _ in ins[i + 1:i + 3])]
+    if len(follows) != 1 or sum(1 for _, o, _ in ins[follows[0] + 1:follows[0] + 8] if o == "v_readfirstlane_b32") < 2:
+        return ["%s: the ticket and the ok word are not read into scalar registers right behind the trip's first barrier" % k.name]
+    return []
+
+
+def alg1_mix(k):
+    if k.fn.count("v_add_u32_sdwa") != 15:
+        return ["%s: keystream instruction mix changed (%d v_add_u32_sdwa, expected 15: ALG 1)" % (k.name, k.fn.count("v_add_u32_sdwa"))]
+    return []
+
+
+def carry_mix(k, blocks):
+    if k.fn.count("v_addc_co_u32_sdwa") != blocks * 15 or "v_add_u32_sdwa" in k.fn:
+        return ["%s: keystream instruction mix changed (%d addc)" % (k.name, k.fn.count("v_addc_co_u32_sdwa"))]
+    return []
+
+
+def atomic_adds(k, n):
+    return ["%s: %d global_atomic_add, expected %d" % (k.name, k.fn.count("global_atomic_add"), n)] if k.fn.count("global_atomic_add") != n else []
+
+
+def mailbox_is_ds(k):
+    return ["%s: flat_ accesses (the LDS mailbox must be ds_ instructions)" % k.name] if "flat_" in k.fn else []
+
+
+def mailbox_traffic(k, n):
+    if k.fn.count("ds_write_b32") != n or k.fn.count("ds_read_b32") != n:
+        return ["%s: ticket mailbox traffic changed: %d ds_write_b32, %d ds_read_b32" % (k.name, k.fn.count("ds_write_b32"), k.fn.count("ds_read_b32"))]
+    return []
+
+
+def init_only_stores(k):
+    if re.search(r"^\s+(buffer|global)_load", k.fn, re.M) or not re.search(r"^\s+global_store_dword", k.fn, re.M) or "global_atomic" in k.fn:
+        return ["%s: the init kernel does something other than store its results" % k.name]
+    return []
+
+
+# ---- rules of a whole TU.  They take a Unit: the TU's words, the source names of ALL kernels of the file, and (not yet in a spec's
+# `first` rules, which run before any kernel is looked at and end the check when they find something) its own Kernels. ----
+Unit = namedtuple("Unit", "words names kernels")
+
+
+def kernel_count(u, n, note=""):
+    return ["%s holds %d kernels, expected %d%s" % (u.words, len(u.names), n, note)] if len(u.names) != n else []
+
+
+def one_of_each(u, *sources):
+    return ["%s holds %d %s, expected 1" % (u.words, u.names.count(s), s) for s in sources if u.names.count(s) != 1]
+
+
+def verify_kernel_counts(u):
+    init, stream = u.names.count("modgpu_cycle_verify_init"), u.names.count("modgpu_cycle_verify_kernel")
+    return ["%s holds %d init and %d stream kernels, expected 1 and 4" % (u.words, init, stream)] if (init, stream) != (1, 4) else []
+
+
+def one_queue_kernel(u):
+    n = u.names.count("modgpu_cycle_queue_kernel")
+    return ["expected exactly one work-queue kernel, found %d" % n] if n != 1 else []
+
+
+def block_in_two_kernels(u):
+    n = sum(1 for k in u.kernels if carry_blocks(k.fn))
+    return ["expected the keystream block in exactly the two streaming kernels, found it in %d" % n] if n != 2 else []
+
+
+def on_kernel(u, source, name, rules):
+    """further rules for the kernels of one source name, whose findings call it `name`"""
+    return [f for k in u.kernels if k.source == source for f in run(rules, k._replace(name=name))]
+
+
+def run(rules, subject):
+    """a rule is a function of the subject, or a tuple of one and its further arguments"""
     bad = []
-    kinds = {}
-    for name, fn in bodies.items():
-        kind = next((k for k in VERIFY_KERNELS if k in name), None)
-        if kind is None:
-            bad.append("%s: the verify kernels' TU holds another kernel" % name)
-            continue
-        kinds[kind] = kinds.get(kind, 0) + 1
-        md = metadata(asm, name)
-        if md.get("vgpr_count", 999) > 128 or md.get("sgpr_count", 999) > 102:
-            bad.append("%s: register counts beyond the budget: %s" % (name, md))
-        if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0) or "scratch_" in fn:
-            bad.append("%s: spills, scratch or a private segment: %s" % (name, md))
-        found, findings = keystream_blocks(name, fn)
-        bad += findings
-        if re.search(r"^\s+buffer_(store|atomic)", fn, re.M):
-            bad.append("%s: a verify kernel stores through a buffer descriptor (its inputs are read-only; the stream has no store at all)" % name)
-        if re.search(r"^\s+flat_", fn, re.M):
-            bad.append("%s: flat_ accesses (LDS must be ds_ instructions, results global_)" % name)
-        if kind == "modgpu_cycle_verify_init":
-            if found:
-                bad.append("%s: the init kernel carries a keystream block" % name)
-            if re.search(r"^\s+(buffer|global)_load", fn, re.M) or not re.search(r"^\s+global_store_dword", fn, re.M) or "global_atomic" in fn:
-                bad.append("%s: the init kernel does something other than store its results" % name)
-            continue
-        keyed = name.endswith("Lb1EEv15CycleVerifyArgs")
-        blocks = len([b for b in BLOCK.findall(fn) if "s[94:95]" in b])
-        if keyed and blocks != 9:
-            bad.append("%s: %d keystream blocks, expected 9 (4 words x 2 unrolled trips + the cut first chunk)" % (name, blocks))
-        if not keyed and blocks:
-            bad.append("%s: an identity form carries a keystream block" % name)
-        loads = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_load_dword", ln)]
-        if not loads or not all(ln.endswith(" nt") for ln in loads):
-            bad.append("%s: a data load is not nt" % name)
-        stores = re.findall(r"^\s+(global_store_\w+)", fn, re.M)
-        if stores != ["global_store_dwordx2"]:
-            bad.append("%s: global stores %s, expected the one global_store_dwordx2 of the entry's n" % (name, stores))
-        atomics = re.findall(r"^\s+(global_atomic_\w+)", fn, re.M)
-        adds, mins = atomics.count("global_atomic_add_x2"), atomics.count("global_atomic_umin_x2")
-        if not adds or adds != mins or adds + mins != len(atomics):
-            bad.append("%s: result atomics %s, expected 64-bit adds and unsigned mins in equal numbers and nothing else" % (name, sorted(set(atomics))))
-        if md.get("group_segment_fixed_size", -1) != 16:
-            bad.append("%s: LDS is %s bytes, expected the 16 of the workgroup's count and lowest index" % (name, md.get("group_segment_fixed_size")))
-    if kinds.get("modgpu_cycle_verify_init", 0) != 1 or kinds.get("modgpu_cycle_verify_kernel", 0) != 4:
-        bad.append("the verify kernels' TU holds %d init and %d stream kernels, expected 1 and 4" % (kinds.get("modgpu_cycle_verify_init", 0), kinds.get("modgpu_cycle_verify_kernel", 0)))
+    for rule in rules:
+        fn, *args = rule if isinstance(rule, tuple) else (rule,)
+        bad += fn(subject, *args)
     return bad
 
 
-def check_rekey_verify(asm, bodies):
-    """the rekey verify kernel's TU (cycle_rekey_verify_kernel.s): the plain and the funnel form of modgpu_cycle_rekey_verify_kernel"""
-    bad = []
-    for name, fn in bodies.items():
-        if "modgpu_cycle_rekey_verify_kernel" not in name:
-            bad.append("%s: the rekey verify kernel's TU holds another kernel" % name)
-            continue
-        md = metadata(asm, name)
-        if md.get("vgpr_count", 999) > 128 or md.get("sgpr_count", 999) > 102:
-            bad.append("%s: register counts beyond the budget: %s" % (name, md))
-        if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0) or "scratch_" in fn:
-            bad.append("%s: spills, scratch or a private segment: %s" % (name, md))
-        bad += rekey_blocks(name, fn)
-        blocks = len([b for b in BLOCK.findall(fn) if "s[94:95]" in b])
-        if blocks != 9:
-            bad.append("%s: %d two-keystream blocks, expected 9 (4 words x 2 unrolled trips + the cut first chunk)" % (name, blocks))
-        if re.search(r"^\s+buffer_(store|atomic)", fn, re.M):
-            bad.append("%s: a rekey verify kernel stores through a buffer descriptor (its inputs are read-only; the stream has no store at all)" % name)
-        if re.search(r"^\s+flat_", fn, re.M):
-            bad.append("%s: flat_ accesses (LDS must be ds_ instructions, results global_)" % name)
-        loads = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_load_dword", ln)]
-        if not loads or not all(ln.endswith(" nt") for ln in loads):
-            bad.append("%s: a data load is not nt" % name)
-        stores = re.findall(r"^\s+(global_store_\w+)", fn, re.M)
-        if stores != ["global_store_dwordx2"]:
-            bad.append("%s: global stores %s, expected the one global_store_dwordx2 of the entry's n" % (name, stores))
-        atomics = re.findall(r"^\s+(global_atomic_\w+)", fn, re.M)
-        adds, mins = atomics.count("global_atomic_add_x2"), atomics.count("global_atomic_umin_x2")
-        if not adds or adds != mins or adds + mins != len(atomics):
-            bad.append("%s: result atomics %s, expected 64-bit adds and unsigned mins in equal numbers and nothing else" % (name, sorted(set(atomics))))
-        if md.get("group_segment_fixed_size", -1) != 16:
-            bad.append("%s: LDS is %s bytes, expected the 16 of the workgroup's count and lowest index" % (name, md.get("group_segment_fixed_size")))
-    if len(bodies) != 2:
-        bad.append("the rekey verify kernel's TU holds %d kernels, expected 2 (plain and funnel)" % len(bodies))
-    return bad
+# ---- the TUs.  file: what the Makefile hands over; words: how findings call the TU; kinds: the kernels it may hold, by source name
+# and, where forms of one template differ, a pattern over the rest of the mangled name (the first kind that fits is the kernel's), each
+# with its rules in the order their findings are printed; first / then: rules of the whole TU before / behind its kernels'. ----
+Kind = namedtuple("Kind", "source rules form", defaults=("",))
+TU = namedtuple("TU", "file words kinds first then", defaults=((), ()))
+
+BUDGET = [register_budget, no_spills]
+TICKET = (atomic_optimizer_off, "the ticket atomic")
+TRIPS = "4 words x 2 unrolled trips"
+TRIPS_AND_CUT = TRIPS + " + the cut first chunk"
+# the in-place TU (its spill finding is worded apart); none of its kernels is required to carry the block: exactly two of the three do
+MAIN = [register_budget, (no_spills, True)]
+# the work-queue loop (cycle_kernel_impl.h, modgpu_cycle_queue_kernel; the keep kernel is the same loop): one ticket fetch per unrolled
+# trip (2) + a helper's first tickets + the exit count = 4 global_atomic_add; the mailbox's 3 writes and 3 reads are ds_ instructions;
+# 9 blocks of 15 addc and no v_add_u32_sdwa (that is ALG 1's): 4 words x 2 unrolled trips + the peeled first chunk
+QUEUE_LOOP = [(atomic_adds, 4), mailbox_is_ds, (mailbox_traffic, 3)]
+# a host-fed trip (cycle_feed_kernel.h): occupancy-bound (<= 64 VGPRs, 8 waves per SIMD), 8 bytes of LDS, thread 0 fetches the ticket
+# and the ok word between exactly two barriers, ALG 1
+HOST_FED = [(lds_bytes, 8, "the ticket / ok mailbox"), two_barriers]
+XFER = [(register_budget, 64), no_spills] + HOST_FED + [mailbox_read_scalar, alg1_mix, loads_nt]
+# the table calls' three launches (cycle_table_kernel.h): no atomic of any of them is wave-aggregated; plan and finish carry no block
+TABLE_HEAD = BUDGET + [(atomic_optimizer_off, "an atomic")]
+PLANNING = [(keystream_blocks, False), (no_block, "a planning kernel")]
+REKEY_PLANNING = [(no_block, "a planning kernel")]
+# a verify stream (cycle_verify_kernel.h): it reads its inputs and nothing else; 16 bytes of LDS; its only global store the 8 bytes of
+# the entry's n
+VERIFY_HEAD = BUDGET + [(keystream_blocks, False), (read_only_stream, "a verify kernel")]
+VERIFY_TAIL = [loads_nt, one_global_store, result_atomics, (lds_bytes, 16, "the workgroup's count and lowest index")]
 
 
-VERIFY_TABLE_KERNELS = ("modgpu_cycle_verify_table_plan", "modgpu_cycle_verify_table_finish", "modgpu_cycle_verify_table_kernel")
+def table_tu(file, words, stem, planning, stream):
+    """a table call's TU: <stem>_plan, <stem>_finish and the stream kernel <stem>_kernel, one of each"""
+    sources = (stem + "_plan", stem + "_finish", stem + "_kernel")
+    return TU(file, words, tuple(Kind(s, TABLE_HEAD + (stream if s.endswith("_kernel") else planning)) for s in sources), then=[(one_of_each,) + sources])
 
 
-def check_verify_table(asm, bodies):
-    """the verify table kernels' TU (cycle_verify_table_kernel.s): the plan and finish kernels and the stream kernel"""
-    bad = []
-    kinds = {}
-    for name, fn in bodies.items():
-        kind = next((k for k in VERIFY_TABLE_KERNELS if k in name), None)
-        if kind is None:
-            bad.append("%s: the verify table kernels' TU holds another kernel" % name)
-            continue
-        kinds[kind] = kinds.get(kind, 0) + 1
-        md = metadata(asm, name)
-        if md.get("vgpr_count", 999) > 128 or md.get("sgpr_count", 999) > 102:
-            bad.append("%s: register counts beyond the budget: %s" % (name, md))
-        if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0) or "scratch_" in fn:
-            bad.append("%s: spills, scratch or a private segment: %s" % (name, md))
-        if "v_mbcnt" in fn:
-            bad.append("%s: the atomic optimizer rewrote an atomic (build the TU with -mllvm -amdgpu-atomic-optimizer-strategy=None)" % name)
-        found, findings = keystream_blocks(name, fn)
-        bad += findings
-        if kind != "modgpu_cycle_verify_table_kernel":
-            if found:
-                bad.append("%s: a planning kernel carries a keystream block" % name)
-            continue
-        if not found:
-            bad.append("%s: no keystream block (ks_word_carry)" % name)
-        blocks = len([b for b in BLOCK.findall(fn) if "s[94:95]" in b])
-        if blocks != 8:
-            bad.append("%s: %d keystream blocks, expected 8 (4 words x 2 unrolled trips)" % (name, blocks))
-        loads = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_load_dword", ln)]
-        if not loads or not all(ln.endswith(" nt") for ln in loads):
-            bad.append("%s: a data load is not nt" % name)
-        if re.search(r"^\s+(buffer|global|flat|scratch)_store", fn, re.M):
-            bad.append("%s: a verify kernel stores through a buffer descriptor or a pointer (its inputs are read-only; the stream has no store at all)" % name)
-        if re.search(r"^\s+(buffer|flat)_atomic", fn, re.M) or re.search(r"^\s+flat_", fn, re.M):
-            bad.append("%s: buffer atomics or flat_ accesses (LDS must be ds_ instructions, results global_ atomics)" % name)
-        atomics = [(m.group(1), m.group(2)) for m in re.finditer(r"^\s+(global_atomic_\w+)\b([^;\n]*)", fn, re.M)]
-        tickets = [args for op, args in atomics if op == "global_atomic_add"]
-        if len(tickets) != 2 or not all(args.rstrip().endswith(" sc0") for args in tickets):
-            bad.append("%s: %d 32-bit global_atomic_add, expected the ticket fetch of each unrolled trip (2), each returning (sc0)" % (name, len(tickets)))
-        rest = [(op, args) for op, args in atomics if op != "global_atomic_add"]
-        adds = sum(1 for op, _ in rest if op == "global_atomic_add_x2")
-        mins = sum(1 for op, _ in rest if op == "global_atomic_umin_x2")
-        if not adds or adds != mins or adds + mins != len(rest) or any(" sc0" in args for _, args in rest):
-            bad.append("%s: result atomics %s, expected non-returning 64-bit adds and unsigned mins in equal numbers and nothing else"
-                       % (name, sorted(set(op for op, _ in rest))))
-        vec = len(re.findall(r"^\s+(?:global|flat)_load", fn, re.M))
-        if fn.count("s_load_dwordx16") < 2 or vec > 2:
-            bad.append("%s: the entry search is not scalar (%d s_load_dwordx16, %d vector loads besides the data)" % (name, fn.count("s_load_dwordx16"), vec))
-    for k in VERIFY_TABLE_KERNELS:
-        if kinds.get(k, 0) != 1:
-            bad.append("the verify table kernels' TU holds %d %s, expected 1" % (kinds.get(k, 0), k))
-    return bad
-
-
-REKEY_VERIFY_TABLE_KERNELS = ("modgpu_cycle_rekey_verify_table_plan", "modgpu_cycle_rekey_verify_table_finish", "modgpu_cycle_rekey_verify_table_kernel")
-
-
-def check_rekey_verify_table(asm, bodies):
-    """the rekey verify table kernels' TU (cycle_rekey_verify_table_kernel.s): the plan and finish kernels and the stream kernel"""
-    bad = []
-    kinds = {}
-    for name, fn in bodies.items():
-        kind = next((k for k in REKEY_VERIFY_TABLE_KERNELS if k in name), None)
-        if kind is None:
-            bad.append("%s: the rekey verify table kernels' TU holds another kernel" % name)
-            continue
-        kinds[kind] = kinds.get(kind, 0) + 1
-        md = metadata(asm, name)
-        if md.get("vgpr_count", 999) > 128 or md.get("sgpr_count", 999) > 102:
-            bad.append("%s: register counts beyond the budget: %s" % (name, md))
-        if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0) or "scratch_" in fn:
-            bad.append("%s: spills, scratch or a private segment: %s" % (name, md))
-        if "v_mbcnt" in fn:
-            bad.append("%s: the atomic optimizer rewrote an atomic (build the TU with -mllvm -amdgpu-atomic-optimizer-strategy=None)" % name)
-        blocks = len([b for b in BLOCK.findall(fn) if "s[94:95]" in b])
-        if kind != "modgpu_cycle_rekey_verify_table_kernel":
-            if blocks:
-                bad.append("%s: a planning kernel carries a keystream block" % name)
-            continue
-        bad += rekey_blocks(name, fn)
-        if blocks != 8:
-            bad.append("%s: %d two-keystream blocks, expected 8 (4 words x 2 unrolled trips)" % (name, blocks))
-        loads = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_load_dword", ln)]
-        if not loads or not all(ln.endswith(" nt") for ln in loads):
-            bad.append("%s: a data load is not nt" % name)
-        if re.search(r"^\s+(buffer|global|flat|scratch)_store", fn, re.M):
-            bad.append("%s: a rekey verify kernel stores through a buffer descriptor or a pointer (its inputs are read-only; the stream has no store at all)" % name)
-        if re.search(r"^\s+(buffer|flat)_atomic", fn, re.M) or re.search(r"^\s+flat_", fn, re.M):
-            bad.append("%s: buffer atomics or flat_ accesses (LDS must be ds_ instructions, results global_ atomics)" % name)
-        atomics = [(m.group(1), m.group(2)) for m in re.finditer(r"^\s+(global_atomic_\w+)\b([^;\n]*)", fn, re.M)]
-        tickets = [args for op, args in atomics if op == "global_atomic_add"]
-        if len(tickets) != 2 or not all(args.rstrip().endswith(" sc0") for args in tickets):
-            bad.append("%s: %d 32-bit global_atomic_add, expected the ticket fetch of each unrolled trip (2), each returning (sc0)" % (name, len(tickets)))
-        rest = [(op, args) for op, args in atomics if op != "global_atomic_add"]
-        adds = sum(1 for op, _ in rest if op == "global_atomic_add_x2")
-        mins = sum(1 for op, _ in rest if op == "global_atomic_umin_x2")
-        if not adds or adds != mins or adds + mins != len(rest) or any(" sc0" in args for _, args in rest):
-            bad.append("%s: result atomics %s, expected non-returning 64-bit adds and unsigned mins in equal numbers and nothing else"
-                       % (name, sorted(set(op for op, _ in rest))))
-        vec = len(re.findall(r"^\s+(?:global|flat)_load", fn, re.M))
-        if fn.count("s_load_dwordx16") < 2 or vec > 2:
-            bad.append("%s: the entry search is not scalar (%d s_load_dwordx16, %d vector loads besides the data)" % (name, fn.count("s_load_dwordx16"), vec))
-    for k in REKEY_VERIFY_TABLE_KERNELS:
-        if kinds.get(k, 0) != 1:
-            bad.append("the rekey verify table kernels' TU holds %d %s, expected 1" % (kinds.get(k, 0), k))
-    return bad
-
-
-def check_xfer(asm, bodies):
-    """the transfer kernels' TU (cycle_xfer_kernel.s): the upload (ILb1) and the download (ILb0), each plain and funnel"""
-    bad = []
-    for name, fn in bodies.items():
-        if "modgpu_cycle_xfer_kernel" not in name:
-            bad.append("%s: the transfer kernels' TU holds another kernel" % name)
-            continue
-        md = metadata(asm, name)
-        if md.get("vgpr_count", 999) > 64:
-            bad.append("%s: %d VGPRs -- more than 64, fewer than 8 waves per SIMD" % (name, md.get("vgpr_count", 999)))
-        if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0) or "scratch_" in fn:
-            bad.append("%s: spills, scratch or a private segment: %s" % (name, md))
-        if md.get("group_segment_fixed_size", -1) != 8:
-            bad.append("%s: LDS is %s bytes, expected the 8 of the ticket / ok mailbox" % (name, md.get("group_segment_fixed_size")))
-        if fn.count("s_barrier") != 2:
-            bad.append("%s: %d s_barrier, expected 2 (one behind thread 0's region, one at the end of the trip)" % (name, fn.count("s_barrier")))
-        ins = instructions(fn)
-        follows = [k for k, (_, op, _) in enumerate(ins) if op == "s_barrier" and any(o.startswith("ds_read") for _, o, _ in ins[k + 1:k + 3])]
-        if len(follows) != 1 or sum(1 for _, o, _ in ins[follows[0] + 1:follows[0] + 8] if o == "v_readfirstlane_b32") < 2:
-            bad.append("%s: the ticket and the ok word are not read into scalar registers right behind the trip's first barrier" % name)
-        if fn.count("v_add_u32_sdwa") != 15:
-            bad.append("%s: keystream instruction mix changed (%d v_add_u32_sdwa, expected 15: ALG 1)" % (name, fn.count("v_add_u32_sdwa")))
-        loads = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_load_dword", ln)]
-        stores = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_store_dword", ln)]
-        if not loads or not all(ln.endswith(" nt") for ln in loads):
-            bad.append("%s: a data load is not nt" % name)
-        upload = "kernelILb1E" in name
-        if upload and (not stores or not all(ln.endswith(" nt sc1") for ln in stores)):
-            bad.append("%s: an upload store into HBM is not nt sc1" % name)
-        if not upload and (not stores or not all(ln.endswith(" sc1") and " nt" not in ln for ln in stores)):
-            bad.append("%s: a download store across PCIe is not `sc1` without nt (nt stores across PCIe: -15..20 %%)" % name)
-    return bad
-
-
-def check_keep(asm, bodies):
-    """the keep kernel's TU (cycle_keep_kernel.s): modgpu_cycle_keep_kernel, the work-queue kernel with a cache policy per chunk"""
-    bad = []
-    for name, fn in bodies.items():
-        if "modgpu_cycle_keep_kernel" not in name:
-            bad.append("%s: the keep kernel's TU holds another kernel" % name)
-            continue
-        md = metadata(asm, name)
-        if md.get("vgpr_count", 999) > 128 or md.get("sgpr_count", 999) > 102:
-            bad.append("%s: register counts beyond the budget: %s" % (name, md))
-        if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0) or "scratch_" in fn:
-            bad.append("%s: spills, scratch or a private segment: %s" % (name, md))
-        found, findings = keystream_blocks(name, fn)
-        bad += findings
-        if not found:
-            bad.append("%s: no keystream block (ks_word_carry)" % name)
-        if "v_mbcnt" in fn:
-            bad.append("%s: the atomic optimizer rewrote the ticket atomic (build the TU with -mllvm -amdgpu-atomic-optimizer-strategy=None)" % name)
-        if fn.count("global_atomic_add") != 4:  # one ticket fetch per unrolled trip (2) + a helper's first tickets + the exit count
-            bad.append("%s: %d global_atomic_add, expected 4" % (name, fn.count("global_atomic_add")))
-        if "flat_" in fn:
-            bad.append("%s: flat_ accesses (the LDS mailbox must be ds_ instructions)" % name)
-        if fn.count("ds_write_b32") != 3 or fn.count("ds_read_b32") != 3:
-            bad.append("%s: ticket mailbox traffic changed: %d ds_write_b32, %d ds_read_b32" % (name, fn.count("ds_write_b32"), fn.count("ds_read_b32")))
-        if fn.count("v_addc_co_u32_sdwa") != 9 * 15 or "v_add_u32_sdwa" in fn:  # 4 words x 2 unrolled trips + the peeled first chunk
-            bad.append("%s: keystream instruction mix changed (%d addc)" % (name, fn.count("v_addc_co_u32_sdwa")))
-        loads = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_load_dword", ln)]
-        stores = [ln.split(";")[0].rstrip() for ln in fn.splitlines() if re.match(r"\s+buffer_store_dword", ln)]
-        if not loads or not all(ln.endswith(" nt") for ln in loads):
-            bad.append("%s: a data load is not nt" % name)
-        streaming = len([ln for ln in stores if ln.endswith(" nt sc1")])
-        resident = len([ln for ln in stores if ln.endswith(" sc1") and " nt" not in ln])
-        if streaming + resident != len(stores):
-            bad.append("%s: a data store is neither nt sc1 nor sc1" % name)
-        # the cut first chunk's loop (cold, not unrolled) stores once, streaming; the rest is the unrolled stream loop
-        if resident != 8 or streaming - 1 != 8:
-            bad.append("%s: %d sc1-only and %d nt sc1 stores in the stream loop, expected 8 of each (4 words x 2 unrolled trips, one burst per "
-                       "cache policy)" % (name, resident, streaming - 1))
-    if len(bodies) != 1:
-        bad.append("the keep kernel's TU holds %d kernels, expected 1" % len(bodies))
-    return bad
+TUS = (
+    # the in-place TU: the small shape <1, 256, ...> (one word per lane, launch-latency-bound sizes and every launch across PCIe; ALG 1,
+    # no block) has no pipeline of its own and lives on occupancy; the big shape and the work-queue kernel carry the block.  The queue
+    # kernel's stores: 4 words x 2 unrolled trips (+ the cold peel loop)
+    TU("cycle_kernel.s", "the streaming kernels' TU",
+       (Kind("modgpu_cycle_kernel", MAIN + [(register_budget, 64, "the small shape needs "), (keystream_blocks, False)], "^ILi1ELi256E"),
+        Kind("modgpu_cycle_kernel", MAIN + [(keystream_blocks, False)]),
+        Kind("modgpu_cycle_queue_kernel", MAIN + [(keystream_blocks, False)])),
+       first=[one_queue_kernel],
+       then=[block_in_two_kernels,
+             (on_kernel, "modgpu_cycle_queue_kernel", "queue kernel", [TICKET] + QUEUE_LOOP + [loads_nt, (stores_nt_sc1_at_least, 8), (carry_mix, 9)])]),
+    # the host-fed kernel of the host-buffer routes: its stores go across PCIe
+    TU("cycle_feed_kernel.s", "the host-fed kernel's TU",
+       (Kind("modgpu_cycle_feed_kernel", [no_spills, (register_budget, 64)] + HOST_FED + [loads_nt, (stores, "sc1"), mailbox_read_scalar, alg1_mix]),),
+       first=[(kernel_count, 1)]),
+    # out-of-place, plain and funnel: the work-queue loop with a destination of its own
+    TU("cycle_to_kernel.s", "the out-of-place kernel's TU",
+       (Kind("modgpu_cycle_to_kernel", BUDGET + [keystream_blocks, TICKET, loads_nt, (stores, "nt sc1")]),)),
+    # transfer, each direction plain and funnel: host-fed trips; the upload <true, .> stores into HBM, the download across PCIe
+    TU("cycle_xfer_kernel.s", "the transfer kernels' TU",
+       (Kind("modgpu_cycle_xfer_kernel", XFER + [(stores, "nt sc1", "an upload store into HBM")], "^ILb1E"),
+        Kind("modgpu_cycle_xfer_kernel", XFER + [(stores, "sc1", "a download store across PCIe")]))),
+    # rekey, plain and funnel
+    TU("cycle_rekey_kernel.s", "the rekey kernel's TU",
+       (Kind("modgpu_cycle_rekey_kernel", BUDGET + [rekey_blocks, TICKET, loads_nt, (stores, "nt sc1")]),)),
+    # table of out-of-place entries
+    table_tu("cycle_table_kernel.s", "the table kernels' TU", "modgpu_cycle_table", PLANNING,
+             [keystream_blocks, (block_count, KEYSTREAM, 8, TRIPS), loads_nt, (stores, "nt sc1"), scalar_entry_search]),
+    # table of rekey entries
+    table_tu("cycle_rekey_table_kernel.s", "the rekey table kernels' TU", "modgpu_cycle_rekey_table", REKEY_PLANNING,
+             [rekey_blocks, (block_count, TWO_KEYSTREAM, 8, TRIPS), loads_nt, (stores, "nt sc1"), scalar_entry_search]),
+    # verify: the init kernel and the stream kernel plain / funnel x keyed <..., true> (compares with src ^ keystream) / identity (compares
+    # the buffers as they are: no block).  Chunks are assigned statically: no ticket, nothing for the atomic optimizer to rewrite
+    TU("cycle_verify_kernel.s", "the verify kernels' TU",
+       (Kind("modgpu_cycle_verify_init", VERIFY_HEAD + [(no_block, "the init kernel"), init_only_stores]),
+        Kind("modgpu_cycle_verify_kernel", VERIFY_HEAD + [(block_count, KEYSTREAM, 9, TRIPS_AND_CUT)] + VERIFY_TAIL, "Lb1EEv15CycleVerifyArgs$"),
+        Kind("modgpu_cycle_verify_kernel", VERIFY_HEAD + [(no_block, "an identity form")] + VERIFY_TAIL)),
+       then=[verify_kernel_counts]),
+    # table of verify entries: chunks come from a ticket counter, ONE plain returning 32-bit fetch per unrolled trip (2)
+    table_tu("cycle_verify_table_kernel.s", "the verify table kernels' TU", "modgpu_cycle_verify_table", PLANNING,
+             [keystream_blocks, (block_count, KEYSTREAM, 8, TRIPS), loads_nt, (read_only_stream, "a verify kernel", True), (result_atomics, 2), scalar_entry_search]),
+    # rekey verify (verify against two keystreams), plain and funnel
+    TU("cycle_rekey_verify_kernel.s", "the rekey verify kernel's TU",
+       (Kind("modgpu_cycle_rekey_verify_kernel", BUDGET + [rekey_blocks, (block_count, TWO_KEYSTREAM, 9, TRIPS_AND_CUT), (read_only_stream, "a rekey verify kernel")] + VERIFY_TAIL),),
+       then=[(kernel_count, 2, " (plain and funnel)")]),
+    # keep: the work-queue kernel with a cache policy per chunk
+    TU("cycle_keep_kernel.s", "the keep kernel's TU",
+       (Kind("modgpu_cycle_keep_kernel", BUDGET + [keystream_blocks, TICKET] + QUEUE_LOOP + [(carry_mix, 9), loads_nt, keep_store_bursts]),),
+       then=[(kernel_count, 1)]),
+    # table of rekey verify entries: the rules of both parents
+    table_tu("cycle_rekey_verify_table_kernel.s", "the rekey verify table kernels' TU", "modgpu_cycle_rekey_verify_table", REKEY_PLANNING,
+             [rekey_blocks, (block_count, TWO_KEYSTREAM, 8, TRIPS), loads_nt, (read_only_stream, "a rekey verify kernel", True), (result_atomics, 2), scalar_entry_search]),
+)
+OWNER = {kind.source: tu for tu in TUS for kind in tu.kinds}
+__doc__ = "check_isa.py " + " | ".join("<%s>" % tu.file for tu in TUS) + __doc__
 
 
 def check(asm):
-    """one TU's assembly: the rules for every kernel, then those of the TU it is (the streaming kernels' or the host-fed kernel's)"""
+    """one TU's assembly: the rules for every kernel, then those of the TU it is -- the one that owns the first kernel whose source name is
+    in the table"""
     bad = []
     bodies = kernel_bodies(asm)
     for name, fn in kernel_texts(asm).items():
         bad += sdwa_forwarding_hazards(name, fn)
         bad += barriers_at_full_exec(name, fn)
-    feed = [n for n in bodies if "modgpu_cycle_feed_kernel" in n]
-    if feed:
-        if len(bodies) != 1:
-            return bad + ["the host-fed kernel's TU holds %d kernels, expected 1" % len(bodies)]
-        md = metadata(asm, feed[0])
-        if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0) or "scratch_" in bodies[feed[0]]:
-            bad.append("%s: spills, scratch or a private segment: %s" % (feed[0], md))
-        return bad + check_feed(asm, feed[0], bodies[feed[0]])
-    if any("modgpu_cycle_rekey_verify_table" in n for n in bodies):  # (before the rekey verify kernel: its name is the start of this one)
-        return bad + check_rekey_verify_table(asm, bodies)
-    if any("modgpu_cycle_rekey_verify" in n for n in bodies):  # (no other branch's name is part of this one but the one above)
-        return bad + check_rekey_verify(asm, bodies)
-    if any("modgpu_cycle_verify_table" in n for n in bodies):  # (before the verify kernels: their name is the start of this one)
-        return bad + check_verify_table(asm, bodies)
-    if any("modgpu_cycle_verify" in n for n in bodies):
-        return bad + check_verify(asm, bodies)
-    if any("modgpu_cycle_rekey_table" in n for n in bodies):
-        return bad + check_rekey_table(asm, bodies)
-    if any("modgpu_cycle_table" in n for n in bodies):
-        return bad + check_table(asm, bodies)
-    if any("modgpu_cycle_to_kernel" in n for n in bodies):
-        return bad + check_to(asm, bodies)
-    if any("modgpu_cycle_xfer_kernel" in n for n in bodies):
-        return bad + check_xfer(asm, bodies)
-    if any("modgpu_cycle_rekey_kernel" in n for n in bodies):
-        return bad + check_rekey(asm, bodies)
-    if any("modgpu_cycle_keep_kernel" in n for n in bodies):
-        return bad + check_keep(asm, bodies)
-    queue = [n for n in bodies if "modgpu_cycle_queue_kernel" in n]
-    if len(queue) != 1:
-        return bad + ["expected exactly one work-queue kernel, found %d" % len(queue)]
-    n_carry_kernels = 0
+    named = {name: source_name(name) for name in bodies}
+    tu = next((OWNER[source] for source, _ in named.values() if source in OWNER), None)
+    if tu is None:
+        return bad + ["expected exactly one work-queue kernel, found 0"]
+    names = [source for source, _ in named.values()]
+    found = run(tu.first, Unit(tu.words, names, []))
+    if found:
+        return bad + found
+    kernels = []
     for name, fn in bodies.items():
-        md = metadata(asm, name)
-        if md.get("vgpr_count", 999) > 128 or md.get("sgpr_count", 999) > 102:
-            bad.append("%s: register counts beyond the budget: %s" % (name, md))
-        if md.get("vgpr_spill_count", 0) or md.get("sgpr_spill_count", 0) or md.get("private_segment_fixed_size", 0):
-            bad.append("%s: spills or a private segment: %s" % (name, md))
-        if "scratch_" in fn:
-            bad.append("%s: scratch instructions" % name)
-        # the small shape (one word per lane, launch-latency-bound sizes and every launch across PCIe) lives on occupancy: it has
-        # no pipeline of its own, so it must keep 8 waves per SIMD, i.e. at most 64 VGPRs (512 per SIMD lane / 8)
-        if "modgpu_cycle_kernelILi1ELi256E" in name and md.get("vgpr_count", 999) > 64:
-            bad.append("%s: the small shape needs %d VGPRs -- more than 64, fewer than 8 waves per SIMD" % (name, md.get("vgpr_count", 999)))
-        found, findings = keystream_blocks(name, fn)
-        bad += findings
-        n_carry_kernels += 1 if found else 0
-    if n_carry_kernels != 2:
-        bad.append("expected the keystream block in exactly the two streaming kernels, found it in %d" % n_carry_kernels)
-    q = bodies[queue[0]]
-    if "v_mbcnt" in q:
-        bad.append("queue kernel: the atomic optimizer rewrote the ticket atomic (build the TU with -mllvm -amdgpu-atomic-optimizer-strategy=None)")
-    if q.count("global_atomic_add") != 4:  # one ticket fetch per unrolled trip (2) + a helper's first tickets + the exit count
-        bad.append("queue kernel: %d global_atomic_add, expected 4" % q.count("global_atomic_add"))
-    if "flat_" in q:
-        bad.append("queue kernel: flat_ accesses (the LDS mailbox must be ds_ instructions)")
-    if q.count("ds_write_b32") != 3 or q.count("ds_read_b32") != 3:
-        bad.append("queue kernel: ticket mailbox traffic changed: %d ds_write_b32, %d ds_read_b32" % (q.count("ds_write_b32"), q.count("ds_read_b32")))
-    loads = [ln for ln in q.splitlines() if "buffer_load_dwordx4" in ln]
-    stores = [ln for ln in q.splitlines() if "buffer_store_dwordx4" in ln]
-    if not loads or not all(ln.rstrip().endswith(" nt") for ln in loads):
-        bad.append("queue kernel: a data load is not nt")
-    if len([ln for ln in stores if ln.rstrip().endswith("nt sc1")]) < 8:  # 4 words x 2 unrolled trips (+ the cold peel loop)
-        bad.append("queue kernel: fewer than 8 nt sc1 stores")
-    if q.count("v_addc_co_u32_sdwa") != 9 * 15 or "v_add_u32_sdwa" in q:  # 4 words x 2 unrolled trips + the peeled first chunk
-        bad.append("queue kernel: keystream instruction mix changed (%d addc)" % q.count("v_addc_co_u32_sdwa"))
-    return bad
+        source, form = named[name]
+        kind = next((kd for kd in tu.kinds if kd.source == source and re.search(kd.form, form)), None)
+        if kind is None:
+            bad.append("%s: %s holds another kernel" % (name, tu.words))
+            continue
+        kernels.append(Kernel(name, source, fn, metadata(asm, name)))
+        bad += run(kind.rules, kernels[-1])
+    return bad + run(tu.then, Unit(tu.words, names, kernels))
 
 
 def main():

@@ -414,21 +414,33 @@ def test_kernel_codegen_guard_passes_the_tree_and_rejects_a_broken_build():
 
 
 def test_isa_check_covers_every_tu_and_the_plan_guards_the_main_pair():
-    """What `make` itself plans and prints, not how the Makefile spells it.  `make isa-check` passes the tree with one line per TU:
-    main first, then the order of the Makefile's table.  The TUs with a ticket
+    """What `make` itself plans and prints, not how the Makefile spells it.  `make isa-check` is the one aggregate: it plans one guard run
+    per TU of the library -- main first, then the order of the Makefile's table -- over exactly the TUs whose objects `libmodgpu.so` is
+    linked from, and passes the tree with one line per run.  The TUs with a ticket
     atomic, and only they, are assembled and compiled with the atomic-optimizer flag.  Both objects of the main pair wait for the one
     guard run over both files, which ISA_CHECK=0 leaves out without touching a stamp; the stand-in is wired; the source lists are the
     hashed ones (test_kernel_source_hash_matches_sources)."""
+    runs = ["cycle_kernel.s cycle_feed_kernel.s", "cycle_to_kernel.s", "cycle_xfer_kernel.s", "cycle_rekey_kernel.s", "cycle_table_kernel.s",
+            "cycle_rekey_table_kernel.s", "cycle_verify_kernel.s", "cycle_verify_table_kernel.s", "cycle_rekey_verify_kernel.s",
+            "cycle_keep_kernel.s", "cycle_rekey_verify_table_kernel.s"]
+    assert [ln for ln in B.dry_run("isa-check") if ln.startswith("python3 check_isa.py")] == ["python3 check_isa.py " + r for r in runs]
     good = subprocess.run(["make", "-s", "-C", B.CSRC, "isa-check"], capture_output=True, text=True, timeout=900)
     assert good.returncode == 0, good.stdout[-3000:] + good.stderr[-2000:]
     assert [ln for ln in good.stdout.splitlines() if ln.startswith("check_isa:")] == [
-        "check_isa: ok (4 kernels)", "check_isa: ok (2 kernels)", "check_isa: ok (4 kernels)", "check_isa: ok (2 kernels)",
-        "check_isa: ok (3 kernels)", "check_isa: ok (3 kernels)", "check_isa: ok (5 kernels)"], good.stdout
+        f"check_isa: ok ({n} kernels)" for n in (4, 2, 4, 2, 3, 3, 5, 3, 2, 1, 3)], good.stdout
     flag = "-amdgpu-atomic-optimizer-strategy=None"
     assert flag in B.make_var("KERNEL_FLAGS").split()
     plan = B.dry_run("all")
-    ticket = {"cycle_kernel", "cycle_to_kernel", "cycle_rekey_kernel", "cycle_table_kernel", "cycle_rekey_table_kernel"}
-    for tu in sorted(ticket | {"cycle_feed_kernel", "cycle_xfer_kernel", "cycle_verify_kernel"}):
+    # no TU can be linked without being in `isa-check`: the assembly files its runs name are the kernel objects of the link line
+    links = [ln.split() for ln in plan if " -shared " in ln and " -o ../libmodgpu.so " in ln]
+    assert len(links) == 1, links
+    linked = {w[:-2] for w in links[0] if w.startswith("cycle_") and w.endswith("_kernel.o")}
+    assert len(linked) == 12 and linked == {f[:-2] for r in runs for f in r.split()}, (sorted(linked), runs)
+    ticket = {"cycle_kernel", "cycle_to_kernel", "cycle_rekey_kernel", "cycle_table_kernel", "cycle_rekey_table_kernel", "cycle_verify_table_kernel",
+              "cycle_keep_kernel", "cycle_rekey_verify_table_kernel"}
+    plain = {"cycle_feed_kernel", "cycle_xfer_kernel", "cycle_verify_kernel", "cycle_rekey_verify_kernel"}
+    assert ticket | plain == linked
+    for tu in sorted(ticket | plain):
         for step in ("-S --cuda-device-only", "-c"):
             lines = [ln for ln in plan if f" {step} {tu}.hip " in ln]
             assert len(lines) == 1 and (f" -mllvm {flag} " in lines[0]) == (tu in ticket), (tu, step, lines)

@@ -1,7 +1,7 @@
 """CPU checks of the keep kernel's TU and route (cycle_keep_kernel.hip: the work-queue kernel with a resident slice, what a single in-place
 buffer of 1 GiB or more is launched on): the TU has a source hash of its own and leaves the main TU's alone, the symbols are declared,
 exported and listed, the host's policy for a call's size is the stated arithmetic, the TU's code-generation guard passes the tree and
-rejects a broken build and hand-made faults without changing what the three earlier guard tiers plan, and the host code runs clean under
+rejects a broken build and hand-made faults, and the host code runs clean under
 ASan/UBSan and TSan against the CPU stand-in of the HIP runtime."""
 import hashlib
 import os
@@ -72,8 +72,7 @@ def test_host_policy_for_a_size(modgpu):
 def test_codegen_guard_of_the_new_tu():
     """`make isa-check-keep` is the TU's own pass (1 kernel); the TU with one of its two store forms gone is REJECTED by name; the object
     waits for its own guard run, which ISA_CHECK=0 leaves out; the stand-in is wired; the TU is built WITH the atomic-optimizer flag (it
-    has the ticket).  It is a prerequisite of none of `isa-check`, `isa-check-all`, `isa-check-every`: `isa-check-whole` plans exactly
-    `isa-check-every`'s runs and then this TU's."""
+    has the ticket)."""
     B.isa_check_target("isa-check-keep", 1)
     broken = subprocess.run(["make", "-s", "-C", CSRC, "isa-check-broken-keep"], capture_output=True, text=True, timeout=900)
     assert broken.returncode != 0, "the guard accepted a keep kernel with one store form"
@@ -87,13 +86,6 @@ def test_codegen_guard_of_the_new_tu():
         lines = [ln for ln in plan if f" {step} cycle_keep_kernel.hip " in ln]
         assert len(lines) == 1 and " -mllvm -amdgpu-atomic-optimizer-strategy=None " in lines[0], (step, lines)
     assert sum("cycle_keep_kernel.o" in ln for ln in plan if " -shared " in ln and "libmodgpu" in ln) == 2  # both link lines
-
-    def guard_runs(target):
-        return [ln for ln in B.dry_run(target) if ln.startswith("python3 check_isa.py")]
-
-    every = guard_runs("isa-check-every")
-    assert len(every) == 9 and not any("keep" in ln for ln in every)
-    assert guard_runs("isa-check-whole") == every + ["python3 check_isa.py cycle_keep_kernel.s"]
 
 
 def test_codegen_guard_rules_on_altered_assembly():

@@ -1,8 +1,7 @@
 """CPU checks of the rekey verify table call (modgpu_verify_rekey_table_device & co., include/modgpu.h): the symbols are declared,
 exported and listed, the new TU has a source list and hash of its own, the workspace is the rekey table call's plus one line, tier 1
-comes before the device, the TU's code-generation guard passes the tree, rejects a broken build and hand-made faults and sits behind
-`make isa-check-whole` (whose plan stays what it was) in `make isa-check-total`.  The CPU stand-in of the three launches is wired into
-the sanitizer builds of the library; no case file runs it under a sanitizer yet."""
+comes before the device, and the TU's code-generation guard passes the tree and rejects a broken build and hand-made faults.  The CPU
+stand-in of the three launches is wired into the sanitizer builds of the library; no case file runs it under a sanitizer yet."""
 import hashlib
 import os
 import re
@@ -112,18 +111,6 @@ def test_codegen_guard_of_the_new_tu():
     assert sum(" cycle_rekey_verify_table_kernel.o " in ln for ln in plan if " -shared " in ln and "libmodgpu" in ln and "libmodulate_host" not in ln) == 2
     B.guard_then_compile("cycle_rekey_verify_table_kernel")
     B.unguarded_plan("cycle_rekey_verify_table_kernel")
-
-
-def test_guard_plans():
-    """`isa-check-whole` plans exactly the check_isa.py runs it planned; `isa-check-total` plans those and then this TU's."""
-
-    def guard_runs(target):
-        return [ln for ln in B.dry_run(target) if ln.startswith("python3 check_isa.py")]
-
-    whole = ["cycle_kernel.s cycle_feed_kernel.s", "cycle_to_kernel.s", "cycle_xfer_kernel.s", "cycle_rekey_kernel.s", "cycle_table_kernel.s",
-             "cycle_rekey_table_kernel.s", "cycle_verify_kernel.s", "cycle_verify_table_kernel.s", "cycle_rekey_verify_kernel.s", "cycle_keep_kernel.s"]
-    assert guard_runs("isa-check-whole") == ["python3 check_isa.py " + t for t in whole]
-    assert guard_runs("isa-check-total") == ["python3 check_isa.py " + t for t in whole + ["cycle_rekey_verify_table_kernel.s"]]
 
 
 def test_codegen_guard_rules_on_altered_assembly():

@@ -1,7 +1,6 @@
 """CPU checks of the verify table call (modgpu_verify_table_device & co., include/modgpu.h): the workspace size, the refusal without a
-device, the new TU's source list and hash, its code-generation guard (outside `make isa-check`, whose output is pinned, and inside
-`make isa-check-all`), a broken build the guard must reject, the stand-in's wiring, and the host code under ASan/UBSan and TSan against
-the CPU stand-in of the HIP runtime."""
+device, the new TU's source list and hash, its code-generation guard, a broken build the guard must reject, the stand-in's wiring, and
+the host code under ASan/UBSan and TSan against the CPU stand-in of the HIP runtime."""
 import hashlib
 import os
 import subprocess
@@ -73,14 +72,6 @@ def test_codegen_guard_of_the_new_tu():
         assert " cycle_verify_table_kernel.o " in link, link
     B.guard_then_compile("cycle_verify_table_kernel")
     B.unguarded_plan("cycle_verify_table_kernel")
-
-
-def test_isa_check_all_runs_every_tu():
-    """`make isa-check-all`: the seven lines of `make isa-check`, then the verify table TU's."""
-    r = subprocess.run(["make", "-s", "-C", CSRC, "isa-check-all"], capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("check_isa:")]
-    assert len(lines) == 8 and all(ln.startswith("check_isa: ok (") for ln in lines) and lines[-1] == "check_isa: ok (3 kernels)", r.stdout
 
 
 def test_codegen_guard_rules_on_altered_assembly():
