@@ -183,9 +183,50 @@ int modgpu_cycle_batch_device_to(void *const *dst_parts, const void *const *src_
  * Degenerate keystreams take the out-of-place call: key_from == 0 mod 2^31-1 is modgpu_cycle_device_to with key_to at off_to;
  * key_to == 0 is modgpu_cycle_device_to with key_from at off_from; both zero, or the same reduced key at the same stream position
  * (offsets equal mod 2^31-2), copy.  A launch that finds no scratch runs two passes on the same stream: out of place under
- * key_from, then in place under key_to (correct and capturable; modgpu_last_launch then reports the in-place launch). */
+ * key_from, then in place under key_to (correct and capturable; modgpu_last_launch then reports the in-place launch).
+ * A destination that partly overlaps its source is what modgpu_rekey_move_device takes. */
 int modgpu_rekey_device_to(void *dev_dst, const void *dev_src, uint64_t n, int32_t key_from, uint64_t off_from, int32_t key_to,
                            uint64_t off_to, int device, void *hip_stream);
+
+/* ---- MOVE and rekey: the same bytes for ANY overlap of [dev_dst, dev_dst+n) with [dev_src, dev_src+n), in ONE pass ------------------
+ * memmove rules: dev_dst[j] = SRC0[j] ^ ks(key_from)[off_from + j] ^ ks(key_to)[off_to + j], where SRC0 is the source as it was when
+ * the call started on the device -- every source byte is read before it is overwritten, in either direction.  Nothing outside
+ * [dev_dst, dev_dst+n) is written; source bytes outside the destination range keep their values.  What closing the gap behind a
+ * removed file of a resident part is (every later byte slides down by d: dev_dst = dev_src - d, one key, off_to = off_from - d), and
+ * what opening one is; with equal keys and offsets, or two keys == 0 mod 2^31-1, it is the library's memmove.
+ * The contract is otherwise modgpu_rekey_device_to's, word for word: asynchronous on `hip_stream`, `device` -1 = the current device,
+ * allocation-free, capturable into a hipGraph; either side any byte alignment, the two offsets any 64-bit values (their phases mod 16
+ * independent of each other and of the pointers'); n == 0 does nothing; a NULL pointer with n > 0 is MODGPU_ERR_INVALID; an entry
+ * of 2^24 chunks of 64 KiB or more is MODGPU_ERR_INVALID; no host loop.  Page-locked host memory on either side is refused
+ * (MODGPU_ERR_INVALID): the ordering below is for device memory.
+ * The WORKSPACE is the caller's: device memory of `device`, 8-byte aligned, at least modgpu_move_workspace_bytes(n) bytes, checked on
+ * the host before anything is queued, as the table calls check theirs.  It holds a header line (a status word and a ticket pair of the
+ * call's own: the call never depends on the library's scratch and never degrades for lack of it), one 32-bit "loaded" flag per 64 KiB
+ * chunk, and scratch for the ragged pieces.  The call resets it in stream order (hipMemsetAsync), so a replayed graph starts clean.
+ * Two calls on one workspace must not overlap in time; a workspace that meets [dev_dst, dev_dst+n) or [dev_src, dev_src+n) is
+ * MODGPU_ERR_INVALID.
+ * Routes, chosen on the host:
+ *   * disjoint ranges, or dev_dst == dev_src: modgpu_rekey_device_to, unchanged (the workspace is still checked, and its header
+ *     reset);
+ *   * a partial overlap: the bytes before the destination's first 64 KiB boundary and the last < 16 are rekeyed INTO the workspace by
+ *     one ordinary rekey launch, the body in between is moved by the rekey kernel's move loop -- chunks in the direction of the move,
+ *     each stored only once every chunk whose source it overwrites has been loaded --, and two copies put the pieces in place: 2
+ *     kernel launches (path_stats().gpu_launches), 1 when the body is empty (n < 64 KiB or so) or there are no pieces;
+ *     modgpu_last_launch reports the body launch as variant 14 with `bytes` = n;
+ *   * keystreams that cancel (the same reduced key at the same stream position) or are both the identity: the same, bit-exact;
+ *   * exactly ONE key == 0 mod 2^31-1 with a partial overlap: TWO passes on the same stream, the plain move, then the other key
+ *     applied in place on dev_dst (path_stats().gpu_launches gains the in-place pass's launches too, and modgpu_last_launch
+ *     then reports the in-place launch, not variant 14).
+ * No wait inside the pass is unbounded: a workgroup that has waited 2 s for another one gives up, stores nothing more, and the call
+ * ends; modgpu_move_status then returns MODGPU_ERR_HIP and the contents of [dev_dst, dev_dst+n) are unspecified.  That is a bug in
+ * the library or a device in trouble, never a property of the arguments. */
+uint64_t modgpu_move_workspace_bytes(uint64_t n); /* 0 for n == 0 or an entry of 2^24 chunks or more */
+int modgpu_rekey_move_device(void *dev_dst, const void *dev_src, uint64_t n, int32_t key_from, uint64_t off_from, int32_t key_to,
+                             uint64_t off_to, void *dev_workspace, uint64_t workspace_bytes, int device, void *hip_stream);
+/* Status of the last modgpu_rekey_move_device that ran on dev_workspace, read after the caller has synchronised: MODGPU_OK with
+ * *stalled_chunk = UINT64_MAX, or MODGPU_ERR_HIP with *stalled_chunk = the 64 KiB chunk of the body whose wait ran out.
+ * Synchronous, like modgpu_table_status (a small copy from the device). */
+int modgpu_move_status(const void *dev_workspace, int device, uint64_t *stalled_chunk);
 
 /* n_parts rekey entries of ONE device: dst_parts[i][j] = src_parts[i][j] ^ ks(key_from)[offs_from[i] + j] ^ ks(key_to)[offs_to[i] + j]
  * (a NULL offs_from or offs_to means 0 for every entry).  Relocating the files of an encrypted part is this call with

@@ -233,6 +233,11 @@ void modgpu_debug_set_table_grid(uint32_t grid);
  * (tools/bench_rekey_table.py) and parity tests of both grids. */
 void modgpu_debug_set_rekey_table_grid(uint32_t grid);
 
+/* modgpu_rekey_move_device's body launch: `grid` workgroups (1..4096), 0 = the shipped rule (the rekey call's grid).  A forced value is
+ * still capped at what the device holds at once.  Parity tests: a grid of 4 over 40 chunks makes every workgroup draw many tickets
+ * and wait for its neighbours. */
+void modgpu_debug_set_move_grid(uint32_t grid);
+
 /* The verify call's compare launch: at most `grid` workgroups (1..4096), 0 or less = the shipped grid (one workgroup per CU on
  * every CU; DESIGN.md 4.10 has the A/B against the out-of-place kernel's 25 per 32 CUs).  The kernel has one chunk assignment, the
  * static one; its plain / funnel and keyed / identity forms follow from the call's pointers and key.  The same cap holds for the

@@ -67,6 +67,9 @@ EXPORTS = {
     "modgpu_rekey_device_to": (_int, [_vp, _vp, _u64, _i32, _u64, _i32, _u64, _int, _vp]),
     "modgpu_rekey_batch_device_to": (_int, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64), ctypes.POINTER(_u64),
                                             ctypes.POINTER(_u64), _int, _i32, _i32, _int, _vp]),
+    "modgpu_move_workspace_bytes": (_u64, [_u64]),
+    "modgpu_rekey_move_device": (_int, [_vp, _vp, _u64, _i32, _u64, _i32, _u64, _vp, _u64, _int, _vp]),
+    "modgpu_move_status": (_int, [_vp, _int, ctypes.POINTER(_u64)]),
     "modgpu_cycle_host_to_device": (_int, [_vp, _vp, _u64, _i32, _u64, _int]),
     "modgpu_cycle_device_to_host": (_int, [_vp, _vp, _u64, _i32, _u64, _int]),
     "modgpu_cycle_file_to_device": (_int, [ctypes.c_char_p, _u64, _vp, _u64, _i32, _u64, _int]),
@@ -203,6 +206,7 @@ DEBUG_EXPORTS = {
     "modgpu_debug_set_rekey_form": (None, [_int]),
     "modgpu_debug_set_table_grid": (None, [ctypes.c_uint32]),
     "modgpu_debug_set_rekey_table_grid": (None, [ctypes.c_uint32]),
+    "modgpu_debug_set_move_grid": (None, [ctypes.c_uint32]),
     "modgpu_debug_set_verify_form": (None, [_int]),
     "modgpu_debug_set_verify_table_grid": (None, [ctypes.c_uint32]),
     "modgpu_debug_set_rekey_verify_table_grid": (None, [ctypes.c_uint32]),
@@ -707,6 +711,50 @@ def time_rekey_device_to(dst, src, n, key_from, key_to, off_from=0, off_to=0, de
     _check(lib().modgpu_time_rekey_device_to(_vp(_dev_addr(dst)), _vp(_dev_addr(src)), n, as_int32(key_from), off_from, as_int32(key_to),
                                              off_to, device, _vp(stream or 0), iters, ctypes.byref(ms)))
     return ms.value
+
+
+def move_workspace_bytes(n):
+    """bytes of device workspace rekey_move_device needs for n bytes (0 for n == 0, or an entry of 2^24 chunks or more)"""
+    return lib().modgpu_move_workspace_bytes(n)
+
+
+def rekey_move_device(dst, src, n, key_from, key_to, off_from=0, off_to=0, workspace=None, device=-1, stream=None):
+    """Asynchronous REKEY of n bytes at raw device addresses with memmove rules: dst[j] = SRC0[j] ^ ks(key_from)[off_from + j] ^
+    ks(key_to)[off_to + j] for ANY overlap of the two ranges, every source byte read before it is overwritten.  `workspace` is a
+    DeviceBuffer or address of at least move_workspace_bytes(n) bytes of the same device; None makes one, waits for the call and
+    raises if the pass gave up (move_status).  Otherwise move_status(workspace) tells the outcome after a synchronise."""
+    if workspace is None:
+        if not n:
+            return
+        ws = DeviceBuffer(move_workspace_bytes(n), device)
+        try:
+            rekey_move_device(dst, src, n, key_from, key_to, off_from, off_to, ws, device, stream)
+            ws.sync(stream)
+            stalled = move_status(ws, device)
+            if stalled is not None:
+                raise ModGpuError(3, f"the move gave up waiting at chunk {stalled}")
+        finally:
+            ws.free()
+        return
+    ws_bytes = workspace.nbytes if isinstance(workspace, DeviceBuffer) else move_workspace_bytes(n)
+    _check(lib().modgpu_rekey_move_device(_vp(_dev_addr(dst)), _vp(_dev_addr(src)), n, as_int32(key_from), off_from, as_int32(key_to), off_to,
+                                          _vp(_dev_addr(workspace)), ws_bytes, device, _vp(stream or 0)))
+
+
+def move_status(workspace, device=-1):
+    """None if the last rekey_move_device on `workspace` ran clean, else the chunk of the body whose wait ran out (the destination's
+    contents are then unspecified).  Synchronise the call's stream first."""
+    out = _u64(0)
+    rc = lib().modgpu_move_status(_vp(_dev_addr(workspace)), device, ctypes.byref(out))
+    if rc == 3 and out.value != (1 << 64) - 1:
+        return int(out.value)
+    _check(rc)
+    return None
+
+
+def debug_set_move_grid(grid=0):
+    """Testing flavour: the grid of rekey_move_device's body launch (0 = shipped; capped at what the device holds at once)."""
+    _debug_lib().modgpu_debug_set_move_grid(grid)
 
 
 REKEY_FORMS = {None: -1, "shipped": -1, "queue": 0, "all": 1}
@@ -1267,6 +1315,12 @@ class DeviceBuffer:
         n = self.nbytes - offset if n is None else n
         assert offset + n <= self.nbytes
         cycle_device(self.ptr + offset, n, key, stream_off, self.device, stream)
+
+    def move(self, dst_offset, src_offset, n, key_from=0, key_to=0, off_from=0, off_to=0, workspace=None, stream=None):
+        """Moves n bytes inside the buffer from src_offset to dst_offset, the ranges overlapping in any way (memmove rules), rekeying
+        on the way (rekey_move_device; with the default keys a plain memmove)."""
+        assert max(dst_offset, src_offset) + n <= self.nbytes
+        rekey_move_device(self.ptr + dst_offset, self.ptr + src_offset, n, key_from, key_to, off_from, off_to, workspace, self.device, stream)
 
     def sync(self, stream=None):
         _check(self._lib.modgpu_sync(self.device, _vp(stream or 0)))

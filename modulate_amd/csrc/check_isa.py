@@ -253,6 +253,48 @@ def rekey_blocks(k):
     return bad
 
 
+def move_loop(k):
+    """the rekey kernel's second loop (cycle_rekey_kernel.h: a destination that partly overlaps its source).  Per unrolled trip (2): a
+    barrier behind the chunk's blocks, thread 0's poll of the other chunks' flags, a barrier in front of the stores -- with the stream
+    loop's 4 and the one behind each of the first two tickets, 12 s_barrier.  In front of the first of them every wave waits, in an asm
+    statement of its own, until the chunk's loads have returned: the flag must not go up before.  The poll sleeps between reads (s_sleep) and is bounded by the
+    constant-rate clock (s_memrealtime: one stamp where it starts, one per round); flags are read and written at agent scope (sc1)
+    and NOTHING is fenced: a release or acquire there (buffer_wbl2 / buffer_inv) would drain the loads of the next chunk -- the hazard
+    is write-after-read, the flag speaks for loads that have returned.  Both loops' ticket fetches are plain returning atomics: the
+    stream loop's 2, the move loop's 2 and the two that draw its first positions a barrier apart (+ the exit count = 7)."""
+    bad = []
+    counts = {m: len(code_lines(k.fn, m)) for m in ("s_barrier", "s_sleep", "s_memrealtime", "buffer_wbl2", "buffer_inv", "global_atomic_add", "global_atomic_cmpswap")}
+    if counts["s_barrier"] != 12:
+        bad.append("%s: %d s_barrier, expected 12 (stream loop 4, move loop 2 + 2 x 3)" % (k.name, counts["s_barrier"]))
+    if counts["s_sleep"] != 2 or counts["s_memrealtime"] != 4:
+        bad.append("%s: the move loop's poll is not a sleeping, clock-bounded one (%d s_sleep, %d s_memrealtime; expected 2 and 4)"
+                   % (k.name, counts["s_sleep"], counts["s_memrealtime"]))
+    if counts["buffer_wbl2"] or counts["buffer_inv"]:
+        bad.append("%s: a cache write-back or invalidate inside the kernel (the move loop's flags need no fence)" % k.name)
+    # the explicit wait for the chunk's loads: one asm statement per unrolled trip, s_waitcnt vmcnt(the next chunk's loads: 4 words, twice
+    # that through the funnel <..., true>), and between it and the next s_barrier no store and no flag access
+    waits = [m for m in BLOCK.finditer(k.fn) if re.fullmatch(r"\s*s_waitcnt vmcnt\([1-9]\d*\)\s*", m.group(1))]  # (vmcnt(0): the exit's)
+    ahead = 8 if "ELb1EEv" in k.name else 4
+    if len(waits) != 2 or any(m.group(1).strip() != "s_waitcnt vmcnt(%d)" % ahead for m in waits):
+        bad.append("%s: the move loop's wait for the chunk's loads is not one `s_waitcnt vmcnt(%d)` per unrolled trip (found %s)"
+                   % (k.name, ahead, [m.group(1).strip() for m in waits]))
+    for m in waits:
+        upto = k.fn.find("s_barrier", m.end())
+        if upto < 0 or re.search(r"^\s+(buffer_store|global_store|global_load|global_atomic)", k.fn[m.end():upto], re.M):
+            bad.append("%s: a store or a flag access lies between the wait for the chunk's loads and the barrier behind it" % k.name)
+    polls = code_lines(k.fn, "global_load_dword v")
+    flags = [ln for ln in polls if ln.endswith(" sc1")]
+    if len(flags) != 4:
+        bad.append("%s: %d agent-scope flag reads (global_load_dword ... sc1), expected 4 (first look + poll, per unrolled trip)" % (k.name, len(flags)))
+    ups = [ln for ln in code_lines(k.fn, "global_store_dword v") if ln.endswith(" sc1") and " sc0" not in ln]
+    if len(ups) != 4:
+        bad.append("%s: %d agent-scope dword stores, expected 4 (a flag per unrolled trip + the pair's reset)" % (k.name, len(ups)))
+    if counts["global_atomic_add"] != 7 or counts["global_atomic_cmpswap"] != 2:
+        bad.append("%s: %d global_atomic_add and %d global_atomic_cmpswap, expected 7 (tickets 2 + 2 + 2, the exit count) and 2 (the status word)"
+                   % (k.name, counts["global_atomic_add"], counts["global_atomic_cmpswap"]))
+    return bad
+
+
 def block_count(k, family, expected, made_of):
     blocks = len(carry_blocks(k.fn))
     return ["%s: %d %s blocks, expected %d (%s)" % (k.name, blocks, family.a, expected, made_of)] if blocks != expected else []
@@ -500,9 +542,11 @@ TUS = (
     TU("cycle_xfer_kernel.s", "the transfer kernels' TU",
        (Kind("modgpu_cycle_xfer_kernel", XFER + [(stores, "nt sc1", "an upload store into HBM")], "^ILb1E"),
         Kind("modgpu_cycle_xfer_kernel", XFER + [(stores, "sc1", "a download store across PCIe")]))),
-    # rekey, plain and funnel
+    # rekey, plain and funnel: one uniform branch chooses between the stream loop and the move loop; the fixed registers, the ticket's
+    # form, the cache policies, the budget (and, for every kernel, barriers at full EXEC) hold over both
     TU("cycle_rekey_kernel.s", "the rekey kernel's TU",
-       (Kind("modgpu_cycle_rekey_kernel", BUDGET + [rekey_blocks, TICKET, loads_nt, (stores, "nt sc1")]),)),
+       (Kind("modgpu_cycle_rekey_kernel", BUDGET + [rekey_blocks, (block_count, TWO_KEYSTREAM, 17, TRIPS + " in the stream and in the move loop + the cut first chunk"),
+                                                   TICKET, loads_nt, (stores, "nt sc1"), move_loop]),)),
     # table of out-of-place entries
     table_tu("cycle_table_kernel.s", "the table kernels' TU", "modgpu_cycle_table", PLANNING,
              [keystream_blocks, (block_count, KEYSTREAM, 8, TRIPS), loads_nt, (stores, "nt sc1"), scalar_entry_search]),

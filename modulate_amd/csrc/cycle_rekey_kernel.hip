@@ -207,8 +207,124 @@ __global__ __launch_bounds__(BLOCK) MODGPU_REKEY_KEEP_OFF_THE_FIXED_TEMPORARIES 
         return (uint32_t)PREFIX * G + (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
     };
 
+    // ---- the MOVE loop (cycle_rekey_kernel.h): the destination partly overlaps the source.  The stream loop's pipeline with two things
+    // added per chunk, both between the moment its source is in registers and its stores: the chunk's "loaded" flag goes up, and the
+    // flags of the chunks whose source reads meet this chunk's destination are waited for.  The hazard is write-after-read only: no
+    // reader needs a byte another workgroup wrote, so only the flags need agent scope, and nothing needs a fence -- the loads a flag
+    // speaks for have RETURNED when it is stored (their data went through the two-keystream block in front of the barrier), and the
+    // stores it permits are issued behind the poll (a release fence would only drain wave 0's loads of the NEXT chunk).
+    // Positions are tickets only, drawn in rising order, the first two where the workgroup starts: whoever holds a position is running, a position waits for
+    // lower ones only, so the lowest unfinished position is never blocked -- whether or not the whole grid is resident.
+    __shared__ uint32_t q_dead; // the wait ran out: this workgroup stores nothing more (it still loads, flags and draws tickets)
+    const uint32_t q_dead_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)&q_dead;
+    auto chunk_at = [&](uint32_t p) { return a.move_down != 0 && p < total ? total - 1u - p : p; };
+    auto flag_up = [&](const uint32_t *f) { // thread 0; false: gave up
+        if (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return true;
+        const uint32_t t0 = (uint32_t)wall_clock64(); // (the bound fits 32 bits: the low word's difference is enough)
+        do {
+            __builtin_amdgcn_s_sleep(8);
+            if (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return true;
+        } while ((uint32_t)wall_clock64() - t0 < (uint32_t)kRekeyMoveStallTicks);
+        return false;
+    };
+    // (one entry, lead 0, no edges: the views of the stream loop shrink to the entry's three words, which saves their scalar registers)
+    const CycleRekeyPart &M = a.part[0];
+    auto move_left = [&](uint32_t g) {
+        const uint64_t o = (uint64_t)g * CHUNK;
+        const uint64_t left = g < total && o < M.end ? M.end - o : 0; // past the end: zero-size descriptors
+        return (uint32_t)(left < CHUNK ? left : CHUNK);
+    };
+    auto load_move = [&](Raw(&w)[U], uint32_t g) {
+        const SrcRsrc rs = src_rsrc<FUNNEL>(M.src_body + (uint64_t)g * CHUNK, move_left(g));
+#pragma unroll
+        for (int u = 0; u < U; ++u) load_src<FUNNEL>(w[u], rs, voff + u * SUB);
+    };
+    auto process_move = [&](Raw(&w)[U], uint32_t g) {
+        auto r = __builtin_amdgcn_make_buffer_rsrc(M.dst_body + (uint64_t)g * CHUNK, 0, (int)move_left(g), 0x00020000);
+        const uint32_t sh = FUNNEL ? (uint32_t)(uintptr_t)M.src_body & 3u : 0u; // (CHUNK is a multiple of 4)
+        uint32_t sa[U], sb[U];
+        states(g, vs, sa, sb); // (of vs only lo, first and the lane's bases: set where the loop starts)
+        u32x4 d[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) d[u] = rekey_word(src_word<FUNNEL>(w[u], sh), sa[u], sb[u]);
+        // every wave waits HERE until this chunk's loads have returned: the only vector-memory instructions younger than them are the
+        // next chunk's loads (U, twice that in the funnel form).  The blocks above consume the data, so the compiler's own waits say
+        // the same; this one does not depend on where an optimiser leaves them (check_isa.py pins it in front of the barrier).
+        asm volatile("s_waitcnt vmcnt(%0)" : : "n"(FUNNEL ? 2 * U : U) : "memory");
+        if (tid == 0)
+            asm volatile("ds_write_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : : "v"(q_next_lds + 4u * (trip & 1u)), "v"(pending) : "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier(); // every wave has this chunk's source in registers
+        if (tid == 0 && g < total) {
+            __hip_atomic_store(a.move_flags + g, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            uint32_t dead;
+            asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(dead) : "v"(q_dead_lds) : "memory");
+#pragma unroll 1
+            for (uint32_t i = 0; i < a.move_win_n && dead == 0; ++i) {
+                const uint32_t k = g + (uint32_t)a.move_win_lo + i; // (below chunk 0: wraps past total)
+                if (k < total && !flag_up(a.move_flags + k)) {
+                    atomicCAS(a.move_status, 0u, 1u + g);
+                    dead = 1;
+                    asm volatile("ds_write_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : : "v"(q_dead_lds), "v"(dead) : "memory");
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        uint32_t dd;
+        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(dd) : "v"(q_dead_lds) : "memory");
+        if (__builtin_amdgcn_readfirstlane((int)dd) == 0) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) __builtin_amdgcn_raw_buffer_store_b128(d[u], r, voff + u * SUB, 0, SAUX);
+        }
+        ++trip;
+    };
+
     uint32_t cq[NB];
     static_assert(PREFIX == NB, "the static positions are exactly the ones cq[] starts with");
+    if (a.move_flags != nullptr) {
+        // the first DEPTH + 1 positions: one fetch EACH, a barrier apart.  (One fetch of two would give a workgroup two CONSECUTIVE
+        // positions; with a shift below a chunk, position p waits for p - 1's flag, which goes up only once its workgroup has stored the
+        // position before it -- every workgroup's first store would wait for its neighbour's, a chain as long as the grid (DESIGN.md
+        // 4.14 has the figures).  A barrier apart, the other workgroups' first fetches come in between.)
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+            if (tid == 0) {
+                pending = __hip_atomic_fetch_add(a.queue, one, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                asm volatile("ds_write_b32 %0, %1\n\tds_write_b32 %2, %3\n\ts_waitcnt lgkmcnt(0)" : : "v"(q_next_lds + 4u * ((uint32_t)(i + 1) & 1u)), "v"(pending), "v"(q_dead_lds), "v"(0u) : "memory");
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_barrier();
+            uint32_t t;
+            asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(t) : "v"(q_next_lds + 4u * ((uint32_t)(i + 1) & 1u)) : "memory");
+            cq[i] = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
+        }
+        if (cq[0] < total) {
+            vs.lane_base[0] = mulmod_canon(M.base_body[0], lane_mul);
+            vs.lane_base[1] = mulmod_canon(M.base_body[1], lane_mul);
+            Raw w[NB][U];
+#pragma unroll
+            for (int i = 0; i < DEPTH; ++i) load_move(w[i], chunk_at(cq[i]));
+            bool finished = false;
+            while (!finished) {
+#pragma unroll
+                for (int p = 0; p < NB; ++p) {
+                    __builtin_amdgcn_s_barrier();
+                    if (tid == 0) pending = __hip_atomic_fetch_add(a.queue, one, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    load_move(w[(p + DEPTH) % NB], chunk_at(cq[DEPTH]));
+                    __builtin_amdgcn_sched_barrier(0);
+                    process_move(w[p], chunk_at(cq[0]));
+#pragma unroll
+                    for (int i = 0; i < DEPTH; ++i) cq[i] = cq[i + 1];
+                    cq[DEPTH] = take_published() - (uint32_t)PREFIX * G; // tickets ARE positions here
+                    if (cq[0] >= total) {
+                        finished = true;
+                        break;
+                    }
+                }
+            }
+        }
+    } else {
 #pragma unroll
     for (int i = 0; i < NB; ++i) cq[i] = blk + (uint32_t)i * G;
     if (cq[0] < total) {
@@ -234,6 +350,7 @@ __global__ __launch_bounds__(BLOCK) MODGPU_REKEY_KEEP_OFF_THE_FIXED_TEMPORARIES 
             }
         }
     }
+    } // (the stream loop keeps its indentation: it is the out-of-place kernel's, line for line)
     // leave: the last workgroup out resets the pair, then signs off in the host-visible word
     if (tid == 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -278,4 +395,18 @@ hipError_t modgpu_launch_cycle_rekey(const CycleRekeyArgs &a, int form, uint32_t
     if (form == CYCLE_REKEY_FUNNEL) RekeyFunnel::launch(a, grid, stream);
     else RekeyPlain::launch(a, grid, stream);
     return hipGetLastError();
+}
+hipError_t modgpu_launch_cycle_rekey_move(const CycleRekeyArgs &a, int form, uint32_t *grid, hipStream_t stream)
+{
+    int per_cu = 0, cus = 0, dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e == hipSuccess)
+        e = form == CYCLE_REKEY_FUNNEL ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, modgpu_cycle_rekey_kernel<4, 1024, true>, 1024, 0)
+                                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, modgpu_cycle_rekey_kernel<4, 1024, false>, 1024, 0);
+    if (e != hipSuccess) return e;
+    const uint64_t resident = (uint64_t)(per_cu > 0 ? per_cu : 1) * (uint64_t)(cus > 0 ? cus : 1);
+    if (*grid > resident) *grid = (uint32_t)resident;
+    if (*grid == 0) *grid = 1;
+    return modgpu_launch_cycle_rekey(a, form, *grid, stream);
 }

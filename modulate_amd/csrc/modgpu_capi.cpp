@@ -888,8 +888,9 @@ constexpr int rekey_shape() { return kRekeyShapeShipped; }
 
 // One launch of the rekey kernel over 1..kCycleBatchMax non-empty entries of the current device, both keys non-zero residues.
 // MODGPU_OK, an error, or 1: no ticket pair to be had right now (or an entry beyond the three-byte chunk jump tables).
+// `own_pair`: a clean ticket pair of the caller's (the move call's workspace header) instead of one of the ring's.
 int launch_rekey(uint8_t *const *dst, const uint8_t *const *src, const uint64_t *sizes, const uint64_t *offs_from, const uint64_t *offs_to,
-                 int n, uint32_t key_from, uint32_t key_to, hipStream_t stream)
+                 int n, uint32_t key_from, uint32_t key_to, hipStream_t stream, uint32_t *own_pair = nullptr)
 {
     CycleRekeyArgs a{};
     const uint64_t chunk = modgpu_rekey_chunk_bytes();
@@ -915,8 +916,13 @@ int launch_rekey(uint8_t *const *dst, const uint8_t *const *src, const uint64_t 
     }
     for (int k = n; k <= kCycleBatchMax; ++k) a.start[k] = (uint32_t)total;
     a.n_parts = (uint32_t)n;
-    const QueuePair q = queue_pair(stream);
-    if (!q.pair) return 1;
+    QueuePair q;
+    if (own_pair) {
+        q.pair = own_pair;
+    } else {
+        q = queue_pair(stream);
+        if (!q.pair) return 1;
+    }
     a.queue = q.pair;
     a.queue_done = q.done;
     a.queue_seq = q.seq;
@@ -975,6 +981,155 @@ int rekey_impl(void *const *dst, const void *const *src, const uint64_t *sizes, 
         }
         if (rc != MODGPU_OK) return rc;
     }
+    return MODGPU_OK;
+}
+
+// ---- move: rekey with memmove rules, any overlap of destination and source (modgpu_rekey_move_device) ----
+// The workspace: a header line -- words 0, 1 the ticket pair, word kMoveStatusWord the status (0, or 1 + the stalled chunk) --, one
+// 32-bit flag per chunk the body can have, and scratch for the ragged pieces: a head of less than a chunk (or all of a range whose
+// body is empty: less than a chunk + 16 bytes) and a tail of less than 16 bytes.
+constexpr uint64_t kMoveHdrBytes = 128;
+constexpr uint32_t kMoveStatusWord = 16; // (a line of the pair's own would be wasted: the word is written by a pass that has failed)
+constexpr uint64_t kMoveMaxChunks = 1ull << 24;
+struct MoveLayout {
+    uint64_t flags, head, tail, bytes;
+};
+MoveLayout move_layout(uint64_t n)
+{
+    const uint64_t chunk = modgpu_rekey_chunk_bytes();
+    MoveLayout L;
+    L.flags = kMoveHdrBytes;
+    L.head = L.flags + ((n / chunk + 2) * sizeof(uint32_t) + 127) / 128 * 128;
+    L.tail = L.head + chunk + 64;
+    L.bytes = L.tail + 64;
+    return L;
+}
+#ifdef MODGPU_TESTING_HOOKS
+std::atomic<uint32_t> g_move_grid{0}; // modgpu_debug_set_move_grid
+uint32_t move_grid_forced() { return g_move_grid.load(std::memory_order_relaxed); }
+#else
+constexpr uint32_t move_grid_forced() { return 0; }
+#endif
+
+// The chunks, other than chunk c itself, whose source reads meet chunk c's destination: c + lo .. c + lo + count - 1.  delta = src -
+// dst.  A chunk's reads span its source rounded out to whole dwords of the SOURCE (the funnel form reads the dword below a misaligned
+// start and the one that holds the last byte; the body's destination is chunk-aligned, so delta's phase mod 4 is the source's).
+// Rounded like that no chunk's reads reach below its own destination when delta > 0, nor above it when delta < 0: every chunk of the
+// window lies on the side the move walks AWAY from, at a lower position.
+void move_window(int64_t delta, int64_t chunk, int32_t *lo, uint32_t *count)
+{
+    const int64_t dlo = delta - ((delta % 4 + 4) % 4), dhi = dlo + (delta % 4 != 0 ? 4 : 0);
+    const int64_t mid = dlo >= 0 ? -(dlo / chunk) : (-dlo + chunk - 1) / chunk; // about -delta / chunk
+    *lo = 0;
+    *count = 0;
+    for (int64_t m = mid - 3; m <= mid + 3; ++m) {
+        // chunk c + m reads [m * chunk + dlo, (m + 1) * chunk + dhi) counted from chunk c's first destination byte
+        if (m == 0 || !(m * chunk + dlo < chunk && (m + 1) * chunk + dhi > 0)) continue;
+        if (!*count) *lo = (int32_t)m;
+        ++*count;
+    }
+}
+
+// The launches of a move whose ranges partly overlap, both keys non-zero residues, offsets already reduced: memset, pieces into
+// scratch, body, pieces into place.
+int move_launches(uint8_t *dst, const uint8_t *src, uint64_t n, uint32_t kf, uint64_t of, uint32_t kt, uint64_t ot, uint8_t *ws, const MoveLayout &L,
+                  hipStream_t stream)
+{
+    const uint64_t chunk = modgpu_rekey_chunk_bytes();
+    uint64_t head = std::min<uint64_t>(n, (chunk - (reinterpret_cast<uintptr_t>(dst) & (chunk - 1))) & (chunk - 1));
+    uint64_t body = (n - head) & ~15ull, tail = n - head - body;
+    if (body == 0) { // all of it goes through scratch
+        head = n;
+        tail = 0;
+    }
+    uint32_t *const hdr = reinterpret_cast<uint32_t *>(ws);
+    (void)hipGetLastError();
+    HIP_TRY(hipMemsetAsync(ws, 0, L.head, stream)); // header and flags
+    // the pieces are READ first: nothing of the source has been written yet
+    if (head || tail) {
+        uint8_t *pd[2];
+        const uint8_t *ps[2];
+        uint64_t pn[2], pf[2], pt[2];
+        int k = 0;
+        if (head) pd[k] = ws + L.head, ps[k] = src, pn[k] = head, pf[k] = of, pt[k] = ot, ++k;
+        if (tail) pd[k] = ws + L.tail, ps[k] = src + head + body, pn[k] = tail, pf[k] = of + head + body, pt[k] = ot + head + body, ++k;
+        const int rc = launch_rekey(pd, ps, pn, pf, pt, k, kf, kt, stream, hdr);
+        if (rc != MODGPU_OK) return rc == 1 ? fail(MODGPU_ERR_INVALID, "move: a ragged piece beyond the chunk tables") : rc;
+    }
+    if (body) {
+        CycleRekeyArgs a{};
+        CycleRekeyPart &P = a.part[0];
+        P.dst_body = dst + head;
+        P.src_body = src + head;
+        P.end = body;
+        P.base_body[0] = lcg::state_residue(kf, of + head);
+        P.base_body[1] = lcg::state_residue(kt, ot + head);
+        const uint64_t total = (body + chunk - 1) / chunk;
+        for (int k = 1; k <= kCycleBatchMax; ++k) a.start[k] = (uint32_t)total;
+        a.n_parts = 1;
+        a.queue = hdr;
+        a.move_flags = reinterpret_cast<uint32_t *>(ws + L.flags);
+        a.move_status = hdr + kMoveStatusWord;
+        a.move_down = dst > src ? 1u : 0u;
+        const int64_t delta = (int64_t)(reinterpret_cast<uintptr_t>(src) - reinterpret_cast<uintptr_t>(dst));
+        move_window(delta, (int64_t)chunk, &a.move_win_lo, &a.move_win_n);
+        if (a.move_win_n > 3 || (a.move_win_n && (delta > 0 ? a.move_win_lo + (int32_t)a.move_win_n > 0 : a.move_win_lo < 1)))
+            return fail(MODGPU_ERR_INVALID, "move: internal error (a chunk would wait for a later one)");
+        // the rekey call's grid; every position is a ticket, so the pass needs no workgroup that is not running, but a grid the
+        // device holds at once wastes none (modgpu_launch_cycle_rekey_move caps it)
+        uint64_t cap = 0, helpers = 0;
+        queue_grid(total, large_grid(), &cap, &helpers);
+        if (rekey_shape() == CYCLE_REKEY_SHAPE_ALL) cap = large_grid();
+        if (move_grid_forced()) cap = move_grid_forced();
+        uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(total, cap));
+        const int form = (delta & 3) != 0 ? CYCLE_REKEY_FUNNEL : CYCLE_REKEY_PLAIN;
+        const hipError_t e = modgpu_launch_cycle_rekey_move(a, form, &grid, stream);
+        if (e != hipSuccess) return fail_hip(e, "cycle kernel launch (move)");
+        g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+        t_last_launch = {modgpu_rekey_kernel_name(form), CYCLE_REKEY_MOVE, grid, modgpu_rekey_block(), (uint32_t)chunk, n, grid, MODGPU_REKEY_KERNEL_SOURCE_HASH};
+    }
+    if (head) HIP_TRY(hipMemcpyAsync(dst, ws + L.head, head, hipMemcpyDeviceToDevice, stream));
+    if (tail) HIP_TRY(hipMemcpyAsync(dst + head + body, ws + L.tail, tail, hipMemcpyDeviceToDevice, stream));
+    return MODGPU_OK;
+}
+
+// One fixed non-zero key at one offset on both sides: ks ^ ks = 0, the two-keystream block as a bit-exact memmove
+constexpr uint32_t kMovePlainKey = 1u;
+
+int rekey_move_impl(void *dev_dst, const void *dev_src, uint64_t n, int32_t key_from, uint64_t off_from, int32_t key_to, uint64_t off_to, void *ws,
+                    uint64_t ws_bytes, int device, hipStream_t stream)
+{
+    if (n == 0) return MODGPU_OK;
+    if (!dev_dst || !dev_src) return fail(MODGPU_ERR_INVALID, "null buffer");
+    const uint64_t chunk = modgpu_rekey_chunk_bytes();
+    if (n >= kMoveMaxChunks * chunk || entry_geom(static_cast<const uint8_t *>(dev_dst), n, chunk).n_chunks >= kMoveMaxChunks)
+        return fail(MODGPU_ERR_INVALID, "an entry of 2^24 chunks or more (the move call's limit)");
+    if (!ws) return fail(MODGPU_ERR_INVALID, "null workspace");
+    if (reinterpret_cast<uintptr_t>(ws) & 7) return fail(MODGPU_ERR_INVALID, "workspace not 8-byte aligned");
+    const MoveLayout L = move_layout(n);
+    if (ws_bytes < L.bytes) return fail(MODGPU_ERR_INVALID, "workspace smaller than modgpu_move_workspace_bytes(n)");
+    if (ranges_meet(ws, L.bytes, dev_dst, n) || ranges_meet(ws, L.bytes, dev_src, n))
+        return fail(MODGPU_ERR_INVALID, "the workspace meets the destination or the source");
+    DeviceScope scope(device);
+    if (scope.rc) return scope.rc;
+    int phys = -1;
+    HIP_TRY(hipGetDevice(&phys));
+    if (modgpu_xfer_device_of(ws, L.bytes) != phys) return fail(MODGPU_ERR_INVALID, "the workspace is not device memory of the call's device");
+    if (dev_dst == dev_src || !ranges_meet(dev_dst, n, dev_src, n)) {
+        // (the header is reset on this route too: modgpu_move_status speaks of the LAST call on the workspace, whatever its route)
+        HIP_TRY(hipMemsetAsync(ws, 0, kMoveHdrBytes, stream));
+        return rekey_impl(&dev_dst, &dev_src, &n, &off_from, &off_to, 1, key_from, key_to, stream);
+    }
+    if (modgpu_xfer_device_of(dev_dst, n) != phys || modgpu_xfer_device_of(dev_src, n) != phys)
+        return fail(MODGPU_ERR_INVALID, "overlapping ranges that are not device memory of the call's device");
+    uint8_t *const d = static_cast<uint8_t *>(dev_dst), *const w = static_cast<uint8_t *>(ws);
+    const uint8_t *const s = static_cast<const uint8_t *>(dev_src);
+    const uint32_t kf = lcg::key_residue(key_from), kt = lcg::key_residue(key_to);
+    const uint64_t of = off_from % lcg::PERIOD, ot = off_to % lcg::PERIOD;
+    if (kf && kt && !(kf == kt && of == ot)) return move_launches(d, s, n, kf, of, kt, ot, w, L, stream);
+    // keystreams that cancel or are both the identity: a plain move; exactly one identity: the move, then the other key in place
+    if (int rc = move_launches(d, s, n, kMovePlainKey, 0, kMovePlainKey, 0, w, L, stream)) return rc;
+    if (!kf != !kt) return kf ? cycle_device_impl(d, n, key_from, off_from, stream) : cycle_device_impl(d, n, key_to, off_to, stream);
     return MODGPU_OK;
 }
 
@@ -1777,6 +1932,39 @@ int modgpu_rekey_device_to(void *dev_dst, const void *dev_src, uint64_t n, int32
         DeviceScope scope(device);
         if (scope.rc) return scope.rc;
         return rekey_impl(&dev_dst, &dev_src, &n, &off_from, &off_to, 1, key_from, key_to, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+uint64_t modgpu_move_workspace_bytes(uint64_t n)
+{
+    return n == 0 || n >= kMoveMaxChunks * modgpu_rekey_chunk_bytes() ? 0 : move_layout(n).bytes;
+}
+
+int modgpu_rekey_move_device(void *dev_dst, const void *dev_src, uint64_t n, int32_t key_from, uint64_t off_from, int32_t key_to, uint64_t off_to,
+                             void *dev_workspace, uint64_t workspace_bytes, int device, void *hip_stream)
+{
+    return guarded([&]() -> int {
+        return rekey_move_impl(dev_dst, dev_src, n, key_from, off_from, key_to, off_to, dev_workspace, workspace_bytes, device,
+                               static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int modgpu_move_status(const void *dev_workspace, int device, uint64_t *stalled_chunk)
+{
+    return guarded([&]() -> int {
+        if (!dev_workspace || !stalled_chunk) return fail(MODGPU_ERR_INVALID, "null workspace or out pointer");
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        int phys = -1;
+        HIP_TRY(hipGetDevice(&phys));
+        if (modgpu_xfer_device_of(dev_workspace, kMoveHdrBytes) != phys)
+            return fail(MODGPU_ERR_INVALID, "the workspace is not device memory of the call's device");
+        uint32_t h[kMoveHdrBytes / sizeof(uint32_t)];
+        HIP_TRY(hipMemcpy(h, dev_workspace, sizeof h, hipMemcpyDeviceToHost));
+        *stalled_chunk = h[kMoveStatusWord] ? (uint64_t)h[kMoveStatusWord] - 1 : ~0ull;
+        if (h[kMoveStatusWord])
+            return fail(MODGPU_ERR_HIP, "the move gave up waiting at chunk " + std::to_string(*stalled_chunk) + " (the destination's contents are unspecified)");
+        return MODGPU_OK;
     });
 }
 
@@ -2882,6 +3070,7 @@ void modgpu_debug_set_rekey_form(int shape)
 }
 
 void modgpu_debug_set_table_grid(uint32_t grid) { g_table_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
+void modgpu_debug_set_move_grid(uint32_t grid) { g_move_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
 void modgpu_debug_set_rekey_table_grid(uint32_t grid) { g_rekey_table_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
 
 void modgpu_debug_set_verify_table_grid(uint32_t grid) { g_verify_table_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
