@@ -44,12 +44,15 @@ struct ByteSource
     uint32_t U32() { if( !Need( 4 ) ) return 0; uint32_t v = 0; for( int i = 0; i < 4; ++i ) v |= (uint32_t)p[ at + i ] << ( 8 * i ); at += 4; return v; }
     int64_t I64() { if( !Need( 8 ) ) return 0; uint64_t v = 0; for( int i = 0; i < 8; ++i ) v |= (uint64_t)p[ at + i ] << ( 8 * i ); at += 8; return (int64_t)v; }
     void Skip( size_t k ) { if( Need( k ) ) at += k; }
-    std::string Str() // length-prefixed; the value is clipped to 255 chars but the cursor moves the full length (CArk.cpp:604-621)
+    // length-prefixed, the value clipped to 255 chars.  Past an ark path the cursor moves the full length (sStringList, CArk.cpp:533-592).
+    // Past an entry's NAME the reference moves it by the CLIPPED length (CArk.cpp:619-629), so a name of more than 255 bytes leaves its
+    // reader inside the name and the rest of the table is misread -- in practice refused; lbClipCursor keeps that (-fixquirks: full length).
+    std::string Str( bool lbClipCursor = false )
     {
         int32_t len = (int32_t)U32();
         if( len < 0 || !Need( (size_t)len ) ) { ok = false; return std::string(); }
         std::string s( (const char*)p + at, (size_t)std::min( len, kiMaxStringLength ) );
-        at += (size_t)len;
+        at += lbClipCursor ? s.size() : (size_t)len;
         size_t z = s.find( '\0' ); // the reference builds the value through a C string
         if( z != std::string::npos ) s.resize( z );
         return s;
@@ -257,7 +260,7 @@ eError CArk::ParseHeader( std::vector< unsigned char > lImage )
     for( sFileDefinition& f : lFiles ) // sFileDefinition::InitialiseFromData (CArk.cpp:594-650)
     {
         f.mi64Offset = in.I64();
-        f.mName = in.Str();
+        f.mName = in.Str( !CSettings::mbFixReferenceQuirks );
         f.miFlags1 = (int)in.U32();
         f.miSize = (int)in.U32();
         f.miHash = (int)in.U32();

@@ -110,6 +110,7 @@ public:
     int64_t GetFileOffset( int ii ) const { return maFiles[ ii ].mi64Offset; }
     int GetFileFlags1( int ii ) const { return maFiles[ ii ].miFlags1; }
     int GetFileFlags2( int ii ) const { return maFiles[ ii ].miFlags2; }
+    unsigned int GetFileHash( int ii ) const { return (unsigned int)maFiles[ ii ].miHash; }
     const char* GetArkData() const { return maArkData.data(); }
     bool IsArkDataPinned() const;
     uint64_t GetArkDataSize() const { return maArkData.size(); }

@@ -21,7 +21,9 @@ template < typename F > int Guard( F&& f )
 {
     try
     {
-        return (int)f();
+        const int rc = (int)f();
+        if( rc != 0 ) t_err = "eError " + std::to_string( rc ); // a refusal leaves its ordinal behind, as an exception leaves its text
+        return rc;
     }
     catch( const std::exception& e )
     {
@@ -144,6 +146,7 @@ uint32_t modhost_ark_file_size( const void* ark, int i ) { return A( ark )->GetF
 int64_t modhost_ark_file_offset( const void* ark, int i ) { return A( ark )->GetFileOffset( i ); }
 int modhost_ark_file_flags1( const void* ark, int i ) { return A( ark )->GetFileFlags1( i ); }
 int modhost_ark_file_flags2( const void* ark, int i ) { return A( ark )->GetFileFlags2( i ); }
+uint32_t modhost_ark_file_hash( const void* ark, int i ) { return A( ark )->GetFileHash( i ); }
 uint64_t modhost_ark_data_size( const void* ark ) { return A( ark )->GetArkDataSize(); }
 const uint8_t* modhost_ark_data( const void* ark ) { return reinterpret_cast< const uint8_t* >( A( ark )->GetArkData() ); }
 int modhost_ark_data_pinned( const void* ark ) { return A( ark )->IsArkDataPinned() ? 1 : 0; }

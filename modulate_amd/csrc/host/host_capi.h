@@ -2,7 +2,7 @@
 // Python test-suite and bench scripts can drive it with ctypes.  These are test/bench hooks of
 // libmodulate_host.so; the drop-in boundary itself is include/modgpu.h.
 // All functions return an eError ordinal (0 = eError_NoError) unless noted; -1 = C++ exception
-// (text in modhost_last_error()).
+// (text in modhost_last_error(); a non-zero ordinal leaves "eError <n>" there).
 #pragma once
 #include <stdint.h>
 
@@ -50,6 +50,7 @@ uint32_t modhost_ark_file_size(const void *ark, int i);
 int64_t modhost_ark_file_offset(const void *ark, int i);
 int modhost_ark_file_flags1(const void *ark, int i);
 int modhost_ark_file_flags2(const void *ark, int i);
+uint32_t modhost_ark_file_hash(const void *ark, int i);                                   /* the entry's hash field as loaded */
 uint64_t modhost_ark_data_size(const void *ark);
 const uint8_t *modhost_ark_data(const void *ark);
 int modhost_ark_data_pinned(const void *ark);                                             /* 1: the part buffer is page-locked */

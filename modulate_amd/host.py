@@ -44,6 +44,7 @@ HOOKS = {
     "modhost_ark_file_offset": (_i64, [_vp, _int]),
     "modhost_ark_file_flags1": (_int, [_vp, _int]),
     "modhost_ark_file_flags2": (_int, [_vp, _int]),
+    "modhost_ark_file_hash": (_u32, [_vp, _int]),
     "modhost_ark_data_size": (_u64, [_vp]),
     "modhost_ark_data": (_vp, [_vp]),
     "modhost_ark_data_pinned": (_int, [_vp]),
@@ -193,7 +194,8 @@ class Ark:
         L = lib()
         return [{"name": L.modhost_ark_file_name(self.h, i).decode("latin-1"), "size": L.modhost_ark_file_size(self.h, i),
                  "offset": L.modhost_ark_file_offset(self.h, i), "flags1": L.modhost_ark_file_flags1(self.h, i),
-                 "flags2": L.modhost_ark_file_flags2(self.h, i)} for i in range(self.num_files)]
+                 "flags2": L.modhost_ark_file_flags2(self.h, i), "hash": L.modhost_ark_file_hash(self.h, i)}
+                for i in range(self.num_files)]
 
     @property
     def data_pinned(self):

@@ -13,9 +13,9 @@
  * Parity status: PINNED for rows a1-a3 (the arithmetic) -- validated against the
  * reference object compiled from /root/reference (oracle/_ref, see oracle/Makefile)
  * and against the golden vectors that build emitted into tests/golden/.
- * Rows a4-a6 (framing) are "parity unpinned": the reference has no tests and its
- * Win32 translation units cannot be built here; the framing below is
- * a restatement of the cited lines only.
+ * Rows a4-a6 (framing): the framing below is a restatement of the cited lines; the
+ * reference's own CArk.cpp, compiled behind oracle/ref_host_main.cpp, pins it through
+ * tests/test_ref_host_parity.py (headers the reference wrote and read).
  */
 #ifndef MODULATE_ORACLE_CYCLE_H
 #define MODULATE_ORACLE_CYCLE_H

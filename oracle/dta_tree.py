@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE -- pure-Python restatement of the binary DTA tree format, used to check
-modulate_amd/csrc/host/CDtaFile.cpp.  PARITY UNPINNED (no reference tests; CDtaFile.cpp needs Win32
-headers through Utils.h).  Follows Modulate/CDtaFile.cpp:57-100, 393-509 (load) and
+modulate_amd/csrc/host/CDtaFile.cpp.  PARITY PINNED for Load -> Save since tests/test_ref_host_parity.py (the
+reference's own CDtaFile.cpp on the DTA cases of tests/golden/host_golden.json).  Follows Modulate/CDtaFile.cpp:57-100, 393-509 (load) and
 :362-391, 1302-1326 + CDtaFile.h:262-284 (save).
 
 A node is a tuple:  ("tree", type(16|17), node_id, [children])  |  ("int", type, value)

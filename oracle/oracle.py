@@ -4,6 +4,8 @@
   (oracle/cycle_oracle.c).
 * ``_ref/libref_cycler.so`` -- the reference's own CEncryptionCycler.cpp compiled where it
   lies (oracle/Makefile target ``ref``); optional, absent if it was never built.
+* ``_ref/ref_host`` -- the reference's own host classes (CArk, CDtaFile, ...) behind
+  oracle/ref_host_main.cpp, a program started as a child process; optional in the same way.
 
 Nothing here reads /root/reference at run time.
 """
@@ -16,6 +18,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ORACLE_SO = os.path.join(_HERE, "liboracle_cycle.so")
 _REF_SO = os.path.join(_HERE, "_ref", "libref_cycler.so")
+_REF_HOST = os.path.join(_HERE, "_ref", "ref_host")
 
 MAGIC_PS3 = 0xC64EED30  # Settings.h:16
 MAGIC_PS4 = 0x6F303F55  # Settings.h:17
@@ -30,6 +33,7 @@ __all__ = [
     "MAGIC_PS3", "MAGIC_PS4", "KEY_PS3", "KEY_PS4", "LCG_M", "LCG_A", "PERIOD", "FNV_OFFSET",
     "build", "as_int32", "cycle_key", "cycle", "cycle_serial64", "cycle_at", "state_at",
     "keystream_at", "keystream", "fnv1a64", "hdr_decrypt", "hdr_encrypt", "have_ref", "ref_cycle",
+    "have_ref_host", "ref_host",
     "pure_cycle_key", "pure_cycle", "splitmix_bytes",
 ]
 
@@ -152,6 +156,18 @@ def ref_cycle(buf, key):
     assert buf.size <= 0xFFFFFFFF
     _ref.ref_cycle(_ptr(buf), buf.size, as_int32(key))
     return buf
+
+
+def have_ref_host():
+    return os.path.exists(_REF_HOST)
+
+
+def ref_host(action, *args, switches=(), cwd=None, timeout=120):
+    """One action of oracle/ref_host_main.cpp in a child process -> (exit status, stdout bytes).
+    The status is the reference's eError ordinal, or negative (the signal) where the reference died."""
+    r = subprocess.run([_REF_HOST, *switches, action, *[os.fspath(a) for a in args]], cwd=cwd, timeout=timeout,
+                       stdout=subprocess.PIPE, stderr=subprocess.DEVNULL)
+    return r.returncode, r.stdout
 
 
 # --- pure-Python loops, small cases only (a third, independent statement) -------------

@@ -1,6 +1,6 @@
 """CPU-only checks of the C++ host mirror (libmodulate_host.so): it loads, the CArk header writer
 and part-split bookkeeping agree with the independent Python restatement (oracle/ark_header.py;
-parity unpinned -- the reference has no fixtures for this format), CEncryptionCycler::Cycle keeps
+both are held to the compiled reference itself in tests/test_ref_host_parity.py), CEncryptionCycler::Cycle keeps
 the reference's "cannot fail" contract on a GPU-less host (BASELINE config 1) unless
 MODGPU_REQUIRE_GPU forbids it, and the reference's deterministic quirks are the default with their
 fixes behind one switch."""
@@ -395,7 +395,7 @@ def test_cli_usage_and_unknown_flag():
     assert r.returncode != 0 and "ERROR: Failed to open file" in r.stdout
 
 
-# ---- binary DTA tree (parity unpinned) -------------------------------------
+# ---- binary DTA tree (parity: test_ref_host_parity.py) -------------------------------------
 def test_dta_roundtrip_matches_restatement(host):
     from oracle import dta_tree as DT
     rng = np.random.default_rng(12)

@@ -163,6 +163,48 @@ def test_config4_pack_with_part_cipher(host, oracle, modgpu, tmp_path, header_cw
     a.close(), b.close()
 
 
+@pytest.mark.parametrize("case", ["n57_parts3_ps3", "n57_parts3_ps4", "n1000_parts3_ps3", "n1000_parts3_ps4"])
+def test_reference_written_headers_load_and_resave_on_the_gpu(host, modgpu, tmp_path, monkeypatch, case):
+    """Load -> LoadArkData -> SaveArk of the 57- and 1000-file cases of tests/golden/host_golden.json (recorded from the
+    REFERENCE's own compiled CArk.cpp, oracle/make_host_golden.py): the header's decryption and its encryption both go through
+    CEncryptionCycler::Cycle, which in this process is the kernel or an error, and the bytes and the table that come out must
+    be the reference's.  Reads the golden file and nothing of the reference."""
+    import json
+    from oracle import make_host_golden as MG
+    with open(MG.GOLDEN) as f:
+        c = json.load(f)["cases"][case]
+    recipe, ref = c["recipe"], c["ref"]
+    work = str(tmp_path)
+    monkeypatch.chdir(work)  # SaveArk wants the header in the working directory, and part paths resolve against it
+    T = MG.materialise(recipe, work)
+    hdr = T["header_name"]
+    os.mkdir("out")
+    host.select_platform(recipe["ps4"])
+    try:
+        before = modgpu.path_stats()
+        a = host.Ark().load(hdr)
+        loaded = modgpu.path_stats()
+        assert modgpu.last_launch()["kernel"].startswith("modgpu_cycle") and loaded["gpu_launches"] > before["gpu_launches"]
+        assert loaded["gpu_bytes"] - before["gpu_bytes"] == os.path.getsize(hdr) - 4  # the seed header's body went through a kernel
+        table = [(f["name"].encode("latin-1"), f["size"], f["offset"], f["flags1"], f["flags2"], f["hash"]) for f in a.files()]
+        assert {"status": 0, **MG.table_record(zip(a.ark_sizes(), [p.encode("latin-1") for p in a.ark_paths()]), table)} == ref["dump"]
+        a.load_data()
+        a.save("out/", hdr)
+        a.close()
+        after = modgpu.path_stats()
+        assert modgpu.last_launch()["kernel"].startswith("modgpu_cycle") and after["gpu_launches"] > loaded["gpu_launches"]
+        assert after["gpu_bytes"] - loaded["gpu_bytes"] == os.path.getsize("out/" + hdr) - 4  # ... and so did the saved one's
+        assert after["scalar_calls"] == before["scalar_calls"] == 0
+        got = MG.saved_record("out", hdr)
+        assert got["header"] == ref["resave"]["header"] and got["parts"] == ref["resave"]["parts"]
+        b = host.Ark().load("out/" + hdr)
+        table = [(f["name"].encode("latin-1"), f["size"], f["offset"], f["flags1"], f["flags2"], f["hash"]) for f in b.files()]
+        assert {"status": 0, **MG.table_record(zip(b.ark_sizes(), [p.encode("latin-1") for p in b.ark_paths()]), table)} == ref["resave"]["table"]
+        b.close()
+    finally:
+        host.select_platform(True)
+
+
 def test_load_rejects_corrupt_headers(host, oracle, tmp_path):
     host.select_platform(True)
     names, sizes, data = synth(50, 2)
