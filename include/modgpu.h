@@ -338,6 +338,54 @@ int modgpu_rekey_table_device(const modgpu_rekey_table_entry_t *dev_entries, uin
  * a destination meeting another entry's source or destination).  No device is touched. */
 int modgpu_rekey_table_validate(const modgpu_rekey_table_entry_t *host_entries, uint64_t n_entries);
 
+/* ---- a TABLE of rekey entries MOVED with memmove rules: compacting a resident part in one pass, five launches --------------------
+ * For every entry i of a modgpu_rekey_table_entry_t table in device memory, used as it stands (56 bytes, flags and reserved 0):
+ *     dst_i[j] = SRC0_i[j] ^ ks(key_from_i)[off_from_i + j] ^ ks(key_to_i)[off_to_i + j],   j = 0 .. n_i-1
+ * where SRC0 is device memory as it was when the call started on the device: every source byte of every entry is read before any
+ * entry overwrites it, and nothing outside the entries' [dst, dst+n) is written.  A destination may meet ANY entry's source, its own
+ * or another's: removing or resizing k files of a resident part leaves k surviving segments, each sliding by its own distance onto
+ * the previous one's source, and this call moves them all in one pass over HBM.  Per entry everything modgpu_rekey_table_device says
+ * holds: any byte alignment on either side, each offset with its own phase, 64-bit offsets, n == 0 is skipped, a key == 0 mod 2^31-1
+ * is the identity keystream, the same reduced key at offsets equal mod 2^31-2 copies -- every degenerate key pair in the same single
+ * pass (modgpu_rekey_move_device takes two passes when exactly one key is the identity).
+ * WHICH TABLES ARE TAKEN.  After dropping empty entries the table must be DOWNWARD -- for every i: dst_i <= src_i,
+ * src_i + n_i <= src_{i+1}, dst_i + n_i <= dst_{i+1} -- or UPWARD: the same listing order and the same two disjointness conditions
+ * with dst_i >= src_i.  So the entries are listed by rising address, sources are pairwise disjoint, destinations are pairwise
+ * disjoint, all entries slide the same way (dst == src is allowed in either kind; the first entry with dst != src says which kind
+ * the table is).  DESIGN.md 4.15 has the argument why one pass then suffices.
+ * total_bytes is the caller's upper bound on the sum of the n_i: the table is read when the call runs on the device, so the host
+ * cannot know the chunk count; the workspace is sized for total_bytes / 64 KiB + 2 * n_entries chunks (a 32-bit "loaded" flag and an
+ * 8-byte window per chunk) and 32 bytes of scratch per entry for the ragged ends (the < 16 bytes before and after each body).
+ * modgpu_rekey_move_table_workspace_bytes returns 0 for no entries, for more than MODGPU_TABLE_MAX_ENTRIES, and for a total_bytes
+ * whose chunks pass 2^31.
+ * The contract is modgpu_rekey_table_device's, word for word where it applies: asynchronous on `hip_stream`, `device` -1 = the current
+ * device, allocation-free, capturable into a hipGraph; THE TABLE IS READ WHEN THE CALL RUNS ON THE DEVICE, so a replayed graph picks
+ * up entries rewritten between replays and starts from a clean workspace, which the first launch resets in stream order; the
+ * WORKSPACE is the caller's, device memory of `device`, 8-byte aligned; two calls on one workspace must not overlap in time.  The
+ * call draws its tickets from the workspace: it never touches the library's ring and has no degraded route.  FIVE kernel launches
+ * whatever n_entries is (plan, finish, window, move, place; path_stats().gpu_launches counts them), no memset and no copy;
+ * modgpu_last_launch reports the move launch as variant 15 (`bytes` = 0, as for 8).  Page-locked host memory anywhere in a table
+ * is not supported: the ordering inside the pass is for device memory.
+ * Checks, in three tiers:
+ *   1. on the host, before anything is queued -- MODGPU_ERR_INVALID: the table call's tier 1, with this call's workspace size.
+ *   2. on the device, by the plan: an entry with a NULL dst or src and n > 0, nonzero flags or reserved, an entry of 1 TiB or more,
+ *      more chunks than the workspace was sized for, or AN ENTRY THAT BREAKS THE DIRECTION AND ORDER RULE above (each non-empty
+ *      entry is compared with the non-empty entry before it).  Any of these makes the WHOLE CALL WRITE NOTHING, and the status names
+ *      the lowest such entry.
+ *   3. modgpu_rekey_move_table_validate checks a host copy against tiers 1 and 2 in O(n) and names an entry at fault in
+ *      modgpu_last_error().  No device is touched.
+ * No wait inside the pass is unbounded: a workgroup that has waited 2 s for another one gives up, records the chunk, stores nothing
+ * more, and the call ends.  That is a bug in the library or a device in trouble, never a property of the arguments.
+ * The workspace starts with the table call's header, so modgpu_table_status reads it unchanged.  modgpu_rekey_move_table_status
+ * (synchronous, read after the caller has synchronised) reports one thing more: MODGPU_OK with both outputs UINT64_MAX;
+ * MODGPU_ERR_INVALID with *first_bad_entry = the lowest entry the device refused (the call wrote nothing); MODGPU_ERR_HIP with
+ * *stalled_chunk = the global 64 KiB chunk whose wait ran out (the contents of the destinations are then unspecified). */
+uint64_t modgpu_rekey_move_table_workspace_bytes(uint64_t n_entries, uint64_t total_bytes);
+int modgpu_rekey_move_table_device(const modgpu_rekey_table_entry_t *dev_entries, uint64_t n_entries, uint64_t total_bytes,
+                                   void *dev_workspace, uint64_t workspace_bytes, int device, void *hip_stream);
+int modgpu_rekey_move_table_validate(const modgpu_rekey_table_entry_t *host_entries, uint64_t n_entries);
+int modgpu_rekey_move_table_status(const void *dev_workspace, int device, uint64_t *first_bad_entry, uint64_t *stalled_chunk);
+
 /* ---- VERIFY: is this buffer what the cipher would have produced from that one?  One read-only pass, two numbers -------------------
  * The result of one entry, in device memory.  The layout is pinned (32 bytes, 8-byte aligned). */
 typedef struct modgpu_verify_result {

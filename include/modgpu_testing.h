@@ -78,7 +78,9 @@ typedef struct modgpu_launch_info {
                              11 = the verify table call's stream kernel (modgpu_verify_table_device; `bytes` = 0, as for 8),
                              12 = the rekey verify call's two-keystream compare kernel (modgpu_verify_rekey_device / _batch_device;
                                   `bytes` = all entries of the launch); its entries with coinciding streams are a variant 10 launch,
-                             13 = the rekey verify table call's stream kernel (modgpu_verify_rekey_table_device; `bytes` = 0, as for 8) */
+                             13 = the rekey verify table call's stream kernel (modgpu_verify_rekey_table_device; `bytes` = 0, as for 8),
+                             14 = the body launch of modgpu_rekey_move_device (the rekey kernel's move loop; `bytes` = n),
+                             15 = the move launch of modgpu_rekey_move_table_device (`bytes` = 0, as for 8) */
     uint32_t grid;        /* workgroups launched                                                  */
     uint32_t block;       /* threads per workgroup                                                */
     uint32_t chunk_bytes; /* bytes one workgroup trip covers                                      */
@@ -95,7 +97,8 @@ typedef struct modgpu_launch_info {
                                 modgpu_verify_kernel_source_hash() for variant 10,
                                 modgpu_verify_table_kernel_source_hash() for variant 11,
                                 modgpu_rekey_verify_kernel_source_hash() for variant 12,
-                                modgpu_rekey_verify_table_kernel_source_hash() for variant 13; static storage */
+                                modgpu_rekey_verify_table_kernel_source_hash() for variant 13,
+                                modgpu_rekey_move_table_kernel_source_hash() for variant 15; static storage */
 } modgpu_launch_info_t;
 int modgpu_last_launch(modgpu_launch_info_t *out);
 
@@ -201,6 +204,9 @@ const char *modgpu_keep_kernel_source_hash(void);
  * cycle_rekey_table_kernel.h, cycle_verify_table_kernel.h, cycle_table_kernel.h, cycle_verify_kernel.h, cycle_rekey_impl.h,
  * cycle_kernel_impl.h, cycle_kernel.h, lcg.h). */
 const char *modgpu_rekey_verify_table_kernel_source_hash(void);
+/* The same for the rekey move table kernels' TU (cycle_rekey_move_table_kernel.hip, cycle_rekey_move_table_kernel.h,
+ * cycle_rekey_table_kernel.h, cycle_table_kernel.h, cycle_rekey_impl.h, cycle_kernel_impl.h, cycle_kernel.h, lcg.h). */
+const char *modgpu_rekey_move_table_kernel_source_hash(void);
 /* What a single in-place device buffer of `bytes` bytes is launched with: returns 1 if it takes the keep kernel (0: the main
  * work-queue kernel, or a smaller shape), and the cache policy it would carry -- of every *mask + 1 chunks of 64 KiB, counted by
  * absolute address, the first *run are stored so that they stay in the Infinity Cache.  Either pointer may be NULL. */
@@ -237,6 +243,11 @@ void modgpu_debug_set_rekey_table_grid(uint32_t grid);
  * still capped at what the device holds at once.  Parity tests: a grid of 4 over 40 chunks makes every workgroup draw many tickets
  * and wait for its neighbours. */
 void modgpu_debug_set_move_grid(uint32_t grid);
+
+/* modgpu_rekey_move_table_device's move launch: `grid` workgroups (1..4096), 0 = the shipped grid (one workgroup per CU).  A forced
+ * value is still capped at what the device holds at once.  Parity tests: a grid of 4 makes every workgroup draw many tickets and
+ * wait across entries. */
+void modgpu_debug_set_move_table_grid(uint32_t grid);
 
 /* The verify call's compare launch: at most `grid` workgroups (1..4096), 0 or less = the shipped grid (one workgroup per CU on
  * every CU; DESIGN.md 4.10 has the A/B against the out-of-place kernel's 25 per 32 CUs).  The kernel has one chunk assignment, the

@@ -17,6 +17,8 @@ from .capi import (  # noqa: F401
     cycle_device_to, cycle_batch_device_to, time_cycle_device_to, to_kernel_source_hash, debug_set_to_form, TO_FORMS,
     rekey_device_to, rekey_batch_device_to, time_rekey_device_to, rekey_kernel_source_hash, debug_set_rekey_form, REKEY_FORMS,
     rekey_move_device, move_workspace_bytes, move_status, debug_set_move_grid,
+    rekey_move_table_device, rekey_move_table_workspace_bytes, rekey_move_table_validate, rekey_move_table_status, compaction_table,
+    rekey_move_table_kernel_source_hash, debug_set_move_table_grid,
     cycle_table_device, time_cycle_table_device, table, table_workspace_bytes, table_status, table_validate, table_kernel_source_hash,
     debug_set_table_grid, TableEntry, TABLE_DTYPE,
     rekey_table_device, time_rekey_table_device, rekey_table, rekey_table_workspace_bytes, rekey_table_validate,

@@ -81,6 +81,10 @@ EXPORTS = {
     "modgpu_rekey_table_workspace_bytes": (_u64, [_u64]),
     "modgpu_rekey_table_device": (_int, [_vp, _u64, _vp, _u64, _int, _vp]),
     "modgpu_rekey_table_validate": (_int, [_vp, _u64]),
+    "modgpu_rekey_move_table_workspace_bytes": (_u64, [_u64, _u64]),
+    "modgpu_rekey_move_table_device": (_int, [_vp, _u64, _u64, _vp, _u64, _int, _vp]),
+    "modgpu_rekey_move_table_validate": (_int, [_vp, _u64]),
+    "modgpu_rekey_move_table_status": (_int, [_vp, _int, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     "modgpu_verify_device": (_int, [_vp, _vp, _u64, _i32, _u64, _vp, _int, _vp]),
     "modgpu_verify_batch_device": (_int, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64), ctypes.POINTER(_u64), _int, _i32,
                                           _vp, _int, _vp]),
@@ -183,6 +187,7 @@ TESTING_EXPORTS = {
     "modgpu_keep_kernel_source_hash": (ctypes.c_char_p, []),
     "modgpu_time_verify_rekey_table_device": (_int, [_vp, _u64, _vp, _vp, _u64, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
     "modgpu_rekey_verify_table_kernel_source_hash": (ctypes.c_char_p, []),
+    "modgpu_rekey_move_table_kernel_source_hash": (ctypes.c_char_p, []),
     "modgpu_keep_policy": (_int, [_u64, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
 }
 # include/modgpu_testing.h, modgpu_debug_* group: ONLY in libmodgpu_testing.so
@@ -207,6 +212,7 @@ DEBUG_EXPORTS = {
     "modgpu_debug_set_table_grid": (None, [ctypes.c_uint32]),
     "modgpu_debug_set_rekey_table_grid": (None, [ctypes.c_uint32]),
     "modgpu_debug_set_move_grid": (None, [ctypes.c_uint32]),
+    "modgpu_debug_set_move_table_grid": (None, [ctypes.c_uint32]),
     "modgpu_debug_set_verify_form": (None, [_int]),
     "modgpu_debug_set_verify_table_grid": (None, [ctypes.c_uint32]),
     "modgpu_debug_set_rekey_verify_table_grid": (None, [ctypes.c_uint32]),
@@ -930,6 +936,108 @@ def debug_set_rekey_table_grid(grid=0):
     _debug_lib().modgpu_debug_set_rekey_table_grid(grid)
 
 
+def rekey_move_table_workspace_bytes(n_entries, total_bytes):
+    """bytes of device workspace a rekey move table call needs for n_entries entries of at most total_bytes bytes together (0 for no
+    entries, above the limit, or a total beyond 2^31 chunks)"""
+    return lib().modgpu_rekey_move_table_workspace_bytes(n_entries, total_bytes)
+
+
+def rekey_move_table_validate(entries):
+    """the pointer / flags / direction / order rules of rekey_move_table_device over a host table (REKEY_TABLE_DTYPE array); raises
+    ModGpuError naming an entry at fault"""
+    t = np.ascontiguousarray(entries, dtype=REKEY_TABLE_DTYPE)
+    _check(lib().modgpu_rekey_move_table_validate(_vp(t.ctypes.data if t.size else 0), t.size))
+
+
+def rekey_move_table_status(workspace, device=-1):
+    """(first_bad_entry, stalled_chunk) of the last rekey_move_table_device on `workspace`, each None when it does not apply: (None,
+    None) if the call ran clean, (i, None) if the device refused entry i (the call wrote nothing), (None, c) if the wait of chunk c
+    ran out (the destinations are then unspecified).  Synchronise the call's stream first."""
+    bad, stalled = _u64(0), _u64(0)
+    rc = lib().modgpu_rekey_move_table_status(_vp(_dev_addr(workspace)), device, ctypes.byref(bad), ctypes.byref(stalled))
+    none = (1 << 64) - 1
+    if rc == 1 and bad.value != none:
+        return int(bad.value), None
+    if rc == 3 and stalled.value != none:
+        return None, int(stalled.value)
+    _check(rc)
+    return None, None
+
+
+def rekey_move_table_device(entries, total_bytes=None, workspace=None, device=-1, stream=None, check=True, *, n=None):
+    """Moves and rekeys a TABLE of entries with memmove rules -- dst_i[j] = SRC0_i[j] ^ ks(key_from_i)[off_from_i + j] ^
+    ks(key_to_i)[off_to_i + j], every source byte of every entry read before any entry overwrites it -- in one pass, five launches
+    whatever its length.  The table must be downward or upward (include/modgpu.h).  `entries` is a host table (a REKEY_TABLE_DTYPE
+    array: uploaded, and checked with rekey_move_table_validate first unless check=False; total_bytes then defaults to the sum of its
+    sizes) or a table already in device memory (a DeviceBuffer or an address; then n, the entry count, and total_bytes, an upper
+    bound on the sum of the sizes, are needed).  `workspace` is a DeviceBuffer or address of at least
+    rekey_move_table_workspace_bytes(n, total_bytes) bytes; None makes one.  When this function made a buffer itself it waits for the
+    call before freeing it and raises ModGpuError if the device refused an entry or the pass gave up; otherwise the call is
+    asynchronous on `stream` and rekey_move_table_status(workspace) tells the outcome after a synchronise."""
+    own = []
+    try:
+        if isinstance(entries, np.ndarray):
+            t = np.ascontiguousarray(entries, dtype=REKEY_TABLE_DTYPE)
+            n = t.size
+            if check:
+                rekey_move_table_validate(t)
+            if n == 0:
+                return
+            if total_bytes is None:
+                total_bytes = int(t["n"].sum(dtype=np.uint64))
+            buf = DeviceBuffer(t.nbytes, device)
+            own.append(buf)
+            buf.upload(t.view(np.uint8))
+            addr = buf.ptr
+        else:
+            if n is None or total_bytes is None:
+                raise TypeError("n (the entry count) and total_bytes are needed for a table in device memory")
+            addr = _dev_addr(entries)
+        if workspace is None and n:
+            workspace = DeviceBuffer(rekey_move_table_workspace_bytes(n, total_bytes), device)
+            own.append(workspace)
+        ws = _dev_addr(workspace) if workspace is not None else 0
+        ws_bytes = workspace.nbytes if isinstance(workspace, DeviceBuffer) else rekey_move_table_workspace_bytes(n, total_bytes)
+        _check(lib().modgpu_rekey_move_table_device(_vp(addr), n, total_bytes, _vp(ws), ws_bytes, device, _vp(stream or 0)))
+        if own:
+            _check(lib().modgpu_sync(device, _vp(stream or 0)))
+            bad, stalled = rekey_move_table_status(ws, device)
+            if bad is not None:
+                raise ModGpuError(1, f"the device refused move table entry {bad}; nothing was written")
+            if stalled is not None:
+                raise ModGpuError(3, f"the move table pass gave up waiting at chunk {stalled}")
+    finally:
+        for b in own:
+            b.free()
+
+
+def compaction_table(base_ptr, keep, key, part_off=0):
+    """The downward table that compacts a resident part: `keep` is a rising list of (offset, n) ranges of the part at device address
+    base_ptr that survive; the result (REKEY_TABLE_DTYPE) packs them end to end from the first range's offset, under one key, with
+    off_from = part_off + offset and off_to = part_off + the new offset."""
+    keep = [(int(o), int(n)) for o, n in keep]
+    t = rekey_table(len(keep))
+    at = keep[0][0] if keep else 0
+    for i, (o, n) in enumerate(keep):
+        if o < at:
+            raise ValueError(f"kept range {i} starts at {o}, below the end of the one before it ({at})")
+        t[i]["dst"], t[i]["src"], t[i]["n"] = base_ptr + at, base_ptr + o, n
+        t[i]["off_from"], t[i]["off_to"] = part_off + o, part_off + at
+        t[i]["key_from"] = t[i]["key_to"] = as_int32(key)
+        at += n
+    return t
+
+
+def rekey_move_table_kernel_source_hash():
+    """identity of the rekey move table kernels' TU (cycle_rekey_move_table_kernel.hip and what it includes)"""
+    return lib().modgpu_rekey_move_table_kernel_source_hash().decode()
+
+
+def debug_set_move_table_grid(grid=0):
+    """Testing flavour: the grid of rekey_move_table_device's move launch (0 = shipped; capped at what the device holds at once)."""
+    _debug_lib().modgpu_debug_set_move_table_grid(grid)
+
+
 def verify_device(expect, src, key, stream_off=0, result=None, device=-1, stream=None, *, n=None):
     """Asynchronous VERIFY of n bytes at raw device addresses: counts the j with expect[j] != (src[j] ^ ks(key)[stream_off + j]) and
     finds the lowest, in one read-only pass; only the 32-byte result (device memory: a DeviceBuffer or an address) is written.
@@ -1321,6 +1429,17 @@ class DeviceBuffer:
         on the way (rekey_move_device; with the default keys a plain memmove)."""
         assert max(dst_offset, src_offset) + n <= self.nbytes
         rekey_move_device(self.ptr + dst_offset, self.ptr + src_offset, n, key_from, key_to, off_from, off_to, workspace, self.device, stream)
+
+    def compact(self, keep, key, part_off=0, workspace=None, stream=None):
+        """Packs the surviving ranges `keep` -- a rising list of (offset, n) -- of the part this buffer holds end to end from the
+        first range's offset, in one pass (compaction_table, rekey_move_table_device): each range slides down onto whatever lay
+        before it and is rekeyed from its old stream offset part_off + offset to its new one.  Returns the new length: the offset
+        just behind the last packed range."""
+        keep = [(int(o), int(n)) for o, n in keep]
+        assert all(o + n <= self.nbytes for o, n in keep)
+        t = compaction_table(self.ptr, keep, key, part_off)
+        rekey_move_table_device(t, None, workspace, self.device, stream)
+        return keep[0][0] + sum(n for _, n in keep) if keep else 0
 
     def sync(self, stream=None):
         _check(self._lib.modgpu_sync(self.device, _vp(stream or 0)))

@@ -295,6 +295,48 @@ def move_loop(k):
     return bad
 
 
+def table_move_loop(k):
+    """the move kernel of the rekey move table call (cycle_rekey_move_table_kernel.h): the rekey kernel's move loop per chunk of a table.
+    Per unrolled trip (2): the barrier at its top, a barrier behind the chunk's blocks, thread 0's poll of the flags of the chunk's
+    window, a barrier in front of the stores -- with the one behind each of the first two tickets, 8 s_barrier.  In front of the barrier
+    behind the blocks every wave waits, in an asm statement of its own, until the chunk's loads have returned: vmcnt(4) when the next
+    chunk's loads are 4 words, vmcnt(8) when they took the funnel's extra dwords -- one of each per trip, a uniform branch apart.  The
+    poll sleeps between reads and is bounded by the constant-rate clock; flags are read and written at agent scope (sc1) and NOTHING is
+    fenced.  Tickets are plain returning atomics: one per trip and the two that draw the first positions a barrier apart.  A chunk's
+    entry and its window come through scalar loads: the only vector loads besides the data are the flag reads and the lane's two
+    start-up table lookups."""
+    bad = []
+    counts = {m: len(code_lines(k.fn, m)) for m in ("s_barrier", "s_sleep", "s_memrealtime", "buffer_wbl2", "buffer_inv", "global_atomic_add", "global_atomic_cmpswap")}
+    if counts["s_barrier"] != 8:
+        bad.append("%s: %d s_barrier, expected 8 (2 x 3 in the loop, one behind each of the first two tickets)" % (k.name, counts["s_barrier"]))
+    if counts["s_sleep"] != 2 or counts["s_memrealtime"] != 4:
+        bad.append("%s: the poll is not a sleeping, clock-bounded one (%d s_sleep, %d s_memrealtime; expected 2 and 4)"
+                   % (k.name, counts["s_sleep"], counts["s_memrealtime"]))
+    if counts["buffer_wbl2"] or counts["buffer_inv"]:
+        bad.append("%s: a cache write-back or invalidate inside the kernel (the flags need no fence)" % k.name)
+    waits = [m for m in BLOCK.finditer(k.fn) if re.fullmatch(r"\s*s_waitcnt vmcnt\([1-9]\d*\)\s*", m.group(1))]
+    if sorted(m.group(1).strip() for m in waits) != ["s_waitcnt vmcnt(4)"] * 2 + ["s_waitcnt vmcnt(8)"] * 2:
+        bad.append("%s: the wait for the chunk's loads is not one `s_waitcnt vmcnt(4)` and one `s_waitcnt vmcnt(8)` per unrolled trip (found %s)"
+                   % (k.name, [m.group(1).strip() for m in waits]))
+    for m in waits:
+        upto = k.fn.find("s_barrier", m.end())
+        if upto < 0 or re.search(r"^\s+(buffer_store|global_store|global_load|global_atomic)", k.fn[m.end():upto], re.M):
+            bad.append("%s: a store or a flag access lies between the wait for the chunk's loads and the barrier behind it" % k.name)
+    vec = code_lines(k.fn, "(?:global|flat)_load")
+    flags = [ln for ln in vec if re.match(r"\s+global_load_dword v", ln) and ln.endswith(" sc1")]
+    if len(flags) != 4 or len(vec) - len(flags) > 2 or k.fn.count("s_load_dwordx16") < 2:
+        bad.append("%s: %d agent-scope flag reads (expected 4: first look + poll, per unrolled trip), %d other vector loads besides the data "
+                   "(at most the 2 start-up lookups), %d s_load_dwordx16 (the entry search is scalar)" % (k.name, len(flags), len(vec) - len(flags), k.fn.count("s_load_dwordx16")))
+    ups = [ln for ln in code_lines(k.fn, "global_store_dword v") if ln.endswith(" sc1") and " sc0" not in ln]
+    if len(ups) != 2 or len(code_lines(k.fn, "global_store")) != 2:
+        bad.append("%s: %d agent-scope dword stores among %d global stores, expected 2 and 2 (a flag per unrolled trip)" % (k.name, len(ups), len(code_lines(k.fn, "global_store"))))
+    fetches = code_lines(k.fn, "global_atomic_add")
+    if len(fetches) != 4 or not all(ln.endswith(" sc0") for ln in fetches) or counts["global_atomic_cmpswap"] != 2:
+        bad.append("%s: %d global_atomic_add (expected 4 returning ones: tickets 2 + 2) and %d global_atomic_cmpswap (expected 2: the status word)"
+                   % (k.name, len(fetches), counts["global_atomic_cmpswap"]))
+    return bad
+
+
 def block_count(k, family, expected, made_of):
     blocks = len(carry_blocks(k.fn))
     return ["%s: %d %s blocks, expected %d (%s)" % (k.name, blocks, family.a, expected, made_of)] if blocks != expected else []
@@ -574,6 +616,12 @@ TUS = (
     # table of rekey verify entries: the rules of both parents
     table_tu("cycle_rekey_verify_table_kernel.s", "the rekey verify table kernels' TU", "modgpu_cycle_rekey_verify_table", REKEY_PLANNING,
              [rekey_blocks, (block_count, TWO_KEYSTREAM, 8, TRIPS), loads_nt, (read_only_stream, "a rekey verify kernel", True), (result_atomics, 2), scalar_entry_search]),
+    # table of rekey entries moved with memmove rules: the rekey table call's planning kernels with a window and a place launch, and
+    # the rekey TU's move loop over the chunks of a table
+    TU("cycle_rekey_move_table_kernel.s", "the rekey move table kernels' TU",
+       tuple(Kind("modgpu_cycle_rekey_move_table_" + s, TABLE_HEAD + REKEY_PLANNING) for s in ("plan", "finish", "window", "place")) +
+       (Kind("modgpu_cycle_rekey_move_table_kernel", TABLE_HEAD + [rekey_blocks, (block_count, TWO_KEYSTREAM, 8, TRIPS), loads_nt, (stores, "nt sc1"), table_move_loop]),),
+       then=[(one_of_each,) + tuple("modgpu_cycle_rekey_move_table_" + s for s in ("plan", "finish", "window", "kernel", "place"))]),
 )
 OWNER = {kind.source: tu for tu in TUS for kind in tu.kinds}
 __doc__ = "check_isa.py " + " | ".join("<%s>" % tu.file for tu in TUS) + __doc__

@@ -1,0 +1,626 @@
+// cycle_rekey_move_table_kernel.hip -- a TABLE of rekey entries in device memory moved with memmove rules in one pass over HBM:
+// dst_i[j] = SRC0_i[j] ^ ks(key_from_i)[off_from_i + j] ^ ks(key_to_i)[off_to_i + j], SRC0 the memory as the call found it; a
+// destination may lie on top of any entry's source.  cycle_rekey_move_table_kernel.h has the rule for the tables taken and the five
+// launches.  The two-keystream block: cycle_rekey_impl.h; the jump tables and the single-state arithmetic: cycle_kernel_impl.h; both
+// included and not changed.
+//
+// Built from two shipped kernels, neither changed: the plan, the chunk grid (64 KiB chunks on absolute chunk-aligned DESTINATION
+// addresses, a cut first chunk per entry), the 16-ary chunk -> entry levels, the views and the identity keystream as the state 2^31-1
+// are the rekey table kernels' (cycle_rekey_table_kernel.hip); the order of a chunk's trip -- loads returned, barrier, flag up, poll,
+// barrier, stores -- and the tickets drawn one at a time are the move loop's of cycle_rekey_kernel.hip.
+//
+// Why a position waits for lower positions only.  Downward table, positions = global chunks in table order: a chunk's
+// destination starts at or below its own source, ends at or below its own source's end, and the sources of the chunks rise with the
+// position -- inside an entry because the chunks do, across entries because the rule lists the entries by rising source.  A later
+// chunk's source therefore starts where this chunk's source ends or above, which is at or above the end of this chunk's destination;
+// rounding that start down to a source dword cannot pass the 16-byte aligned destination address paired with it.  Upward: the mirror
+// image, walked from the last chunk down.  Positions are tickets only, so whoever holds a position is running, and the lowest
+// unfinished position is never blocked -- whether or not the whole grid is resident.
+#include <hip/hip_runtime.h>
+#include <cstdint>
+
+#include "cycle_rekey_impl.h"
+#include "cycle_rekey_move_table_kernel.h"
+
+#include <cstdio>
+
+namespace {
+
+// a^(b * 256^k) for the four bytes of an exponent < 2^32: a^e by three multiplies
+__constant__ lcg::Table<256> c_pow_b0 = lcg::make_pow_table<256>(1);
+__constant__ lcg::Table<256> c_pow_b1 = lcg::make_pow_table<256>(256);
+__constant__ lcg::Table<256> c_pow_b2 = lcg::make_pow_table<256>(65536);
+__constant__ lcg::Table<256> c_pow_b3 = lcg::make_pow_table<256>(1u << 24);
+
+__device__ __forceinline__ uint32_t pow_a(uint32_t e)
+{
+    uint32_t p = mulmod_canon(c_pow_b0.v[e & 255], c_pow_b1.v[(e >> 8) & 255]);
+    p = mulmod_canon(p, c_pow_b2.v[(e >> 16) & 255]);
+    return mulmod_canon(p, c_pow_b3.v[e >> 24]);
+}
+
+// x * y mod m for a state x (canonical, or 2^31-1 for the identity keystream) and a power y of a; 2^31-1 stays 2^31-1
+__device__ __forceinline__ uint32_t mulmod_keep(uint32_t x, uint32_t y)
+{
+    const uint32_t X = mul_fold(x, 2u * y);
+    return X >= 0x80000000u ? X - lcg::M : X;
+}
+
+__device__ __forceinline__ uint32_t state_at(uint32_t k, uint64_t e) { return k ? mulmod_canon(k, pow_a((uint32_t)(e % lcg::PERIOD))) : lcg::M; }
+
+__device__ __forceinline__ uint32_t key_res(int32_t key)
+{
+    const int64_t kr = (int64_t)key % (int64_t)lcg::M;
+    return (uint32_t)(kr < 0 ? kr + lcg::M : kr);
+}
+
+// reads of memory no launch of this TU writes while it runs: scalar loads when the address is uniform
+#if defined(__HIP_DEVICE_COMPILE__)
+#define MOVE_TABLE_CONST_AS __attribute__((address_space(4)))
+#else
+#define MOVE_TABLE_CONST_AS
+#endif
+template <class T> __device__ __forceinline__ const MOVE_TABLE_CONST_AS T *as_const(const T *p) { return (const MOVE_TABLE_CONST_AS T *)p; }
+struct Keys16 {
+    uint32_t v[16];
+};
+
+constexpr uint32_t kChunk = 65536; // the move kernel's chunk: 4 words x 1024 threads x 16 bytes
+constexpr uint32_t kNone = ~0u;
+constexpr uint32_t kWindowBlock = 256;
+
+__device__ __forceinline__ uint64_t at(const void *p) { return (uint64_t)reinterpret_cast<uintptr_t>(p); }
+
+} // namespace
+
+// ---- plan: one thread per entry ----------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kTableBlock) void modgpu_cycle_rekey_move_table_plan(MoveTableArgs a)
+{
+    __shared__ uint64_t sc[kTableBlock];
+    __shared__ uint32_t sl[kTableBlock];
+    __shared__ uint32_t sbad, sdown, sup;
+    const uint32_t tid = threadIdx.x;
+    const uint64_t i = (uint64_t)blockIdx.x * kTableBlock + tid;
+    if (blockIdx.x == 0 && tid == 0) {
+        a.hdr->ticket = 0;
+        a.hdr->stalled = 0;
+        a.hdr->first_bad = kTableNoBad;
+        a.hdr->total = 0;
+        a.hdr->up = 0;
+    }
+    for (uint64_t k = i; k < a.cap; k += (uint64_t)gridDim.x * kTableBlock) a.flags[k] = 0;
+    if (tid == 0) {
+        sbad = 0;
+        sdown = kNone;
+        sup = kNone;
+    }
+    uint64_t cnt = 0;
+    uint32_t bad = 0, full = 0, way = 0; // way: 1 dst < src, 2 dst > src
+    if (i < a.n) {
+        const RekeyTableEntry E = a.entries[i];
+        const uintptr_t d = reinterpret_cast<uintptr_t>(E.dst);
+        const uint64_t head = E.n < ((16 - (d & 15)) & 15) ? E.n : ((16 - (d & 15)) & 15);
+        const uint64_t words = (E.n - head) / 16;
+        const uint64_t tail = E.n - head - words * 16;
+        const uint32_t lead = (uint32_t)((d + head) & (kChunk - 1));
+        const uint64_t end = lead + words * 16;
+        cnt = words ? (end + kChunk - 1) / kChunk : 0;
+        bad = (E.n && (!E.dst || !E.src)) || E.flags != 0 || E.reserved != 0 || cnt > kTableMaxEntryChunks ? 1u : 0u;
+        if (bad) cnt = 0;
+        full = E.n != 0 ? 1u : 0u;
+        way = !full ? 0u : at(E.dst) < at(E.src) ? 1u : at(E.dst) > at(E.src) ? 2u : 0u;
+        const uint32_t kf = key_res(E.key_from), kt = key_res(E.key_to);
+        const uint64_t of = E.off_from % lcg::PERIOD + 1, ot = E.off_to % lcg::PERIOD + 1;
+        const uint64_t body = head + lcg::PERIOD - lead, after = head + (words * 16) % lcg::PERIOD;
+        MoveTablePlan P;
+        P.dst_origin = reinterpret_cast<uint8_t *>(reinterpret_cast<uintptr_t>(E.dst) + head - lead); // (as integers: a refused entry's pointer may be NULL)
+        P.src_origin = reinterpret_cast<const uint8_t *>(reinterpret_cast<uintptr_t>(E.src) + head - lead);
+        P.end = end;
+        P.start = 0;
+        P.lead = lead;
+        P.chunks = (uint32_t)cnt;
+        P.base_from = state_at(kf, of + body);
+        P.base_to = state_at(kt, ot + body);
+        P.bad = bad;
+        P.head_n = (uint32_t)head;
+        P.tail_n = (uint32_t)tail;
+        P.prev = 0;
+        a.plan[i] = P;
+        RekeyTableEdge X;
+        X.head[0] = state_at(kf, of);
+        X.head[1] = state_at(kt, ot);
+        X.tail[0] = state_at(kf, of + after);
+        X.tail[1] = state_at(kt, ot + after);
+        a.edge[i] = X;
+    }
+    sc[tid] = cnt;
+    sl[tid] = full ? tid + 1 : 0;
+    __syncthreads();
+    if (bad) atomicOr(&sbad, 1u);
+    if (way == 1) atomicMin(&sdown, (uint32_t)i);
+    if (way == 2) atomicMin(&sup, (uint32_t)i);
+    // inclusive scans over the 1024 entries (Hillis-Steele; every thread reaches every barrier): the sum of the chunk counts, and the
+    // last non-empty entry at or before each
+    for (uint32_t s = 1; s < kTableBlock; s <<= 1) {
+        const uint64_t v = tid >= s ? sc[tid - s] : 0;
+        const uint32_t l = tid >= s ? sl[tid - s] : 0;
+        __syncthreads();
+        sc[tid] += v;
+        sl[tid] = sl[tid] > l ? sl[tid] : l;
+        __syncthreads();
+    }
+    if (i < a.n) {
+        a.plan[i].start = sc[tid] - cnt;
+        a.plan[i].prev = tid ? sl[tid - 1] : 0;
+    }
+    if (tid == kTableBlock - 1) {
+        MoveTableBlk B;
+        B.chunks = sc[tid];
+        B.bad = sbad;
+        B.last = sl[tid] ? blockIdx.x * kTableBlock + sl[tid] : 0;
+        B.first_down = sdown;
+        B.first_up = sup;
+        B.pad[0] = B.pad[1] = 0;
+        a.blk[blockIdx.x] = B;
+    }
+}
+
+// ---- finish: global starts, the direction, the order rule, the status, the search levels, the ragged ends into scratch ----------------
+__global__ __launch_bounds__(kTableBlock) void modgpu_cycle_rekey_move_table_finish(MoveTableArgs a)
+{
+    __shared__ uint64_t r_before[kTableBlock], r_total[kTableBlock];
+    __shared__ uint32_t sbad, sprev, sdown, sup;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t b = blockIdx.x;
+    const uint64_t i = (uint64_t)b * kTableBlock + tid;
+    if (tid == 0) {
+        sbad = 0;
+        sprev = 0;
+        sdown = kNone;
+        sup = kNone;
+    }
+    uint64_t before = 0, total = 0;
+    uint32_t bad = 0, prev = 0, down = kNone, up = kNone;
+    for (uint32_t k = tid; k < a.n_blk; k += kTableBlock) {
+        const MoveTableBlk B = a.blk[k];
+        total += B.chunks;
+        before += k < b ? B.chunks : 0;
+        bad |= B.bad;
+        if (k < b && B.last > prev) prev = B.last;
+        down = B.first_down < down ? B.first_down : down;
+        up = B.first_up < up ? B.first_up : up;
+    }
+    r_before[tid] = before;
+    r_total[tid] = total;
+    __syncthreads();
+    if (bad) atomicOr(&sbad, 1u);
+    if (prev) atomicMax(&sprev, prev);
+    if (down != kNone) atomicMin(&sdown, down);
+    if (up != kNone) atomicMin(&sup, up);
+    for (uint32_t s = kTableBlock / 2; s > 0; s >>= 1) {
+        if (tid < s) {
+            r_before[tid] += r_before[tid + s];
+            r_total[tid] += r_total[tid + s];
+        }
+        __syncthreads();
+    }
+    before = r_before[0];
+    total = r_total[0];
+    const uint64_t room = a.cap < kTableMaxChunks ? a.cap : kTableMaxChunks;
+    const bool ok = sbad == 0 && total <= room;
+    const bool upward = sup < sdown; // the first entry with dst != src says which way the table slides
+    if (b == 0 && tid == 0) {
+        a.hdr->total = ok ? total : 0;
+        a.hdr->up = upward ? 1u : 0u;
+    }
+    if (i < a.n) {
+        const MoveTablePlan P = a.plan[i];
+        const uint64_t start = before + P.start;
+        // refused by the plan, or the first whose chunks pass what the workspace was sized for
+        if (!ok && (P.bad || start + P.chunks > room)) atomicMin((unsigned long long *)&a.hdr->first_bad, (unsigned long long)i);
+        // the direction and order rule: this entry against the non-empty entry before it
+        const RekeyTableEntry E = a.entries[i];
+        if (E.n != 0 && !P.bad) {
+            const uint64_t d = at(E.dst), s = at(E.src);
+            bool breaks = upward ? d < s : d > s;
+            const uint64_t q = P.prev ? (uint64_t)b * kTableBlock + P.prev - 1 : sprev ? (uint64_t)sprev - 1 : kTableNoBad;
+            if (q != kTableNoBad) {
+                const RekeyTableEntry Q = a.entries[q];
+                breaks = breaks || s < at(Q.src) || s - at(Q.src) < Q.n || d < at(Q.dst) || d - at(Q.dst) < Q.n;
+            }
+            if (breaks) atomicMin((unsigned long long *)&a.hdr->first_bad, (unsigned long long)i);
+        }
+        if (ok) {
+            a.plan[i].start = start;
+            for (uint32_t k = 0; k < kTableLevels; ++k)
+                if (k <= a.top && (i & ((1ull << (4 * k)) - 1)) == 0) a.level[k][i >> (4 * k)] = (uint32_t)start;
+            // the < 16 bytes in front of the body and behind it under both keystreams, into scratch: nothing outside the workspace
+            // has been written yet, so these are bytes of SRC0 whatever the later launches store on top of them
+            const RekeyTableEdge X = a.edge[i];
+            const uint8_t *sb = P.src_origin + P.lead;
+            uint8_t *out = a.scratch + i * kMoveTableScratch;
+            const uint64_t body = P.end - P.lead;
+#pragma unroll
+            for (uint32_t j = 0; j < 15; ++j) {
+                const uint32_t y = c_pow_b0.v[j];
+                if (j < P.head_n) out[j] = rekey_byte(sb[(int64_t)j - P.head_n], mulmod_keep(X.head[0], y), mulmod_keep(X.head[1], y));
+                if (j < P.tail_n) out[16 + j] = rekey_byte(sb[body + j], mulmod_keep(X.tail[0], y), mulmod_keep(X.tail[1], y));
+            }
+        }
+    }
+    // each level padded with ~0 to a whole line of 16 keys: the descent reads 16 at a time
+    if (ok && b == 0 && tid < 16)
+        for (uint32_t k = 0; k < kTableLevels; ++k)
+            if (k <= a.top && a.level_n[k] + tid < ((a.level_n[k] + 15) & ~15ull)) a.level[k][a.level_n[k] + tid] = ~0u;
+}
+
+// ---- window: one thread per chunk ------------------------------------------------------------------------------------------------
+namespace {
+// destination and source of global chunk g, the source rounded out to whole source dwords
+struct ChunkSpan {
+    uint64_t d0, d1, s0, s1;
+};
+__device__ ChunkSpan chunk_span(const MoveTableArgs &a, uint32_t g)
+{
+    uint32_t j = 0;
+    for (int k = (int)a.top; k >= 0; --k) {
+        const uint32_t *keys = a.level[k] + 16u * j;
+        uint32_t c = 0;
+#pragma unroll
+        for (int t = 0; t < 16; ++t) c += keys[t] <= g ? 1u : 0u;
+        j = 16u * j + c - 1u;
+    }
+    const MoveTablePlan P = a.plan[j];
+    const uint64_t c = g - P.start, off = c * kChunk, cut = c ? 0 : P.lead;
+    const uint64_t lim = P.end < off + kChunk ? P.end : off + kChunk;
+    ChunkSpan s;
+    s.d0 = at(P.dst_origin) + off + cut;
+    s.d1 = at(P.dst_origin) + lim;
+    s.s0 = (at(P.src_origin) + off + cut) & ~3ull;
+    s.s1 = (at(P.src_origin) + lim + 3) & ~3ull;
+    return s;
+}
+} // namespace
+
+__global__ __launch_bounds__(kWindowBlock) void modgpu_cycle_rekey_move_table_window(MoveTableArgs a)
+{
+    if (a.hdr->first_bad != kTableNoBad) return;
+    const uint64_t total = a.hdr->total;
+    const uint64_t g64 = (uint64_t)blockIdx.x * kWindowBlock + threadIdx.x;
+    if (g64 >= total) return;
+    const uint32_t g = (uint32_t)g64;
+    const bool up = a.hdr->up != 0;
+    const ChunkSpan me = chunk_span(a, g);
+    // the chunks on the side the table walks away from, this one included: their sources rise with the index
+    const uint32_t A = up ? g : 0u, B = up ? (uint32_t)total : g + 1u;
+    // lo: the first whose source ends above this destination's start; hi: the first whose source starts at or above its end
+    uint32_t lo = A, n = B - A;
+    while (n) {
+        const uint32_t h = n / 2;
+        if (chunk_span(a, lo + h).s1 <= me.d0) {
+            lo += h + 1;
+            n -= h + 1;
+        } else {
+            n = h;
+        }
+    }
+    uint32_t hi = lo;
+    n = B - lo;
+    while (n) {
+        const uint32_t h = n / 2;
+        if (chunk_span(a, hi + h).s0 < me.d1) {
+            hi += h + 1;
+            n -= h + 1;
+        } else {
+            n = h;
+        }
+    }
+    // without the chunk itself, and never a higher position: lower ones below g in a downward table, above g in an upward one
+    if (up) lo = lo > g + 1u ? lo : g + 1u;
+    else hi = hi < g ? hi : g;
+    MoveTableWin w;
+    w.lo = lo;
+    w.n = hi > lo ? hi - lo : 0u;
+    a.win[g] = w;
+}
+
+// ---- move ------------------------------------------------------------------------------------------------------------------------
+namespace {
+struct Raw {
+    u32x4 d;
+    uint32_t e; // the dword after d, read when the chunk's source is not dword-aligned
+};
+__device__ __forceinline__ u32x4 funnel(const Raw &w, uint32_t sh)
+{
+    u32x4 d;
+    d.x = __builtin_amdgcn_alignbyte(w.d.y, w.d.x, sh);
+    d.y = __builtin_amdgcn_alignbyte(w.d.z, w.d.y, sh);
+    d.z = __builtin_amdgcn_alignbyte(w.d.w, w.d.z, sh);
+    d.w = __builtin_amdgcn_alignbyte(w.e, w.d.w, sh);
+    return d;
+}
+} // namespace
+
+template <int U, int BLOCK>
+__global__ __launch_bounds__(BLOCK) MODGPU_REKEY_KEEP_OFF_THE_FIXED_TEMPORARIES void modgpu_cycle_rekey_move_table_kernel(MoveTableArgs a)
+{
+    static_assert(BLOCK % 256 == 0 && BLOCK <= 1024, "BLOCK is a whole number of 4096-byte tiles");
+    constexpr int SAUX = AUX_SC1 | AUX_NT;
+    constexpr int DEPTH = 1;
+    constexpr uint32_t CHUNK = (uint32_t)U * BLOCK * lcg::WORD;
+    static_assert(CHUNK == kChunk, "the plan lays entries on this chunk grid");
+    constexpr uint32_t SUB = BLOCK * lcg::WORD;
+    constexpr int NB = DEPTH + 1;
+    const uint32_t tid = threadIdx.x;
+    // 0 when the call was refused: nothing is loaded, flagged or stored
+    const uint32_t total = *as_const(&a.hdr->first_bad) == kTableNoBad ? (uint32_t)*as_const(&a.hdr->total) : 0u;
+    const uint32_t up = *as_const(&a.hdr->up);
+    __shared__ uint32_t q_next[2]; // ticket mailbox, two words used alternately
+    __shared__ uint32_t q_dead;    // the wait ran out: this workgroup stores nothing more (it still loads, flags and draws tickets)
+    uint32_t trip = 0;
+    const uint32_t voff = tid * lcg::WORD;
+    const uint32_t lane_mul = mulmod_canon(c_tile_lo.v[tid >> 8], c_lane_pow.v[tid & 255]);
+
+    struct View {
+        uint8_t *dst0;       // the entry's chunk origin
+        const uint8_t *src0; // the source byte that pairs with it
+        uint64_t end;
+        uint32_t lead, lo;     // global chunk lo is the entry's chunk 0
+        uint32_t lane_base[2]; // per lane: both keystreams' states of this lane's word 0 in the entry's chunk 0
+    };
+    // (an entry the search finds has a body, so its chunk count is that of `end`; the empty view's is 0.  One scalar register less per
+    // view than keeping the count: the kernel sits at its scalar budget)
+    auto in = [](uint32_t g, const View &v) { return g - v.lo < (uint32_t)((v.end + CHUNK - 1) / CHUNK); };
+    // the entry of chunk g < total: the last entry whose start is <= g, by a 16-ary descent of the levels
+    auto search = [&](uint32_t g, View &v) {
+        uint32_t j = 0;
+#pragma unroll 1
+        for (int k = (int)a.top; k >= 0; --k) {
+            const Keys16 keys = *as_const(reinterpret_cast<const Keys16 *>(a.level[k] + 16u * j));
+            uint32_t c = 0;
+#pragma unroll
+            for (int t = 0; t < 16; ++t) c += keys.v[t] <= g ? 1u : 0u;
+            j = 16u * j + c - 1u;
+        }
+        const MoveTablePlan P = *as_const(a.plan + j);
+        v.dst0 = P.dst_origin;
+        v.src0 = P.src_origin;
+        v.end = P.end;
+        v.lead = P.lead;
+        v.lo = (uint32_t)P.start;
+        v.lane_base[0] = mulmod_keep(P.base_from, lane_mul);
+        v.lane_base[1] = mulmod_keep(P.base_to, lane_mul);
+    };
+    struct Span {
+        uint64_t off;
+        uint32_t cut, bytes;
+    };
+    auto span = [&](uint32_t g, const View &v) {
+        Span s{0, 0, 0};
+        if (g >= total) return s; // past the last position: zero-size descriptors, loads give 0, stores drop
+        const uint32_t c = g - v.lo;
+        s.off = (uint64_t)c * CHUNK;
+        s.cut = c ? 0u : v.lead;
+        const uint64_t lim = v.end < s.off + CHUNK ? v.end : s.off + CHUNK;
+        s.bytes = (uint32_t)(lim - s.off - s.cut);
+        return s;
+    };
+    View vb[NB];
+#pragma unroll
+    for (int i = 0; i < NB; ++i) vb[i] = View{nullptr, nullptr, 0, 0, 0, {lcg::M, lcg::M}};
+    // the phase of chunk g's source in its dword: not 0 = its loads take the funnel's extra dwords
+    auto phase = [&](uint32_t g, const View &v) {
+        const Span s = span(g, v);
+        return (uint32_t)(uintptr_t)(v.src0 + s.off + s.cut) & 3u;
+    };
+    auto load = [&](Raw(&w)[U], View &v, const View &prev, uint32_t g) {
+        if (g < total && !in(g, v)) {
+            if (in(g, prev)) v = prev;
+            else search(g, v);
+        }
+        const Span s = span(g, v);
+        const uint8_t *p = v.src0 + s.off + s.cut;
+        const uint32_t sh = (uint32_t)(uintptr_t)p & 3u;
+        // the extra dword of the last word is the aligned dword that holds the body's last source byte: num_records grows by 4
+        const auto r = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(p - sh), 0, (int)(s.bytes + (sh && s.bytes ? 4u : 0u)), 0x00020000);
+#pragma unroll
+        for (int u = 0; u < U; ++u) w[u].d = __builtin_amdgcn_raw_buffer_load_b128(r, voff + u * SUB - s.cut, 0, AUX_NT);
+        if (sh) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) w[u].e = __builtin_amdgcn_raw_buffer_load_b32(r, voff + u * SUB - s.cut + lcg::WORD, 0, AUX_NT);
+        }
+    };
+    uint32_t pending = 0;
+    const uint32_t q_next_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)&q_next[0];
+    const uint32_t q_dead_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)&q_dead;
+    const uint32_t one = 1u;
+    auto chunk_at = [&](uint32_t p) { return up != 0 && p < total ? total - 1u - p : p; };
+    auto flag_up = [&](const uint32_t *f) { // thread 0; false: gave up
+        if (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return true;
+        const uint32_t t0 = (uint32_t)wall_clock64(); // (the bound fits 32 bits: the low word's difference is enough)
+        do {
+            __builtin_amdgcn_s_sleep(8);
+            if (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0) return true;
+        } while ((uint32_t)wall_clock64() - t0 < (uint32_t)kMoveTableStallTicks);
+        return false;
+    };
+    // chunk g; gn in view vn is the NEXT chunk, whose loads are in flight behind this one's
+    auto process_move = [&](Raw(&w)[U], const View &v, uint32_t g, const View &vn, uint32_t gn) {
+        // the chunks this one waits for: a scalar load (the window launch wrote it: constant while this launch runs) that returns
+        // while the blocks below run
+        MoveTableWin wn{0, 0};
+        if (g < total) wn = *as_const(a.win + g);
+        const uint32_t next_fun = phase(gn, vn);
+        const Span s = span(g, v);
+        const uint32_t sh = (uint32_t)(uintptr_t)(v.src0 + s.off + s.cut) & 3u;
+        auto r = __builtin_amdgcn_make_buffer_rsrc(v.dst0 + s.off + s.cut, 0, (int)s.bytes, 0x00020000);
+        const uint32_t c = g - v.lo;
+        uint32_t p = mulmod_canon(c_chunk_pow0<CHUNK>.v[c & 255], c_chunk_pow1<CHUNK>.v[(c >> 8) & 255]);
+        p = mulmod_canon(p, c_chunk_pow2<CHUNK>.v[(c >> 16) & 255]);
+        uint32_t sa = mulmod_keep(v.lane_base[0], p), sb = mulmod_keep(v.lane_base[1], p);
+        u32x4 d[U];
+        if (sh) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) d[u] = funnel(w[u], sh);
+        } else {
+#pragma unroll
+            for (int u = 0; u < U; ++u) d[u] = w[u].d;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            d[u] = rekey_word(d[u], sa, sb);
+            sa = mulmod_keep(sa, lcg::kTileLo.v[BLOCK / 256]);
+            sb = mulmod_keep(sb, lcg::kTileLo.v[BLOCK / 256]);
+        }
+        // every wave waits HERE until this chunk's loads have returned: the only vector-memory instructions younger than them are the
+        // next chunk's loads (U, twice that when it took the funnel).  The blocks above consumed the data, so the compiler's own waits
+        // say the same; this one does not depend on where an optimiser leaves them (check_isa.py pins it in front of the barrier).
+        if (next_fun) asm volatile("s_waitcnt vmcnt(%0)" : : "n"(2 * U) : "memory");
+        else asm volatile("s_waitcnt vmcnt(%0)" : : "n"(U) : "memory");
+        if (tid == 0)
+            asm volatile("ds_write_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : : "v"(q_next_lds + 4u * (trip & 1u)), "v"(pending) : "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier(); // every wave has this chunk's source in registers
+        if (tid == 0 && g < total) {
+            __hip_atomic_store(a.flags + g, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            uint32_t dead;
+            asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(dead) : "v"(q_dead_lds) : "memory");
+#pragma unroll 1
+            for (uint32_t i = 0; i < wn.n && dead == 0; ++i) {
+                if (!flag_up(a.flags + wn.lo + i)) {
+                    atomicCAS(&a.hdr->stalled, 0u, 1u + g);
+                    dead = 1;
+                    asm volatile("ds_write_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : : "v"(q_dead_lds), "v"(dead) : "memory");
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        uint32_t dd;
+        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(dd) : "v"(q_dead_lds) : "memory");
+        if (__builtin_amdgcn_readfirstlane((int)dd) == 0) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) __builtin_amdgcn_raw_buffer_store_b128(d[u], r, voff + u * SUB - s.cut, 0, SAUX);
+        }
+        ++trip;
+    };
+    auto take_published = [&]() {
+        uint32_t t;
+        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(t) : "v"(q_next_lds + 4u * ((trip - 1u) & 1u)) : "memory");
+        return (uint32_t)__builtin_amdgcn_readfirstlane((int)t); // tickets ARE positions
+    };
+
+    // the first DEPTH + 1 positions: one fetch EACH, a barrier apart, so that no workgroup starts with two consecutive positions
+    // (cycle_rekey_kernel.hip's move loop says why)
+    uint32_t cq[NB];
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+        if (tid == 0) {
+            pending = __hip_atomic_fetch_add(&a.hdr->ticket, one, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            asm volatile("ds_write_b32 %0, %1\n\tds_write_b32 %2, %3\n\ts_waitcnt lgkmcnt(0)" : : "v"(q_next_lds + 4u * ((uint32_t)(i + 1) & 1u)), "v"(pending), "v"(q_dead_lds), "v"(0u) : "memory");
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_barrier();
+        uint32_t t;
+        asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(t) : "v"(q_next_lds + 4u * ((uint32_t)(i + 1) & 1u)) : "memory");
+        cq[i] = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
+    }
+    if (cq[0] < total) {
+        Raw w[NB][U];
+#pragma unroll
+        for (int i = 0; i < DEPTH; ++i) load(w[i], vb[i], vb[(i + NB - 1) % NB], chunk_at(cq[i]));
+        bool finished = false;
+        while (!finished) {
+#pragma unroll
+            for (int p = 0; p < NB; ++p) {
+                const int q = (p + DEPTH) % NB;
+                __builtin_amdgcn_s_barrier();
+                if (tid == 0) pending = __hip_atomic_fetch_add(&a.hdr->ticket, one, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                load(w[q], vb[q], vb[p], chunk_at(cq[DEPTH]));
+                __builtin_amdgcn_sched_barrier(0);
+                process_move(w[p], vb[p], chunk_at(cq[0]), vb[q], chunk_at(cq[DEPTH]));
+#pragma unroll
+                for (int i = 0; i < DEPTH; ++i) cq[i] = cq[i + 1];
+                cq[DEPTH] = take_published();
+                if (cq[0] >= total) {
+                    finished = true;
+                    break;
+                }
+            }
+        }
+    }
+}
+
+// ---- place: the ragged ends from scratch into place ------------------------------------------------------------------------------
+__global__ __launch_bounds__(kTableBlock) void modgpu_cycle_rekey_move_table_place(MoveTableArgs a)
+{
+    if (a.hdr->first_bad != kTableNoBad) return;
+    const uint64_t i = (uint64_t)blockIdx.x * kTableBlock + threadIdx.x;
+    if (i >= a.n) return;
+    const MoveTablePlan P = a.plan[i];
+    const uint8_t *in = a.scratch + i * kMoveTableScratch;
+    uint8_t *db = P.dst_origin + P.lead;
+    const uint64_t body = P.end - P.lead;
+#pragma unroll
+    for (uint32_t j = 0; j < 15; ++j) {
+        if (j < P.head_n) db[(int64_t)j - P.head_n] = in[j];
+        if (j < P.tail_n) db[body + j] = in[16 + j];
+    }
+}
+
+namespace {
+template <int U, int BLOCK> struct MoveTableShape {
+    static constexpr uint32_t chunk = (uint32_t)U * BLOCK * lcg::WORD;
+    static constexpr uint32_t block = BLOCK;
+    static void launch(const MoveTableArgs &a, uint32_t grid, hipStream_t stream)
+    {
+        hipLaunchKernelGGL((modgpu_cycle_rekey_move_table_kernel<U, BLOCK>), dim3(grid), dim3(BLOCK), 0, stream, a);
+    }
+    static const char *name() // as a profiler prints it
+    {
+        static char buf[96];
+        static const int n = std::snprintf(buf, sizeof buf, "modgpu_cycle_rekey_move_table_kernel<%d, %d>", U, BLOCK);
+        (void)n;
+        return buf;
+    }
+};
+using MoveTableMove = MoveTableShape<4, 1024>; // the rekey kernel's shape: 64 KiB chunks
+static_assert(MoveTableMove::chunk == kChunk, "one chunk size for the plan and the move");
+} // namespace
+
+uint32_t modgpu_rekey_move_table_chunk_bytes() { return MoveTableMove::chunk; }
+uint32_t modgpu_rekey_move_table_block() { return MoveTableMove::block; }
+const char *modgpu_rekey_move_table_kernel_name() { return MoveTableMove::name(); }
+hipError_t modgpu_launch_rekey_move_table_plan(const MoveTableArgs &a, hipStream_t stream)
+{
+    hipLaunchKernelGGL(modgpu_cycle_rekey_move_table_plan, dim3(a.n_blk), dim3(kTableBlock), 0, stream, a);
+    return hipGetLastError();
+}
+hipError_t modgpu_launch_rekey_move_table_finish(const MoveTableArgs &a, hipStream_t stream)
+{
+    hipLaunchKernelGGL(modgpu_cycle_rekey_move_table_finish, dim3(a.n_blk), dim3(kTableBlock), 0, stream, a);
+    return hipGetLastError();
+}
+hipError_t modgpu_launch_rekey_move_table_window(const MoveTableArgs &a, hipStream_t stream)
+{
+    hipLaunchKernelGGL(modgpu_cycle_rekey_move_table_window, dim3((uint32_t)((a.cap + kWindowBlock - 1) / kWindowBlock)), dim3(kWindowBlock), 0, stream, a);
+    return hipGetLastError();
+}
+hipError_t modgpu_launch_rekey_move_table_move(const MoveTableArgs &a, uint32_t *grid, hipStream_t stream)
+{
+    int per_cu = 0, cus = 0, dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess) e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, modgpu_cycle_rekey_move_table_kernel<4, 1024>, 1024, 0);
+    if (e != hipSuccess) return e;
+    const uint64_t resident = (uint64_t)(per_cu > 0 ? per_cu : 1) * (uint64_t)(cus > 0 ? cus : 1);
+    if (*grid > resident) *grid = (uint32_t)resident;
+    if (*grid == 0) *grid = 1;
+    MoveTableMove::launch(a, *grid, stream);
+    return hipGetLastError();
+}
+hipError_t modgpu_launch_rekey_move_table_place(const MoveTableArgs &a, hipStream_t stream)
+{
+    hipLaunchKernelGGL(modgpu_cycle_rekey_move_table_place, dim3(a.n_blk), dim3(kTableBlock), 0, stream, a);
+    return hipGetLastError();
+}

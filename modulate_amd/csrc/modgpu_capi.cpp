@@ -22,6 +22,7 @@
 #include "cycle_kernel.h"
 #include "cycle_rekey_kernel.h"
 #include "cycle_rekey_table_kernel.h"
+#include "cycle_rekey_move_table_kernel.h"
 #include "cycle_verify_table_kernel.h"
 #include "cycle_rekey_verify_table_kernel.h"
 #include "cycle_verify_kernel.h"
@@ -1692,6 +1693,147 @@ int rekey_table_impl(const modgpu_rekey_table_entry_t *entries, uint64_t n, void
     return MODGPU_OK;
 }
 
+// ---- a table of rekey entries in device memory, moved with memmove rules (modgpu_rekey_move_table_device) -------------
+// The workspace: the table call's header first (modgpu_table_status reads it), then the 1024-entry records, the plan records, the
+// edge states, 32 bytes of scratch per entry for the ragged ends, one "loaded" flag and one window per chunk the call may have
+// (total_bytes / 64 KiB + 2 per entry: a body of n bytes lies on at most n / 64 KiB + 2 chunks of its destination), the search levels.
+struct MoveTableLayout {
+    uint32_t n_blk, top;
+    uint64_t cap, blk, plan, edge, scratch, flags, win, level[kTableLevels], level_n[kTableLevels], bytes;
+};
+uint64_t move_table_chunks(uint64_t n, uint64_t total_bytes) { return total_bytes / modgpu_rekey_move_table_chunk_bytes() + 2 * n; }
+MoveTableLayout move_table_layout(uint64_t n, uint64_t total_bytes)
+{
+    MoveTableLayout L{};
+    auto line = [](uint64_t x) { return (x + 63) & ~63ull; };
+    L.n_blk = (uint32_t)((n + kTableBlock - 1) / kTableBlock);
+    L.cap = move_table_chunks(n, total_bytes);
+    uint64_t at = sizeof(MoveTableHdr);
+    L.blk = at;
+    at = line(at + (uint64_t)L.n_blk * sizeof(MoveTableBlk));
+    L.plan = at;
+    at = line(at + n * sizeof(MoveTablePlan));
+    L.edge = at;
+    at = line(at + n * sizeof(RekeyTableEdge));
+    L.scratch = at;
+    at = line(at + n * kMoveTableScratch);
+    L.flags = at;
+    at = line(at + L.cap * sizeof(uint32_t));
+    L.win = at;
+    at = line(at + L.cap * sizeof(MoveTableWin));
+    uint64_t cnt = n;
+    for (uint32_t k = 0; k < (uint32_t)kTableLevels; ++k) {
+        L.level[k] = at;
+        L.level_n[k] = cnt;
+        L.top = k;
+        at = line(at + ((cnt + 15) & ~15ull) * sizeof(uint32_t));
+        if (cnt <= 16) break;
+        cnt = (cnt + 15) / 16;
+    }
+    L.bytes = at;
+    return L;
+}
+bool move_table_sizes_ok(uint64_t n, uint64_t total_bytes)
+{
+    return n != 0 && n <= kTableMaxEntries && total_bytes / modgpu_rekey_move_table_chunk_bytes() <= kTableMaxChunks - 2 * kTableMaxEntries;
+}
+
+// The move launch's grid: one workgroup per CU on every CU, as the rekey kernel (never more than the device holds at once)
+#ifdef MODGPU_TESTING_HOOKS
+std::atomic<uint32_t> g_move_table_grid{0}; // modgpu_debug_set_move_table_grid
+uint32_t move_table_grid_forced() { return g_move_table_grid.load(std::memory_order_relaxed); }
+#else
+constexpr uint32_t move_table_grid_forced() { return 0; }
+#endif
+
+// Tier 1 (include/modgpu.h): everything checked before anything is queued; then the five launches on `stream`.
+int rekey_move_table_impl(const modgpu_rekey_table_entry_t *entries, uint64_t n, uint64_t total_bytes, void *ws, uint64_t ws_bytes, int device,
+                          hipStream_t stream)
+{
+    if (n == 0) return MODGPU_OK;
+    if (n > kTableMaxEntries) return fail(MODGPU_ERR_INVALID, "more than 4194304 entries (the table call's limit)");
+    if (!move_table_sizes_ok(n, total_bytes)) return fail(MODGPU_ERR_INVALID, "total_bytes beyond 2^31 chunks of 64 KiB");
+    if (!entries || !ws) return fail(MODGPU_ERR_INVALID, "null table or workspace");
+    if ((reinterpret_cast<uintptr_t>(entries) | reinterpret_cast<uintptr_t>(ws)) & 7) return fail(MODGPU_ERR_INVALID, "table or workspace not 8-byte aligned");
+    const MoveTableLayout L = move_table_layout(n, total_bytes);
+    if (ws_bytes < L.bytes) return fail(MODGPU_ERR_INVALID, "workspace smaller than modgpu_rekey_move_table_workspace_bytes(n_entries, total_bytes)");
+    DeviceScope scope(device);
+    if (scope.rc) return scope.rc;
+    int phys = -1;
+    HIP_TRY(hipGetDevice(&phys));
+    if (modgpu_xfer_device_of(entries, n * sizeof(modgpu_rekey_table_entry_t)) != phys || modgpu_xfer_device_of(ws, L.bytes) != phys)
+        return fail(MODGPU_ERR_INVALID, "the table or the workspace is not device memory of the call's device");
+    uint8_t *const w = static_cast<uint8_t *>(ws);
+    MoveTableArgs a{};
+    a.entries = reinterpret_cast<const RekeyTableEntry *>(entries);
+    a.n = n;
+    a.cap = L.cap;
+    a.hdr = reinterpret_cast<MoveTableHdr *>(w);
+    a.blk = reinterpret_cast<MoveTableBlk *>(w + L.blk);
+    a.plan = reinterpret_cast<MoveTablePlan *>(w + L.plan);
+    a.edge = reinterpret_cast<RekeyTableEdge *>(w + L.edge);
+    a.scratch = w + L.scratch;
+    a.flags = reinterpret_cast<uint32_t *>(w + L.flags);
+    a.win = reinterpret_cast<MoveTableWin *>(w + L.win);
+    for (uint32_t k = 0; k <= L.top; ++k) {
+        a.level[k] = reinterpret_cast<uint32_t *>(w + L.level[k]);
+        a.level_n[k] = L.level_n[k];
+    }
+    a.top = L.top;
+    a.n_blk = L.n_blk;
+    uint32_t grid = move_table_grid_forced() ? move_table_grid_forced() : std::max<uint32_t>(1, large_grid());
+    (void)hipGetLastError(); // (the launches report hipGetLastError: an earlier call's error must not be taken for theirs)
+    hipError_t e = modgpu_launch_rekey_move_table_plan(a, stream);
+    if (e != hipSuccess) return fail_hip(e, "rekey move table plan launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    e = modgpu_launch_rekey_move_table_finish(a, stream);
+    if (e != hipSuccess) return fail_hip(e, "rekey move table finish launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    e = modgpu_launch_rekey_move_table_window(a, stream);
+    if (e != hipSuccess) return fail_hip(e, "rekey move table window launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    e = modgpu_launch_rekey_move_table_move(a, &grid, stream);
+    if (e != hipSuccess) return fail_hip(e, "rekey move table move launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    e = modgpu_launch_rekey_move_table_place(a, stream);
+    if (e != hipSuccess) return fail_hip(e, "rekey move table place launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    t_last_launch = {modgpu_rekey_move_table_kernel_name(), CYCLE_REKEY_MOVE_TABLE, grid, modgpu_rekey_move_table_block(), modgpu_rekey_move_table_chunk_bytes(), 0, grid,
+                     MODGPU_REKEY_MOVE_TABLE_KERNEL_SOURCE_HASH};
+    return MODGPU_OK;
+}
+
+// Tiers 1 and 2 over a host copy, in O(n), as the device decides them: the direction is that of the first entry with dst != src, and
+// every non-empty entry is compared with the non-empty entry before it.  (The chunk count against the workspace is the one check that
+// needs total_bytes: it is not made here.)
+int rekey_move_table_validate_impl(const modgpu_rekey_table_entry_t *t, uint64_t n)
+{
+    if (n > kTableMaxEntries) return fail(MODGPU_ERR_INVALID, "more than 4194304 entries (the table call's limit)");
+    if (n && !t) return fail(MODGPU_ERR_INVALID, "null table");
+    auto at = [](const void *p) { return (uint64_t)reinterpret_cast<uintptr_t>(p); };
+    auto entry = [](uint64_t i, const char *what) { return fail(MODGPU_ERR_INVALID, "entry " + std::to_string(i) + ": " + what); };
+    const uint64_t chunk = modgpu_rekey_move_table_chunk_bytes();
+    int way = 0; // -1 downward, +1 upward
+    for (uint64_t i = 0; i < n && !way; ++i)
+        if (t[i].n) way = at(t[i].dst) < at(t[i].src) ? -1 : at(t[i].dst) > at(t[i].src) ? 1 : 0;
+    uint64_t prev = UINT64_MAX;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (entry_reserved(t[i])) return entry(i, "nonzero flags or reserved");
+        if (!t[i].n) continue;
+        if (!t[i].dst || !t[i].src) return entry(i, "null buffer");
+        const uint64_t d = at(t[i].dst), s = at(t[i].src);
+        if (t[i].n >= kTableMaxEntryChunks * chunk) return entry(i, "1 TiB or more");
+        if (way > 0 ? d < s : d > s) return entry(i, way > 0 ? "slides down in an upward table" : "slides up in a downward table");
+        if (prev != UINT64_MAX) {
+            const uint64_t ps = at(t[prev].src), pd = at(t[prev].dst), pn = t[prev].n;
+            if (s < ps || s - ps < pn) return entry(i, "source below the end of the previous entry's source (entries are listed by rising address, sources disjoint)");
+            if (d < pd || d - pd < pn) return entry(i, "destination below the end of the previous entry's destination (entries are listed by rising address, destinations disjoint)");
+        }
+        prev = i;
+    }
+    return MODGPU_OK;
+}
+
 // ---- a table of verify entries in device memory (modgpu_verify_table_device) --------------------------------------------------------
 static_assert(sizeof(modgpu_verify_table_summary_t) == 32 && offsetof(modgpu_verify_table_summary_t, first_bad_entry) == offsetof(VerifyTableSummary, first_bad_entry) &&
                   offsetof(modgpu_verify_table_summary_t, entries) == offsetof(VerifyTableSummary, entries) &&
@@ -2097,6 +2239,46 @@ int modgpu_rekey_table_device(const modgpu_rekey_table_entry_t *dev_entries, uin
 int modgpu_rekey_table_validate(const modgpu_rekey_table_entry_t *host_entries, uint64_t n_entries)
 {
     return guarded([&]() -> int { return table_validate_impl(host_entries, n_entries); });
+}
+
+uint64_t modgpu_rekey_move_table_workspace_bytes(uint64_t n_entries, uint64_t total_bytes)
+{
+    return move_table_sizes_ok(n_entries, total_bytes) ? move_table_layout(n_entries, total_bytes).bytes : 0;
+}
+
+int modgpu_rekey_move_table_device(const modgpu_rekey_table_entry_t *dev_entries, uint64_t n_entries, uint64_t total_bytes, void *dev_workspace,
+                                   uint64_t workspace_bytes, int device, void *hip_stream)
+{
+    return guarded([&]() -> int {
+        return rekey_move_table_impl(dev_entries, n_entries, total_bytes, dev_workspace, workspace_bytes, device, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int modgpu_rekey_move_table_validate(const modgpu_rekey_table_entry_t *host_entries, uint64_t n_entries)
+{
+    return guarded([&]() -> int { return rekey_move_table_validate_impl(host_entries, n_entries); });
+}
+
+int modgpu_rekey_move_table_status(const void *dev_workspace, int device, uint64_t *first_bad_entry, uint64_t *stalled_chunk)
+{
+    return guarded([&]() -> int {
+        if (!dev_workspace || !first_bad_entry || !stalled_chunk) return fail(MODGPU_ERR_INVALID, "null workspace or out pointer");
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        int phys = -1;
+        HIP_TRY(hipGetDevice(&phys));
+        if (modgpu_xfer_device_of(dev_workspace, sizeof(MoveTableHdr)) != phys)
+            return fail(MODGPU_ERR_INVALID, "the workspace is not device memory of the call's device");
+        MoveTableHdr h;
+        HIP_TRY(hipMemcpy(&h, dev_workspace, sizeof h, hipMemcpyDeviceToHost));
+        *first_bad_entry = h.first_bad;
+        *stalled_chunk = h.stalled ? (uint64_t)h.stalled - 1 : UINT64_MAX;
+        if (h.first_bad != kTableNoBad)
+            return fail(MODGPU_ERR_INVALID, "the device refused entry " + std::to_string(h.first_bad) + " (the call wrote nothing)");
+        if (h.stalled)
+            return fail(MODGPU_ERR_HIP, "move table: the wait of chunk " + std::to_string(h.stalled - 1) + " ran out (the destinations are unspecified)");
+        return MODGPU_OK;
+    });
 }
 
 uint64_t modgpu_verify_table_workspace_bytes(uint64_t n_entries)
@@ -2915,6 +3097,7 @@ const char *modgpu_verify_table_kernel_source_hash(void) { return MODGPU_VERIFY_
 const char *modgpu_rekey_verify_kernel_source_hash(void) { return MODGPU_REKEY_VERIFY_KERNEL_SOURCE_HASH; }
 const char *modgpu_keep_kernel_source_hash(void) { return MODGPU_KEEP_KERNEL_SOURCE_HASH; }
 const char *modgpu_rekey_verify_table_kernel_source_hash(void) { return MODGPU_REKEY_VERIFY_TABLE_KERNEL_SOURCE_HASH; }
+const char *modgpu_rekey_move_table_kernel_source_hash(void) { return MODGPU_REKEY_MOVE_TABLE_KERNEL_SOURCE_HASH; }
 
 int modgpu_keep_policy(uint64_t bytes, uint32_t *mask, uint32_t *run)
 {
@@ -3071,6 +3254,7 @@ void modgpu_debug_set_rekey_form(int shape)
 
 void modgpu_debug_set_table_grid(uint32_t grid) { g_table_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
 void modgpu_debug_set_move_grid(uint32_t grid) { g_move_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
+void modgpu_debug_set_move_table_grid(uint32_t grid) { g_move_table_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
 void modgpu_debug_set_rekey_table_grid(uint32_t grid) { g_rekey_table_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
 
 void modgpu_debug_set_verify_table_grid(uint32_t grid) { g_verify_table_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
