@@ -2,7 +2,9 @@
 // dst_i[j] = SRC0_i[j] ^ ks(key_from_i)[off_from_i + j] ^ ks(key_to_i)[off_to_i + j], SRC0 the memory as the call found it; a
 // destination may lie on top of any entry's source.  cycle_rekey_move_table_kernel.h has the rule for the tables taken and the five
 // launches.  The two-keystream block: cycle_rekey_impl.h; the jump tables and the single-state arithmetic: cycle_kernel_impl.h; both
-// included and not changed.
+// included and not changed.  What the table TUs have in common -- an entry on the chunk grid and its six states, the totals, the search
+// levels and one level of their descent, a chunk's span, the funnel, mulmod_keep -- is cycle_table_impl.h; the plan launch's scan is this
+// TU's own (it carries the last non-empty entry beside the chunk counts).
 //
 // Built from two shipped kernels, neither changed: the plan, the chunk grid (64 KiB chunks on absolute chunk-aligned DESTINATION
 // addresses, a cut first chunk per entry), the 16-ary chunk -> entry levels, the views and the identity keystream as the state 2^31-1
@@ -20,52 +22,11 @@
 #include <cstdint>
 
 #include "cycle_rekey_impl.h"
+#include "cycle_table_impl.h"
 #include "cycle_rekey_move_table_kernel.h"
-
-#include <cstdio>
 
 namespace {
 
-// a^(b * 256^k) for the four bytes of an exponent < 2^32: a^e by three multiplies
-__constant__ lcg::Table<256> c_pow_b0 = lcg::make_pow_table<256>(1);
-__constant__ lcg::Table<256> c_pow_b1 = lcg::make_pow_table<256>(256);
-__constant__ lcg::Table<256> c_pow_b2 = lcg::make_pow_table<256>(65536);
-__constant__ lcg::Table<256> c_pow_b3 = lcg::make_pow_table<256>(1u << 24);
-
-__device__ __forceinline__ uint32_t pow_a(uint32_t e)
-{
-    uint32_t p = mulmod_canon(c_pow_b0.v[e & 255], c_pow_b1.v[(e >> 8) & 255]);
-    p = mulmod_canon(p, c_pow_b2.v[(e >> 16) & 255]);
-    return mulmod_canon(p, c_pow_b3.v[e >> 24]);
-}
-
-// x * y mod m for a state x (canonical, or 2^31-1 for the identity keystream) and a power y of a; 2^31-1 stays 2^31-1
-__device__ __forceinline__ uint32_t mulmod_keep(uint32_t x, uint32_t y)
-{
-    const uint32_t X = mul_fold(x, 2u * y);
-    return X >= 0x80000000u ? X - lcg::M : X;
-}
-
-__device__ __forceinline__ uint32_t state_at(uint32_t k, uint64_t e) { return k ? mulmod_canon(k, pow_a((uint32_t)(e % lcg::PERIOD))) : lcg::M; }
-
-__device__ __forceinline__ uint32_t key_res(int32_t key)
-{
-    const int64_t kr = (int64_t)key % (int64_t)lcg::M;
-    return (uint32_t)(kr < 0 ? kr + lcg::M : kr);
-}
-
-// reads of memory no launch of this TU writes while it runs: scalar loads when the address is uniform
-#if defined(__HIP_DEVICE_COMPILE__)
-#define MOVE_TABLE_CONST_AS __attribute__((address_space(4)))
-#else
-#define MOVE_TABLE_CONST_AS
-#endif
-template <class T> __device__ __forceinline__ const MOVE_TABLE_CONST_AS T *as_const(const T *p) { return (const MOVE_TABLE_CONST_AS T *)p; }
-struct Keys16 {
-    uint32_t v[16];
-};
-
-constexpr uint32_t kChunk = 65536; // the move kernel's chunk: 4 words x 1024 threads x 16 bytes
 constexpr uint32_t kNone = ~0u;
 constexpr uint32_t kWindowBlock = 256;
 
@@ -98,39 +59,16 @@ __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_rekey_move_table_pla
     uint32_t bad = 0, full = 0, way = 0; // way: 1 dst < src, 2 dst > src
     if (i < a.n) {
         const RekeyTableEntry E = a.entries[i];
-        const uintptr_t d = reinterpret_cast<uintptr_t>(E.dst);
-        const uint64_t head = E.n < ((16 - (d & 15)) & 15) ? E.n : ((16 - (d & 15)) & 15);
-        const uint64_t words = (E.n - head) / 16;
-        const uint64_t tail = E.n - head - words * 16;
-        const uint32_t lead = (uint32_t)((d + head) & (kChunk - 1));
-        const uint64_t end = lead + words * 16;
-        cnt = words ? (end + kChunk - 1) / kChunk : 0;
-        bad = (E.n && (!E.dst || !E.src)) || E.flags != 0 || E.reserved != 0 || cnt > kTableMaxEntryChunks ? 1u : 0u;
-        if (bad) cnt = 0;
+        const TableGrid g = table_grid(E, E.flags | E.reserved);
+        cnt = g.cnt;
+        bad = g.bad;
         full = E.n != 0 ? 1u : 0u;
         way = !full ? 0u : at(E.dst) < at(E.src) ? 1u : at(E.dst) > at(E.src) ? 2u : 0u;
-        const uint32_t kf = key_res(E.key_from), kt = key_res(E.key_to);
-        const uint64_t of = E.off_from % lcg::PERIOD + 1, ot = E.off_to % lcg::PERIOD + 1;
-        const uint64_t body = head + lcg::PERIOD - lead, after = head + (words * 16) % lcg::PERIOD;
         MoveTablePlan P;
-        P.dst_origin = reinterpret_cast<uint8_t *>(reinterpret_cast<uintptr_t>(E.dst) + head - lead); // (as integers: a refused entry's pointer may be NULL)
-        P.src_origin = reinterpret_cast<const uint8_t *>(reinterpret_cast<uintptr_t>(E.src) + head - lead);
-        P.end = end;
-        P.start = 0;
-        P.lead = lead;
-        P.chunks = (uint32_t)cnt;
-        P.base_from = state_at(kf, of + body);
-        P.base_to = state_at(kt, ot + body);
-        P.bad = bad;
-        P.head_n = (uint32_t)head;
-        P.tail_n = (uint32_t)tail;
+        RekeyTableEdge X;
+        rekey_table_plan_entry(P, X, E, g);
         P.prev = 0;
         a.plan[i] = P;
-        RekeyTableEdge X;
-        X.head[0] = state_at(kf, of);
-        X.head[1] = state_at(kt, ot);
-        X.tail[0] = state_at(kf, of + after);
-        X.tail[1] = state_at(kt, ot + after);
         a.edge[i] = X;
     }
     sc[tid] = cnt;
@@ -168,54 +106,39 @@ __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_rekey_move_table_pla
 // ---- finish: global starts, the direction, the order rule, the status, the search levels, the ragged ends into scratch ----------------
 __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_rekey_move_table_finish(MoveTableArgs a)
 {
-    __shared__ uint64_t r_before[kTableBlock], r_total[kTableBlock];
-    __shared__ uint32_t sbad, sprev, sdown, sup;
+    __shared__ uint32_t sprev, sdown, sup;
     const uint32_t tid = threadIdx.x;
     const uint32_t b = blockIdx.x;
     const uint64_t i = (uint64_t)b * kTableBlock + tid;
     if (tid == 0) {
-        sbad = 0;
         sprev = 0;
         sdown = kNone;
         sup = kNone;
     }
-    uint64_t before = 0, total = 0;
-    uint32_t bad = 0, prev = 0, down = kNone, up = kNone;
-    for (uint32_t k = tid; k < a.n_blk; k += kTableBlock) {
-        const MoveTableBlk B = a.blk[k];
-        total += B.chunks;
-        before += k < b ? B.chunks : 0;
-        bad |= B.bad;
-        if (k < b && B.last > prev) prev = B.last;
-        down = B.first_down < down ? B.first_down : down;
-        up = B.first_up < up ? B.first_up : up;
-    }
-    r_before[tid] = before;
-    r_total[tid] = total;
-    __syncthreads();
-    if (bad) atomicOr(&sbad, 1u);
-    if (prev) atomicMax(&sprev, prev);
-    if (down != kNone) atomicMin(&sdown, down);
-    if (up != kNone) atomicMin(&sup, up);
-    for (uint32_t s = kTableBlock / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            r_before[tid] += r_before[tid + s];
-            r_total[tid] += r_total[tid + s];
-        }
-        __syncthreads();
-    }
-    before = r_before[0];
-    total = r_total[0];
+    // beside the totals: the last non-empty entry before this workgroup's, and the first entry that moves down / up
+    uint32_t prev = 0, down = kNone, up = kNone;
+    const TableTotals T = table_totals(
+        a.blk, a.n_blk, b, tid,
+        [&](uint32_t k, const MoveTableBlk &B) {
+            if (k < b && B.last > prev) prev = B.last;
+            down = B.first_down < down ? B.first_down : down;
+            up = B.first_up < up ? B.first_up : up;
+        },
+        [&] {
+            if (prev) atomicMax(&sprev, prev);
+            if (down != kNone) atomicMin(&sdown, down);
+            if (up != kNone) atomicMin(&sup, up);
+        });
     const uint64_t room = a.cap < kTableMaxChunks ? a.cap : kTableMaxChunks;
-    const bool ok = sbad == 0 && total <= room;
+    const bool ok = T.bad == 0 && T.total <= room;
     const bool upward = sup < sdown; // the first entry with dst != src says which way the table slides
     if (b == 0 && tid == 0) {
-        a.hdr->total = ok ? total : 0;
+        a.hdr->total = ok ? T.total : 0;
         a.hdr->up = upward ? 1u : 0u;
     }
     if (i < a.n) {
         const MoveTablePlan P = a.plan[i];
-        const uint64_t start = before + P.start;
+        const uint64_t start = T.before + P.start;
         // refused by the plan, or the first whose chunks pass what the workspace was sized for
         if (!ok && (P.bad || start + P.chunks > room)) atomicMin((unsigned long long *)&a.hdr->first_bad, (unsigned long long)i);
         // the direction and order rule: this entry against the non-empty entry before it
@@ -232,8 +155,7 @@ __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_rekey_move_table_fin
         }
         if (ok) {
             a.plan[i].start = start;
-            for (uint32_t k = 0; k < kTableLevels; ++k)
-                if (k <= a.top && (i & ((1ull << (4 * k)) - 1)) == 0) a.level[k][i >> (4 * k)] = (uint32_t)start;
+            for (uint32_t k = 0; k < kTableLevels; ++k) table_set_level(a.level[k], k, a.top, i, start);
             // the < 16 bytes in front of the body and behind it under both keystreams, into scratch: nothing outside the workspace
             // has been written yet, so these are bytes of SRC0 whatever the later launches store on top of them
             const RekeyTableEdge X = a.edge[i];
@@ -248,10 +170,8 @@ __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_rekey_move_table_fin
             }
         }
     }
-    // each level padded with ~0 to a whole line of 16 keys: the descent reads 16 at a time
     if (ok && b == 0 && tid < 16)
-        for (uint32_t k = 0; k < kTableLevels; ++k)
-            if (k <= a.top && a.level_n[k] + tid < ((a.level_n[k] + 15) & ~15ull)) a.level[k][a.level_n[k] + tid] = ~0u;
+        for (uint32_t k = 0; k < kTableLevels; ++k) table_pad_level(a.level[k], a.level_n[k], k, a.top, tid);
 }
 
 // ---- window: one thread per chunk ------------------------------------------------------------------------------------------------
@@ -263,13 +183,7 @@ struct ChunkSpan {
 __device__ ChunkSpan chunk_span(const MoveTableArgs &a, uint32_t g)
 {
     uint32_t j = 0;
-    for (int k = (int)a.top; k >= 0; --k) {
-        const uint32_t *keys = a.level[k] + 16u * j;
-        uint32_t c = 0;
-#pragma unroll
-        for (int t = 0; t < 16; ++t) c += keys[t] <= g ? 1u : 0u;
-        j = 16u * j + c - 1u;
-    }
+    for (int k = (int)a.top; k >= 0; --k) j = table_descend(a.level[k], j, g);
     const MoveTablePlan P = a.plan[j];
     const uint64_t c = g - P.start, off = c * kChunk, cut = c ? 0 : P.lead;
     const uint64_t lim = P.end < off + kChunk ? P.end : off + kChunk;
@@ -325,22 +239,6 @@ __global__ __launch_bounds__(kWindowBlock) void modgpu_cycle_rekey_move_table_wi
 }
 
 // ---- move ------------------------------------------------------------------------------------------------------------------------
-namespace {
-struct Raw {
-    u32x4 d;
-    uint32_t e; // the dword after d, read when the chunk's source is not dword-aligned
-};
-__device__ __forceinline__ u32x4 funnel(const Raw &w, uint32_t sh)
-{
-    u32x4 d;
-    d.x = __builtin_amdgcn_alignbyte(w.d.y, w.d.x, sh);
-    d.y = __builtin_amdgcn_alignbyte(w.d.z, w.d.y, sh);
-    d.z = __builtin_amdgcn_alignbyte(w.d.w, w.d.z, sh);
-    d.w = __builtin_amdgcn_alignbyte(w.e, w.d.w, sh);
-    return d;
-}
-} // namespace
-
 template <int U, int BLOCK>
 __global__ __launch_bounds__(BLOCK) MODGPU_REKEY_KEEP_OFF_THE_FIXED_TEMPORARIES void modgpu_cycle_rekey_move_table_kernel(MoveTableArgs a)
 {
@@ -375,13 +273,7 @@ __global__ __launch_bounds__(BLOCK) MODGPU_REKEY_KEEP_OFF_THE_FIXED_TEMPORARIES 
     auto search = [&](uint32_t g, View &v) {
         uint32_t j = 0;
 #pragma unroll 1
-        for (int k = (int)a.top; k >= 0; --k) {
-            const Keys16 keys = *as_const(reinterpret_cast<const Keys16 *>(a.level[k] + 16u * j));
-            uint32_t c = 0;
-#pragma unroll
-            for (int t = 0; t < 16; ++t) c += keys.v[t] <= g ? 1u : 0u;
-            j = 16u * j + c - 1u;
-        }
+        for (int k = (int)a.top; k >= 0; --k) j = table_descend(a.level[k], j, g);
         const MoveTablePlan P = *as_const(a.plan + j);
         v.dst0 = P.dst_origin;
         v.src0 = P.src_origin;
@@ -391,20 +283,7 @@ __global__ __launch_bounds__(BLOCK) MODGPU_REKEY_KEEP_OFF_THE_FIXED_TEMPORARIES 
         v.lane_base[0] = mulmod_keep(P.base_from, lane_mul);
         v.lane_base[1] = mulmod_keep(P.base_to, lane_mul);
     };
-    struct Span {
-        uint64_t off;
-        uint32_t cut, bytes;
-    };
-    auto span = [&](uint32_t g, const View &v) {
-        Span s{0, 0, 0};
-        if (g >= total) return s; // past the last position: zero-size descriptors, loads give 0, stores drop
-        const uint32_t c = g - v.lo;
-        s.off = (uint64_t)c * CHUNK;
-        s.cut = c ? 0u : v.lead;
-        const uint64_t lim = v.end < s.off + CHUNK ? v.end : s.off + CHUNK;
-        s.bytes = (uint32_t)(lim - s.off - s.cut);
-        return s;
-    };
+    auto span = [&](uint32_t g, const View &v) { return table_span<CHUNK>(g, total, v); };
     View vb[NB];
 #pragma unroll
     for (int i = 0; i < NB; ++i) vb[i] = View{nullptr, nullptr, 0, 0, 0, {lcg::M, lcg::M}};
@@ -576,13 +455,7 @@ template <int U, int BLOCK> struct MoveTableShape {
     {
         hipLaunchKernelGGL((modgpu_cycle_rekey_move_table_kernel<U, BLOCK>), dim3(grid), dim3(BLOCK), 0, stream, a);
     }
-    static const char *name() // as a profiler prints it
-    {
-        static char buf[96];
-        static const int n = std::snprintf(buf, sizeof buf, "modgpu_cycle_rekey_move_table_kernel<%d, %d>", U, BLOCK);
-        (void)n;
-        return buf;
-    }
+    static const char *name() { return table_kernel_name<U, BLOCK>("modgpu_cycle_rekey_move_table_kernel"); }
 };
 using MoveTableMove = MoveTableShape<4, 1024>; // the rekey kernel's shape: 64 KiB chunks
 static_assert(MoveTableMove::chunk == kChunk, "one chunk size for the plan and the move");

@@ -1,6 +1,8 @@
 // cycle_table_kernel.hip -- a TABLE of out-of-place entries that lives in device memory, any number of them, in three launches:
 // dst_i[j] = src_i[j] ^ ks(key_i)[off_i + j].  Device code of the arithmetic, the jump tables and the keystream block:
-// cycle_kernel_impl.h, included and not changed (its hash is modgpu_kernel_source_hash; this TU has its own).
+// cycle_kernel_impl.h, included and not changed (its hash is modgpu_kernel_source_hash; this TU has its own).  What the five table TUs
+// have in common -- an entry on the chunk grid, the scan, the totals, the search levels and one level of their descent, a chunk's span,
+// the funnel -- is cycle_table_impl.h.
 //
 //   plan    one thread per entry: reads the entry where the caller left it (when the launch RUNS, not when it is queued), checks it
 //           (a NULL pointer with bytes to move, nonzero flags, a body beyond the chunk jump tables), lays it on the chunk grid of its
@@ -28,47 +30,12 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
-#include "cycle_kernel_impl.h"
+#include "cycle_table_impl.h"
 #include "cycle_table_kernel.h"
-
-#include <cstdio>
-
-namespace {
-
-// a^(b * 256^k) for the four bytes of an exponent < 2^32: a^e by three multiplies
-__constant__ lcg::Table<256> c_pow_b0 = lcg::make_pow_table<256>(1);
-__constant__ lcg::Table<256> c_pow_b1 = lcg::make_pow_table<256>(256);
-__constant__ lcg::Table<256> c_pow_b2 = lcg::make_pow_table<256>(65536);
-__constant__ lcg::Table<256> c_pow_b3 = lcg::make_pow_table<256>(1u << 24);
-
-__device__ __forceinline__ uint32_t pow_a(uint32_t e)
-{
-    uint32_t p = mulmod_canon(c_pow_b0.v[e & 255], c_pow_b1.v[(e >> 8) & 255]);
-    p = mulmod_canon(p, c_pow_b2.v[(e >> 16) & 255]);
-    return mulmod_canon(p, c_pow_b3.v[e >> 24]);
-}
-
-// reads of memory no launch of this TU writes while it runs: scalar loads when the address is uniform (address space 4; the host pass
-// of the compiler only needs the types)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define TABLE_CONST_AS __attribute__((address_space(4)))
-#else
-#define TABLE_CONST_AS
-#endif
-template <class T> __device__ __forceinline__ const TABLE_CONST_AS T *as_const(const T *p) { return (const TABLE_CONST_AS T *)p; }
-struct Keys16 {
-    uint32_t v[16];
-};
-
-constexpr uint32_t kChunk = 65536; // the stream kernel's chunk: 4 words x 1024 threads x 16 bytes
-
-} // namespace
 
 // ---- plan: one thread per entry ----------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_table_plan(CycleTableArgs a)
 {
-    __shared__ uint64_t sc[kTableBlock];
-    __shared__ uint32_t sbad;
     const uint32_t tid = threadIdx.x;
     const uint64_t i = (uint64_t)blockIdx.x * kTableBlock + tid;
     if (blockIdx.x == 0 && tid == 0) {
@@ -76,98 +43,38 @@ __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_table_plan(CycleTabl
         a.hdr->first_bad = kTableNoBad;
         a.hdr->total = 0;
     }
-    if (tid == 0) sbad = 0;
     uint64_t cnt = 0;
     uint32_t bad = 0;
     if (i < a.n) {
         const CycleTableEntry E = a.entries[i];
-        const uintptr_t d = reinterpret_cast<uintptr_t>(E.dst);
-        const uint64_t head = E.n < ((16 - (d & 15)) & 15) ? E.n : ((16 - (d & 15)) & 15);
-        const uint64_t words = (E.n - head) / 16;
-        const uint64_t tail = E.n - head - words * 16;
-        const uint32_t lead = (uint32_t)((d + head) & (kChunk - 1));
-        const uint64_t end = lead + words * 16;
-        cnt = words ? (end + kChunk - 1) / kChunk : 0;
-        bad = (E.n && (!E.dst || !E.src)) || E.flags != 0 || cnt > kTableMaxEntryChunks ? 1u : 0u;
-        if (bad) cnt = 0;
-        // states: key * a^(o + 1 + position), positions mod the period
-        const int64_t kr = (int64_t)E.key % (int64_t)lcg::M;
-        const uint32_t k = (uint32_t)(kr < 0 ? kr + lcg::M : kr);
-        const uint64_t o1 = E.stream_off % lcg::PERIOD + 1;
+        const TableGrid g = table_grid(E, E.flags);
+        cnt = g.cnt;
+        bad = g.bad;
         CycleTablePlan P;
-        P.dst_origin = reinterpret_cast<uint8_t *>(reinterpret_cast<uintptr_t>(E.dst) + head - lead); // (as integers: a refused entry's pointer may be NULL)
-        P.src_origin = reinterpret_cast<const uint8_t *>(reinterpret_cast<uintptr_t>(E.src) + head - lead);
-        P.end = end;
-        P.start = 0;
-        P.lead = lead;
-        P.chunks = (uint32_t)cnt;
-        P.base_head = mulmod_canon(k, pow_a((uint32_t)(o1 % lcg::PERIOD)));
-        P.base = mulmod_canon(k, pow_a((uint32_t)((o1 + head + lcg::PERIOD - lead) % lcg::PERIOD)));
-        P.base_tail = mulmod_canon(k, pow_a((uint32_t)((o1 + head + (words * 16) % lcg::PERIOD) % lcg::PERIOD)));
-        P.bad = bad;
-        P.head_n = (uint32_t)head;
-        P.tail_n = (uint32_t)tail;
+        table_plan_entry(P, E, g);
         a.plan[i] = P;
     }
-    sc[tid] = cnt;
-    __syncthreads();
-    if (bad) atomicOr(&sbad, 1u);
-    // inclusive scan of the 1024 counts (Hillis-Steele; every thread reaches every barrier)
-    for (uint32_t s = 1; s < kTableBlock; s <<= 1) {
-        const uint64_t v = tid >= s ? sc[tid - s] : 0;
-        __syncthreads();
-        sc[tid] += v;
-        __syncthreads();
-    }
-    if (i < a.n) a.plan[i].start = sc[tid] - cnt;
-    if (tid == kTableBlock - 1) {
-        a.blk[blockIdx.x].chunks = sc[tid];
-        a.blk[blockIdx.x].bad = sbad;
-    }
+    table_plan_store(a.plan, a.blk, a.n, i, cnt, bad, tid);
 }
 
 // ---- finish: global starts, the status, the search levels, the ragged edges --------------------------------------------------------
 __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_table_finish(CycleTableArgs a)
 {
-    __shared__ uint64_t r_before[kTableBlock], r_total[kTableBlock];
-    __shared__ uint32_t sbad;
     const uint32_t tid = threadIdx.x;
     const uint32_t b = blockIdx.x;
     const uint64_t i = (uint64_t)b * kTableBlock + tid;
-    if (tid == 0) sbad = 0;
-    uint64_t before = 0, total = 0;
-    uint32_t bad = 0;
-    for (uint32_t k = tid; k < a.n_blk; k += kTableBlock) {
-        const uint64_t c = a.blk[k].chunks;
-        total += c;
-        before += k < b ? c : 0;
-        bad |= a.blk[k].bad;
-    }
-    r_before[tid] = before;
-    r_total[tid] = total;
-    __syncthreads();
-    if (bad) atomicOr(&sbad, 1u);
-    for (uint32_t s = kTableBlock / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            r_before[tid] += r_before[tid + s];
-            r_total[tid] += r_total[tid + s];
-        }
-        __syncthreads();
-    }
-    before = r_before[0];
-    total = r_total[0];
-    const bool ok = sbad == 0 && total <= kTableMaxChunks;
-    if (b == 0 && tid == 0) a.hdr->total = ok ? total : 0;
+    const TableTotals T = table_totals(a.blk, a.n_blk, b, tid);
+    const bool ok = T.bad == 0 && T.total <= kTableMaxChunks;
+    if (b == 0 && tid == 0) a.hdr->total = ok ? T.total : 0;
     if (i < a.n) {
         const CycleTablePlan P = a.plan[i];
-        const uint64_t start = before + P.start;
+        const uint64_t start = T.before + P.start;
         if (!ok) {
             // refused: write nothing; the lowest bad entry -- a refused one, or the first whose chunks pass the ticket range
             if (P.bad || start + P.chunks > kTableMaxChunks) atomicMin((unsigned long long *)&a.hdr->first_bad, (unsigned long long)i);
         } else {
             a.plan[i].start = start;
-            for (uint32_t k = 0; k < kTableLevels; ++k)
-                if (k <= a.top && (i & ((1ull << (4 * k)) - 1)) == 0) a.level[k][i >> (4 * k)] = (uint32_t)start;
+            for (uint32_t k = 0; k < kTableLevels; ++k) table_set_level(a.level[k], k, a.top, i, start);
             // the < 16 bytes in front of the body and behind it: all loads first (dst may be src), then the stores
             const uint8_t *sb = P.src_origin + P.lead;
             uint8_t *db = P.dst_origin + P.lead;
@@ -186,29 +93,11 @@ __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_table_finish(CycleTa
             }
         }
     }
-    // each level padded with ~0 to a whole line of 16 keys: the descent reads 16 at a time
     if (ok && b == 0 && tid < 16)
-        for (uint32_t k = 0; k < kTableLevels; ++k)
-            if (k <= a.top && a.level_n[k] + tid < ((a.level_n[k] + 15) & ~15ull)) a.level[k][a.level_n[k] + tid] = ~0u;
+        for (uint32_t k = 0; k < kTableLevels; ++k) table_pad_level(a.level[k], a.level_n[k], k, a.top, tid);
 }
 
 // ---- stream ------------------------------------------------------------------------------------------------------------------------
-namespace {
-struct Raw {
-    u32x4 d;
-    uint32_t e; // the dword after d, read when the chunk's source is not dword-aligned
-};
-__device__ __forceinline__ u32x4 funnel(const Raw &w, uint32_t sh) // sh == 0: alignbyte by 0 is the low dword itself
-{
-    u32x4 d;
-    d.x = __builtin_amdgcn_alignbyte(w.d.y, w.d.x, sh);
-    d.y = __builtin_amdgcn_alignbyte(w.d.z, w.d.y, sh);
-    d.z = __builtin_amdgcn_alignbyte(w.d.w, w.d.z, sh);
-    d.w = __builtin_amdgcn_alignbyte(w.e, w.d.w, sh);
-    return d;
-}
-} // namespace
-
 template <int U, int BLOCK>
 __global__ __launch_bounds__(BLOCK) MODGPU_KEEP_OFF_THE_FIXED_TEMPORARIES void modgpu_cycle_table_kernel(CycleTableArgs a)
 {
@@ -243,13 +132,7 @@ __global__ __launch_bounds__(BLOCK) MODGPU_KEEP_OFF_THE_FIXED_TEMPORARIES void m
     auto search = [&](uint32_t g, View &v) {
         uint32_t j = 0;
 #pragma unroll 1
-        for (int k = (int)a.top; k >= 0; --k) {
-            const Keys16 keys = *as_const(reinterpret_cast<const Keys16 *>(a.level[k] + 16u * j));
-            uint32_t c = 0;
-#pragma unroll
-            for (int t = 0; t < 16; ++t) c += keys.v[t] <= g ? 1u : 0u;
-            j = 16u * j + c - 1u;
-        }
+        for (int k = (int)a.top; k >= 0; --k) j = table_descend(a.level[k], j, g);
         const CycleTablePlan P = *as_const(a.plan + j);
         v.dst0 = P.dst_origin;
         v.src0 = P.src_origin;
@@ -261,20 +144,7 @@ __global__ __launch_bounds__(BLOCK) MODGPU_KEEP_OFF_THE_FIXED_TEMPORARIES void m
         v.lane_base = mulmod_canon(P.base, lane_mul);
     };
     // where chunk g lies: offset of its chunk from the entry's origin, the cut in front of the body (chunk 0 only), its bytes
-    struct Span {
-        uint64_t off;
-        uint32_t cut, bytes;
-    };
-    auto span = [&](uint32_t g, const View &v) {
-        Span s{0, 0, 0};
-        if (g >= total) return s; // past the last entry: zero-size descriptors, loads give 0, stores drop
-        const uint32_t c = g - v.lo;
-        s.off = (uint64_t)c * CHUNK;
-        s.cut = c ? 0u : v.lead;
-        const uint64_t lim = v.end < s.off + CHUNK ? v.end : s.off + CHUNK;
-        s.bytes = (uint32_t)(lim - s.off - s.cut);
-        return s;
-    };
+    auto span = [&](uint32_t g, const View &v) { return table_span<CHUNK>(g, total, v); };
     View vb[NB];
 #pragma unroll
     for (int i = 0; i < NB; ++i) vb[i] = View{nullptr, nullptr, 0, 0, 0, 0, 0, 1};
@@ -369,13 +239,7 @@ template <int U, int BLOCK> struct TableShape {
     {
         hipLaunchKernelGGL((modgpu_cycle_table_kernel<U, BLOCK>), dim3(grid), dim3(BLOCK), 0, stream, a);
     }
-    static const char *name() // as a profiler prints it
-    {
-        static char buf[96];
-        static const int n = std::snprintf(buf, sizeof buf, "modgpu_cycle_table_kernel<%d, %d>", U, BLOCK);
-        (void)n;
-        return buf;
-    }
+    static const char *name() { return table_kernel_name<U, BLOCK>("modgpu_cycle_table_kernel"); }
 };
 using TableStream = TableShape<4, 1024>; // the work-queue kernel's measured shape: 64 KiB chunks
 static_assert(TableStream::chunk == kChunk, "one chunk size for the plan and the stream");

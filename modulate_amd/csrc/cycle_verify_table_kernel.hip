@@ -3,8 +3,9 @@
 // are read once; nothing is written but the results and the workspace.  Device code of the arithmetic, the jump tables and the keystream
 // block: cycle_kernel_impl.h, included and not changed (this TU has a hash of its own).
 //
-// The structure is the table call's (cycle_table_kernel.hip; its plan, finish and search are copied here, not shared: every TU keeps a
-// source list and a hash of its own), the compare the verify kernel's (cycle_verify_kernel.hip):
+// The structure is the table call's (cycle_table_kernel.hip): what the two have in common -- an entry on the chunk grid, the scan, the
+// totals, the search levels and one level of their descent, a chunk's span, the funnel -- and a lane's findings
+// are cycle_table_impl.h, shared by the table TUs; the compare is the verify kernel's (cycle_verify_kernel.hip):
 //   plan    one thread per entry: reads the entry where the caller left it (when the launch RUNS), checks it (a NULL pointer with bytes
 //           to compare, nonzero flags, a body beyond the chunk jump tables), lays it on the chunk grid of its COMPARAND, computes its
 //           three base states, scans the chunk counts of its 1024 entries in LDS.  Workgroup 0 resets the ticket, the status and the
@@ -30,47 +31,12 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
-#include "cycle_kernel_impl.h"
+#include "cycle_table_impl.h"
 #include "cycle_verify_table_kernel.h"
-
-#include <cstdio>
-
-namespace {
-
-// a^(b * 256^k) for the four bytes of an exponent < 2^32: a^e by three multiplies
-__constant__ lcg::Table<256> c_pow_b0 = lcg::make_pow_table<256>(1);
-__constant__ lcg::Table<256> c_pow_b1 = lcg::make_pow_table<256>(256);
-__constant__ lcg::Table<256> c_pow_b2 = lcg::make_pow_table<256>(65536);
-__constant__ lcg::Table<256> c_pow_b3 = lcg::make_pow_table<256>(1u << 24);
-
-__device__ __forceinline__ uint32_t pow_a(uint32_t e)
-{
-    uint32_t p = mulmod_canon(c_pow_b0.v[e & 255], c_pow_b1.v[(e >> 8) & 255]);
-    p = mulmod_canon(p, c_pow_b2.v[(e >> 16) & 255]);
-    return mulmod_canon(p, c_pow_b3.v[e >> 24]);
-}
-
-// reads of memory no launch of this TU writes while it runs: scalar loads when the address is uniform (address space 4; the host pass
-// of the compiler only needs the types)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define VERIFY_TABLE_CONST_AS __attribute__((address_space(4)))
-#else
-#define VERIFY_TABLE_CONST_AS
-#endif
-template <class T> __device__ __forceinline__ const VERIFY_TABLE_CONST_AS T *as_const(const T *p) { return (const VERIFY_TABLE_CONST_AS T *)p; }
-struct Keys16 {
-    uint32_t v[16];
-};
-
-constexpr uint32_t kChunk = 65536; // the stream kernel's chunk: 4 words x 1024 threads x 16 bytes
-
-} // namespace
 
 // ---- plan: one thread per entry ----------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_verify_table_plan(VerifyTableArgs a)
 {
-    __shared__ uint64_t sc[kTableBlock];
-    __shared__ uint32_t sbad;
     const uint32_t tid = threadIdx.x;
     const uint64_t i = (uint64_t)blockIdx.x * kTableBlock + tid;
     if (blockIdx.x == 0 && tid == 0) {
@@ -82,98 +48,38 @@ __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_verify_table_plan(Ve
         a.sum->entries = a.n;
         a.sum->reserved = 0ull;
     }
-    if (tid == 0) sbad = 0;
     uint64_t cnt = 0;
     uint32_t bad = 0;
     if (i < a.n) {
         const CycleTableEntry E = a.entries[i];
-        const uintptr_t d = reinterpret_cast<uintptr_t>(E.dst); // the comparand: the chunk grid is laid on it
-        const uint64_t head = E.n < ((16 - (d & 15)) & 15) ? E.n : ((16 - (d & 15)) & 15);
-        const uint64_t words = (E.n - head) / 16;
-        const uint64_t tail = E.n - head - words * 16;
-        const uint32_t lead = (uint32_t)((d + head) & (kChunk - 1));
-        const uint64_t end = lead + words * 16;
-        cnt = words ? (end + kChunk - 1) / kChunk : 0;
-        bad = (E.n && (!E.dst || !E.src)) || E.flags != 0 || cnt > kTableMaxEntryChunks ? 1u : 0u;
-        if (bad) cnt = 0;
-        // states: key * a^(o + 1 + position), positions mod the period
-        const int64_t kr = (int64_t)E.key % (int64_t)lcg::M;
-        const uint32_t k = (uint32_t)(kr < 0 ? kr + lcg::M : kr);
-        const uint64_t o1 = E.stream_off % lcg::PERIOD + 1;
+        const TableGrid g = table_grid(E, E.flags); // (dst is the comparand: the chunk grid is laid on it)
+        cnt = g.cnt;
+        bad = g.bad;
         CycleTablePlan P;
-        P.dst_origin = reinterpret_cast<uint8_t *>(reinterpret_cast<uintptr_t>(E.dst) + head - lead); // (as integers: a refused entry's pointer may be NULL)
-        P.src_origin = reinterpret_cast<const uint8_t *>(reinterpret_cast<uintptr_t>(E.src) + head - lead);
-        P.end = end;
-        P.start = 0;
-        P.lead = lead;
-        P.chunks = (uint32_t)cnt;
-        P.base_head = mulmod_canon(k, pow_a((uint32_t)(o1 % lcg::PERIOD)));
-        P.base = mulmod_canon(k, pow_a((uint32_t)((o1 + head + lcg::PERIOD - lead) % lcg::PERIOD)));
-        P.base_tail = mulmod_canon(k, pow_a((uint32_t)((o1 + head + (words * 16) % lcg::PERIOD) % lcg::PERIOD)));
-        P.bad = bad;
-        P.head_n = (uint32_t)head;
-        P.tail_n = (uint32_t)tail;
+        table_plan_entry(P, E, g);
         a.plan[i] = P;
     }
-    sc[tid] = cnt;
-    __syncthreads();
-    if (bad) atomicOr(&sbad, 1u);
-    // inclusive scan of the 1024 counts (Hillis-Steele; every thread reaches every barrier)
-    for (uint32_t s = 1; s < kTableBlock; s <<= 1) {
-        const uint64_t v = tid >= s ? sc[tid - s] : 0;
-        __syncthreads();
-        sc[tid] += v;
-        __syncthreads();
-    }
-    if (i < a.n) a.plan[i].start = sc[tid] - cnt;
-    if (tid == kTableBlock - 1) {
-        a.blk[blockIdx.x].chunks = sc[tid];
-        a.blk[blockIdx.x].bad = sbad;
-    }
+    table_plan_store(a.plan, a.blk, a.n, i, cnt, bad, tid);
 }
 
 // ---- finish: global starts, the status, the search levels, the ragged edges compared, every result initialised ---------------------
 __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_verify_table_finish(VerifyTableArgs a)
 {
-    __shared__ uint64_t r_before[kTableBlock], r_total[kTableBlock];
-    __shared__ uint32_t sbad;
     const uint32_t tid = threadIdx.x;
     const uint32_t b = blockIdx.x;
     const uint64_t i = (uint64_t)b * kTableBlock + tid;
-    if (tid == 0) sbad = 0;
-    uint64_t before = 0, total = 0;
-    uint32_t bad = 0;
-    for (uint32_t k = tid; k < a.n_blk; k += kTableBlock) {
-        const uint64_t c = a.blk[k].chunks;
-        total += c;
-        before += k < b ? c : 0;
-        bad |= a.blk[k].bad;
-    }
-    r_before[tid] = before;
-    r_total[tid] = total;
-    __syncthreads();
-    if (bad) atomicOr(&sbad, 1u);
-    for (uint32_t s = kTableBlock / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            r_before[tid] += r_before[tid + s];
-            r_total[tid] += r_total[tid + s];
-        }
-        __syncthreads();
-    }
-    before = r_before[0];
-    total = r_total[0];
-    const bool ok = sbad == 0 && total <= kTableMaxChunks;
-    if (b == 0 && tid == 0) a.hdr->total = ok ? total : 0;
+    const TableTotals T = table_totals(a.blk, a.n_blk, b, tid);
+    const bool ok = T.bad == 0 && T.total <= kTableMaxChunks;
+    if (b == 0 && tid == 0) a.hdr->total = ok ? T.total : 0;
     if (i < a.n) {
         const CycleTablePlan P = a.plan[i];
-        const uint64_t start = before + P.start;
+        const uint64_t start = T.before + P.start;
         if (!ok) {
             // refused: no result is written; the lowest bad entry -- a refused one, or the first whose chunks pass the ticket range
             if (P.bad || start + P.chunks > kTableMaxChunks) atomicMin((unsigned long long *)&a.hdr->first_bad, (unsigned long long)i);
         } else {
             a.plan[i].start = start;
-            for (uint32_t k = 0; k < kTableLevels; ++k)
-                if (k <= a.top && (i & ((1ull << (4 * k)) - 1)) == 0) a.level[k][i >> (4 * k)] = (uint32_t)start;
+            for (uint32_t k = 0; k < kTableLevels; ++k) table_set_level(a.level[k], k, a.top, i, start);
             // the < 16 bytes in front of the body and behind it, compared bytewise; the index counts from the entry's first byte
             const uint8_t *sb = P.src_origin + P.lead;
             const uint8_t *eb = P.dst_origin + P.lead;
@@ -210,54 +116,11 @@ __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_verify_table_finish(
             }
         }
     }
-    // each level padded with ~0 to a whole line of 16 keys: the descent reads 16 at a time
     if (ok && b == 0 && tid < 16)
-        for (uint32_t k = 0; k < kTableLevels; ++k)
-            if (k <= a.top && a.level_n[k] + tid < ((a.level_n[k] + 15) & ~15ull)) a.level[k][a.level_n[k] + tid] = ~0u;
+        for (uint32_t k = 0; k < kTableLevels; ++k) table_pad_level(a.level[k], a.level_n[k], k, a.top, tid);
 }
 
 // ---- stream ------------------------------------------------------------------------------------------------------------------------
-namespace {
-struct Raw {
-    u32x4 d;
-    uint32_t e; // the dword after d, read when the chunk's source is not dword-aligned
-};
-__device__ __forceinline__ u32x4 funnel(const Raw &w, uint32_t sh) // sh == 0: alignbyte by 0 is the low dword itself
-{
-    u32x4 d;
-    d.x = __builtin_amdgcn_alignbyte(w.d.y, w.d.x, sh);
-    d.y = __builtin_amdgcn_alignbyte(w.d.z, w.d.y, sh);
-    d.z = __builtin_amdgcn_alignbyte(w.d.w, w.d.z, sh);
-    d.w = __builtin_amdgcn_alignbyte(w.e, w.d.w, sh);
-    return d;
-}
-
-// what a lane has found in the entry its workgroup is in: mismatching bytes and the lowest of their indices
-struct Found {
-    uint32_t cnt;
-    unsigned long long first;
-};
-// number of nonzero bytes of a dword
-__device__ __forceinline__ uint32_t nonzero_bytes(uint32_t w)
-{
-    w |= w >> 4;
-    w |= w >> 2;
-    w |= w >> 1;
-    return (uint32_t)__builtin_popcount(w & 0x01010101u);
-}
-// the slow path: x != 0 is one word's difference, at `pos` bytes from the chunk's origin; `low` = the lowest such position so far
-__device__ __forceinline__ void note_word(uint32_t &cnt, uint32_t &low, u32x4 x, uint32_t pos)
-{
-    cnt += nonzero_bytes(x.x) + nonzero_bytes(x.y) + nonzero_bytes(x.z) + nonzero_bytes(x.w);
-    uint32_t b = 12u + ((uint32_t)__builtin_ctz(x.w | 0x80000000u) >> 3);
-    if (x.z) b = 8u + ((uint32_t)__builtin_ctz(x.z) >> 3);
-    if (x.y) b = 4u + ((uint32_t)__builtin_ctz(x.y) >> 3);
-    if (x.x) b = (uint32_t)__builtin_ctz(x.x) >> 3;
-    low = pos + b < low ? pos + b : low;
-}
-__device__ __forceinline__ uint32_t any_bits(u32x4 x) { return x.x | x.y | x.z | x.w; }
-} // namespace
-
 template <int U, int BLOCK>
 __global__ __launch_bounds__(BLOCK) MODGPU_KEEP_OFF_THE_FIXED_TEMPORARIES void modgpu_cycle_verify_table_kernel(VerifyTableArgs a)
 {
@@ -292,36 +155,19 @@ __global__ __launch_bounds__(BLOCK) MODGPU_KEEP_OFF_THE_FIXED_TEMPORARIES void m
         uint32_t j = 0;
         int k = (int)a.top;
 #pragma unroll 1
-        do { // (level 0 always exists)
-            const Keys16 keys = *as_const(reinterpret_cast<const Keys16 *>(a.level[k] + 16u * j));
-            uint32_t c = 0;
-#pragma unroll
-            for (int t = 0; t < 16; ++t) c += keys.v[t] <= g ? 1u : 0u;
-            j = 16u * j + c - 1u;
-        } while (--k >= 0);
+        do j = table_descend(a.level[k], j, g); // (level 0 always exists)
+        while (--k >= 0);
         const CycleTablePlan P = *as_const(a.plan + j);
         v.exp0 = P.dst_origin;
         v.src0 = P.src_origin;
-        v.lead_rem = P.lead | ((uint32_t)(P.end - (uint64_t)(P.chunks - 1u) * CHUNK) - 1u) << 16;
+        v.lead_rem = table_lead_rem(P);
         v.lo = (uint32_t)P.start;
         v.hi = (uint32_t)P.start + P.chunks;
         v.entry = j | (P.head_n << 24);
         v.lane_base = mulmod_canon(P.base, lane_mul);
     };
     // where chunk g lies: offset of its chunk from the entry's origin, the cut in front of the body (chunk 0 only), its bytes
-    struct Span {
-        uint64_t off;
-        uint32_t cut, bytes;
-    };
-    auto span = [&](uint32_t g, const View &v) {
-        Span s{0, 0, 0};
-        if (g >= total) return s; // past the last entry: zero-size descriptors, loads give 0
-        const uint32_t c = g - v.lo;
-        s.off = (uint64_t)c * CHUNK;
-        s.cut = c ? 0u : v.lead_rem & 0xFFFFu;
-        s.bytes = (c + 1u == v.hi - v.lo ? (v.lead_rem >> 16) + 1u : CHUNK) - s.cut;
-        return s;
-    };
+    auto span = [&](uint32_t g, const View &v) { return table_span_packed<CHUNK>(g, total, v); };
     View vb[NB];
 #pragma unroll
     for (int i = 0; i < NB; ++i) vb[i] = View{nullptr, nullptr, 0, 0, 0, ~0u, 1};
@@ -351,8 +197,8 @@ __global__ __launch_bounds__(BLOCK) MODGPU_KEEP_OFF_THE_FIXED_TEMPORARIES void m
 
     // What this lane found in the entry of the chunks compared since the last flush.
     Found f{0u, kVerifyNone};
-    // The workgroup leaves an entry (uniform: every wave comes here at the same chunk).  Each wave for itself, with no barrier: nothing
-    // found by any lane -- nothing done; else the wave's sum and minimum, and lane 0 sends them on.
+    // The workgroup leaves an entry (uniform: every wave comes here at the same chunk): each wave flushes for itself, with no barrier.
+    // (The summary is the line behind the header: a.sum.)
     auto flush = [&](uint32_t entry) {
         unsigned long long found = __builtin_amdgcn_ballot_w64(f.cnt != 0u);
         if (found != 0ull) {
@@ -474,13 +320,7 @@ template <int U, int BLOCK> struct VerifyTableShape {
     {
         hipLaunchKernelGGL((modgpu_cycle_verify_table_kernel<U, BLOCK>), dim3(grid), dim3(BLOCK), 0, stream, a);
     }
-    static const char *name() // as a profiler prints it
-    {
-        static char buf[96];
-        static const int n = std::snprintf(buf, sizeof buf, "modgpu_cycle_verify_table_kernel<%d, %d>", U, BLOCK);
-        (void)n;
-        return buf;
-    }
+    static const char *name() { return table_kernel_name<U, BLOCK>("modgpu_cycle_verify_table_kernel"); }
 };
 using VerifyTableStream = VerifyTableShape<4, 1024>; // the verify kernel's shape: 64 KiB chunks
 static_assert(VerifyTableStream::chunk == kChunk, "one chunk size for the plan and the stream");

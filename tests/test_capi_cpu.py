@@ -422,12 +422,12 @@ def test_isa_check_covers_every_tu_and_the_plan_guards_the_main_pair():
     hashed ones (test_kernel_source_hash_matches_sources)."""
     runs = ["cycle_kernel.s cycle_feed_kernel.s", "cycle_to_kernel.s", "cycle_xfer_kernel.s", "cycle_rekey_kernel.s", "cycle_table_kernel.s",
             "cycle_rekey_table_kernel.s", "cycle_verify_kernel.s", "cycle_verify_table_kernel.s", "cycle_rekey_verify_kernel.s",
-            "cycle_keep_kernel.s", "cycle_rekey_verify_table_kernel.s"]
+            "cycle_keep_kernel.s", "cycle_rekey_verify_table_kernel.s", "cycle_rekey_move_table_kernel.s"]
     assert [ln for ln in B.dry_run("isa-check") if ln.startswith("python3 check_isa.py")] == ["python3 check_isa.py " + r for r in runs]
     good = subprocess.run(["make", "-s", "-C", B.CSRC, "isa-check"], capture_output=True, text=True, timeout=900)
     assert good.returncode == 0, good.stdout[-3000:] + good.stderr[-2000:]
     assert [ln for ln in good.stdout.splitlines() if ln.startswith("check_isa:")] == [
-        f"check_isa: ok ({n} kernels)" for n in (4, 2, 4, 2, 3, 3, 5, 3, 2, 1, 3)], good.stdout
+        f"check_isa: ok ({n} kernels)" for n in (4, 2, 4, 2, 3, 3, 5, 3, 2, 1, 3, 5)], good.stdout
     flag = "-amdgpu-atomic-optimizer-strategy=None"
     assert flag in B.make_var("KERNEL_FLAGS").split()
     plan = B.dry_run("all")
@@ -435,9 +435,9 @@ def test_isa_check_covers_every_tu_and_the_plan_guards_the_main_pair():
     links = [ln.split() for ln in plan if " -shared " in ln and " -o ../libmodgpu.so " in ln]
     assert len(links) == 1, links
     linked = {w[:-2] for w in links[0] if w.startswith("cycle_") and w.endswith("_kernel.o")}
-    assert len(linked) == 12 and linked == {f[:-2] for r in runs for f in r.split()}, (sorted(linked), runs)
+    assert len(linked) == 13 and linked == {f[:-2] for r in runs for f in r.split()}, (sorted(linked), runs)
     ticket = {"cycle_kernel", "cycle_to_kernel", "cycle_rekey_kernel", "cycle_table_kernel", "cycle_rekey_table_kernel", "cycle_verify_table_kernel",
-              "cycle_keep_kernel", "cycle_rekey_verify_table_kernel"}
+              "cycle_keep_kernel", "cycle_rekey_verify_table_kernel", "cycle_rekey_move_table_kernel"}
     plain = {"cycle_feed_kernel", "cycle_xfer_kernel", "cycle_verify_kernel", "cycle_rekey_verify_kernel"}
     assert ticket | plain == linked
     for tu in sorted(ticket | plain):

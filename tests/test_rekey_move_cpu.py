@@ -82,8 +82,8 @@ def test_validation_comes_before_the_device(modgpu):
 def test_codegen_guard_still_passes_and_the_standin_is_wired():
     B.isa_check_target("isa-check-rekey", 2)
     B.standin_is_wired("standin_launch_rekey_move.cpp")
-    # not a row of the TU table: the kernel objects of the link line are the twelve they were
-    assert "rekey_move" not in B.make_var("KERNEL_OBJS") and len(B.make_var("KERNEL_OBJS").split()) == 12
+    # not a row of the TU table (the move loop is part of the rekey TU's kernel): no object of its own among the thirteen
+    assert "cycle_rekey_move_kernel.o" not in B.make_var("KERNEL_OBJS").split() and len(B.make_var("KERNEL_OBJS").split()) == 13
 
 
 def test_codegen_guard_rules_of_the_move_loop_on_altered_assembly():

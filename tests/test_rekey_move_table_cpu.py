@@ -20,7 +20,7 @@ CSRC = os.path.join(ROOT, "modulate_amd", "csrc")
 PUBLIC = ("modgpu_rekey_move_table_workspace_bytes", "modgpu_rekey_move_table_device", "modgpu_rekey_move_table_validate", "modgpu_rekey_move_table_status")
 TESTING = ("modgpu_rekey_move_table_kernel_source_hash",)
 DEBUG = "modgpu_debug_set_move_table_grid"
-SRC = ("cycle_rekey_move_table_kernel.hip", "cycle_rekey_move_table_kernel.h", "cycle_rekey_table_kernel.h", "cycle_table_kernel.h", "cycle_rekey_impl.h",
+SRC = ("cycle_rekey_move_table_kernel.hip", "cycle_table_impl.h", "cycle_rekey_move_table_kernel.h", "cycle_rekey_table_kernel.h", "cycle_table_kernel.h", "cycle_rekey_impl.h",
        "cycle_kernel_impl.h", "cycle_kernel.h", "lcg.h")
 CHUNK = 65536
 MAX_ENTRIES = 1 << 22
@@ -69,11 +69,11 @@ def test_layouts_are_reused():
 def test_source_list_hash_and_row(modgpu):
     assert tuple(B.make_var("REKEY_MOVE_TABLE_SRC").split()) == SRC
     assert "cycle_rekey_move_table_kernel.h" in B.make_var("CAPI_HDR").split()
-    # written out next to the table, not a row of it (the rows are pinned by tests/test_capi_cpu.py): its object is on both link lines
-    assert B.make_var("MOVE_TABLE_OBJ") == "rekey_move_table_tu.o" and "rekey_move_table" not in B.make_var("TUS")
+    # a row of the Makefile's table of TUs like every other: its object is on both link lines, once
+    assert "rekey_move_table" in B.make_var("TUS").split() and "cycle_rekey_move_table_kernel.o" in B.make_var("KERNEL_OBJS").split()
     for lib in ("libmodgpu.so", "libmodgpu_testing.so"):
         links = [ln.split() for ln in B.dry_run("all") if " -shared " in ln and f" -o ../{lib} " in ln]
-        assert len(links) == 1 and "rekey_move_table_tu.o" in links[0], links
+        assert len(links) == 1 and links[0].count("cycle_rekey_move_table_kernel.o") == 1, links
     h = hashlib.sha256()
     for f in SRC:
         h.update(open(os.path.join(CSRC, f), "rb").read())
@@ -202,14 +202,12 @@ def test_tier_1_comes_before_the_device(modgpu):
 def test_codegen_guard_passes_and_the_standin_is_wired():
     B.isa_check_target("isa-check-rekey-move-table", 5)
     # the object waits for its guard, which ISA_CHECK=0 leaves out without touching a stamp
-    plan = B.dry_run("rekey_move_table_tu.o")
+    B.guard_then_compile("cycle_rekey_move_table_kernel")
+    B.unguarded_plan("cycle_rekey_move_table_kernel")
+    # `isa-check`, the aggregate of every TU, runs this one's guard, once
     guard = "python3 check_isa.py cycle_rekey_move_table_kernel.s"
-    assert guard in plan and plan.index(guard) < next(i for i, ln in enumerate(plan) if " -c cycle_rekey_move_table_kernel.hip " in ln), plan
-    plan = B.dry_run("rekey_move_table_tu.o", ISA_CHECK="0")
-    assert not any("check_isa.py" in ln or ln.startswith("touch") for ln in plan) and any(" -c cycle_rekey_move_table_kernel.hip " in ln for ln in plan), plan
-    # `isa-check-all` is the aggregate of every TU and this one
-    runs = [ln for ln in B.dry_run("isa-check-all") if ln.startswith("python3 check_isa.py")]
-    assert len(runs) == 12 and runs[-1] == guard and runs[:-1] == [ln for ln in B.dry_run("isa-check") if ln.startswith("python3 check_isa.py")], runs
+    runs = [ln for ln in B.dry_run("isa-check") if ln.startswith("python3 check_isa.py")]
+    assert len(runs) == 12 and runs.count(guard) == 1, runs
     B.standin_is_wired("standin_launch_rekey_move_table.cpp")
     flag = "-amdgpu-atomic-optimizer-strategy=None"
     for step in ("-S --cuda-device-only", "-c"):

@@ -18,7 +18,7 @@ CSRC = os.path.join(ROOT, "modulate_amd", "csrc")
 PUBLIC = ("modgpu_rekey_table_workspace_bytes", "modgpu_rekey_table_device", "modgpu_rekey_table_validate")
 TESTING = ("modgpu_time_rekey_table_device", "modgpu_rekey_table_kernel_source_hash")
 DEBUG = "modgpu_debug_set_rekey_table_grid"
-REKEY_TABLE_SRC = ("cycle_rekey_table_kernel.hip", "cycle_rekey_table_kernel.h", "cycle_table_kernel.h", "cycle_rekey_impl.h",
+REKEY_TABLE_SRC = ("cycle_rekey_table_kernel.hip", "cycle_table_impl.h", "cycle_rekey_table_kernel.h", "cycle_table_kernel.h", "cycle_rekey_impl.h",
                    "cycle_kernel_impl.h", "cycle_kernel.h", "lcg.h")
 
 
@@ -75,7 +75,7 @@ def test_source_hashes(modgpu):
     assert modgpu.rekey_kernel_source_hash() == _sha(("cycle_rekey_kernel.hip", "cycle_rekey_kernel.h", "cycle_rekey_impl.h", "cycle_kernel_impl.h",
                                                      "cycle_kernel.h", "lcg.h"))
     assert modgpu.feed_kernel_source_hash() == _sha(("cycle_feed_kernel.hip", "cycle_feed_kernel.h", "cycle_kernel_impl.h", "lcg.h"))
-    assert modgpu.table_kernel_source_hash() == _sha(("cycle_table_kernel.hip", "cycle_table_kernel.h", "cycle_kernel_impl.h", "cycle_kernel.h", "lcg.h"))
+    assert modgpu.table_kernel_source_hash() == _sha(("cycle_table_kernel.hip", "cycle_table_impl.h", "cycle_table_kernel.h", "cycle_kernel_impl.h", "cycle_kernel.h", "lcg.h"))
     assert len({modgpu.rekey_table_kernel_source_hash(), modgpu.table_kernel_source_hash(), modgpu.rekey_kernel_source_hash()}) == 3
 
 

@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "modulate_amd", "csrc")
 PUBLIC = ("modgpu_table_workspace_bytes", "modgpu_cycle_table_device", "modgpu_table_status", "modgpu_table_validate")
 TESTING = ("modgpu_time_cycle_table_device", "modgpu_table_kernel_source_hash")
-TABLE_SRC = ("cycle_table_kernel.hip", "cycle_table_kernel.h", "cycle_kernel_impl.h", "cycle_kernel.h", "lcg.h")
+TABLE_SRC = ("cycle_table_kernel.hip", "cycle_table_impl.h", "cycle_table_kernel.h", "cycle_kernel_impl.h", "cycle_kernel.h", "lcg.h")
 
 
 def _sha(files):
@@ -177,6 +177,21 @@ def test_codegen_guard_of_the_new_tu():
     B.unguarded_plan("cycle_table_kernel")
     B.standin_is_wired("standin_launch_table.cpp")
     assert tuple(B.make_var("TABLE_SRC").split()) == TABLE_SRC
+
+
+def test_the_table_tus_share_one_copy_of_their_device_code():
+    """The five table TUs take what they have in common from cycle_table_impl.h: each of these lines of it -- the power tables, the line
+    of 16 keys, the funnel, mulmod_keep, the descent's count -- is in that header and in none of the five .hip files, and every one of
+    the five source lists (so every one of the five hashes) names the header."""
+    header = "cycle_table_impl.h"
+    tus = {"TABLE_SRC": "cycle_table_kernel.hip", "REKEY_TABLE_SRC": "cycle_rekey_table_kernel.hip", "VERIFY_TABLE_SRC": "cycle_verify_table_kernel.hip",
+           "REKEY_VERIFY_TABLE_SRC": "cycle_rekey_verify_table_kernel.hip", "REKEY_MOVE_TABLE_SRC": "cycle_rekey_move_table_kernel.hip"}
+    text = {f: open(os.path.join(CSRC, f)).read() for f in [header] + list(tus.values())}
+    for token in ("make_pow_table<256>(1)", "struct Keys16", "__builtin_amdgcn_alignbyte(w.e", "mul_fold(x, 2u * y)", "keys.v[t] <= g"):
+        assert [f for f, t in text.items() if token in t] == [header], token
+    for var, hip in tus.items():
+        src = B.make_var(var).split()
+        assert src[0] == hip and src.count(header) == 1 and f'#include "{header}"' in text[hip], var
 
 
 def test_codegen_guard_rules_on_altered_assembly():

@@ -17,7 +17,7 @@ CSRC = os.path.join(ROOT, "modulate_amd", "csrc")
 PUBLIC = ("modgpu_verify_rekey_table_workspace_bytes", "modgpu_verify_rekey_table_device")
 TESTING = ("modgpu_time_verify_rekey_table_device", "modgpu_rekey_verify_table_kernel_source_hash")
 DEBUG = ("modgpu_debug_set_rekey_verify_table_grid",)
-REKEY_VERIFY_TABLE_SRC = ("cycle_rekey_verify_table_kernel.hip", "cycle_rekey_verify_table_kernel.h", "cycle_rekey_table_kernel.h",
+REKEY_VERIFY_TABLE_SRC = ("cycle_rekey_verify_table_kernel.hip", "cycle_table_impl.h", "cycle_rekey_verify_table_kernel.h", "cycle_rekey_table_kernel.h",
                           "cycle_verify_table_kernel.h", "cycle_table_kernel.h", "cycle_verify_kernel.h", "cycle_rekey_impl.h",
                           "cycle_kernel_impl.h", "cycle_kernel.h", "lcg.h")
 MAX_ENTRIES = 1 << 22  # MODGPU_TABLE_MAX_ENTRIES

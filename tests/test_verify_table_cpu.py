@@ -12,7 +12,7 @@ import _csrc_build as B
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "modulate_amd", "csrc")
-VERIFY_TABLE_SRC = ("cycle_verify_table_kernel.hip", "cycle_verify_table_kernel.h", "cycle_table_kernel.h", "cycle_verify_kernel.h",
+VERIFY_TABLE_SRC = ("cycle_verify_table_kernel.hip", "cycle_table_impl.h", "cycle_verify_table_kernel.h", "cycle_table_kernel.h", "cycle_verify_kernel.h",
                     "cycle_kernel_impl.h", "cycle_kernel.h", "lcg.h")
 MAX_ENTRIES = 1 << 22  # MODGPU_TABLE_MAX_ENTRIES
 
