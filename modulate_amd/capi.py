@@ -799,6 +799,34 @@ def table_status(workspace, device=-1):
     return None
 
 
+def _table_arg(entries, dtype, n, device, own, validate=None, needed="n (the entry count) is", known=True):
+    """The table of a *_table_device call, as (address, n, host array or None): a host array is checked with `validate` and uploaded
+    (the buffer joins `own`; an empty one is not, and has no address: the caller returns); a table already in device memory needs n,
+    and whatever else the caller says is `known` -- its address goes to the library as it is, which refuses a NULL one."""
+    if isinstance(entries, np.ndarray):
+        t = np.ascontiguousarray(entries, dtype=dtype)
+        if validate:
+            validate(t)
+        if t.size == 0:
+            return None, 0, t
+        buf = DeviceBuffer(t.nbytes, device)
+        own.append(buf)
+        buf.upload(t.view(np.uint8))
+        return buf.ptr, t.size, t
+    if n is None or not known:
+        raise TypeError(f"{needed} needed for a table in device memory")
+    return _dev_addr(entries), n, None
+
+
+def _workspace_arg(workspace, n, need, device, own):
+    """The workspace of a *_table_device call, as (address, bytes): None makes one of need() bytes (it joins `own`)."""
+    if workspace is None and n:
+        workspace = DeviceBuffer(need(), device)
+        own.append(workspace)
+    ws = _dev_addr(workspace) if workspace is not None else 0
+    return ws, workspace.nbytes if isinstance(workspace, DeviceBuffer) else need()
+
+
 def cycle_table_device(entries, workspace=None, device=-1, stream=None, check=True, *, n=None):
     """Cycles a TABLE of out-of-place entries -- dst_i[j] = src_i[j] ^ ks(key_i)[stream_off_i + j] -- in three launches, whatever its
     length.  `entries` is a host table (a TABLE_DTYPE array: uploaded, and checked with table_validate first unless check=False) or a
@@ -808,26 +836,10 @@ def cycle_table_device(entries, workspace=None, device=-1, stream=None, check=Tr
     call is asynchronous on `stream` and table_status(workspace) tells the outcome after a synchronise."""
     own = []
     try:
-        if isinstance(entries, np.ndarray):
-            t = np.ascontiguousarray(entries, dtype=TABLE_DTYPE)
-            n = t.size
-            if check:
-                table_validate(t)
-            if n == 0:
-                return
-            buf = DeviceBuffer(t.nbytes, device)
-            own.append(buf)
-            buf.upload(t.view(np.uint8))
-            addr = buf.ptr
-        else:
-            if n is None:
-                raise TypeError("n (the entry count) is needed for a table in device memory")
-            addr = _dev_addr(entries)
-        if workspace is None and n:
-            workspace = DeviceBuffer(table_workspace_bytes(n), device)
-            own.append(workspace)
-        ws = _dev_addr(workspace) if workspace is not None else 0
-        ws_bytes = workspace.nbytes if isinstance(workspace, DeviceBuffer) else table_workspace_bytes(n)
+        addr, n, t = _table_arg(entries, TABLE_DTYPE, n, device, own, table_validate if check else None)
+        if t is not None and t.size == 0:
+            return
+        ws, ws_bytes = _workspace_arg(workspace, n, lambda: table_workspace_bytes(n), device, own)
         _check(lib().modgpu_cycle_table_device(_vp(addr), n, _vp(ws), ws_bytes, device, _vp(stream or 0)))
         if own:
             _check(lib().modgpu_sync(device, _vp(stream or 0)))
@@ -885,26 +897,10 @@ def rekey_table_device(entries, workspace=None, device=-1, stream=None, check=Tr
     entry; otherwise the call is asynchronous on `stream` and table_status(workspace) tells the outcome after a synchronise."""
     own = []
     try:
-        if isinstance(entries, np.ndarray):
-            t = np.ascontiguousarray(entries, dtype=REKEY_TABLE_DTYPE)
-            n = t.size
-            if check:
-                rekey_table_validate(t)
-            if n == 0:
-                return
-            buf = DeviceBuffer(t.nbytes, device)
-            own.append(buf)
-            buf.upload(t.view(np.uint8))
-            addr = buf.ptr
-        else:
-            if n is None:
-                raise TypeError("n (the entry count) is needed for a table in device memory")
-            addr = _dev_addr(entries)
-        if workspace is None and n:
-            workspace = DeviceBuffer(rekey_table_workspace_bytes(n), device)
-            own.append(workspace)
-        ws = _dev_addr(workspace) if workspace is not None else 0
-        ws_bytes = workspace.nbytes if isinstance(workspace, DeviceBuffer) else rekey_table_workspace_bytes(n)
+        addr, n, t = _table_arg(entries, REKEY_TABLE_DTYPE, n, device, own, rekey_table_validate if check else None)
+        if t is not None and t.size == 0:
+            return
+        ws, ws_bytes = _workspace_arg(workspace, n, lambda: rekey_table_workspace_bytes(n), device, own)
         _check(lib().modgpu_rekey_table_device(_vp(addr), n, _vp(ws), ws_bytes, device, _vp(stream or 0)))
         if own:
             _check(lib().modgpu_sync(device, _vp(stream or 0)))
@@ -976,28 +972,13 @@ def rekey_move_table_device(entries, total_bytes=None, workspace=None, device=-1
     asynchronous on `stream` and rekey_move_table_status(workspace) tells the outcome after a synchronise."""
     own = []
     try:
-        if isinstance(entries, np.ndarray):
-            t = np.ascontiguousarray(entries, dtype=REKEY_TABLE_DTYPE)
-            n = t.size
-            if check:
-                rekey_move_table_validate(t)
-            if n == 0:
-                return
-            if total_bytes is None:
-                total_bytes = int(t["n"].sum(dtype=np.uint64))
-            buf = DeviceBuffer(t.nbytes, device)
-            own.append(buf)
-            buf.upload(t.view(np.uint8))
-            addr = buf.ptr
-        else:
-            if n is None or total_bytes is None:
-                raise TypeError("n (the entry count) and total_bytes are needed for a table in device memory")
-            addr = _dev_addr(entries)
-        if workspace is None and n:
-            workspace = DeviceBuffer(rekey_move_table_workspace_bytes(n, total_bytes), device)
-            own.append(workspace)
-        ws = _dev_addr(workspace) if workspace is not None else 0
-        ws_bytes = workspace.nbytes if isinstance(workspace, DeviceBuffer) else rekey_move_table_workspace_bytes(n, total_bytes)
+        addr, n, t = _table_arg(entries, REKEY_TABLE_DTYPE, n, device, own, rekey_move_table_validate if check else None,
+                                "n (the entry count) and total_bytes are", total_bytes is not None)
+        if t is not None and t.size == 0:
+            return
+        if total_bytes is None:
+            total_bytes = int(t["n"].sum(dtype=np.uint64))
+        ws, ws_bytes = _workspace_arg(workspace, n, lambda: rekey_move_table_workspace_bytes(n, total_bytes), device, own)
         _check(lib().modgpu_rekey_move_table_device(_vp(addr), n, total_bytes, _vp(ws), ws_bytes, device, _vp(stream or 0)))
         if own:
             _check(lib().modgpu_sync(device, _vp(stream or 0)))
@@ -1195,27 +1176,13 @@ def verify_table_device(entries, results=None, workspace=None, device=-1, stream
     verify_table_summary(workspace) and verify_results(results, n) tell the outcome after a synchronise."""
     own = []
     try:
-        if isinstance(entries, np.ndarray):
-            t = np.ascontiguousarray(entries, dtype=TABLE_DTYPE)
-            n = t.size
-            if n == 0:
-                return np.zeros(0, dtype=VERIFY_RESULT_DTYPE)
-            buf = DeviceBuffer(t.nbytes, device)
-            own.append(buf)
-            buf.upload(t.view(np.uint8))
-            addr = buf.ptr
-        else:
-            if n is None:
-                raise TypeError("n (the entry count) is needed for a table in device memory")
-            addr = _dev_addr(entries)
+        addr, n, t = _table_arg(entries, TABLE_DTYPE, n, device, own)
+        if t is not None and t.size == 0:
+            return np.zeros(0, dtype=VERIFY_RESULT_DTYPE)
         if results is None and n:
             results = DeviceBuffer(n * VERIFY_RESULT_DTYPE.itemsize, device)
             own.append(results)
-        if workspace is None and n:
-            workspace = DeviceBuffer(verify_table_workspace_bytes(n), device)
-            own.append(workspace)
-        ws = _dev_addr(workspace) if workspace is not None else 0
-        ws_bytes = workspace.nbytes if isinstance(workspace, DeviceBuffer) else verify_table_workspace_bytes(n)
+        ws, ws_bytes = _workspace_arg(workspace, n, lambda: verify_table_workspace_bytes(n), device, own)
         res = _dev_addr(results) if results is not None else 0
         _check(lib().modgpu_verify_table_device(_vp(addr), n, _vp(res), _vp(ws), ws_bytes, device, _vp(stream or 0)))
         if not own:
@@ -1267,27 +1234,13 @@ def verify_rekey_table_device(entries, results=None, workspace=None, device=-1, 
     outcome after a synchronise."""
     own = []
     try:
-        if isinstance(entries, np.ndarray):
-            t = np.ascontiguousarray(entries, dtype=REKEY_TABLE_DTYPE)
-            n = t.size
-            if n == 0:
-                return np.zeros(0, dtype=VERIFY_RESULT_DTYPE)
-            buf = DeviceBuffer(t.nbytes, device)
-            own.append(buf)
-            buf.upload(t.view(np.uint8))
-            addr = buf.ptr
-        else:
-            if n is None:
-                raise TypeError("n (the entry count) is needed for a table in device memory")
-            addr = _dev_addr(entries)
+        addr, n, t = _table_arg(entries, REKEY_TABLE_DTYPE, n, device, own)
+        if t is not None and t.size == 0:
+            return np.zeros(0, dtype=VERIFY_RESULT_DTYPE)
         if results is None and n:
             results = DeviceBuffer(n * VERIFY_RESULT_DTYPE.itemsize, device)
             own.append(results)
-        if workspace is None and n:
-            workspace = DeviceBuffer(verify_rekey_table_workspace_bytes(n), device)
-            own.append(workspace)
-        ws = _dev_addr(workspace) if workspace is not None else 0
-        ws_bytes = workspace.nbytes if isinstance(workspace, DeviceBuffer) else verify_rekey_table_workspace_bytes(n)
+        ws, ws_bytes = _workspace_arg(workspace, n, lambda: verify_rekey_table_workspace_bytes(n), device, own)
         res = _dev_addr(results) if results is not None else 0
         _check(lib().modgpu_verify_rekey_table_device(_vp(addr), n, _vp(res), _vp(ws), ws_bytes, device, _vp(stream or 0)))
         if not own:

@@ -1463,94 +1463,306 @@ void store_le32(uint8_t *p, uint32_t v)
 }
 
 } // namespace
-// ---- a table of out-of-place entries in device memory (modgpu_cycle_table_device) --------------------------------------------------
+// ---- the five calls over a table in device memory: modgpu_cycle_table_device, modgpu_rekey_table_device, modgpu_verify_table_device,
+// modgpu_verify_rekey_table_device (three launches: plan, finish, stream) and modgpu_rekey_move_table_device (five).
+// One workspace walk, one set of grid hooks and one call body (table_call); a call is its layout, its launches and its names. --------
 namespace {
 static_assert(sizeof(modgpu_table_entry_t) == sizeof(CycleTableEntry) && offsetof(modgpu_table_entry_t, key) == offsetof(CycleTableEntry, key) &&
                   offsetof(modgpu_table_entry_t, flags) == offsetof(CycleTableEntry, flags),
               "the kernels read the public entry layout");
 static_assert(MODGPU_TABLE_MAX_ENTRIES == kTableMaxEntries, "one limit");
+static_assert(sizeof(modgpu_rekey_table_entry_t) == sizeof(RekeyTableEntry) && offsetof(modgpu_rekey_table_entry_t, off_to) == offsetof(RekeyTableEntry, off_to) &&
+                  offsetof(modgpu_rekey_table_entry_t, key_from) == offsetof(RekeyTableEntry, key_from) &&
+                  offsetof(modgpu_rekey_table_entry_t, key_to) == offsetof(RekeyTableEntry, key_to) &&
+                  offsetof(modgpu_rekey_table_entry_t, flags) == offsetof(RekeyTableEntry, flags) &&
+                  offsetof(modgpu_rekey_table_entry_t, reserved) == offsetof(RekeyTableEntry, reserved) && sizeof(modgpu_rekey_table_entry_t) == 56,
+              "the kernels read the public entry layout");
+static_assert(sizeof(RekeyTablePlan) == sizeof(CycleTablePlan), "the table call's layout holds the rekey plan records");
+static_assert(sizeof(modgpu_verify_table_summary_t) == 32 && offsetof(modgpu_verify_table_summary_t, first_bad_entry) == offsetof(VerifyTableSummary, first_bad_entry) &&
+                  offsetof(modgpu_verify_table_summary_t, entries) == offsetof(VerifyTableSummary, entries) &&
+                  offsetof(modgpu_verify_table_summary_t, reserved) == offsetof(VerifyTableSummary, reserved),
+              "the summary line starts with the public record");
+static_assert(sizeof(CycleTableHdr) == 64 && sizeof(MoveTableHdr) == 64 && sizeof(VerifyTableSummary) == 64, "the header and the summary are one line each");
 
-// Where everything of a call over n entries lies in its workspace (offsets from its start, each section on a 64-byte line): the header,
-// the 1024-entry records, the plan records, then the search levels -- level k holds ceil(n / 16^k) keys padded to a multiple of 16,
-// up to the first level of at most 16 keys (the top).
+// Where everything of a call over n entries lies in its workspace: offsets from its start, each section on a 64-byte line.  The header
+// comes first in every kind (modgpu_table_status reads them all), a verifying call's summary line right behind it
+// (modgpu_verify_table_summary).  A section the call does not have is 0.
 struct TableLayout {
-    uint64_t blk, plan, level[kTableLevels], level_n[kTableLevels], bytes;
+    uint64_t sum, blk, plan, edge, scratch, flags, win, level[kTableLevels], level_n[kTableLevels], cap, bytes;
     uint32_t top, n_blk;
 };
-TableLayout table_layout(uint64_t n)
+// The next section of a workspace: its offset; the cursor `at` moves past it to the next line
+uint64_t take(uint64_t &at, uint64_t bytes)
 {
-    TableLayout L{};
-    auto line = [](uint64_t x) { return (x + 63) & ~63ull; };
-    L.n_blk = (uint32_t)((n + kTableBlock - 1) / kTableBlock);
-    uint64_t at = sizeof(CycleTableHdr);
-    L.blk = at;
-    at = line(at + (uint64_t)L.n_blk * sizeof(CycleTableBlk));
-    L.plan = at;
-    at = line(at + n * sizeof(CycleTablePlan));
+    const uint64_t section = at;
+    at = (at + bytes + 63) & ~63ull;
+    return section;
+}
+// The search levels: level k holds ceil(n / 16^k) keys padded to a multiple of 16, up to the first level of at most 16 keys (the top)
+void take_levels(TableLayout &L, uint64_t &at, uint64_t n)
+{
     uint64_t cnt = n;
     for (uint32_t k = 0; k < (uint32_t)kTableLevels; ++k) {
-        L.level[k] = at;
+        L.level[k] = take(at, ((cnt + 15) & ~15ull) * sizeof(uint32_t));
         L.level_n[k] = cnt;
         L.top = k;
-        at = line(at + ((cnt + 15) & ~15ull) * sizeof(uint32_t));
         if (cnt <= 16) break;
         cnt = (cnt + 15) / 16;
     }
+}
+// The three-launch calls: header, [summary,] the 1024-entry records, the plan records, the search levels[, the edge states]
+TableLayout three_launch_layout(uint64_t n, bool summary, bool edges)
+{
+    TableLayout L{};
+    L.n_blk = (uint32_t)((n + kTableBlock - 1) / kTableBlock);
+    uint64_t at = sizeof(CycleTableHdr);
+    if (summary) L.sum = take(at, sizeof(VerifyTableSummary));
+    L.blk = take(at, (uint64_t)L.n_blk * sizeof(CycleTableBlk));
+    L.plan = take(at, n * sizeof(CycleTablePlan));
+    take_levels(L, at, n);
+    if (edges) L.edge = take(at, n * sizeof(RekeyTableEdge));
     L.bytes = at;
     return L;
 }
+TableLayout table_layout(uint64_t n) { return three_launch_layout(n, false, false); }
+TableLayout rekey_table_layout(uint64_t n) { return three_launch_layout(n, false, true); }
+TableLayout verify_table_layout(uint64_t n) { return three_launch_layout(n, true, false); }
+TableLayout rekey_verify_table_layout(uint64_t n) { return three_launch_layout(n, true, true); }
 
-// The stream launch's grid: the out-of-place kernel's (25 workgroups per 32 CUs; DESIGN.md 4.8 has the A/B against one per CU)
+// The move call: header, the 1024-entry records, the plan records, the edge states, 32 bytes of scratch per entry for the ragged ends,
+// one "loaded" flag and one window per chunk the call may have (total_bytes / 64 KiB + 2 per entry: a body of n bytes lies on at most
+// n / 64 KiB + 2 chunks of its destination), the search levels.
+uint64_t move_table_chunks(uint64_t n, uint64_t total_bytes) { return total_bytes / modgpu_rekey_move_table_chunk_bytes() + 2 * n; }
+TableLayout move_table_layout(uint64_t n, uint64_t total_bytes)
+{
+    uint64_t at = sizeof(MoveTableHdr);
+    TableLayout L{};
+    L.n_blk = (uint32_t)((n + kTableBlock - 1) / kTableBlock);
+    L.cap = move_table_chunks(n, total_bytes);
+    L.blk = take(at, (uint64_t)L.n_blk * sizeof(MoveTableBlk));
+    L.plan = take(at, n * sizeof(MoveTablePlan));
+    L.edge = take(at, n * sizeof(RekeyTableEdge));
+    L.scratch = take(at, n * kMoveTableScratch);
+    L.flags = take(at, L.cap * sizeof(uint32_t));
+    L.win = take(at, L.cap * sizeof(MoveTableWin));
+    take_levels(L, at, n);
+    L.bytes = at;
+    return L;
+}
+bool move_table_sizes_ok(uint64_t n, uint64_t total_bytes)
+{
+    return n != 0 && n <= kTableMaxEntries && total_bytes / modgpu_rekey_move_table_chunk_bytes() <= kTableMaxChunks - 2 * kTableMaxEntries;
+}
+
+// The grid of a call's stream (move) launch.  The out-of-place table takes the out-of-place kernel's (25 workgroups per 32 CUs;
+// DESIGN.md 4.8 has the A/B against one per CU); the others one workgroup per CU on every CU, as the rekey and verify kernels
+// (the move launch never gets more than the device holds at once).  modgpu_debug_set_*_table_grid forces one.
+enum TableCall { kCycleTable, kRekeyTable, kVerifyTable, kRekeyVerifyTable, kMoveTable, kTableCalls };
 #ifdef MODGPU_TESTING_HOOKS
-std::atomic<uint32_t> g_table_grid{0}; // modgpu_debug_set_table_grid
-uint32_t table_grid_forced() { return g_table_grid.load(std::memory_order_relaxed); }
+std::atomic<uint32_t> g_table_grid[kTableCalls] = {};
+uint32_t table_grid_forced(TableCall c) { return g_table_grid[c].load(std::memory_order_relaxed); }
+void force_table_grid(TableCall c, uint32_t grid) { g_table_grid[c].store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
 #else
-constexpr uint32_t table_grid_forced() { return 0; }
+constexpr uint32_t table_grid_forced(TableCall) { return 0; }
 #endif
+uint32_t table_grid(TableCall c)
+{
+    if (const uint32_t forced = table_grid_forced(c)) return forced;
+    if (c != kCycleTable) return std::max<uint32_t>(1, large_grid());
+    uint64_t cap = 0, helpers = 0;
+    queue_grid(0, large_grid(), &cap, &helpers);
+    return (uint32_t)std::max<uint64_t>(1, cap);
+}
 
-// Tier 1 (include/modgpu.h): everything checked before anything is queued; then the three launches on `stream`.
-int table_impl(const modgpu_table_entry_t *entries, uint64_t n, void *ws, uint64_t ws_bytes, int device, hipStream_t stream)
+// What a call is: which of the five (its grid), whether it verifies (it then writes `results`, which no other call looks at), and what
+// it is called -- in tier 1's words for a short workspace, and in modgpu_last_launch's report of its stream (move) launch
+struct TableKind {
+    TableCall call;
+    bool verifies;
+    const char *short_workspace;
+    const char *(*kernel)();
+    int variant;
+    uint32_t (*block)(), (*chunk_bytes)();
+    const char *source_hash;
+};
+// One launch of a call and what fail_hip calls it.  The launches take the grid by reference: the move launch lowers it to what the device
+// holds at once (the one in-out argument among them, so all of them get it rather than that launch a path of its own).
+template <class Args> struct TableLaunch {
+    const char *what;
+    hipError_t (*launch)(const Args &a, uint32_t &grid, hipStream_t stream);
+};
+template <class Args, hipError_t (*F)(const Args &, hipStream_t)> hipError_t no_grid(const Args &a, uint32_t &, hipStream_t s) { return F(a, s); }
+template <class Args, hipError_t (*F)(const Args &, uint32_t, hipStream_t)> hipError_t on_grid(const Args &a, uint32_t &grid, hipStream_t s) { return F(a, grid, s); }
+
+// A table call.  Tier 1 (include/modgpu.h): everything checked before anything is queued; then the launches on `stream`, in order.
+// `refused`: a refusal of the call's own, made right behind the limit (the move call's total_bytes), or nullptr;
+// `layout()` plans the workspace once the pointers are known to be sound; `bind(a, w, L)` puts the call's own sections into a.
+template <class Args, class Entry, size_t N, class Layout, class Bind>
+int table_call(const TableKind &kind, const TableLaunch<Args> (&launches)[N], const Entry *entries, uint64_t n, modgpu_verify_result_t *results,
+               const char *refused, void *ws, uint64_t ws_bytes, int device, hipStream_t stream, Layout layout, Bind bind)
 {
     if (n == 0) return MODGPU_OK;
     if (n > kTableMaxEntries) return fail(MODGPU_ERR_INVALID, "more than 4194304 entries (the table call's limit)");
+    if (refused) return fail(MODGPU_ERR_INVALID, refused);
     if (!entries || !ws) return fail(MODGPU_ERR_INVALID, "null table or workspace");
+    if (kind.verifies && !results) return fail(MODGPU_ERR_INVALID, "null results");
     if ((reinterpret_cast<uintptr_t>(entries) | reinterpret_cast<uintptr_t>(ws)) & 7) return fail(MODGPU_ERR_INVALID, "table or workspace not 8-byte aligned");
-    const TableLayout L = table_layout(n);
-    if (ws_bytes < L.bytes) return fail(MODGPU_ERR_INVALID, "workspace smaller than modgpu_table_workspace_bytes(n_entries)");
+    if (kind.verifies && (reinterpret_cast<uintptr_t>(results) & 7)) return fail(MODGPU_ERR_INVALID, "results not 8-byte aligned");
+    const TableLayout L = layout();
+    if (ws_bytes < L.bytes) return fail(MODGPU_ERR_INVALID, kind.short_workspace);
     DeviceScope scope(device);
     if (scope.rc) return scope.rc;
     int phys = -1;
     HIP_TRY(hipGetDevice(&phys));
-    if (modgpu_xfer_device_of(entries, n * sizeof(modgpu_table_entry_t)) != phys || modgpu_xfer_device_of(ws, L.bytes) != phys)
+    if (modgpu_xfer_device_of(entries, n * sizeof(Entry)) != phys || modgpu_xfer_device_of(ws, L.bytes) != phys)
         return fail(MODGPU_ERR_INVALID, "the table or the workspace is not device memory of the call's device");
+    if (kind.verifies && modgpu_xfer_device_of(results, n * sizeof(modgpu_verify_result_t)) != phys)
+        return fail(MODGPU_ERR_INVALID, "the results are not device memory of the call's device");
     uint8_t *const w = static_cast<uint8_t *>(ws);
-    CycleTableArgs a{};
-    a.entries = reinterpret_cast<const CycleTableEntry *>(entries);
+    Args a{};
+    a.entries = reinterpret_cast<decltype(a.entries)>(entries);
     a.n = n;
-    a.hdr = reinterpret_cast<CycleTableHdr *>(w);
-    a.blk = reinterpret_cast<CycleTableBlk *>(w + L.blk);
-    a.plan = reinterpret_cast<CycleTablePlan *>(w + L.plan);
+    a.hdr = reinterpret_cast<decltype(a.hdr)>(w);
+    a.blk = reinterpret_cast<decltype(a.blk)>(w + L.blk);
+    a.plan = reinterpret_cast<decltype(a.plan)>(w + L.plan);
     for (uint32_t k = 0; k <= L.top; ++k) {
         a.level[k] = reinterpret_cast<uint32_t *>(w + L.level[k]);
         a.level_n[k] = L.level_n[k];
     }
     a.top = L.top;
     a.n_blk = L.n_blk;
-    uint64_t cap = 0, helpers = 0;
-    queue_grid(0, large_grid(), &cap, &helpers);
-    if (table_grid_forced()) cap = table_grid_forced();
-    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, cap);
+    bind(a, w, L);
+    uint32_t grid = table_grid(kind.call);
     (void)hipGetLastError(); // (the launches report hipGetLastError: an earlier call's error must not be taken for theirs)
-    hipError_t e = modgpu_launch_table_plan(a, stream);
-    if (e != hipSuccess) return fail_hip(e, "table plan launch");
-    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    e = modgpu_launch_table_finish(a, stream);
-    if (e != hipSuccess) return fail_hip(e, "table finish launch");
-    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    e = modgpu_launch_table_stream(a, grid, stream);
-    if (e != hipSuccess) return fail_hip(e, "table stream launch");
-    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    t_last_launch = {modgpu_table_kernel_name(), CYCLE_TABLE, grid, modgpu_table_block(), modgpu_table_chunk_bytes(), 0, grid, MODGPU_TABLE_KERNEL_SOURCE_HASH};
+    for (const TableLaunch<Args> &l : launches) {
+        const hipError_t e = l.launch(a, grid, stream);
+        if (e != hipSuccess) return fail_hip(e, l.what);
+        g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    }
+    t_last_launch = {kind.kernel(), kind.variant, grid, kind.block(), kind.chunk_bytes(), 0, grid, kind.source_hash};
+    return MODGPU_OK;
+}
+
+int table_impl(const modgpu_table_entry_t *entries, uint64_t n, void *ws, uint64_t ws_bytes, int device, hipStream_t stream)
+{
+    using A = CycleTableArgs;
+    static constexpr TableKind kind = {kCycleTable, false, "workspace smaller than modgpu_table_workspace_bytes(n_entries)", modgpu_table_kernel_name, CYCLE_TABLE,
+                                         modgpu_table_block, modgpu_table_chunk_bytes, MODGPU_TABLE_KERNEL_SOURCE_HASH};
+    static constexpr TableLaunch<A> launches[] = {{"table plan launch", no_grid<A, modgpu_launch_table_plan>},
+                                                  {"table finish launch", no_grid<A, modgpu_launch_table_finish>},
+                                                  {"table stream launch", on_grid<A, modgpu_launch_table_stream>}};
+    return table_call(kind, launches, entries, n, nullptr, nullptr, ws, ws_bytes, device, stream, [&] { return table_layout(n); },
+                      [](A &, uint8_t *, const TableLayout &) {});
+}
+
+int rekey_table_impl(const modgpu_rekey_table_entry_t *entries, uint64_t n, void *ws, uint64_t ws_bytes, int device, hipStream_t stream)
+{
+    using A = RekeyTableArgs;
+    static constexpr TableKind kind = {kRekeyTable, false, "workspace smaller than modgpu_rekey_table_workspace_bytes(n_entries)", modgpu_rekey_table_kernel_name,
+                                         CYCLE_REKEY_TABLE, modgpu_rekey_table_block, modgpu_rekey_table_chunk_bytes, MODGPU_REKEY_TABLE_KERNEL_SOURCE_HASH};
+    static constexpr TableLaunch<A> launches[] = {{"rekey table plan launch", no_grid<A, modgpu_launch_rekey_table_plan>},
+                                                  {"rekey table finish launch", no_grid<A, modgpu_launch_rekey_table_finish>},
+                                                  {"rekey table stream launch", on_grid<A, modgpu_launch_rekey_table_stream>}};
+    return table_call(kind, launches, entries, n, nullptr, nullptr, ws, ws_bytes, device, stream, [&] { return rekey_table_layout(n); },
+                      [](A &a, uint8_t *w, const TableLayout &L) { a.edge = reinterpret_cast<RekeyTableEdge *>(w + L.edge); });
+}
+
+int verify_table_impl(const modgpu_table_entry_t *entries, uint64_t n, modgpu_verify_result_t *results, void *ws, uint64_t ws_bytes, int device,
+                      hipStream_t stream)
+{
+    using A = VerifyTableArgs;
+    static constexpr TableKind kind = {kVerifyTable, true, "workspace smaller than modgpu_verify_table_workspace_bytes(n_entries)", modgpu_verify_table_kernel_name,
+                                         CYCLE_VERIFY_TABLE, modgpu_verify_table_block, modgpu_verify_table_chunk_bytes, MODGPU_VERIFY_TABLE_KERNEL_SOURCE_HASH};
+    static constexpr TableLaunch<A> launches[] = {{"verify table plan launch", no_grid<A, modgpu_launch_verify_table_plan>},
+                                                  {"verify table finish launch", no_grid<A, modgpu_launch_verify_table_finish>},
+                                                  {"verify table stream launch", on_grid<A, modgpu_launch_verify_table_stream>}};
+    return table_call(kind, launches, entries, n, results, nullptr, ws, ws_bytes, device, stream, [&] { return verify_table_layout(n); },
+                      [&](A &a, uint8_t *w, const TableLayout &L) {
+                          a.sum = reinterpret_cast<VerifyTableSummary *>(w + L.sum);
+                          a.results = reinterpret_cast<CycleVerifyResult *>(results);
+                      });
+}
+
+int verify_rekey_table_impl(const modgpu_rekey_table_entry_t *entries, uint64_t n, modgpu_verify_result_t *results, void *ws, uint64_t ws_bytes,
+                            int device, hipStream_t stream)
+{
+    using A = RekeyVerifyTableArgs;
+    static constexpr TableKind kind = {kRekeyVerifyTable, true, "workspace smaller than modgpu_verify_rekey_table_workspace_bytes(n_entries)",
+                                         modgpu_rekey_verify_table_kernel_name, CYCLE_REKEY_VERIFY_TABLE, modgpu_rekey_verify_table_block,
+                                         modgpu_rekey_verify_table_chunk_bytes, MODGPU_REKEY_VERIFY_TABLE_KERNEL_SOURCE_HASH};
+    static constexpr TableLaunch<A> launches[] = {{"verify rekey table plan launch", no_grid<A, modgpu_launch_rekey_verify_table_plan>},
+                                                  {"verify rekey table finish launch", no_grid<A, modgpu_launch_rekey_verify_table_finish>},
+                                                  {"verify rekey table stream launch", on_grid<A, modgpu_launch_rekey_verify_table_stream>}};
+    return table_call(kind, launches, entries, n, results, nullptr, ws, ws_bytes, device, stream, [&] { return rekey_verify_table_layout(n); },
+                      [&](A &a, uint8_t *w, const TableLayout &L) {
+                          a.sum = reinterpret_cast<VerifyTableSummary *>(w + L.sum);
+                          a.edge = reinterpret_cast<RekeyTableEdge *>(w + L.edge);
+                          a.results = reinterpret_cast<CycleVerifyResult *>(results);
+                      });
+}
+
+hipError_t move_table_move(const MoveTableArgs &a, uint32_t &grid, hipStream_t s) { return modgpu_launch_rekey_move_table_move(a, &grid, s); }
+int rekey_move_table_impl(const modgpu_rekey_table_entry_t *entries, uint64_t n, uint64_t total_bytes, void *ws, uint64_t ws_bytes, int device,
+                          hipStream_t stream)
+{
+    using A = MoveTableArgs;
+    static constexpr TableKind kind = {kMoveTable, false, "workspace smaller than modgpu_rekey_move_table_workspace_bytes(n_entries, total_bytes)",
+                                         modgpu_rekey_move_table_kernel_name, CYCLE_REKEY_MOVE_TABLE, modgpu_rekey_move_table_block,
+                                         modgpu_rekey_move_table_chunk_bytes, MODGPU_REKEY_MOVE_TABLE_KERNEL_SOURCE_HASH};
+    static constexpr TableLaunch<A> launches[] = {{"rekey move table plan launch", no_grid<A, modgpu_launch_rekey_move_table_plan>},
+                                                  {"rekey move table finish launch", no_grid<A, modgpu_launch_rekey_move_table_finish>},
+                                                  {"rekey move table window launch", no_grid<A, modgpu_launch_rekey_move_table_window>},
+                                                  {"rekey move table move launch", move_table_move},
+                                                  {"rekey move table place launch", no_grid<A, modgpu_launch_rekey_move_table_place>}};
+    const char *refused = move_table_sizes_ok(n, total_bytes) ? nullptr : "total_bytes beyond 2^31 chunks of 64 KiB";
+    return table_call(kind, launches, entries, n, nullptr, refused, ws, ws_bytes, device, stream, [&] { return move_table_layout(n, total_bytes); },
+                      [](A &a, uint8_t *w, const TableLayout &L) {
+                          a.cap = L.cap;
+                          a.edge = reinterpret_cast<RekeyTableEdge *>(w + L.edge);
+                          a.scratch = w + L.scratch;
+                          a.flags = reinterpret_cast<uint32_t *>(w + L.flags);
+                          a.win = reinterpret_cast<MoveTableWin *>(w + L.win);
+                      });
+}
+
+// The first `bytes` of a table call's workspace (its header[, its summary line]) read back for modgpu_table_status and
+// modgpu_verify_table_summary: synchronous.  (modgpu_rekey_move_table_status keeps these steps written out: folded in as well, the
+// libraries' lists of exported symbols are no longer the ones they had -- a weak std::to_string instance drops out.)
+int read_workspace_top(const void *dev_workspace, bool out_pointers, int device, void *top, size_t bytes)
+{
+    if (!dev_workspace || !out_pointers) return fail(MODGPU_ERR_INVALID, "null workspace or out pointer");
+    DeviceScope scope(device);
+    if (scope.rc) return scope.rc;
+    int phys = -1;
+    HIP_TRY(hipGetDevice(&phys));
+    if (modgpu_xfer_device_of(dev_workspace, bytes) != phys) return fail(MODGPU_ERR_INVALID, "the workspace is not device memory of the call's device");
+    HIP_TRY(hipMemcpy(top, dev_workspace, bytes, hipMemcpyDeviceToHost));
+    return MODGPU_OK;
+}
+
+// `iters` calls of call(stream) between two events on `stream`, stopped at the first that fails: *ms_per_call = their mean
+// (include/modgpu_testing.h: the modgpu_time_*_device entry points)
+template <class Call> int time_calls(int device, void *hip_stream, int iters, float *ms_per_call, Call call)
+{
+    if (iters <= 0 || !ms_per_call) return fail(MODGPU_ERR_INVALID, "bad timing arguments");
+    DeviceScope scope(device);
+    if (scope.rc) return scope.rc;
+    int rc = MODGPU_OK;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    hipEvent_t e0, e1;
+    HIP_TRY(hipEventCreate(&e0));
+    HIP_TRY(hipEventCreate(&e1));
+    HIP_TRY(hipEventRecord(e0, st));
+    for (int i = 0; i < iters && rc == MODGPU_OK; ++i) rc = call(st);
+    hipError_t e = hipEventRecord(e1, st);
+    if (e == hipSuccess) e = hipEventSynchronize(e1);
+    float ms = 0.f;
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail_hip(e, "event timing");
+    *ms_per_call = ms / (float)iters;
     return MODGPU_OK;
 }
 
@@ -1611,198 +1823,6 @@ template <class Entry> int table_validate_impl(const Entry *t, uint64_t n)
     return MODGPU_OK;
 }
 
-// ---- a table of rekey entries in device memory (modgpu_rekey_table_device) ----------------------------------------------------------
-static_assert(sizeof(modgpu_rekey_table_entry_t) == sizeof(RekeyTableEntry) && offsetof(modgpu_rekey_table_entry_t, off_to) == offsetof(RekeyTableEntry, off_to) &&
-                  offsetof(modgpu_rekey_table_entry_t, key_from) == offsetof(RekeyTableEntry, key_from) &&
-                  offsetof(modgpu_rekey_table_entry_t, key_to) == offsetof(RekeyTableEntry, key_to) &&
-                  offsetof(modgpu_rekey_table_entry_t, flags) == offsetof(RekeyTableEntry, flags) &&
-                  offsetof(modgpu_rekey_table_entry_t, reserved) == offsetof(RekeyTableEntry, reserved) && sizeof(modgpu_rekey_table_entry_t) == 56,
-              "the kernels read the public entry layout");
-static_assert(sizeof(RekeyTablePlan) == sizeof(CycleTablePlan), "the table call's layout holds the rekey plan records");
-
-// The table call's layout (header, 1024-entry records, plan records, search levels) with the edge states behind it, on a line of
-// their own: the header comes first in both, so modgpu_table_status reads either kind of workspace.
-struct RekeyTableLayout {
-    TableLayout t;
-    uint64_t edge, bytes;
-};
-RekeyTableLayout rekey_table_layout(uint64_t n)
-{
-    RekeyTableLayout L{table_layout(n), 0, 0};
-    L.edge = L.t.bytes;
-    L.bytes = (L.edge + n * sizeof(RekeyTableEdge) + 63) & ~63ull;
-    return L;
-}
-
-// The stream launch's grid: one workgroup per CU on every CU, as the rekey kernel (DESIGN.md 4.9 has the A/B against the table
-// call's 25 per 32 CUs, and the rule that picked it)
-#ifdef MODGPU_TESTING_HOOKS
-std::atomic<uint32_t> g_rekey_table_grid{0}; // modgpu_debug_set_rekey_table_grid
-uint32_t rekey_table_grid_forced() { return g_rekey_table_grid.load(std::memory_order_relaxed); }
-#else
-constexpr uint32_t rekey_table_grid_forced() { return 0; }
-#endif
-uint32_t rekey_table_grid()
-{
-    if (rekey_table_grid_forced()) return rekey_table_grid_forced();
-    return std::max<uint32_t>(1, large_grid());
-}
-
-// Tier 1 (include/modgpu.h): everything checked before anything is queued; then the three launches on `stream`.
-int rekey_table_impl(const modgpu_rekey_table_entry_t *entries, uint64_t n, void *ws, uint64_t ws_bytes, int device, hipStream_t stream)
-{
-    if (n == 0) return MODGPU_OK;
-    if (n > kTableMaxEntries) return fail(MODGPU_ERR_INVALID, "more than 4194304 entries (the table call's limit)");
-    if (!entries || !ws) return fail(MODGPU_ERR_INVALID, "null table or workspace");
-    if ((reinterpret_cast<uintptr_t>(entries) | reinterpret_cast<uintptr_t>(ws)) & 7) return fail(MODGPU_ERR_INVALID, "table or workspace not 8-byte aligned");
-    const RekeyTableLayout L = rekey_table_layout(n);
-    if (ws_bytes < L.bytes) return fail(MODGPU_ERR_INVALID, "workspace smaller than modgpu_rekey_table_workspace_bytes(n_entries)");
-    DeviceScope scope(device);
-    if (scope.rc) return scope.rc;
-    int phys = -1;
-    HIP_TRY(hipGetDevice(&phys));
-    if (modgpu_xfer_device_of(entries, n * sizeof(modgpu_rekey_table_entry_t)) != phys || modgpu_xfer_device_of(ws, L.bytes) != phys)
-        return fail(MODGPU_ERR_INVALID, "the table or the workspace is not device memory of the call's device");
-    uint8_t *const w = static_cast<uint8_t *>(ws);
-    RekeyTableArgs a{};
-    a.entries = reinterpret_cast<const RekeyTableEntry *>(entries);
-    a.n = n;
-    a.hdr = reinterpret_cast<CycleTableHdr *>(w);
-    a.blk = reinterpret_cast<CycleTableBlk *>(w + L.t.blk);
-    a.plan = reinterpret_cast<RekeyTablePlan *>(w + L.t.plan);
-    a.edge = reinterpret_cast<RekeyTableEdge *>(w + L.edge);
-    for (uint32_t k = 0; k <= L.t.top; ++k) {
-        a.level[k] = reinterpret_cast<uint32_t *>(w + L.t.level[k]);
-        a.level_n[k] = L.t.level_n[k];
-    }
-    a.top = L.t.top;
-    a.n_blk = L.t.n_blk;
-    const uint32_t grid = rekey_table_grid();
-    (void)hipGetLastError(); // (the launches report hipGetLastError: an earlier call's error must not be taken for theirs)
-    hipError_t e = modgpu_launch_rekey_table_plan(a, stream);
-    if (e != hipSuccess) return fail_hip(e, "rekey table plan launch");
-    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    e = modgpu_launch_rekey_table_finish(a, stream);
-    if (e != hipSuccess) return fail_hip(e, "rekey table finish launch");
-    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    e = modgpu_launch_rekey_table_stream(a, grid, stream);
-    if (e != hipSuccess) return fail_hip(e, "rekey table stream launch");
-    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    t_last_launch = {modgpu_rekey_table_kernel_name(), CYCLE_REKEY_TABLE, grid, modgpu_rekey_table_block(), modgpu_rekey_table_chunk_bytes(), 0, grid,
-                     MODGPU_REKEY_TABLE_KERNEL_SOURCE_HASH};
-    return MODGPU_OK;
-}
-
-// ---- a table of rekey entries in device memory, moved with memmove rules (modgpu_rekey_move_table_device) -------------
-// The workspace: the table call's header first (modgpu_table_status reads it), then the 1024-entry records, the plan records, the
-// edge states, 32 bytes of scratch per entry for the ragged ends, one "loaded" flag and one window per chunk the call may have
-// (total_bytes / 64 KiB + 2 per entry: a body of n bytes lies on at most n / 64 KiB + 2 chunks of its destination), the search levels.
-struct MoveTableLayout {
-    uint32_t n_blk, top;
-    uint64_t cap, blk, plan, edge, scratch, flags, win, level[kTableLevels], level_n[kTableLevels], bytes;
-};
-uint64_t move_table_chunks(uint64_t n, uint64_t total_bytes) { return total_bytes / modgpu_rekey_move_table_chunk_bytes() + 2 * n; }
-MoveTableLayout move_table_layout(uint64_t n, uint64_t total_bytes)
-{
-    MoveTableLayout L{};
-    auto line = [](uint64_t x) { return (x + 63) & ~63ull; };
-    L.n_blk = (uint32_t)((n + kTableBlock - 1) / kTableBlock);
-    L.cap = move_table_chunks(n, total_bytes);
-    uint64_t at = sizeof(MoveTableHdr);
-    L.blk = at;
-    at = line(at + (uint64_t)L.n_blk * sizeof(MoveTableBlk));
-    L.plan = at;
-    at = line(at + n * sizeof(MoveTablePlan));
-    L.edge = at;
-    at = line(at + n * sizeof(RekeyTableEdge));
-    L.scratch = at;
-    at = line(at + n * kMoveTableScratch);
-    L.flags = at;
-    at = line(at + L.cap * sizeof(uint32_t));
-    L.win = at;
-    at = line(at + L.cap * sizeof(MoveTableWin));
-    uint64_t cnt = n;
-    for (uint32_t k = 0; k < (uint32_t)kTableLevels; ++k) {
-        L.level[k] = at;
-        L.level_n[k] = cnt;
-        L.top = k;
-        at = line(at + ((cnt + 15) & ~15ull) * sizeof(uint32_t));
-        if (cnt <= 16) break;
-        cnt = (cnt + 15) / 16;
-    }
-    L.bytes = at;
-    return L;
-}
-bool move_table_sizes_ok(uint64_t n, uint64_t total_bytes)
-{
-    return n != 0 && n <= kTableMaxEntries && total_bytes / modgpu_rekey_move_table_chunk_bytes() <= kTableMaxChunks - 2 * kTableMaxEntries;
-}
-
-// The move launch's grid: one workgroup per CU on every CU, as the rekey kernel (never more than the device holds at once)
-#ifdef MODGPU_TESTING_HOOKS
-std::atomic<uint32_t> g_move_table_grid{0}; // modgpu_debug_set_move_table_grid
-uint32_t move_table_grid_forced() { return g_move_table_grid.load(std::memory_order_relaxed); }
-#else
-constexpr uint32_t move_table_grid_forced() { return 0; }
-#endif
-
-// Tier 1 (include/modgpu.h): everything checked before anything is queued; then the five launches on `stream`.
-int rekey_move_table_impl(const modgpu_rekey_table_entry_t *entries, uint64_t n, uint64_t total_bytes, void *ws, uint64_t ws_bytes, int device,
-                          hipStream_t stream)
-{
-    if (n == 0) return MODGPU_OK;
-    if (n > kTableMaxEntries) return fail(MODGPU_ERR_INVALID, "more than 4194304 entries (the table call's limit)");
-    if (!move_table_sizes_ok(n, total_bytes)) return fail(MODGPU_ERR_INVALID, "total_bytes beyond 2^31 chunks of 64 KiB");
-    if (!entries || !ws) return fail(MODGPU_ERR_INVALID, "null table or workspace");
-    if ((reinterpret_cast<uintptr_t>(entries) | reinterpret_cast<uintptr_t>(ws)) & 7) return fail(MODGPU_ERR_INVALID, "table or workspace not 8-byte aligned");
-    const MoveTableLayout L = move_table_layout(n, total_bytes);
-    if (ws_bytes < L.bytes) return fail(MODGPU_ERR_INVALID, "workspace smaller than modgpu_rekey_move_table_workspace_bytes(n_entries, total_bytes)");
-    DeviceScope scope(device);
-    if (scope.rc) return scope.rc;
-    int phys = -1;
-    HIP_TRY(hipGetDevice(&phys));
-    if (modgpu_xfer_device_of(entries, n * sizeof(modgpu_rekey_table_entry_t)) != phys || modgpu_xfer_device_of(ws, L.bytes) != phys)
-        return fail(MODGPU_ERR_INVALID, "the table or the workspace is not device memory of the call's device");
-    uint8_t *const w = static_cast<uint8_t *>(ws);
-    MoveTableArgs a{};
-    a.entries = reinterpret_cast<const RekeyTableEntry *>(entries);
-    a.n = n;
-    a.cap = L.cap;
-    a.hdr = reinterpret_cast<MoveTableHdr *>(w);
-    a.blk = reinterpret_cast<MoveTableBlk *>(w + L.blk);
-    a.plan = reinterpret_cast<MoveTablePlan *>(w + L.plan);
-    a.edge = reinterpret_cast<RekeyTableEdge *>(w + L.edge);
-    a.scratch = w + L.scratch;
-    a.flags = reinterpret_cast<uint32_t *>(w + L.flags);
-    a.win = reinterpret_cast<MoveTableWin *>(w + L.win);
-    for (uint32_t k = 0; k <= L.top; ++k) {
-        a.level[k] = reinterpret_cast<uint32_t *>(w + L.level[k]);
-        a.level_n[k] = L.level_n[k];
-    }
-    a.top = L.top;
-    a.n_blk = L.n_blk;
-    uint32_t grid = move_table_grid_forced() ? move_table_grid_forced() : std::max<uint32_t>(1, large_grid());
-    (void)hipGetLastError(); // (the launches report hipGetLastError: an earlier call's error must not be taken for theirs)
-    hipError_t e = modgpu_launch_rekey_move_table_plan(a, stream);
-    if (e != hipSuccess) return fail_hip(e, "rekey move table plan launch");
-    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    e = modgpu_launch_rekey_move_table_finish(a, stream);
-    if (e != hipSuccess) return fail_hip(e, "rekey move table finish launch");
-    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    e = modgpu_launch_rekey_move_table_window(a, stream);
-    if (e != hipSuccess) return fail_hip(e, "rekey move table window launch");
-    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    e = modgpu_launch_rekey_move_table_move(a, &grid, stream);
-    if (e != hipSuccess) return fail_hip(e, "rekey move table move launch");
-    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    e = modgpu_launch_rekey_move_table_place(a, stream);
-    if (e != hipSuccess) return fail_hip(e, "rekey move table place launch");
-    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    t_last_launch = {modgpu_rekey_move_table_kernel_name(), CYCLE_REKEY_MOVE_TABLE, grid, modgpu_rekey_move_table_block(), modgpu_rekey_move_table_chunk_bytes(), 0, grid,
-                     MODGPU_REKEY_MOVE_TABLE_KERNEL_SOURCE_HASH};
-    return MODGPU_OK;
-}
-
 // Tiers 1 and 2 over a host copy, in O(n), as the device decides them: the direction is that of the first entry with dst != src, and
 // every non-empty entry is compared with the non-empty entry before it.  (The chunk count against the workspace is the one check that
 // needs total_bytes: it is not made here.)
@@ -1831,182 +1851,6 @@ int rekey_move_table_validate_impl(const modgpu_rekey_table_entry_t *t, uint64_t
         }
         prev = i;
     }
-    return MODGPU_OK;
-}
-
-// ---- a table of verify entries in device memory (modgpu_verify_table_device) --------------------------------------------------------
-static_assert(sizeof(modgpu_verify_table_summary_t) == 32 && offsetof(modgpu_verify_table_summary_t, first_bad_entry) == offsetof(VerifyTableSummary, first_bad_entry) &&
-                  offsetof(modgpu_verify_table_summary_t, entries) == offsetof(VerifyTableSummary, entries) &&
-                  offsetof(modgpu_verify_table_summary_t, reserved) == offsetof(VerifyTableSummary, reserved),
-              "the summary line starts with the public record");
-
-// The table call's layout with one line for the summary put in right behind the header (every later section 64 bytes further on): the
-// header comes first here too, so modgpu_table_status reads this kind of workspace.
-struct VerifyTableLayout {
-    TableLayout t; // offsets already moved
-    uint64_t sum, bytes;
-};
-VerifyTableLayout verify_table_layout(uint64_t n)
-{
-    VerifyTableLayout L{table_layout(n), sizeof(CycleTableHdr), 0};
-    constexpr uint64_t line = sizeof(VerifyTableSummary);
-    L.t.blk += line;
-    L.t.plan += line;
-    for (uint32_t k = 0; k <= L.t.top; ++k) L.t.level[k] += line;
-    L.t.bytes += line;
-    L.bytes = L.t.bytes;
-    return L;
-}
-
-// The stream launch's grid: one workgroup per CU on every CU, as the verify kernel (DESIGN.md 4.11 has the A/B against the table
-// call's 25 per 32 CUs)
-#ifdef MODGPU_TESTING_HOOKS
-std::atomic<uint32_t> g_verify_table_grid{0}; // modgpu_debug_set_verify_table_grid
-uint32_t verify_table_grid_forced() { return g_verify_table_grid.load(std::memory_order_relaxed); }
-#else
-constexpr uint32_t verify_table_grid_forced() { return 0; }
-#endif
-uint32_t verify_table_grid()
-{
-    if (verify_table_grid_forced()) return verify_table_grid_forced();
-    return std::max<uint32_t>(1, large_grid());
-}
-
-// Tier 1 (include/modgpu.h): everything checked before anything is queued; then the three launches on `stream`.
-int verify_table_impl(const modgpu_table_entry_t *entries, uint64_t n, modgpu_verify_result_t *results, void *ws, uint64_t ws_bytes, int device,
-                      hipStream_t stream)
-{
-    if (n == 0) return MODGPU_OK;
-    if (n > kTableMaxEntries) return fail(MODGPU_ERR_INVALID, "more than 4194304 entries (the table call's limit)");
-    if (!entries || !ws) return fail(MODGPU_ERR_INVALID, "null table or workspace");
-    if (!results) return fail(MODGPU_ERR_INVALID, "null results");
-    if ((reinterpret_cast<uintptr_t>(entries) | reinterpret_cast<uintptr_t>(ws)) & 7) return fail(MODGPU_ERR_INVALID, "table or workspace not 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(results) & 7) return fail(MODGPU_ERR_INVALID, "results not 8-byte aligned");
-    const VerifyTableLayout L = verify_table_layout(n);
-    if (ws_bytes < L.bytes) return fail(MODGPU_ERR_INVALID, "workspace smaller than modgpu_verify_table_workspace_bytes(n_entries)");
-    DeviceScope scope(device);
-    if (scope.rc) return scope.rc;
-    int phys = -1;
-    HIP_TRY(hipGetDevice(&phys));
-    if (modgpu_xfer_device_of(entries, n * sizeof(modgpu_table_entry_t)) != phys || modgpu_xfer_device_of(ws, L.bytes) != phys)
-        return fail(MODGPU_ERR_INVALID, "the table or the workspace is not device memory of the call's device");
-    if (modgpu_xfer_device_of(results, n * sizeof(modgpu_verify_result_t)) != phys)
-        return fail(MODGPU_ERR_INVALID, "the results are not device memory of the call's device");
-    uint8_t *const w = static_cast<uint8_t *>(ws);
-    VerifyTableArgs a{};
-    a.entries = reinterpret_cast<const CycleTableEntry *>(entries);
-    a.n = n;
-    a.hdr = reinterpret_cast<CycleTableHdr *>(w);
-    a.sum = reinterpret_cast<VerifyTableSummary *>(w + L.sum);
-    a.blk = reinterpret_cast<CycleTableBlk *>(w + L.t.blk);
-    a.plan = reinterpret_cast<CycleTablePlan *>(w + L.t.plan);
-    a.results = reinterpret_cast<CycleVerifyResult *>(results);
-    for (uint32_t k = 0; k <= L.t.top; ++k) {
-        a.level[k] = reinterpret_cast<uint32_t *>(w + L.t.level[k]);
-        a.level_n[k] = L.t.level_n[k];
-    }
-    a.top = L.t.top;
-    a.n_blk = L.t.n_blk;
-    const uint32_t grid = verify_table_grid();
-    (void)hipGetLastError(); // (the launches report hipGetLastError: an earlier call's error must not be taken for theirs)
-    hipError_t e = modgpu_launch_verify_table_plan(a, stream);
-    if (e != hipSuccess) return fail_hip(e, "verify table plan launch");
-    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    e = modgpu_launch_verify_table_finish(a, stream);
-    if (e != hipSuccess) return fail_hip(e, "verify table finish launch");
-    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    e = modgpu_launch_verify_table_stream(a, grid, stream);
-    if (e != hipSuccess) return fail_hip(e, "verify table stream launch");
-    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    t_last_launch = {modgpu_verify_table_kernel_name(), CYCLE_VERIFY_TABLE, grid, modgpu_verify_table_block(), modgpu_verify_table_chunk_bytes(), 0, grid,
-                     MODGPU_VERIFY_TABLE_KERNEL_SOURCE_HASH};
-    return MODGPU_OK;
-}
-
-// ---- a table of rekey entries in device memory, verified (modgpu_verify_rekey_table_device) -----------------------------------------
-// The rekey table call's layout with one line for the summary put in right behind the header (every later section 64 bytes further on),
-// as verify_table_layout does to table_layout: header and summary sit where the verify table call has them, so modgpu_table_status and
-// modgpu_verify_table_summary read this kind of workspace unchanged.
-struct RekeyVerifyTableLayout {
-    RekeyTableLayout r; // offsets already moved
-    uint64_t sum, bytes;
-};
-RekeyVerifyTableLayout rekey_verify_table_layout(uint64_t n)
-{
-    RekeyVerifyTableLayout L{rekey_table_layout(n), sizeof(CycleTableHdr), 0};
-    constexpr uint64_t line = sizeof(VerifyTableSummary);
-    L.r.t.blk += line;
-    L.r.t.plan += line;
-    for (uint32_t k = 0; k <= L.r.t.top; ++k) L.r.t.level[k] += line;
-    L.r.t.bytes += line;
-    L.r.edge += line;
-    L.r.bytes += line;
-    L.bytes = L.r.bytes;
-    return L;
-}
-
-// The stream launch's grid: one workgroup per CU on every CU, the verify table call's rule
-#ifdef MODGPU_TESTING_HOOKS
-std::atomic<uint32_t> g_rekey_verify_table_grid{0}; // modgpu_debug_set_rekey_verify_table_grid
-uint32_t rekey_verify_table_grid_forced() { return g_rekey_verify_table_grid.load(std::memory_order_relaxed); }
-#else
-constexpr uint32_t rekey_verify_table_grid_forced() { return 0; }
-#endif
-uint32_t rekey_verify_table_grid()
-{
-    if (rekey_verify_table_grid_forced()) return rekey_verify_table_grid_forced();
-    return std::max<uint32_t>(1, large_grid());
-}
-
-// Tier 1 (include/modgpu.h): everything checked before anything is queued; then the three launches on `stream`.
-int verify_rekey_table_impl(const modgpu_rekey_table_entry_t *entries, uint64_t n, modgpu_verify_result_t *results, void *ws, uint64_t ws_bytes,
-                            int device, hipStream_t stream)
-{
-    if (n == 0) return MODGPU_OK;
-    if (n > kTableMaxEntries) return fail(MODGPU_ERR_INVALID, "more than 4194304 entries (the table call's limit)");
-    if (!entries || !ws) return fail(MODGPU_ERR_INVALID, "null table or workspace");
-    if (!results) return fail(MODGPU_ERR_INVALID, "null results");
-    if ((reinterpret_cast<uintptr_t>(entries) | reinterpret_cast<uintptr_t>(ws)) & 7) return fail(MODGPU_ERR_INVALID, "table or workspace not 8-byte aligned");
-    if (reinterpret_cast<uintptr_t>(results) & 7) return fail(MODGPU_ERR_INVALID, "results not 8-byte aligned");
-    const RekeyVerifyTableLayout L = rekey_verify_table_layout(n);
-    if (ws_bytes < L.bytes) return fail(MODGPU_ERR_INVALID, "workspace smaller than modgpu_verify_rekey_table_workspace_bytes(n_entries)");
-    DeviceScope scope(device);
-    if (scope.rc) return scope.rc;
-    int phys = -1;
-    HIP_TRY(hipGetDevice(&phys));
-    if (modgpu_xfer_device_of(entries, n * sizeof(modgpu_rekey_table_entry_t)) != phys || modgpu_xfer_device_of(ws, L.bytes) != phys)
-        return fail(MODGPU_ERR_INVALID, "the table or the workspace is not device memory of the call's device");
-    if (modgpu_xfer_device_of(results, n * sizeof(modgpu_verify_result_t)) != phys)
-        return fail(MODGPU_ERR_INVALID, "the results are not device memory of the call's device");
-    uint8_t *const w = static_cast<uint8_t *>(ws);
-    RekeyVerifyTableArgs a{};
-    a.entries = reinterpret_cast<const RekeyTableEntry *>(entries);
-    a.n = n;
-    a.hdr = reinterpret_cast<CycleTableHdr *>(w);
-    a.sum = reinterpret_cast<VerifyTableSummary *>(w + L.sum);
-    a.blk = reinterpret_cast<CycleTableBlk *>(w + L.r.t.blk);
-    a.plan = reinterpret_cast<RekeyTablePlan *>(w + L.r.t.plan);
-    a.edge = reinterpret_cast<RekeyTableEdge *>(w + L.r.edge);
-    a.results = reinterpret_cast<CycleVerifyResult *>(results);
-    for (uint32_t k = 0; k <= L.r.t.top; ++k) {
-        a.level[k] = reinterpret_cast<uint32_t *>(w + L.r.t.level[k]);
-        a.level_n[k] = L.r.t.level_n[k];
-    }
-    a.top = L.r.t.top;
-    a.n_blk = L.r.t.n_blk;
-    const uint32_t grid = rekey_verify_table_grid();
-    (void)hipGetLastError(); // (the launches report hipGetLastError: an earlier call's error must not be taken for theirs)
-    hipError_t e = modgpu_launch_rekey_verify_table_plan(a, stream);
-    if (e != hipSuccess) return fail_hip(e, "verify rekey table plan launch");
-    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    e = modgpu_launch_rekey_verify_table_finish(a, stream);
-    if (e != hipSuccess) return fail_hip(e, "verify rekey table finish launch");
-    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    e = modgpu_launch_rekey_verify_table_stream(a, grid, stream);
-    if (e != hipSuccess) return fail_hip(e, "verify rekey table stream launch");
-    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    t_last_launch = {modgpu_rekey_verify_table_kernel_name(), CYCLE_REKEY_VERIFY_TABLE, grid, modgpu_rekey_verify_table_block(),
-                     modgpu_rekey_verify_table_chunk_bytes(), 0, grid, MODGPU_REKEY_VERIFY_TABLE_KERNEL_SOURCE_HASH};
     return MODGPU_OK;
 }
 } // namespace
@@ -2202,15 +2046,8 @@ int modgpu_cycle_table_device(const modgpu_table_entry_t *dev_entries, uint64_t 
 int modgpu_table_status(const void *dev_workspace, int device, uint64_t *first_bad_entry)
 {
     return guarded([&]() -> int {
-        if (!dev_workspace || !first_bad_entry) return fail(MODGPU_ERR_INVALID, "null workspace or out pointer");
-        DeviceScope scope(device);
-        if (scope.rc) return scope.rc;
-        int phys = -1;
-        HIP_TRY(hipGetDevice(&phys));
-        if (modgpu_xfer_device_of(dev_workspace, sizeof(CycleTableHdr)) != phys)
-            return fail(MODGPU_ERR_INVALID, "the workspace is not device memory of the call's device");
         CycleTableHdr h;
-        HIP_TRY(hipMemcpy(&h, dev_workspace, sizeof h, hipMemcpyDeviceToHost));
+        if (int rc = read_workspace_top(dev_workspace, first_bad_entry != nullptr, device, &h, sizeof h)) return rc;
         *first_bad_entry = h.first_bad;
         if (h.first_bad != kTableNoBad)
             return fail(MODGPU_ERR_INVALID, "the device refused entry " + std::to_string(h.first_bad) + " (the call wrote nothing)");
@@ -2310,17 +2147,11 @@ int modgpu_verify_rekey_table_device(const modgpu_rekey_table_entry_t *dev_entri
 int modgpu_verify_table_summary(const void *dev_workspace, int device, modgpu_verify_table_summary_t *out)
 {
     return guarded([&]() -> int {
-        if (!dev_workspace || !out) return fail(MODGPU_ERR_INVALID, "null workspace or out pointer");
-        DeviceScope scope(device);
-        if (scope.rc) return scope.rc;
-        int phys = -1;
-        HIP_TRY(hipGetDevice(&phys));
         struct {
             CycleTableHdr h;
             VerifyTableSummary s;
         } top;
-        if (modgpu_xfer_device_of(dev_workspace, sizeof top) != phys) return fail(MODGPU_ERR_INVALID, "the workspace is not device memory of the call's device");
-        HIP_TRY(hipMemcpy(&top, dev_workspace, sizeof top, hipMemcpyDeviceToHost));
+        if (int rc = read_workspace_top(dev_workspace, out != nullptr, device, &top, sizeof top)) return rc;
         if (top.h.first_bad != kTableNoBad)
             return fail(MODGPU_ERR_INVALID, "the device refused entry " + std::to_string(top.h.first_bad) + " (the call wrote no result)");
         out->mismatches = top.s.mismatches;
@@ -2911,26 +2742,7 @@ int modgpu_time_cycle_device(void *dev_buf, uint64_t n, int32_t key, uint64_t st
                              void *hip_stream, int iters, float *ms_per_launch)
 {
     return guarded([&]() -> int {
-        if (iters <= 0 || !ms_per_launch) return fail(MODGPU_ERR_INVALID, "bad timing arguments");
-        DeviceScope scope(device);
-        if (scope.rc) return scope.rc;
-        int rc = MODGPU_OK;
-        hipStream_t st = static_cast<hipStream_t>(hip_stream);
-        hipEvent_t e0, e1;
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, st));
-        for (int i = 0; i < iters && rc == MODGPU_OK; ++i) rc = cycle_device_impl(dev_buf, n, key, stream_off, st);
-        hipError_t e = hipEventRecord(e1, st);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        float ms = 0.f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        if (rc) return rc;
-        if (e != hipSuccess) return fail_hip(e, "event timing");
-        *ms_per_launch = ms / (float)iters;
-        return MODGPU_OK;
+        return time_calls(device, hip_stream, iters, ms_per_launch, [&](hipStream_t st) { return cycle_device_impl(dev_buf, n, key, stream_off, st); });
     });
 }
 
@@ -2938,27 +2750,9 @@ int modgpu_time_cycle_device_to(void *dev_dst, const void *dev_src, uint64_t n, 
                                 void *hip_stream, int iters, float *ms_per_launch)
 {
     return guarded([&]() -> int {
-        if (iters <= 0 || !ms_per_launch) return fail(MODGPU_ERR_INVALID, "bad timing arguments");
-        if (int rc = check_to_entries(&dev_dst, &dev_src, &n, 1)) return rc;
-        DeviceScope scope(device);
-        if (scope.rc) return scope.rc;
-        int rc = MODGPU_OK;
-        hipStream_t st = static_cast<hipStream_t>(hip_stream);
-        hipEvent_t e0, e1;
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, st));
-        for (int i = 0; i < iters && rc == MODGPU_OK; ++i) rc = cycle_to_impl(&dev_dst, &dev_src, &n, &stream_off, 1, key, st);
-        hipError_t e = hipEventRecord(e1, st);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        float ms = 0.f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        if (rc) return rc;
-        if (e != hipSuccess) return fail_hip(e, "event timing");
-        *ms_per_launch = ms / (float)iters;
-        return MODGPU_OK;
+        if (iters > 0 && ms_per_launch) // (the entries are checked behind the timing arguments, which time_calls refuses)
+            if (int rc = check_to_entries(&dev_dst, &dev_src, &n, 1)) return rc;
+        return time_calls(device, hip_stream, iters, ms_per_launch, [&](hipStream_t st) { return cycle_to_impl(&dev_dst, &dev_src, &n, &stream_off, 1, key, st); });
     });
 }
 
@@ -2966,27 +2760,11 @@ int modgpu_time_rekey_device_to(void *dev_dst, const void *dev_src, uint64_t n, 
                                 uint64_t off_to, int device, void *hip_stream, int iters, float *ms_per_launch)
 {
     return guarded([&]() -> int {
-        if (iters <= 0 || !ms_per_launch) return fail(MODGPU_ERR_INVALID, "bad timing arguments");
-        if (int rc = check_to_entries(&dev_dst, &dev_src, &n, 1)) return rc;
-        DeviceScope scope(device);
-        if (scope.rc) return scope.rc;
-        int rc = MODGPU_OK;
-        hipStream_t st = static_cast<hipStream_t>(hip_stream);
-        hipEvent_t e0, e1;
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, st));
-        for (int i = 0; i < iters && rc == MODGPU_OK; ++i) rc = rekey_impl(&dev_dst, &dev_src, &n, &off_from, &off_to, 1, key_from, key_to, st);
-        hipError_t e = hipEventRecord(e1, st);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        float ms = 0.f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        if (rc) return rc;
-        if (e != hipSuccess) return fail_hip(e, "event timing");
-        *ms_per_launch = ms / (float)iters;
-        return MODGPU_OK;
+        if (iters > 0 && ms_per_launch)
+            if (int rc = check_to_entries(&dev_dst, &dev_src, &n, 1)) return rc;
+        return time_calls(device, hip_stream, iters, ms_per_launch, [&](hipStream_t st) {
+            return rekey_impl(&dev_dst, &dev_src, &n, &off_from, &off_to, 1, key_from, key_to, st);
+        });
     });
 }
 
@@ -2994,28 +2772,12 @@ int modgpu_time_verify_device(const void *dev_expect, const void *dev_src, uint6
                               int device, void *hip_stream, int iters, float *ms_per_call)
 {
     return guarded([&]() -> int {
-        if (iters <= 0 || !ms_per_call) return fail(MODGPU_ERR_INVALID, "bad timing arguments");
         modgpu_verify_result_t *res = static_cast<modgpu_verify_result_t *>(dev_result);
-        if (int rc = check_verify_entries(&dev_expect, &dev_src, &n, 1, res)) return rc;
-        DeviceScope scope(device);
-        if (scope.rc) return scope.rc;
-        int rc = MODGPU_OK;
-        hipStream_t st = static_cast<hipStream_t>(hip_stream);
-        hipEvent_t e0, e1;
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, st));
-        for (int i = 0; i < iters && rc == MODGPU_OK; ++i) rc = verify_impl(&dev_expect, &dev_src, &n, &stream_off, 1, key, res, st);
-        hipError_t e = hipEventRecord(e1, st);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        float ms = 0.f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        if (rc) return rc;
-        if (e != hipSuccess) return fail_hip(e, "event timing");
-        *ms_per_call = ms / (float)iters;
-        return MODGPU_OK;
+        if (iters > 0 && ms_per_call)
+            if (int rc = check_verify_entries(&dev_expect, &dev_src, &n, 1, res)) return rc;
+        return time_calls(device, hip_stream, iters, ms_per_call, [&](hipStream_t st) {
+            return verify_impl(&dev_expect, &dev_src, &n, &stream_off, 1, key, res, st);
+        });
     });
 }
 
@@ -3023,28 +2785,12 @@ int modgpu_time_verify_rekey_device(const void *dev_expect, const void *dev_src,
                                     uint64_t off_to, void *dev_result, int device, void *hip_stream, int iters, float *ms_per_call)
 {
     return guarded([&]() -> int {
-        if (iters <= 0 || !ms_per_call) return fail(MODGPU_ERR_INVALID, "bad timing arguments");
         modgpu_verify_result_t *res = static_cast<modgpu_verify_result_t *>(dev_result);
-        if (int rc = check_verify_entries(&dev_expect, &dev_src, &n, 1, res)) return rc;
-        DeviceScope scope(device);
-        if (scope.rc) return scope.rc;
-        int rc = MODGPU_OK;
-        hipStream_t st = static_cast<hipStream_t>(hip_stream);
-        hipEvent_t e0, e1;
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, st));
-        for (int i = 0; i < iters && rc == MODGPU_OK; ++i) rc = verify_rekey_impl(&dev_expect, &dev_src, &n, &off_from, &off_to, 1, key_from, key_to, res, st);
-        hipError_t e = hipEventRecord(e1, st);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        float ms = 0.f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        if (rc) return rc;
-        if (e != hipSuccess) return fail_hip(e, "event timing");
-        *ms_per_call = ms / (float)iters;
-        return MODGPU_OK;
+        if (iters > 0 && ms_per_call)
+            if (int rc = check_verify_entries(&dev_expect, &dev_src, &n, 1, res)) return rc;
+        return time_calls(device, hip_stream, iters, ms_per_call, [&](hipStream_t st) {
+            return verify_rekey_impl(&dev_expect, &dev_src, &n, &off_from, &off_to, 1, key_from, key_to, res, st);
+        });
     });
 }
 
@@ -3111,26 +2857,9 @@ int modgpu_time_cycle_table_device(const void *dev_entries, uint64_t n_entries, 
                                    int device, void *hip_stream, int iters, float *ms_per_call)
 {
     return guarded([&]() -> int {
-        if (iters <= 0 || !ms_per_call) return fail(MODGPU_ERR_INVALID, "bad timing arguments");
-        DeviceScope scope(device);
-        if (scope.rc) return scope.rc;
-        int rc = MODGPU_OK;
-        hipStream_t st = static_cast<hipStream_t>(hip_stream);
-        hipEvent_t e0, e1;
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, st));
-        for (int i = 0; i < iters && rc == MODGPU_OK; ++i) rc = table_impl(static_cast<const modgpu_table_entry_t *>(dev_entries), n_entries, dev_workspace, workspace_bytes, -1, st);
-        hipError_t e = hipEventRecord(e1, st);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        float ms = 0.f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        if (rc) return rc;
-        if (e != hipSuccess) return fail_hip(e, "event timing");
-        *ms_per_call = ms / (float)iters;
-        return MODGPU_OK;
+        return time_calls(device, hip_stream, iters, ms_per_call, [&](hipStream_t st) {
+            return table_impl(static_cast<const modgpu_table_entry_t *>(dev_entries), n_entries, dev_workspace, workspace_bytes, -1, st);
+        });
     });
 }
 
@@ -3138,26 +2867,9 @@ int modgpu_time_rekey_table_device(const void *dev_entries, uint64_t n_entries, 
                                    int device, void *hip_stream, int iters, float *ms_per_call)
 {
     return guarded([&]() -> int {
-        if (iters <= 0 || !ms_per_call) return fail(MODGPU_ERR_INVALID, "bad timing arguments");
-        DeviceScope scope(device);
-        if (scope.rc) return scope.rc;
-        int rc = MODGPU_OK;
-        hipStream_t st = static_cast<hipStream_t>(hip_stream);
-        hipEvent_t e0, e1;
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, st));
-        for (int i = 0; i < iters && rc == MODGPU_OK; ++i) rc = rekey_table_impl(static_cast<const modgpu_rekey_table_entry_t *>(dev_entries), n_entries, dev_workspace, workspace_bytes, -1, st);
-        hipError_t e = hipEventRecord(e1, st);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        float ms = 0.f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        if (rc) return rc;
-        if (e != hipSuccess) return fail_hip(e, "event timing");
-        *ms_per_call = ms / (float)iters;
-        return MODGPU_OK;
+        return time_calls(device, hip_stream, iters, ms_per_call, [&](hipStream_t st) {
+            return rekey_table_impl(static_cast<const modgpu_rekey_table_entry_t *>(dev_entries), n_entries, dev_workspace, workspace_bytes, -1, st);
+        });
     });
 }
 
@@ -3165,28 +2877,9 @@ int modgpu_time_verify_table_device(const void *dev_entries, uint64_t n_entries,
                                     int device, void *hip_stream, int iters, float *ms_per_call)
 {
     return guarded([&]() -> int {
-        if (iters <= 0 || !ms_per_call) return fail(MODGPU_ERR_INVALID, "bad timing arguments");
-        DeviceScope scope(device);
-        if (scope.rc) return scope.rc;
-        int rc = MODGPU_OK;
-        hipStream_t st = static_cast<hipStream_t>(hip_stream);
-        hipEvent_t e0, e1;
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, st));
-        for (int i = 0; i < iters && rc == MODGPU_OK; ++i)
-            rc = verify_table_impl(static_cast<const modgpu_table_entry_t *>(dev_entries), n_entries, static_cast<modgpu_verify_result_t *>(dev_results), dev_workspace,
-                                   workspace_bytes, -1, st);
-        hipError_t e = hipEventRecord(e1, st);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        float ms = 0.f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        if (rc) return rc;
-        if (e != hipSuccess) return fail_hip(e, "event timing");
-        *ms_per_call = ms / (float)iters;
-        return MODGPU_OK;
+        return time_calls(device, hip_stream, iters, ms_per_call, [&](hipStream_t st) {
+            return verify_table_impl(static_cast<const modgpu_table_entry_t *>(dev_entries), n_entries, static_cast<modgpu_verify_result_t *>(dev_results), dev_workspace, workspace_bytes, -1, st);
+        });
     });
 }
 
@@ -3194,28 +2887,9 @@ int modgpu_time_verify_rekey_table_device(const void *dev_entries, uint64_t n_en
                                           int device, void *hip_stream, int iters, float *ms_per_call)
 {
     return guarded([&]() -> int {
-        if (iters <= 0 || !ms_per_call) return fail(MODGPU_ERR_INVALID, "bad timing arguments");
-        DeviceScope scope(device);
-        if (scope.rc) return scope.rc;
-        int rc = MODGPU_OK;
-        hipStream_t st = static_cast<hipStream_t>(hip_stream);
-        hipEvent_t e0, e1;
-        HIP_TRY(hipEventCreate(&e0));
-        HIP_TRY(hipEventCreate(&e1));
-        HIP_TRY(hipEventRecord(e0, st));
-        for (int i = 0; i < iters && rc == MODGPU_OK; ++i)
-            rc = verify_rekey_table_impl(static_cast<const modgpu_rekey_table_entry_t *>(dev_entries), n_entries, static_cast<modgpu_verify_result_t *>(dev_results),
-                                         dev_workspace, workspace_bytes, -1, st);
-        hipError_t e = hipEventRecord(e1, st);
-        if (e == hipSuccess) e = hipEventSynchronize(e1);
-        float ms = 0.f;
-        if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-        (void)hipEventDestroy(e0);
-        (void)hipEventDestroy(e1);
-        if (rc) return rc;
-        if (e != hipSuccess) return fail_hip(e, "event timing");
-        *ms_per_call = ms / (float)iters;
-        return MODGPU_OK;
+        return time_calls(device, hip_stream, iters, ms_per_call, [&](hipStream_t st) {
+            return verify_rekey_table_impl(static_cast<const modgpu_rekey_table_entry_t *>(dev_entries), n_entries, static_cast<modgpu_verify_result_t *>(dev_results), dev_workspace, workspace_bytes, -1, st);
+        });
     });
 }
 
@@ -3252,13 +2926,13 @@ void modgpu_debug_set_rekey_form(int shape)
                         std::memory_order_relaxed);
 }
 
-void modgpu_debug_set_table_grid(uint32_t grid) { g_table_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
+void modgpu_debug_set_table_grid(uint32_t grid) { force_table_grid(kCycleTable, grid); }
 void modgpu_debug_set_move_grid(uint32_t grid) { g_move_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
-void modgpu_debug_set_move_table_grid(uint32_t grid) { g_move_table_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
-void modgpu_debug_set_rekey_table_grid(uint32_t grid) { g_rekey_table_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
+void modgpu_debug_set_move_table_grid(uint32_t grid) { force_table_grid(kMoveTable, grid); }
+void modgpu_debug_set_rekey_table_grid(uint32_t grid) { force_table_grid(kRekeyTable, grid); }
 
-void modgpu_debug_set_verify_table_grid(uint32_t grid) { g_verify_table_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
-void modgpu_debug_set_rekey_verify_table_grid(uint32_t grid) { g_rekey_verify_table_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
+void modgpu_debug_set_verify_table_grid(uint32_t grid) { force_table_grid(kVerifyTable, grid); }
+void modgpu_debug_set_rekey_verify_table_grid(uint32_t grid) { force_table_grid(kRekeyVerifyTable, grid); }
 
 // (caps the compare launches of the verify call and of the rekey verify call alike)
 void modgpu_debug_set_verify_form(int grid) { g_verify_grid.store(grid <= 0 ? 0u : std::min<uint32_t>((uint32_t)grid, 4096u), std::memory_order_relaxed); }

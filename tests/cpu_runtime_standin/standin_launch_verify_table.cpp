@@ -9,68 +9,35 @@
 //           the chunk's span and adds to / lowers the entry's result and the summary as the kernel's atomics do.
 // It READS both sides where the plan says the kernel reads them and writes only results and workspace, so the sanitizer runs see every
 // byte of the workspace layout the host planned and every byte of the caller's buffers the kernels would touch.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <thread>
+#include "standin_table.h"
 
 #include "../../modulate_amd/csrc/cycle_verify_table_kernel.h"
-#include "../../modulate_amd/csrc/lcg.h"
 
 namespace {
+using namespace standin_table;
 std::atomic<unsigned long long> g_verify_table_launches[3] = {};
-constexpr uint64_t kChunk = 65536;
 
-uint32_t state(uint32_t k, uint64_t e) { return k ? lcg::mulmod(k, lcg::powmod(lcg::A, e % lcg::PERIOD)) : 0u; }
+// k * a^e; 0 for the identity keystream: a plain compare
+uint32_t base_state(uint32_t k, uint64_t e) { return k ? lcg::mulmod(k, lcg::powmod(lcg::A, e % lcg::PERIOD)) : 0u; }
 
-void run_plan(void *arg)
+void run_plan(VerifyTableArgs *a)
 {
-    VerifyTableArgs *a = static_cast<VerifyTableArgs *>(arg);
-    a->hdr->ticket = 0;
-    a->hdr->first_bad = kTableNoBad;
-    a->hdr->total = 0;
     a->sum->mismatches = 0;
     a->sum->first_bad_entry = kVerifyNone;
     a->sum->entries = a->n;
     a->sum->reserved = 0;
-    for (uint32_t b = 0; b < a->n_blk; ++b) {
-        uint64_t run = 0;
-        uint32_t bad_any = 0;
-        for (uint64_t i = (uint64_t)b * kTableBlock; i < a->n && i < (uint64_t)(b + 1) * kTableBlock; ++i) {
-            const CycleTableEntry E = a->entries[i];
-            const uint64_t d = reinterpret_cast<uintptr_t>(E.dst);
-            const uint64_t head = std::min<uint64_t>(E.n, (16 - (d & 15)) & 15);
-            const uint64_t words = (E.n - head) / 16;
-            const uint32_t lead = (uint32_t)((d + head) & (kChunk - 1));
-            const uint64_t end = lead + words * 16;
-            uint64_t cnt = words ? (end + kChunk - 1) / kChunk : 0;
-            const uint32_t bad = (E.n && (!E.dst || !E.src)) || E.flags != 0 || cnt > kTableMaxEntryChunks ? 1u : 0u;
-            if (bad) cnt = 0;
-            const uint32_t k = lcg::key_residue(E.key);
-            const uint64_t o1 = E.stream_off % lcg::PERIOD + 1;
-            CycleTablePlan &P = a->plan[i];
-            P.dst_origin = reinterpret_cast<uint8_t *>(reinterpret_cast<uintptr_t>(E.dst) + head - lead); // (as integers: a refused entry's pointer may be NULL)
-            P.src_origin = reinterpret_cast<const uint8_t *>(reinterpret_cast<uintptr_t>(E.src) + head - lead);
-            P.end = end;
-            P.start = run;
-            P.lead = lead;
-            P.chunks = (uint32_t)cnt;
-            P.base_head = state(k, o1);
-            P.base = state(k, o1 + head + lcg::PERIOD - lead);
-            P.base_tail = state(k, o1 + head + (words * 16) % lcg::PERIOD);
-            P.bad = bad;
-            P.head_n = (uint32_t)head;
-            P.tail_n = (uint32_t)(E.n - head - words * 16);
-            run += cnt;
-            bad_any |= bad;
-        }
-        a->blk[b].chunks = run;
-        a->blk[b].bad = bad_any;
-    }
-    g_verify_table_launches[0].fetch_add(1);
-    delete a;
+    plan(a, [&](uint64_t i, uint64_t run) {
+        const CycleTableEntry E = a->entries[i];
+        const Grid g = grid_of(E, E.flags);
+        const uint32_t k = lcg::key_residue(E.key);
+        const uint64_t o1 = E.stream_off % lcg::PERIOD + 1;
+        CycleTablePlan &P = a->plan[i];
+        plan_fields(P, E, g, run);
+        P.base_head = base_state(k, o1);
+        P.base = base_state(k, o1 + g.origin);
+        P.base_tail = base_state(k, o1 + g.tail);
+        return g;
+    });
 }
 
 // bytes [at, at + len) of a span from its origins, s0 the origin byte's state (0: the identity keystream); j0 = index in the entry of
@@ -89,94 +56,43 @@ void span_verify(const uint8_t *exp0, const uint8_t *src0, uint64_t at, uint64_t
     }
 }
 
-void run_finish(void *arg)
+void run_finish(VerifyTableArgs *a)
 {
-    VerifyTableArgs *a = static_cast<VerifyTableArgs *>(arg);
-    uint64_t total = 0;
-    uint32_t bad = 0;
-    for (uint32_t b = 0; b < a->n_blk; ++b) {
-        total += a->blk[b].chunks;
-        bad |= a->blk[b].bad;
-    }
-    const bool ok = !bad && total <= kTableMaxChunks;
-    a->hdr->total = ok ? total : 0;
-    uint64_t before = 0;
-    for (uint32_t b = 0; b < a->n_blk; ++b) {
-        for (uint64_t i = (uint64_t)b * kTableBlock; i < a->n && i < (uint64_t)(b + 1) * kTableBlock; ++i) {
-            CycleTablePlan &P = a->plan[i];
-            const uint64_t start = before + P.start;
-            if (!ok) {
-                if ((P.bad || start + P.chunks > kTableMaxChunks) && i < a->hdr->first_bad) a->hdr->first_bad = i;
-                continue;
-            }
-            P.start = start;
-            for (uint32_t k = 0; k <= a->top; ++k)
-                if ((i & ((1ull << (4 * k)) - 1)) == 0) a->level[k][i >> (4 * k)] = (uint32_t)start;
-            const uint64_t body = P.end - P.lead;
-            unsigned long long count = 0, first = kVerifyNone;
-            span_verify(P.dst_origin + P.lead - P.head_n, P.src_origin + P.lead - P.head_n, 0, P.head_n, P.base_head, 0, count, first);
-            span_verify(P.dst_origin + P.end, P.src_origin + P.end, 0, P.tail_n, P.base_tail, P.head_n + body, count, first);
-            a->results[i] = CycleVerifyResult{count, first, (unsigned long long)P.head_n + body + P.tail_n, 0ull};
-            if (count) {
-                a->sum->mismatches += count;
-                if (i < a->sum->first_bad_entry) a->sum->first_bad_entry = i;
-            }
+    finish(a, kTableMaxChunks, [&](uint64_t i, CycleTablePlan &P, bool ok) {
+        if (!ok) return;
+        const uint64_t body = P.end - P.lead;
+        unsigned long long count = 0, first = kVerifyNone;
+        span_verify(P.dst_origin + P.lead - P.head_n, P.src_origin + P.lead - P.head_n, 0, P.head_n, P.base_head, 0, count, first);
+        span_verify(P.dst_origin + P.end, P.src_origin + P.end, 0, P.tail_n, P.base_tail, P.head_n + body, count, first);
+        a->results[i] = CycleVerifyResult{count, first, (unsigned long long)P.head_n + body + P.tail_n, 0ull};
+        if (count) {
+            a->sum->mismatches += count;
+            if (i < a->sum->first_bad_entry) a->sum->first_bad_entry = i;
         }
-        before += a->blk[b].chunks;
-    }
-    if (ok)
-        for (uint32_t k = 0; k <= a->top; ++k)
-            for (uint64_t j = a->level_n[k]; j < ((a->level_n[k] + 15) & ~15ull); ++j) a->level[k][j] = ~0u;
-    g_verify_table_launches[1].fetch_add(1);
-    delete a;
+    });
 }
 
-void run_stream(void *arg)
+void run_stream(VerifyTableArgs *a)
 {
-    VerifyTableArgs *a = static_cast<VerifyTableArgs *>(arg);
-    std::this_thread::sleep_for(std::chrono::microseconds(200)); // a launch lasts a while: overlaps between streams become likely
-    const uint32_t total = (uint32_t)a->hdr->total;
-    for (uint32_t g = 0; g < total; ++g) {
-        uint64_t j = 0;
-        for (int k = (int)a->top; k >= 0; --k) { // the kernel's descent: 16 keys per level
-            uint32_t c = 0;
-            for (int t = 0; t < 16; ++t) c += a->level[k][16 * j + t] <= g ? 1u : 0u;
-            j = 16 * j + c - 1;
-        }
-        const CycleTablePlan &P = a->plan[j];
-        const uint64_t c = g - P.start, off = c * kChunk, cut = c ? 0 : P.lead;
-        const uint64_t lim = std::min<uint64_t>(P.end, off + kChunk);
+    stream(a, [&](const Span &s) {
+        const CycleTablePlan &P = a->plan[s.entry];
         unsigned long long count = 0, first = kVerifyNone;
-        span_verify(P.dst_origin, P.src_origin, off + cut, lim - off - cut, P.base, (uint64_t)P.head_n - P.lead, count, first);
+        span_verify(P.dst_origin, P.src_origin, s.off + s.cut, s.lim - s.off - s.cut, P.base, (uint64_t)P.head_n - P.lead, count, first);
         if (count) {
-            a->results[j].mismatches += count;
-            if (first < a->results[j].first_mismatch) a->results[j].first_mismatch = first;
+            a->results[s.entry].mismatches += count;
+            if (first < a->results[s.entry].first_mismatch) a->results[s.entry].first_mismatch = first;
             a->sum->mismatches += count;
-            if (j < a->sum->first_bad_entry) a->sum->first_bad_entry = j;
+            if (s.entry < a->sum->first_bad_entry) a->sum->first_bad_entry = s.entry;
         }
-    }
-    g_verify_table_launches[2].fetch_add(1);
-    delete a;
+    });
 }
 } // namespace
 
 uint32_t modgpu_verify_table_chunk_bytes() { return (uint32_t)kChunk; }
 uint32_t modgpu_verify_table_block() { return 1024u; }
 const char *modgpu_verify_table_kernel_name() { return "shim verify table stream"; }
-hipError_t modgpu_launch_verify_table_plan(const VerifyTableArgs &a, hipStream_t stream)
-{
-    shim::enqueue(stream, run_plan, new VerifyTableArgs(a));
-    return hipSuccess;
-}
-hipError_t modgpu_launch_verify_table_finish(const VerifyTableArgs &a, hipStream_t stream)
-{
-    shim::enqueue(stream, run_finish, new VerifyTableArgs(a));
-    return hipSuccess;
-}
-hipError_t modgpu_launch_verify_table_stream(const VerifyTableArgs &a, uint32_t, hipStream_t stream)
-{
-    shim::enqueue(stream, run_stream, new VerifyTableArgs(a));
-    return hipSuccess;
-}
+hipError_t modgpu_launch_verify_table_plan(const VerifyTableArgs &a, hipStream_t stream) { return enqueue<VerifyTableArgs, run_plan, g_verify_table_launches, 0>(a, stream); }
+hipError_t modgpu_launch_verify_table_finish(const VerifyTableArgs &a, hipStream_t stream) { return enqueue<VerifyTableArgs, run_finish, g_verify_table_launches, 1>(a, stream); }
+hipError_t modgpu_launch_verify_table_stream(const VerifyTableArgs &a, uint32_t, hipStream_t stream) { return enqueue<VerifyTableArgs, run_stream, g_verify_table_launches, 2>(a, stream); }
 
-extern "C" unsigned long long modgpu_shim_verify_table_launches(int kind) { return kind >= 0 && kind < 3 ? g_verify_table_launches[kind].load() : 0; }
+extern "C" unsigned long long modgpu_shim_verify_table_launches(int kind) { return count(g_verify_table_launches, kind); }
