@@ -435,6 +435,56 @@ int modgpu_verify_batch_device(const void *const *expect_parts, const void *cons
  * modgpu_table_status): call it after the caller has synchronised the stream the verify calls ran on. */
 int modgpu_verify_results(const modgpu_verify_result_t *dev_results, uint64_t count, int device, modgpu_verify_result_t *host_out);
 
+/* ---- DIGEST: what does the cipher make of this buffer?  One pass that reads n bytes and writes 32 ------------------------------------
+ * Adler-32 (as zlib computes it) of out[j] = src[j] ^ ks(key)[stream_off + j], j = 0 .. n-1 -- the bytes modgpu_cycle_device_to would
+ * write -- with or without storing them.  The device keeps two order-free integer sums, so the value is exact and the same for every
+ * launch shape:   S1 = sum of out[j]      S2 = sum of j * out[j]      (both mod 65521)
+ * and the host finalises them (modgpu_digest_adler32):   A = (1 + S1) mod 65521,  B = (n + n * S1 - S2) mod 65521,  B << 16 | A.
+ * The record of one entry, in device memory.  The layout is pinned (32 bytes, 8-byte aligned). */
+typedef struct modgpu_digest_result {
+    uint64_t s1, s2;   /* only their residues mod 65521 are specified */
+    uint64_t n;        /* the entry's n (lets a reader tell "ran" from "never ran"; it enters B) */
+    uint64_t reserved; /* 0 */
+} modgpu_digest_result_t;
+
+/* dev_dst NULL: DIGEST ONLY -- reads the n bytes of dev_src, writes nothing but *dev_result.  dev_dst given: FUSED -- dev_dst[j] = out[j]
+ * is stored exactly as modgpu_cycle_device_to stores it (byte for byte the same destination) and the same registers are summed.  Same
+ * keystream, 64-bit offsets and key reduction as modgpu_cycle_device.  The contract is modgpu_cycle_device_to's where it applies:
+ * asynchronous on `hip_stream`; `device` -1 = the current device, an explicit device leaves the thread's current device as it was;
+ * allocation-free; capturable into a hipGraph; any byte alignment of either buffer; the source may be page-locked host memory
+ * (supported, not tuned).
+ *   * With a destination the out-of-place overlap rules hold: dst == src exactly is allowed, a partial overlap of dst and src (and, in
+ *     the batch, a destination that meets another entry's source or destination) is MODGPU_ERR_INVALID before anything is queued.  So
+ *     is a NULL src with n > 0, a NULL or misaligned result, a result that the runtime does not report as device memory of the call's
+ *     device, and an entry that spans 2^24 chunks of 64 KiB or more (1 TiB).  Entries without a destination are only read and may
+ *     overlap anything that is not written.
+ *   * THE CALL ZEROES ITS RECORD ITSELF, IN STREAM ORDER (hipMemsetAsync on `hip_stream`): nothing needs clearing beforehand, and the
+ *     memset is a node of a capture, so a replayed graph starts from a clean record on every replay.
+ *   * n == 0 yields {0, 0, 0, 0} -- Adler-32 = 1 -- and no kernel launch.
+ *   * key == 0 mod 2^31-1 (the identity keystream): out = src, the plain Adler-32 of the buffer (fused: a copy with a checksum).
+ *   * The call never fails or degrades for lack of scheduling scratch: chunks are assigned to workgroups statically, no ticket line is
+ *     drawn.
+ *   * Launches (path_stats().gpu_launches counts them): ONE per started group of 16 non-empty entries.  modgpu_last_launch reports
+ *     variant 16 with `bytes` = all entries of the launch. */
+int modgpu_digest_device(void *dev_dst, const void *dev_src, uint64_t n, int32_t key, uint64_t stream_off,
+                         modgpu_digest_result_t *dev_result, int device, void *hip_stream);
+
+/* n_parts entries of ONE device, dev_results[i] the record of entry i: everything modgpu_digest_device says holds per entry.
+ * dst_parts NULL, or a NULL dst_parts[i]: that entry is digest only.  stream_offs NULL = 0 for every entry.  Any n_parts is taken: one
+ * memset zeroes all n_parts records, then up to 16 non-empty entries share a launch and further launches follow in order on the same
+ * stream.  A negative n_parts, or NULL src_parts / sizes / dev_results with n_parts > 0, is MODGPU_ERR_INVALID; n_parts == 0 queues
+ * nothing. */
+int modgpu_digest_batch_device(void *const *dst_parts, const void *const *src_parts, const uint64_t *sizes, const uint64_t *stream_offs,
+                               int n_parts, int32_t key, modgpu_digest_result_t *dev_results, int device, void *hip_stream);
+
+/* `count` records from device memory of `device` into host_out and, if adler32_out is not NULL, their Adler-32 values into
+ * adler32_out[0 .. count).  Synchronous (a small copy from the device): call it after the caller has synchronised the stream. */
+int modgpu_digest_results(const modgpu_digest_result_t *dev_results, uint64_t count, int device, modgpu_digest_result_t *host_out,
+                          uint32_t *adler32_out);
+
+/* Adler-32 from one record in HOST memory.  Pure arithmetic: no device, no error state (NULL gives 1, the Adler-32 of nothing). */
+uint32_t modgpu_digest_adler32(const modgpu_digest_result_t *host_result);
+
 /* ---- VERIFY REKEY: is this buffer what the rekey would have produced from that one?  The verify call against two keystreams ---------
  * Compares dev_expect[j] with dev_src[j] ^ ks(key_from)[off_from + j] ^ ks(key_to)[off_to + j] for j = 0 .. n-1 -- the bytes
  * modgpu_rekey_device_to would have written -- where the data lies, in one pass that READS 2n bytes and writes the 32 bytes of

@@ -45,6 +45,10 @@ int modgpu_time_rekey_table_device(const void *dev_entries, uint64_t n_entries, 
 /* The same for modgpu_verify_device: `iters` back-to-back verify calls (two launches each with n > 0) on one result. */
 int modgpu_time_verify_device(const void *dev_expect, const void *dev_src, uint64_t n, int32_t key, uint64_t stream_off,
                               void *dev_result, int device, void *hip_stream, int iters, float *ms_per_call);
+/* The same for modgpu_digest_device: `iters` back-to-back digest calls (a memset node and one launch each with n > 0) on one record;
+ * dev_dst NULL = digest only. */
+int modgpu_time_digest_device(void *dev_dst, const void *dev_src, uint64_t n, int32_t key, uint64_t stream_off, void *dev_result,
+                              int device, void *hip_stream, int iters, float *ms_per_call);
 /* The same for modgpu_verify_rekey_device: `iters` back-to-back rekey verify calls (two launches each with n > 0) on one result. */
 int modgpu_time_verify_rekey_device(const void *dev_expect, const void *dev_src, uint64_t n, int32_t key_from, uint64_t off_from,
                                     int32_t key_to, uint64_t off_to, void *dev_result, int device, void *hip_stream, int iters,
@@ -80,7 +84,9 @@ typedef struct modgpu_launch_info {
                                   `bytes` = all entries of the launch); its entries with coinciding streams are a variant 10 launch,
                              13 = the rekey verify table call's stream kernel (modgpu_verify_rekey_table_device; `bytes` = 0, as for 8),
                              14 = the body launch of modgpu_rekey_move_device (the rekey kernel's move loop; `bytes` = n),
-                             15 = the move launch of modgpu_rekey_move_table_device (`bytes` = 0, as for 8) */
+                             15 = the move launch of modgpu_rekey_move_table_device (`bytes` = 0, as for 8),
+                             16 = the digest loop of the out-of-place kernel (modgpu_digest_device / _batch_device; `bytes` = all
+                                  entries of the launch; `source_hash` = modgpu_to_kernel_source_hash()) */
     uint32_t grid;        /* workgroups launched                                                  */
     uint32_t block;       /* threads per workgroup                                                */
     uint32_t chunk_bytes; /* bytes one workgroup trip covers                                      */
@@ -98,7 +104,8 @@ typedef struct modgpu_launch_info {
                                 modgpu_verify_table_kernel_source_hash() for variant 11,
                                 modgpu_rekey_verify_kernel_source_hash() for variant 12,
                                 modgpu_rekey_verify_table_kernel_source_hash() for variant 13,
-                                modgpu_rekey_move_table_kernel_source_hash() for variant 15; static storage */
+                                modgpu_rekey_move_table_kernel_source_hash() for variant 15,
+                                modgpu_to_kernel_source_hash() for variant 16; static storage */
 } modgpu_launch_info_t;
 int modgpu_last_launch(modgpu_launch_info_t *out);
 
@@ -255,6 +262,8 @@ void modgpu_debug_set_move_table_grid(uint32_t grid);
  * rekey verify call's compare launches (modgpu_verify_rekey_device, both kernels it may run on).  Measurement
  * (tools/bench_verify.py, tools/bench_verify_rekey.py) and parity tests of small grids. */
 void modgpu_debug_set_verify_form(int grid);
+/* Caps the grid of the digest launches (modgpu_digest_device / _batch_device); <= 0: the shipped grid.  Any grid gives the same sums. */
+void modgpu_debug_set_digest_grid(int grid);
 
 /* The verify table call's stream launch: `grid` workgroups (1..4096), 0 = the shipped grid (one workgroup per CU).
  * Measurement (tools/bench_verify_table.py) and parity tests of small grids, where one workgroup passes several entries. */

@@ -25,6 +25,7 @@ from .capi import (  # noqa: F401
     rekey_table_kernel_source_hash, debug_set_rekey_table_grid, RekeyTableEntry, REKEY_TABLE_DTYPE,
     verify_device, verify_batch_device, verify_results, time_verify_device, verify_kernel_source_hash, debug_set_verify_form,
     VERIFY_RESULT_DTYPE, VERIFY_NONE,
+    digest_device, digest_batch_device, digest_results, digest_adler32, time_digest_device, debug_set_digest_grid, DIGEST_RESULT_DTYPE,
     verify_table_device, verify_table_summary, verify_table_workspace_bytes, time_verify_table_device, verify_table_kernel_source_hash,
     debug_set_verify_table_grid, VERIFY_TABLE_SUMMARY_DTYPE,
     verify_rekey_table_device, verify_rekey_table_workspace_bytes, time_verify_rekey_table_device, rekey_verify_table_kernel_source_hash,

@@ -97,6 +97,11 @@ EXPORTS = {
     "modgpu_verify_rekey_device": (_int, [_vp, _vp, _u64, _i32, _u64, _i32, _u64, _vp, _int, _vp]),
     "modgpu_verify_rekey_batch_device": (_int, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64), ctypes.POINTER(_u64),
                                                 ctypes.POINTER(_u64), _int, _i32, _i32, _vp, _int, _vp]),
+    "modgpu_digest_device": (_int, [_vp, _vp, _u64, _i32, _u64, _vp, _int, _vp]),
+    "modgpu_digest_batch_device": (_int, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64), ctypes.POINTER(_u64), _int, _i32,
+                                          _vp, _int, _vp]),
+    "modgpu_digest_results": (_int, [_vp, _u64, _int, _vp, ctypes.POINTER(ctypes.c_uint32)]),
+    "modgpu_digest_adler32": (ctypes.c_uint32, [_vp]),
 }
 
 
@@ -124,6 +129,8 @@ assert REKEY_TABLE_DTYPE.itemsize == ctypes.sizeof(RekeyTableEntry) == 56
 # modgpu_verify_result_t (include/modgpu.h): 32 bytes
 VERIFY_RESULT_DTYPE = np.dtype([("mismatches", "<u8"), ("first_mismatch", "<u8"), ("n", "<u8"), ("reserved", "<u8")])
 VERIFY_NONE = 0xFFFFFFFFFFFFFFFF  # first_mismatch of a clean entry
+# modgpu_digest_result_t (include/modgpu.h): 32 bytes; only the residues mod 65521 of s1 and s2 are specified
+DIGEST_RESULT_DTYPE = np.dtype([("s1", "<u8"), ("s2", "<u8"), ("n", "<u8"), ("reserved", "<u8")])
 # modgpu_verify_table_summary_t (include/modgpu.h): 32 bytes
 VERIFY_TABLE_SUMMARY_DTYPE = np.dtype([("mismatches", "<u8"), ("first_bad_entry", "<u8"), ("entries", "<u8"), ("reserved", "<u8")])
 
@@ -189,6 +196,7 @@ TESTING_EXPORTS = {
     "modgpu_rekey_verify_table_kernel_source_hash": (ctypes.c_char_p, []),
     "modgpu_rekey_move_table_kernel_source_hash": (ctypes.c_char_p, []),
     "modgpu_keep_policy": (_int, [_u64, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
+    "modgpu_time_digest_device": (_int, [_vp, _vp, _u64, _i32, _u64, _vp, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
 }
 # include/modgpu_testing.h, modgpu_debug_* group: ONLY in libmodgpu_testing.so
 DEBUG_EXPORTS = {
@@ -217,6 +225,7 @@ DEBUG_EXPORTS = {
     "modgpu_debug_set_verify_table_grid": (None, [ctypes.c_uint32]),
     "modgpu_debug_set_rekey_verify_table_grid": (None, [ctypes.c_uint32]),
     "modgpu_debug_set_keep": (None, [_u64, ctypes.c_uint32, ctypes.c_uint32]),
+    "modgpu_debug_set_digest_grid": (None, [_int]),
 }
 
 
@@ -1079,6 +1088,74 @@ def debug_set_verify_form(grid=0):
     _debug_lib().modgpu_debug_set_verify_form(grid)
 
 
+def digest_device(src, key, stream_off=0, dst=None, result=None, device=-1, stream=None, *, n=None):
+    """Asynchronous DIGEST of n bytes at raw device addresses: the Adler-32 (zlib's) of out[j] = src[j] ^ ks(key)[stream_off + j] in one
+    pass that reads n bytes; with `dst` the bytes are stored as cycle_device_to stores them and summed on the way (fused).  `src` /
+    `dst` are addresses or DeviceBuffer; n defaults to the source's size (the smaller one's with a DeviceBuffer dst).  The 32-byte record
+    `result` is device memory (a DeviceBuffer or an address).  With result=None a record is made, the stream synchronised and the
+    Adler-32 returned as an int."""
+    if n is None:
+        if not isinstance(src, DeviceBuffer) or not (dst is None or isinstance(dst, DeviceBuffer)):
+            raise TypeError("n is needed unless the buffers are DeviceBuffer")
+        n = src.nbytes if dst is None else min(src.nbytes, dst.nbytes)
+    own = DeviceBuffer(DIGEST_RESULT_DTYPE.itemsize, device) if result is None else None
+    try:
+        _check(lib().modgpu_digest_device(_vp(_dev_addr(dst) if dst is not None else 0), _vp(_dev_addr(src)), n, as_int32(key), stream_off,
+                                          _vp(_dev_addr(own if own is not None else result)), device, _vp(stream or 0)))
+        if own is None:
+            return None
+        _check(lib().modgpu_sync(device, _vp(stream or 0)))
+        return int(digest_results(own, 1, device)[1][0])
+    finally:
+        if own is not None:
+            own.free()
+
+
+def digest_batch_device(src_ptrs, sizes, key, results, dst_ptrs=None, stream_offs=None, device=-1, stream=None):
+    """Several digest entries of ONE device (entry i from stream_offs[i] or 0, its record at results + 32 * i).  dst_ptrs None, or a None /
+    0 entry: that entry is digest only.  One memset zeroes the records, up to 16 non-empty entries share a launch."""
+    n = len(src_ptrs)
+    assert len(sizes) == n and (dst_ptrs is None or len(dst_ptrs) == n)
+    d = (_vp * n)(*[_dev_addr(x) if x is not None else 0 for x in dst_ptrs]) if dst_ptrs is not None else None
+    s = (_vp * n)(*[_dev_addr(x) for x in src_ptrs])
+    z = (_u64 * n)(*sizes)
+    o = (_u64 * n)(*stream_offs) if stream_offs is not None else None
+    _check(lib().modgpu_digest_batch_device(d, s, z, o, n, as_int32(key), _vp(_dev_addr(results)), device, _vp(stream or 0)))
+
+
+def digest_results(results, count=1, device=-1):
+    """`count` records from device memory (a DeviceBuffer or an address): (a DIGEST_RESULT_DTYPE array, their Adler-32 values as a uint32
+    array); synchronous small copy -- synchronise the stream the digest calls ran on first."""
+    out = np.zeros(count, dtype=DIGEST_RESULT_DTYPE)
+    adler = np.zeros(count, dtype=np.uint32)
+    _check(lib().modgpu_digest_results(_vp(_dev_addr(results)), count, device, _vp(out.ctypes.data if count else 0),
+                                       adler.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) if count else None))
+    return out, adler
+
+
+def digest_adler32(record):
+    """Adler-32 from one record in host memory (a DIGEST_RESULT_DTYPE scalar or a (s1, s2, n) tuple); pure arithmetic in the library."""
+    r = np.zeros(1, dtype=DIGEST_RESULT_DTYPE)
+    if isinstance(record, (tuple, list)):
+        r["s1"], r["s2"], r["n"] = record[:3]
+    else:
+        r[0] = record
+    return int(lib().modgpu_digest_adler32(_vp(r.ctypes.data)))
+
+
+def time_digest_device(src, n, key, result, dst=None, stream_off=0, device=-1, stream=None, iters=2):
+    """Mean ms per digest call (the memset node and one launch) over `iters` calls, HIP events on the launch stream."""
+    ms = ctypes.c_float(0)
+    _check(lib().modgpu_time_digest_device(_vp(_dev_addr(dst) if dst is not None else 0), _vp(_dev_addr(src)), n, as_int32(key), stream_off,
+                                           _vp(_dev_addr(result)), device, _vp(stream or 0), iters, ctypes.byref(ms)))
+    return ms.value
+
+
+def debug_set_digest_grid(grid=0):
+    """Testing flavour: the most workgroups a digest launch takes (0 = shipped: one per CU).  Every grid gives the same sums."""
+    _debug_lib().modgpu_debug_set_digest_grid(grid)
+
+
 def verify_rekey_device(expect, src, key_from, key_to, off_from=0, off_to=0, result=None, device=-1, stream=None, *, n=None):
     """Asynchronous REKEY VERIFY of n bytes at raw device addresses: counts the j with expect[j] != (src[j] ^ ks(key_from)[off_from + j]
     ^ ks(key_to)[off_to + j]) -- the bytes rekey_device_to would have written -- and finds the lowest, in one read-only pass; only the
@@ -1376,6 +1453,12 @@ class DeviceBuffer:
         n = self.nbytes - offset if n is None else n
         assert offset + n <= self.nbytes
         cycle_device(self.ptr + offset, n, key, stream_off, self.device, stream)
+
+    def digest(self, key, n=None, offset=0, stream_off=0, stream=None):
+        """Adler-32 of what the cipher makes of n bytes from `offset` (digest_device, digest only): an int, after a synchronise."""
+        n = self.nbytes - offset if n is None else n
+        assert offset + n <= self.nbytes
+        return digest_device(self.ptr + offset, key, stream_off, None, None, self.device, stream, n=n)
 
     def move(self, dst_offset, src_offset, n, key_from=0, key_to=0, off_from=0, off_to=0, workspace=None, stream=None):
         """Moves n bytes inside the buffer from src_offset to dst_offset, the ranges overlapping in any way (memmove rules), rekeying

@@ -30,10 +30,12 @@ BLOCK = re.compile(r";;#ASMSTART\n(.*?);;#ASMEND", re.S)
 
 
 def kernel_bodies(asm):
-    """mangled name -> text from its label to its s_endpgm"""
+    """mangled name -> text from its label to its s_endpgm -- the LAST one of the function: a kernel with an early way out (the
+    out-of-place kernel's digest loop returns before the stream loop) has one s_endpgm per exit, and the rules are for all of its loops"""
     out = {}
     for m in re.finditer(r"^(_Z\d+modgpu_cycle_\w+):", asm, re.M):
-        out[m.group(1)] = asm[m.end():asm.index("s_endpgm", m.end())]
+        end = re.compile(r"^\.Lfunc_end\d+:", re.M).search(asm, m.end())
+        out[m.group(1)] = asm[m.end():asm.rindex("s_endpgm", m.end(), end.start() if end else len(asm))]
     return out
 
 
@@ -430,6 +432,26 @@ def result_atomics(k, tickets=0):
     return bad
 
 
+def digest_loop(k):
+    """the out-of-place kernel's second loop (cycle_to_kernel.h: the pass whose destination is a sum).  Everything it sends to memory
+    besides an entry's own output is a 64-bit atomic add onto a record the host zeroed: the kernel's 64-bit atomics are
+    global_atomic_add_x2 and nothing else, none of them returning; the sums are taken with v_dot4_u32_u8, one per dword and weight;
+    and nothing is stored through a SOURCE descriptor (the kernel's buffer stores are counted)"""
+    bad = []
+    wide = [(m.group(1), m.group(2)) for m in re.finditer(r"^\s+(global_atomic_\w+_x2)\b([^;\n]*)", k.fn, re.M)]
+    if not wide or any(op != "global_atomic_add_x2" or " sc0" in args for op, args in wide):
+        bad.append("%s: 64-bit atomics %s, expected non-returning global_atomic_add_x2 only (the digest loop's sums)" % (k.name, sorted({op for op, _ in wide})))
+    if "v_dot4_u32_u8" not in k.fn:
+        bad.append("%s: no v_dot4_u32_u8 (the digest loop's byte and position sums)" % k.name)
+    # a descriptor's register quad is reused over a kernel's life, so a store through a SOURCE descriptor shows in the count alone: each
+    # loop stores 4 words in each of its 2 unrolled trips and once in its cut first chunk's (cold, not unrolled) loop, all whole words
+    n_stores = len(code_lines(k.fn, "buffer_store_"))
+    if n_stores != 18 or n_stores != len(code_lines(k.fn, "buffer_store_dwordx4")):
+        bad.append("%s: %d buffer stores, expected 18 whole words (stream loop and digest loop: %s each): the digest loop stores an entry's output "
+                   "through its destination's descriptor and nothing through its source's" % (k.name, n_stores, TRIPS_AND_CUT))
+    return bad
+
+
 def lds_bytes(k, n, of):
     if k.md.get("group_segment_fixed_size", -1) != n:
         return ["%s: LDS is %s bytes, expected the %d of %s" % (k.name, k.md.get("group_segment_fixed_size"), n, of)]
@@ -577,9 +599,10 @@ TUS = (
     TU("cycle_feed_kernel.s", "the host-fed kernel's TU",
        (Kind("modgpu_cycle_feed_kernel", [no_spills, (register_budget, 64)] + HOST_FED + [loads_nt, (stores, "sc1"), mailbox_read_scalar, alg1_mix]),),
        first=[(kernel_count, 1)]),
-    # out-of-place, plain and funnel: the work-queue loop with a destination of its own
+    # out-of-place, plain and funnel: the work-queue loop with a destination of its own, and the digest loop (static chunks, no block
+    # count pinned: one uniform branch chooses between the two)
     TU("cycle_to_kernel.s", "the out-of-place kernel's TU",
-       (Kind("modgpu_cycle_to_kernel", BUDGET + [keystream_blocks, TICKET, loads_nt, (stores, "nt sc1")]),)),
+       (Kind("modgpu_cycle_to_kernel", BUDGET + [keystream_blocks, TICKET, loads_nt, (stores, "nt sc1"), digest_loop]),)),
     # transfer, each direction plain and funnel: host-fed trips; the upload <true, .> stores into HBM, the download across PCIe
     TU("cycle_xfer_kernel.s", "the transfer kernels' TU",
        (Kind("modgpu_cycle_xfer_kernel", XFER + [(stores, "nt sc1", "an upload store into HBM")], "^ILb1E"),

@@ -101,6 +101,221 @@ __global__ __launch_bounds__(BLOCK) MODGPU_KEEP_OFF_THE_FIXED_TEMPORARIES void m
     const uint32_t voff = tid * lcg::WORD;
     const uint32_t lane_mul = mulmod_canon(c_tile_lo.v[tid >> 8], c_lane_pow.v[tid & 255]);
 
+    struct View {
+        uint8_t *origin;           // dst_body - lead
+        const uint8_t *src_origin; // src_body - lead
+        uint64_t end;
+        uint32_t lo, hi;
+        uint32_t first;
+        uint32_t lane_base;
+        uint32_t part; // the entry's index (the digest loop looks its record up by it)
+    };
+    auto locate = [&](uint32_t g, View &v) {
+        if (g - v.lo < v.hi - v.lo) return;
+        uint32_t p = 0;
+#pragma unroll 1
+        for (uint32_t i = 1; i < n_parts; ++i) p += g >= a.start[i] ? 1u : 0u;
+        const CycleToPart &P = a.part[p];
+        v.origin = P.dst_body - P.lead;
+        v.src_origin = P.src_body - P.lead;
+        v.end = P.end;
+        v.first = P.lead != 0 ? 1u : 0u;
+        v.lo = a.start[p];
+        v.hi = a.start[p + 1];
+        v.lane_base = mulmod_canon(P.base_body, lane_mul);
+        v.part = p;
+    };
+    auto chunk_off = [&](uint32_t g, const View &v) { return (uint64_t)(v.first + (g - v.lo)) * CHUNK; };
+    auto chunk_left = [&](uint32_t g, const View &v) {
+        const uint64_t o = chunk_off(g, v);
+        const uint64_t left = g < v.hi && o < v.end ? v.end - o : 0; // past the last entry: zero-size descriptors
+        return (uint32_t)(left < CHUNK ? left : CHUNK);
+    };
+    auto states = [&](uint32_t g, const View &v, uint32_t(&s)[U]) {
+        const uint32_t c = v.first + (g - v.lo);
+        uint32_t p = mulmod_canon(c_chunk_pow0<CHUNK>.v[c & 255], c_chunk_pow1<CHUNK>.v[(c >> 8) & 255]);
+        p = mulmod_canon(p, c_chunk_pow2<CHUNK>.v[(c >> 16) & 255]);
+        s[0] = mulmod_canon(v.lane_base, p);
+#pragma unroll
+        for (int u = 1; u < U; ++u) s[u] = mulmod_canon(s[u - 1], lcg::kTileLo.v[BLOCK / 256]);
+    };
+    View vl{nullptr, nullptr, 0, 0, 0, 0, 1, 0}, vs{nullptr, nullptr, 0, 0, 0, 0, 1, 0}; // load side, store side
+    auto load = [&](Raw(&w)[U], uint32_t g) {
+        locate(g, vl);
+        const SrcRsrc rs = src_rsrc<FUNNEL>(vl.src_origin + chunk_off(g, vl), chunk_left(g, vl));
+#pragma unroll
+        for (int u = 0; u < U; ++u) load_src<FUNNEL>(w[u], rs, voff + u * SUB);
+    };
+
+    // ---- the digest loop (cycle_to_kernel.h): out is summed -- and, for an entry with a destination, stored exactly as the stream loop
+    // stores it.  One uniform branch at the top of the kernel; the stream loop below is not entered.
+    // Widths.  A dword's byte sum and position sum are one v_dot4_u32_u8 each (weights 0x01010101; 0x03020100 + 4k for dword k of the
+    // word).  Per lane-word b = sum of bytes <= 16 * 255 = 4 080 and w = sum of i * byte_i <= 120 * 255 = 30 600.  Per chunk a lane
+    // adds, in 32 bits, c1 = sum of b <= 4 * 4 080 = 16 320 and c2 = sum of (q * b + w), q < 65 536 the word's offset in the chunk:
+    // <= 4 * (65 520 * 4 080 + 30 600) < 1.07e9.  The chunk origin's index in the entry enters reduced (bm < 65 521, stepped by
+    // CHUNK mod 65 521 per chunk): bm * c1 + c2 < 1.07e9 + 1.07e9 < 2^32.  Across chunks the lane keeps 64-bit sums that grow by
+    // < 2^32 per chunk: good for 2^32 chunks per visit of an entry, and an entry has fewer than 2^24.  Leaving an entry, every lane
+    // reduces its two sums mod 65 521 and adds them into LDS (32-bit: 1 024 * 65 520 < 2^27); thread 0 reduces again and sends one pair.
+    // Through LDS and not per wave: one pair per workgroup instead of sixteen, and a wave fold needs either DPP code of its own or a
+    // lane index (v_mbcnt, which this TU's guard reads as a rewritten ticket atomic).
+    if (a.digest != 0u) {
+        const bool ident = (a.digest & CYCLE_TO_DIGEST_IDENTITY) != 0u;
+        __shared__ uint32_t dg_red[2];
+        unsigned long long a1 = 0ull, a2 = 0ull; // the lane's sums over the entry its workgroup is in
+        if (tid == 0) dg_red[0] = dg_red[1] = 0u;
+        __syncthreads();
+        // the workgroup leaves an entry (uniform); n_add: the entry's n, from the workgroup that owns its edges
+        auto flush = [&](CycleToDigest *res, unsigned long long n_add) {
+            const uint32_t r1 = (uint32_t)(a1 % kDigestMod), r2 = (uint32_t)(a2 % kDigestMod);
+            if (r1 != 0u) atomicAdd(&dg_red[0], r1);
+            if (r2 != 0u) atomicAdd(&dg_red[1], r2);
+            a1 = a2 = 0ull;
+            __syncthreads();
+            if (tid == 0) {
+                const unsigned long long t1 = dg_red[0] % kDigestMod, t2 = dg_red[1] % kDigestMod;
+                if (t1 != 0ull) __hip_atomic_fetch_add(&res->s1, t1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (t2 != 0ull) __hip_atomic_fetch_add(&res->s2, t2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (n_add != 0ull) __hip_atomic_fetch_add(&res->n, n_add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                dg_red[0] = dg_red[1] = 0u;
+            }
+            __syncthreads();
+        };
+        // byte sum and position sum (byte i of the word weighs i) of one 16-byte word
+        auto word_sums = [](const u32x4 &d, uint32_t &b, uint32_t &w) {
+            b = __builtin_amdgcn_udot4(d.x, 0x01010101u, 0u, false);
+            b = __builtin_amdgcn_udot4(d.y, 0x01010101u, b, false);
+            b = __builtin_amdgcn_udot4(d.z, 0x01010101u, b, false);
+            b = __builtin_amdgcn_udot4(d.w, 0x01010101u, b, false);
+            w = __builtin_amdgcn_udot4(d.x, 0x03020100u, 0u, false);
+            w = __builtin_amdgcn_udot4(d.y, 0x07060504u, w, false);
+            w = __builtin_amdgcn_udot4(d.z, 0x0B0A0908u, w, false);
+            w = __builtin_amdgcn_udot4(d.w, 0x0F0E0D0Cu, w, false);
+        };
+
+        // edges, cut first chunk and n of entry p: workgroup p, before the stream starts (cold code)
+        for (uint32_t p = blk; p < n_parts; p += G) {
+            const CycleToPart &P = a.part[p];
+            const bool store = ((a.store_mask >> p) & 1u) != 0u;
+            const uint64_t body_bytes = P.end - P.lead;
+            if (tid < 32) {
+                // < 16 bytes before / after the body, bytewise (cycle_edges_to); byte j of the entry weighs j
+                const bool head = tid < P.head_n, tail = tid >= 16 && tid - 16 < P.tail_n;
+                if (head || tail) {
+                    const uint32_t t = head ? tid : tid - 16;
+                    const uint64_t at = head ? 0 : body_bytes;               // from the body's start
+                    const uint8_t *sp = head ? P.src_body - P.head_n : P.src_body;
+                    uint8_t out = sp[at + t];
+                    if (!ident) {
+                        uint32_t s = head ? P.base_head : P.base_tail;
+                        for (uint32_t j = 0; j < t; ++j) s = mulmod_canon(s, lcg::A);
+                        out = cycle_byte(out, s);
+                    }
+                    if (store) (head ? P.dst_body - P.head_n : P.dst_body)[at + t] = out;
+                    const uint64_t j = head ? (uint64_t)t : (uint64_t)P.head_n + body_bytes + t;
+                    a1 += out;
+                    a2 += (j % kDigestMod) * out;
+                }
+            }
+            if (P.lead != 0 && body_bytes != 0) {
+                const uint32_t inside = (uint32_t)(P.end < CHUNK ? body_bytes : CHUNK - P.lead);
+                auto rd = __builtin_amdgcn_make_buffer_rsrc(P.dst_body, 0, (int)inside, 0x00020000);
+                const SrcRsrc rs = src_rsrc<FUNNEL>(P.src_body, inside);
+                uint32_t su = ident ? 0u : mulmod_canon(P.base_body, lane_mul);
+#pragma unroll 1
+                for (uint32_t u = 0; u < (uint32_t)U; ++u) {
+                    const uint32_t o = voff + u * SUB - P.lead; // lanes in front of the body wrap past num_records: dropped, and masked below
+                    Raw w;
+                    load_src<FUNNEL>(w, rs, o);
+                    u32x4 d = src_word<FUNNEL>(w, rs.sh);
+                    if (!ident) {
+                        d = cycle_word<ALG>(d, su);
+                        su = mulmod_canon(su, lcg::kTileLo.v[BLOCK / 256]);
+                    }
+                    if (store) __builtin_amdgcn_raw_buffer_store_b128(d, rd, o, 0, SAUX);
+                    if (o < inside) { // (a lane outside read zeros: its d is the keystream, not output)
+                        uint32_t b, ws;
+                        word_sums(d, b, ws);
+                        a1 += b;
+                        a2 += (P.head_n + o) * b + ws; // < 65 552 * 4 080 + 30 600: 32 bits
+                    }
+                }
+            }
+            flush(a.result[p], (uint64_t)P.head_n + body_bytes + P.tail_n);
+        }
+
+        CycleToDigest *res = nullptr; // of the entry the sums are being kept for
+        bool store = false;
+        uint32_t idxm = 0u; // index in the entry of the byte at the chunk origin (head_n - lead), mod 65 521
+        auto sum = [&](Raw(&w)[U], uint32_t g) {
+            if (g - vs.lo >= vs.hi - vs.lo) {
+                if (res) flush(res, 0ull); // the workgroup moves on to another entry
+                locate(g, vs);
+                const CycleToPart &P = a.part[vs.part];
+                res = a.result[vs.part];
+                store = ((a.store_mask >> vs.part) & 1u) != 0u;
+                idxm = (P.head_n + kDigestMod - P.lead % kDigestMod) % kDigestMod;
+            }
+            const uint64_t o = chunk_off(g, vs);
+            const uint32_t left = chunk_left(g, vs);
+            const uint32_t c = vs.first + (g - vs.lo);                          // < 2^24
+            const uint32_t bm = (idxm + (CHUNK % kDigestMod) * c) % kDigestMod; // (CHUNK mod 65 521 = 15: 32 bits hold it)
+            const uint32_t sh = FUNNEL ? (uint32_t)(uintptr_t)(vs.src_origin + o) & 3u : 0u;
+            u32x4 d[U];
+            if (ident) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) d[u] = src_word<FUNNEL>(w[u], sh);
+            } else {
+                uint32_t s[U];
+                states(g, vs, s);
+#pragma unroll
+                for (int u = 0; u < U; ++u) d[u] = cycle_word<ALG>(src_word<FUNNEL>(w[u], sh), s[u]);
+            }
+            if (store) { // (uniform) a workgroup-synchronous burst, as in the stream loop: every wave's stores leave together
+                auto r = __builtin_amdgcn_make_buffer_rsrc(vs.origin + o, 0, (int)left, 0x00020000);
+                __builtin_amdgcn_sched_barrier(0);
+                __builtin_amdgcn_s_barrier();
+#pragma unroll
+                for (int u = 0; u < U; ++u) __builtin_amdgcn_raw_buffer_store_b128(d[u], r, voff + u * SUB, 0, SAUX);
+            }
+            uint32_t c1 = 0u, c2 = 0u;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const uint32_t q = voff + (uint32_t)u * SUB;
+                uint32_t b, ws;
+                word_sums(d[u], b, ws);
+                // a lane past the ragged end of the entry's last chunk read zeros: its d is the keystream, not output
+                const bool in = q < left;
+                b = in ? b : 0u;
+                ws = in ? ws : 0u;
+                c1 += b;
+                c2 += q * b + ws;
+            }
+            a1 += c1;
+            a2 += bm * c1 + c2;
+        };
+        uint32_t g = blk;
+        if (g < total) {
+            Raw w[2][U];
+            load(w[0], g);
+            bool finished = false;
+            while (!finished) {
+#pragma unroll
+                for (int p = 0; p < 2; ++p) {
+                    __builtin_amdgcn_s_barrier();
+                    load(w[p ^ 1], g + G); // (past the last chunk: zero-size descriptors, nothing is read)
+                    __builtin_amdgcn_sched_barrier(0);
+                    sum(w[p], g);
+                    g += G;
+                    if (g >= total) {
+                        finished = true;
+                        break;
+                    }
+                }
+            }
+            flush(res, 0ull);
+        }
+        return; // no ticket was drawn: nothing to sign off
+    }
     // edges and cut first chunk of entry p: workgroup p, before the stream starts (cold code)
     for (uint32_t p = blk; p < n_parts; p += G) {
         const CycleToPart &P = a.part[p];
@@ -123,49 +338,6 @@ __global__ __launch_bounds__(BLOCK) MODGPU_KEEP_OFF_THE_FIXED_TEMPORARIES void m
         }
     }
 
-    struct View {
-        uint8_t *origin;           // dst_body - lead
-        const uint8_t *src_origin; // src_body - lead
-        uint64_t end;
-        uint32_t lo, hi;
-        uint32_t first;
-        uint32_t lane_base;
-    };
-    auto locate = [&](uint32_t g, View &v) {
-        if (g - v.lo < v.hi - v.lo) return;
-        uint32_t p = 0;
-#pragma unroll 1
-        for (uint32_t i = 1; i < n_parts; ++i) p += g >= a.start[i] ? 1u : 0u;
-        const CycleToPart &P = a.part[p];
-        v.origin = P.dst_body - P.lead;
-        v.src_origin = P.src_body - P.lead;
-        v.end = P.end;
-        v.first = P.lead != 0 ? 1u : 0u;
-        v.lo = a.start[p];
-        v.hi = a.start[p + 1];
-        v.lane_base = mulmod_canon(P.base_body, lane_mul);
-    };
-    auto chunk_off = [&](uint32_t g, const View &v) { return (uint64_t)(v.first + (g - v.lo)) * CHUNK; };
-    auto chunk_left = [&](uint32_t g, const View &v) {
-        const uint64_t o = chunk_off(g, v);
-        const uint64_t left = g < v.hi && o < v.end ? v.end - o : 0; // past the last entry: zero-size descriptors
-        return (uint32_t)(left < CHUNK ? left : CHUNK);
-    };
-    auto states = [&](uint32_t g, const View &v, uint32_t(&s)[U]) {
-        const uint32_t c = v.first + (g - v.lo);
-        uint32_t p = mulmod_canon(c_chunk_pow0<CHUNK>.v[c & 255], c_chunk_pow1<CHUNK>.v[(c >> 8) & 255]);
-        p = mulmod_canon(p, c_chunk_pow2<CHUNK>.v[(c >> 16) & 255]);
-        s[0] = mulmod_canon(v.lane_base, p);
-#pragma unroll
-        for (int u = 1; u < U; ++u) s[u] = mulmod_canon(s[u - 1], lcg::kTileLo.v[BLOCK / 256]);
-    };
-    View vl{nullptr, nullptr, 0, 0, 0, 0, 1}, vs{nullptr, nullptr, 0, 0, 0, 0, 1}; // load side, store side
-    auto load = [&](Raw(&w)[U], uint32_t g) {
-        locate(g, vl);
-        const SrcRsrc rs = src_rsrc<FUNNEL>(vl.src_origin + chunk_off(g, vl), chunk_left(g, vl));
-#pragma unroll
-        for (int u = 0; u < U; ++u) load_src<FUNNEL>(w[u], rs, voff + u * SUB);
-    };
     // lane 0's ticket traffic: a plain returning atomic, waited for only where it is published (TU built with
     // -mllvm -amdgpu-atomic-optimizer-strategy=None); the LDS mailbox in ds_ assembly (a volatile C++ access would be FLAT)
     uint32_t pending = 0;
@@ -266,4 +438,10 @@ hipError_t modgpu_launch_cycle_to(const CycleToArgs &a, int form, uint32_t grid,
     if (form == CYCLE_TO_FUNNEL) ToFunnel::launch(a, grid, stream);
     else ToPlain::launch(a, grid, stream);
     return hipGetLastError();
+}
+hipError_t modgpu_launch_cycle_to_digest(const CycleToArgs &a, int form, uint32_t grid, hipStream_t stream)
+{
+    CycleToArgs d = a;
+    d.digest |= CYCLE_TO_DIGEST_ON;
+    return modgpu_launch_cycle_to(d, form, grid, stream);
 }

@@ -1235,6 +1235,121 @@ int verify_impl(const void *const *expect, const void *const *src, const uint64_
     return MODGPU_OK;
 }
 
+// ---- digest: Adler-32 of out[j] = src[j] ^ ks(key)[off + j], with or without storing out (modgpu_digest_device / modgpu_digest_batch_device) ----
+// The out-of-place kernels' digest loop (cycle_to_kernel.h): static chunk assignment on one workgroup per CU, like verify.  No ticket
+// pair is drawn, so there is nothing to run out of and no second route -- DESIGN.md 4.16, profiles/r16_digest.json.
+static_assert(sizeof(modgpu_digest_result_t) == sizeof(CycleToDigest) && sizeof(modgpu_digest_result_t) == 32 &&
+                  offsetof(modgpu_digest_result_t, s2) == offsetof(CycleToDigest, s2) && offsetof(modgpu_digest_result_t, n) == offsetof(CycleToDigest, n) &&
+                  offsetof(modgpu_digest_result_t, reserved) == offsetof(CycleToDigest, reserved),
+              "the kernel's record is the public one");
+static_assert(sizeof(CycleToArgs) <= 4096, "the table of entries travels in the kernel arguments");
+#ifdef MODGPU_TESTING_HOOKS
+std::atomic<uint32_t> g_digest_grid{0}; // modgpu_debug_set_digest_grid
+uint32_t digest_grid_forced() { return g_digest_grid.load(std::memory_order_relaxed); }
+#else
+constexpr uint32_t digest_grid_forced() { return 0; }
+#endif
+
+// One digest launch over 1..kCycleBatchMax non-empty entries of the current device (key_res == 0: out = src).  An entry without a
+// destination is planned with its source in the destination's role: the chunk grid lies on the source, whose phase against itself is 0.
+int launch_digest(uint8_t *const *dst, const uint8_t *const *src, const uint64_t *sizes, const uint64_t *offs,
+                  modgpu_digest_result_t *const *results, int n, uint32_t key_res, hipStream_t stream)
+{
+    CycleToArgs a{};
+    const uint64_t chunk = modgpu_to_chunk_bytes();
+    uint64_t total = 0, bytes = 0;
+    bool misaligned = false;
+    for (int k = 0; k < n; ++k) {
+        CycleToPart &P = a.part[k];
+        uint8_t *const role = dst[k] ? dst[k] : const_cast<uint8_t *>(src[k]); // (never stored through when it is the source)
+        const EntryGeom g = entry_geom(role, sizes[k], chunk);
+        P.dst_body = role + g.head;
+        P.src_body = src[k] + g.head;
+        P.head_n = (uint32_t)g.head;
+        P.tail_n = (uint32_t)g.tail;
+        P.lead = g.lead;
+        P.end = g.end;
+        if (key_res) entry_bases(g, key_res, offs[k] % lcg::PERIOD, P.base_head, P.base_body, P.base_tail);
+        a.result[k] = reinterpret_cast<CycleToDigest *>(results[k]);
+        if (dst[k]) a.store_mask |= 1u << k;
+        a.start[k] = (uint32_t)total;
+        total += g.n_chunks > g.first ? g.n_chunks - g.first : 0;
+        bytes += sizes[k];
+        misaligned |= g.words != 0 && ((reinterpret_cast<uintptr_t>(src[k]) - reinterpret_cast<uintptr_t>(role)) & 3) != 0;
+    }
+    for (int k = n; k <= kCycleBatchMax; ++k) a.start[k] = (uint32_t)total;
+    a.n_parts = (uint32_t)n;
+    a.digest = CYCLE_TO_DIGEST_ON | (key_res ? 0u : CYCLE_TO_DIGEST_IDENTITY);
+    // digest only: one workgroup per CU, as verify (a read-only stream).  A launch that stores takes the out-of-place kernel's grid,
+    // 25 workgroups per 32 CUs (cycle_kernel.hip: the memory system does best with fewer read/write streams than CUs)
+    uint64_t cap = large_grid(), helpers = 0;
+    if (a.store_mask) queue_grid(total, large_grid(), &cap, &helpers);
+    if (digest_grid_forced()) cap = digest_grid_forced();
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(total, cap));
+    const int form = misaligned ? to_form() : CYCLE_TO_PLAIN;
+    const hipError_t e = modgpu_launch_cycle_to_digest(a, form, grid, stream);
+    if (e != hipSuccess) return fail_hip(e, "digest kernel launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    t_last_launch = {modgpu_to_kernel_name(form), CYCLE_TO_DIGEST, grid, modgpu_to_block(), (uint32_t)chunk, bytes, grid, MODGPU_TO_KERNEL_SOURCE_HASH};
+    return MODGPU_OK;
+}
+
+// Everything that is checked before a device is looked at.  `dst` may be null (digest only), and so may any of its entries; an entry
+// that has a destination keeps the out-of-place rules (check_to_entries).
+int check_digest_entries(void *const *dst, const void *const *src, const uint64_t *sizes, int n, const modgpu_digest_result_t *results)
+{
+    if (n < 0 || (n > 0 && (!src || !sizes))) return fail(MODGPU_ERR_INVALID, "bad entry list");
+    if (n > 0 && !results) return fail(MODGPU_ERR_INVALID, "null result");
+    if (reinterpret_cast<uintptr_t>(results) & 7) return fail(MODGPU_ERR_INVALID, "result not 8-byte aligned");
+    auto dst_of = [&](int i) -> const void * { return dst && sizes[i] ? dst[i] : nullptr; };
+    for (int i = 0; i < n; ++i) {
+        if (!sizes[i]) continue;
+        if (!src[i]) return fail(MODGPU_ERR_INVALID, "null buffer");
+        const void *d = dst_of(i);
+        if (d && d != src[i] && ranges_meet(d, sizes[i], src[i], sizes[i]))
+            return fail(MODGPU_ERR_INVALID, "destination partly overlaps its source (only dst == src may alias)");
+        // (the kernel jumps to a chunk's keystream state by the three bytes of its index in the entry)
+        if (sizes[i] >= (1ull << 41) || entry_geom(static_cast<const uint8_t *>(d ? d : src[i]), sizes[i], modgpu_to_chunk_bytes()).n_chunks >= (1ull << 24))
+            return fail(MODGPU_ERR_INVALID, "an entry that spans 2^24 chunks of 64 KiB or more (1 TiB)");
+    }
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < n; ++j)
+            if (i != j && dst_of(i) && (ranges_meet(dst_of(i), sizes[i], src[j], sizes[j]) || (dst_of(j) && ranges_meet(dst_of(i), sizes[i], dst_of(j), sizes[j]))))
+                return fail(MODGPU_ERR_INVALID, "a destination meets another entry's source or destination");
+    return MODGPU_OK;
+}
+
+// Entries already checked (check_digest_entries), on the current device, asynchronous on `stream`: all n records are zeroed on the
+// call's own stream (a node of a capture, so a replay starts clean), then runs of up to kCycleBatchMax non-empty entries share a launch.
+int digest_impl(void *const *dst, const void *const *src, const uint64_t *sizes, const uint64_t *offs, int n, int32_t key,
+                modgpu_digest_result_t *results, hipStream_t stream)
+{
+    if (n == 0) return MODGPU_OK;
+    int phys = -1;
+    HIP_TRY(hipGetDevice(&phys));
+    if (modgpu_xfer_device_of(results, (uint64_t)n * sizeof(modgpu_digest_result_t)) != phys)
+        return fail(MODGPU_ERR_INVALID, "the result is not device memory of the call's device");
+    const uint32_t key_res = lcg::key_residue(key);
+    HIP_TRY(hipMemsetAsync(results, 0, (size_t)n * sizeof(modgpu_digest_result_t), stream));
+    (void)hipGetLastError(); // (the launch reports hipGetLastError: an earlier call's error must not be taken for its own)
+    int i = 0, idx[kCycleBatchMax];
+    while (const int g = next_run(sizes, n, i, idx, [](int) { return true; })) {
+        uint8_t *gd[kCycleBatchMax];
+        const uint8_t *gs[kCycleBatchMax];
+        uint64_t gn[kCycleBatchMax], go[kCycleBatchMax];
+        modgpu_digest_result_t *gr[kCycleBatchMax];
+        for (int k = 0; k < g; ++k) {
+            gd[k] = dst ? static_cast<uint8_t *>(dst[idx[k]]) : nullptr;
+            gs[k] = static_cast<const uint8_t *>(src[idx[k]]);
+            gn[k] = sizes[idx[k]];
+            go[k] = offs ? offs[idx[k]] : 0;
+            gr[k] = results + idx[k];
+        }
+        if (const int rc = launch_digest(gd, gs, gn, go, gr, g, key_res, stream)) return rc;
+    }
+    return MODGPU_OK;
+}
+
 // ---- rekey verify: count and locate the j with expect[j] != (src[j] ^ ks(key_from)[off_from + j] ^ ks(key_to)[off_to + j])
 // (modgpu_verify_rekey_device / modgpu_verify_rekey_batch_device) ----
 // One two-keystream compare launch over 1..kCycleBatchMax non-empty entries of the current device, both keys non-zero residues:
@@ -2030,6 +2145,57 @@ int modgpu_verify_results(const modgpu_verify_result_t *dev_results, uint64_t co
     });
 }
 
+int modgpu_digest_device(void *dev_dst, const void *dev_src, uint64_t n, int32_t key, uint64_t stream_off, modgpu_digest_result_t *dev_result,
+                         int device, void *hip_stream)
+{
+    return guarded([&]() -> int {
+        if (int rc = check_digest_entries(dev_dst ? &dev_dst : nullptr, &dev_src, &n, 1, dev_result)) return rc;
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        return digest_impl(dev_dst ? &dev_dst : nullptr, &dev_src, &n, &stream_off, 1, key, dev_result, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int modgpu_digest_batch_device(void *const *dst_parts, const void *const *src_parts, const uint64_t *sizes, const uint64_t *stream_offs,
+                               int n_parts, int32_t key, modgpu_digest_result_t *dev_results, int device, void *hip_stream)
+{
+    return guarded([&]() -> int {
+        if (int rc = check_digest_entries(dst_parts, src_parts, sizes, n_parts, dev_results)) return rc;
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        return digest_impl(dst_parts, src_parts, sizes, stream_offs, n_parts, key, dev_results, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+uint32_t modgpu_digest_adler32(const modgpu_digest_result_t *host_result)
+{
+    if (!host_result) return 1u;
+    const uint64_t m = kDigestMod, s1 = host_result->s1 % m, s2 = host_result->s2 % m, n = host_result->n % m;
+    const uint64_t a = (1 + s1) % m, b = (n + n * s1 % m + m - s2) % m;
+    return (uint32_t)(b << 16 | a);
+}
+
+int modgpu_digest_results(const modgpu_digest_result_t *dev_results, uint64_t count, int device, modgpu_digest_result_t *host_out,
+                          uint32_t *adler32_out)
+{
+    return guarded([&]() -> int {
+        if (count > 0 && (!dev_results || !host_out)) return fail(MODGPU_ERR_INVALID, "null results or out pointer");
+        if (reinterpret_cast<uintptr_t>(dev_results) & 7) return fail(MODGPU_ERR_INVALID, "results not 8-byte aligned");
+        if (count > (1ull << 40)) return fail(MODGPU_ERR_INVALID, "too many results");
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        if (count == 0) return MODGPU_OK;
+        int phys = -1;
+        HIP_TRY(hipGetDevice(&phys));
+        if (modgpu_xfer_device_of(dev_results, count * sizeof(modgpu_digest_result_t)) != phys)
+            return fail(MODGPU_ERR_INVALID, "the results are not device memory of the call's device");
+        HIP_TRY(hipMemcpy(host_out, dev_results, count * sizeof(modgpu_digest_result_t), hipMemcpyDeviceToHost));
+        if (adler32_out)
+            for (uint64_t i = 0; i < count; ++i) adler32_out[i] = modgpu_digest_adler32(host_out + i);
+        return MODGPU_OK;
+    });
+}
+
 uint64_t modgpu_table_workspace_bytes(uint64_t n_entries)
 {
     return n_entries == 0 || n_entries > kTableMaxEntries ? 0 : table_layout(n_entries).bytes;
@@ -2794,6 +2960,20 @@ int modgpu_time_verify_rekey_device(const void *dev_expect, const void *dev_src,
     });
 }
 
+int modgpu_time_digest_device(void *dev_dst, const void *dev_src, uint64_t n, int32_t key, uint64_t stream_off, void *dev_result, int device,
+                              void *hip_stream, int iters, float *ms_per_call)
+{
+    return guarded([&]() -> int {
+        modgpu_digest_result_t *res = static_cast<modgpu_digest_result_t *>(dev_result);
+        void *const *dst = dev_dst ? &dev_dst : nullptr;
+        if (iters > 0 && ms_per_call)
+            if (int rc = check_digest_entries(dst, &dev_src, &n, 1, res)) return rc;
+        return time_calls(device, hip_stream, iters, ms_per_call, [&](hipStream_t st) {
+            return digest_impl(dst, &dev_src, &n, &stream_off, 1, key, res, st);
+        });
+    });
+}
+
 int modgpu_last_launch(modgpu_launch_info_t *out)
 {
     if (!out) return fail(MODGPU_ERR_INVALID, "null out pointer");
@@ -2936,6 +3116,8 @@ void modgpu_debug_set_rekey_verify_table_grid(uint32_t grid) { force_table_grid(
 
 // (caps the compare launches of the verify call and of the rekey verify call alike)
 void modgpu_debug_set_verify_form(int grid) { g_verify_grid.store(grid <= 0 ? 0u : std::min<uint32_t>((uint32_t)grid, 4096u), std::memory_order_relaxed); }
+
+void modgpu_debug_set_digest_grid(int grid) { g_digest_grid.store(grid <= 0 ? 0u : std::min<uint32_t>((uint32_t)grid, 4096u), std::memory_order_relaxed); }
 
 void modgpu_debug_set_keep(uint64_t min_bytes, uint32_t mask, uint32_t run)
 {
