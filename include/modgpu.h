@@ -583,6 +583,39 @@ uint64_t modgpu_verify_rekey_table_workspace_bytes(uint64_t n_entries);
 int modgpu_verify_rekey_table_device(const modgpu_rekey_table_entry_t *dev_entries, uint64_t n_entries, modgpu_verify_result_t *dev_results,
                                      void *dev_workspace, uint64_t workspace_bytes, int device, void *hip_stream);
 
+/* ---- DIGEST TABLE: the digest call over a device-resident table of any length, in three launches -------------------------------------
+ * "Are the 100 000 files of this part the files I packed?" for the caller who holds a manifest of checksums and no comparand.  One
+ * entry is a modgpu_table_entry_t as it stands (40 bytes, flags 0) whose `dst` IS IGNORED -- never read, never dereferenced, never
+ * written; NULL or anything else --, so the same device-resident table goes unchanged to modgpu_cycle_table_device,
+ * modgpu_verify_table_device and this call.  dev_results[i] receives the record of
+ *     out[j] = src_i[j] ^ ks(key_i)[stream_off_i + j],  j = 0 .. n_i - 1
+ * as modgpu_digest_device defines it: {s1, s2, n, 0}, only the residues mod 65521 of s1 and s2 specified, n the entry's n; read back
+ * and closed with modgpu_digest_results / modgpu_digest_adler32.  An empty entry gives {0, 0, 0, 0} (Adler-32 = 1); a key == 0 mod
+ * 2^31-1 gives the plain Adler-32 of the source.  Each entry has its own key and stream offset.  The bytes of workspace a call over
+ * n_entries needs (0 for none, or above MODGPU_TABLE_MAX_ENTRIES) -- modgpu_table_workspace_bytes(n_entries), the same layout: */
+uint64_t modgpu_digest_table_workspace_bytes(uint64_t n_entries);
+
+/* The contract is modgpu_verify_table_device's, word for word where it applies: THREE launches (plan, finish, stream) whatever the
+ * count -- path_stats().gpu_launches counts 3, modgpu_last_launch reports the stream launch as variant 17 with `bytes` = 0 --;
+ * asynchronous on `hip_stream`, allocation-free, capturable into a hipGraph; the table is read when the call RUNS on the device, so a
+ * replay picks up rewritten entries; the workspace (modgpu_digest_table_workspace_bytes(n_entries) bytes of device memory of `device`,
+ * 8-byte aligned) is the caller's, reset by the plan launch in stream order, and two calls on one workspace must not overlap in time.
+ * The workspace starts with the table call's header, so modgpu_table_status reports this call too (it has no summary line).
+ *   * EVERYTHING BUT THE RECORDS AND THE WORKSPACE IS READ-ONLY.  There is no overlap rule at all -- sources may overlap anything, each
+ *     other and the records' neighbours included -- and no _validate function.
+ *   * dev_results: n_entries records in device memory of `device`, 8-byte aligned, the caller's.  THE CALL INITIALISES THEM ITSELF, AND
+ *     WITHOUT A MEMSET NODE: the finish launch stores every entry's record whole (the sums of the < 16 ragged bytes at either end of
+ *     the entry, and n), the stream launch then only adds to valid records (64-bit atomic adds).  Nothing needs clearing beforehand; a
+ *     replayed graph starts clean.
+ *   * Tier 1 (host, MODGPU_ERR_INVALID before anything is queued): modgpu_verify_table_device's tier 1 with this call's workspace
+ *     size: a NULL table, workspace or dev_results with n_entries > 0; one of them not 8-byte aligned; a short workspace; memory not
+ *     reported as device memory of `device`; more than MODGPU_TABLE_MAX_ENTRIES entries.  n_entries == 0 queues nothing.
+ *   * Tier 2 (device, by the plan launch): a NULL src with n > 0, nonzero flags, an entry of 1 TiB or more, more than 2^31 chunks of
+ *     64 KiB together.  Any of these makes the whole call write NO RECORD AT ALL -- dev_results stays as the caller left it -- and
+ *     modgpu_table_status names the lowest such entry. */
+int modgpu_digest_table_device(const modgpu_table_entry_t *dev_entries, uint64_t n_entries, modgpu_digest_result_t *dev_results,
+                               void *dev_workspace, uint64_t workspace_bytes, int device, void *hip_stream);
+
 /* Replaces CEncryptionCycler::Cycle (CEncryptionCycler.cpp:4-14) for a caller-owned HOST buffer,
  * on the GPU.  Pageable memory is staged through page-locked slots owned by this library (memcpy ->
  * slot -> kernel across PCIe on the slot -> memcpy back, chunked over several host threads and

@@ -28,6 +28,7 @@ from .capi import (  # noqa: F401
     digest_device, digest_batch_device, digest_results, digest_adler32, time_digest_device, debug_set_digest_grid, DIGEST_RESULT_DTYPE,
     verify_table_device, verify_table_summary, verify_table_workspace_bytes, time_verify_table_device, verify_table_kernel_source_hash,
     debug_set_verify_table_grid, VERIFY_TABLE_SUMMARY_DTYPE,
+    digest_table_device, digest_table_workspace_bytes, time_digest_table_device, debug_set_digest_table_grid,
     verify_rekey_table_device, verify_rekey_table_workspace_bytes, time_verify_rekey_table_device, rekey_verify_table_kernel_source_hash,
     debug_set_rekey_verify_table_grid,
     verify_rekey_device, verify_rekey_batch_device, time_verify_rekey_device, rekey_verify_kernel_source_hash,

@@ -100,6 +100,8 @@ EXPORTS = {
     "modgpu_digest_device": (_int, [_vp, _vp, _u64, _i32, _u64, _vp, _int, _vp]),
     "modgpu_digest_batch_device": (_int, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64), ctypes.POINTER(_u64), _int, _i32,
                                           _vp, _int, _vp]),
+    "modgpu_digest_table_workspace_bytes": (_u64, [_u64]),
+    "modgpu_digest_table_device": (_int, [_vp, _u64, _vp, _vp, _u64, _int, _vp]),
     "modgpu_digest_results": (_int, [_vp, _u64, _int, _vp, ctypes.POINTER(ctypes.c_uint32)]),
     "modgpu_digest_adler32": (ctypes.c_uint32, [_vp]),
 }
@@ -189,6 +191,7 @@ TESTING_EXPORTS = {
     "modgpu_verify_kernel_source_hash": (ctypes.c_char_p, []),
     "modgpu_time_verify_table_device": (_int, [_vp, _u64, _vp, _vp, _u64, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
     "modgpu_verify_table_kernel_source_hash": (ctypes.c_char_p, []),
+    "modgpu_time_digest_table_device": (_int, [_vp, _u64, _vp, _vp, _u64, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
     "modgpu_time_verify_rekey_device": (_int, [_vp, _vp, _u64, _i32, _u64, _i32, _u64, _vp, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
     "modgpu_rekey_verify_kernel_source_hash": (ctypes.c_char_p, []),
     "modgpu_keep_kernel_source_hash": (ctypes.c_char_p, []),
@@ -224,6 +227,7 @@ DEBUG_EXPORTS = {
     "modgpu_debug_set_verify_form": (None, [_int]),
     "modgpu_debug_set_verify_table_grid": (None, [ctypes.c_uint32]),
     "modgpu_debug_set_rekey_verify_table_grid": (None, [ctypes.c_uint32]),
+    "modgpu_debug_set_digest_table_grid": (None, [ctypes.c_uint32]),
     "modgpu_debug_set_keep": (None, [_u64, ctypes.c_uint32, ctypes.c_uint32]),
     "modgpu_debug_set_digest_grid": (None, [_int]),
 }
@@ -1294,6 +1298,58 @@ def debug_set_verify_table_grid(grid=0):
     _debug_lib().modgpu_debug_set_verify_table_grid(grid)
 
 
+def digest_table_workspace_bytes(n_entries):
+    """bytes of device workspace a digest table call over n_entries needs (0 for none, or above the limit): table_workspace_bytes(n)"""
+    return lib().modgpu_digest_table_workspace_bytes(n_entries)
+
+
+def digest_table_device(entries, results=None, workspace=None, device=-1, stream=None, *, n=None):
+    """DIGESTS a TABLE of entries in three launches, whatever its length: for entry i the record of out[j] = src_i[j] ^
+    ks(key_i)[stream_off_i + j] -- `dst` of an entry is ignored, nothing but the records and the workspace is written, anything may
+    overlap anything.  `entries` is a host table (a TABLE_DTYPE array: uploaded) or a table already in device memory (a DeviceBuffer or
+    an address; then n, the entry count, is needed).  `results` is a DeviceBuffer or address of 32 * n bytes, `workspace` one of at
+    least digest_table_workspace_bytes(n) bytes; None makes one.  When this function made a buffer itself it waits for the call, raises
+    ModGpuError if the device refused an entry (no record was written) and returns (the records as a DIGEST_RESULT_DTYPE array, their
+    Adler-32 values as a uint32 array); otherwise the call is asynchronous on `stream`, returns None, and table_status(workspace) and
+    digest_results(results, n) tell the outcome after a synchronise."""
+    own = []
+    try:
+        addr, n, t = _table_arg(entries, TABLE_DTYPE, n, device, own)
+        if t is not None and t.size == 0:
+            return np.zeros(0, dtype=DIGEST_RESULT_DTYPE), np.zeros(0, dtype=np.uint32)
+        if results is None and n:
+            results = DeviceBuffer(n * DIGEST_RESULT_DTYPE.itemsize, device)
+            own.append(results)
+        ws, ws_bytes = _workspace_arg(workspace, n, lambda: digest_table_workspace_bytes(n), device, own)
+        res = _dev_addr(results) if results is not None else 0
+        _check(lib().modgpu_digest_table_device(_vp(addr), n, _vp(res), _vp(ws), ws_bytes, device, _vp(stream or 0)))
+        if not own:
+            return None
+        _check(lib().modgpu_sync(device, _vp(stream or 0)))
+        bad = table_status(ws, device) if n else None
+        if bad is not None:
+            raise ModGpuError(1, f"the device refused digest table entry {bad}; no record was written")
+        return digest_results(res, n, device)
+    finally:
+        for b in own:
+            b.free()
+
+
+def time_digest_table_device(entries, n, results, workspace, device=-1, stream=None, iters=2):
+    """Mean ms per digest table call (three launches) over `iters` calls, HIP events on the launch stream; table, records and
+    workspace resident."""
+    ms = ctypes.c_float(0)
+    ws_bytes = workspace.nbytes if isinstance(workspace, DeviceBuffer) else digest_table_workspace_bytes(n)
+    _check(lib().modgpu_time_digest_table_device(_vp(_dev_addr(entries)), n, _vp(_dev_addr(results)), _vp(_dev_addr(workspace)), ws_bytes, device,
+                                                 _vp(stream or 0), iters, ctypes.byref(ms)))
+    return ms.value
+
+
+def debug_set_digest_table_grid(grid=0):
+    """Testing flavour: the digest table call's stream grid (0 = shipped: one workgroup per CU).  Every grid gives the same residues."""
+    _debug_lib().modgpu_debug_set_digest_table_grid(grid)
+
+
 def verify_rekey_table_workspace_bytes(n_entries):
     """bytes of device workspace a rekey verify table call over n_entries needs (0 for none, or above the limit)"""
     return lib().modgpu_verify_rekey_table_workspace_bytes(n_entries)
@@ -1459,6 +1515,17 @@ class DeviceBuffer:
         n = self.nbytes - offset if n is None else n
         assert offset + n <= self.nbytes
         return digest_device(self.ptr + offset, key, stream_off, None, None, self.device, stream, n=n)
+
+    def digests(self, ranges, key, part_off=0, workspace=None, stream=None):
+        """One Adler-32 per range of `ranges` -- a list of (offset, n) -- of the part this buffer holds, each taken from stream offset
+        part_off + offset, in one digest_table_device call: a uint32 array.  The read-only sibling of compact: "are these files of
+        the part still the files I packed?"."""
+        ranges = [(int(o), int(n)) for o, n in ranges]
+        assert all(o >= 0 and n >= 0 and o + n <= self.nbytes for o, n in ranges)
+        t = table(len(ranges))
+        for i, (o, n) in enumerate(ranges):
+            t[i]["src"], t[i]["n"], t[i]["stream_off"], t[i]["key"] = self.ptr + o, n, part_off + o, as_int32(key)
+        return digest_table_device(t, None, workspace, self.device, stream)[1]
 
     def move(self, dst_offset, src_offset, n, key_from=0, key_to=0, off_from=0, off_to=0, workspace=None, stream=None):
         """Moves n bytes inside the buffer from src_offset to dst_offset, the ranges overlapping in any way (memmove rules), rekeying

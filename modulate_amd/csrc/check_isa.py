@@ -414,9 +414,10 @@ def one_global_store(k):
     return ["%s: global stores %s, expected the one global_store_dwordx2 of the entry's n" % (k.name, found)] if found != ["global_store_dwordx2"] else []
 
 
-def result_atomics(k, tickets=0):
+def result_atomics(k, tickets=0, sums=0):
     """a verify kernel's results: 64-bit adds (the count) and unsigned mins (the lowest index), as many of the one as of the other, and
-    nothing else.  `tickets`: the returning 32-bit ticket fetches that come on top (one per unrolled trip), the results then not returning"""
+    nothing else.  `tickets`: the returning 32-bit ticket fetches that come on top (one per unrolled trip of each loop), the results then
+    not returning.  `sums`: the 64-bit adds of a digest loop in the same kernel (digest_table_loop), which have no min beside them"""
     bad = []
     atomics = [(m.group(1), m.group(2)) for m in re.finditer(r"^\s+(global_atomic_\w+)\b([^;\n]*)", k.fn, re.M)]
     if tickets:
@@ -425,10 +426,29 @@ def result_atomics(k, tickets=0):
             bad.append("%s: %d 32-bit global_atomic_add, expected the ticket fetch of each unrolled trip (%d), each returning (sc0)" % (k.name, len(fetches), tickets))
         atomics = [(op, args) for op, args in atomics if op != "global_atomic_add"]
     ops = [op for op, _ in atomics]
-    adds, mins = ops.count("global_atomic_add_x2"), ops.count("global_atomic_umin_x2")
-    if not adds or adds != mins or adds + mins != len(ops) or (tickets and any(" sc0" in args for _, args in atomics)):
-        bad.append("%s: result atomics %s, expected %s64-bit adds and unsigned mins in equal numbers and nothing else"
-                   % (k.name, sorted(set(ops)), "non-returning " if tickets else ""))
+    adds, mins = ops.count("global_atomic_add_x2") - sums, ops.count("global_atomic_umin_x2")
+    if adds <= 0 or adds != mins or adds + sums + mins != len(ops) or (tickets and any(" sc0" in args for _, args in atomics)):
+        bad.append("%s: result atomics %s, expected %s64-bit adds and unsigned mins in equal numbers%s and nothing else"
+                   % (k.name, sorted(set(ops)), "non-returning " if tickets else "", " (beside the digest loop's %d adds)" % sums if sums else ""))
+    return bad
+
+
+def digest_table_loop(k):
+    """the verify table kernel's second loop (cycle_verify_table_kernel.h: VERIFY_TABLE_DIGEST, one uniform branch apart from the
+    compare).  It reads one side and sends a pair of 64-bit atomic adds onto the entry's record when its workgroup leaves the entry:
+    the sums are taken with v_dot4_u32_u8, no 64-bit atomic of the kernel returns a value (the loop would wait for it), the fold that
+    precedes them goes through LDS (ds_add_u32) and not through memory, and the kernel still has no store of any kind -- a digest
+    that wrote anywhere but into its records would write into what it reads"""
+    bad = []
+    if "v_dot4_u32_u8" not in k.fn:
+        bad.append("%s: no v_dot4_u32_u8 (the digest loop's byte and position sums)" % k.name)
+    wide = [(m.group(1), m.group(2)) for m in re.finditer(r"^\s+(global_atomic_\w+_x2)\b([^;\n]*)", k.fn, re.M)]
+    if any(" sc0" in args for _, args in wide):
+        bad.append("%s: a 64-bit atomic returns its value (sc0): the digest loop's sums are non-returning global_atomic_add_x2" % k.name)
+    if not code_lines(k.fn, "ds_add_u32"):
+        bad.append("%s: no ds_add_u32 (the digest loop folds a workgroup's sums in LDS, one pair per wave)" % k.name)
+    if re.search(r"^\s+(buffer|global|flat|scratch)_store", k.fn, re.M):
+        bad.append("%s: a store in the kernel of the digest loop (it sends 64-bit atomic adds to the records and nothing else)" % k.name)
     return bad
 
 
@@ -625,9 +645,12 @@ TUS = (
         Kind("modgpu_cycle_verify_kernel", VERIFY_HEAD + [(block_count, KEYSTREAM, 9, TRIPS_AND_CUT)] + VERIFY_TAIL, "Lb1EEv15CycleVerifyArgs$"),
         Kind("modgpu_cycle_verify_kernel", VERIFY_HEAD + [(no_block, "an identity form")] + VERIFY_TAIL)),
        then=[verify_kernel_counts]),
-    # table of verify entries: chunks come from a ticket counter, ONE plain returning 32-bit fetch per unrolled trip (2)
+    # table of verify entries: chunks come from a ticket counter, ONE plain returning 32-bit fetch per unrolled trip (2).  The stream
+    # kernel has two loops, the compare and the digest (one uniform branch chooses): twice the blocks and the ticket fetches, and the
+    # digest loop's pair of 64-bit adds per unrolled trip (4) beside the compare's adds and mins
     table_tu("cycle_verify_table_kernel.s", "the verify table kernels' TU", "modgpu_cycle_verify_table", PLANNING,
-             [keystream_blocks, (block_count, KEYSTREAM, 8, TRIPS), loads_nt, (read_only_stream, "a verify kernel", True), (result_atomics, 2), scalar_entry_search]),
+             [keystream_blocks, (block_count, KEYSTREAM, 16, TRIPS + " in the compare and in the digest loop"), loads_nt,
+              (read_only_stream, "a verify kernel", True), (result_atomics, 4, 4), digest_table_loop, scalar_entry_search]),
     # rekey verify (verify against two keystreams), plain and funnel
     TU("cycle_rekey_verify_kernel.s", "the rekey verify kernel's TU",
        (Kind("modgpu_cycle_rekey_verify_kernel", BUDGET + [rekey_blocks, (block_count, TWO_KEYSTREAM, 9, TRIPS_AND_CUT), (read_only_stream, "a rekey verify kernel")] + VERIFY_TAIL),),

@@ -21,6 +21,8 @@
 
 // reporting only (modgpu_last_launch): the stream launch of a verify table call
 constexpr int CYCLE_VERIFY_TABLE = 11;
+// ... and of a digest table call: the same three kernels with VerifyTableArgs::mode set (below)
+constexpr int CYCLE_DIGEST_TABLE = 17;
 
 // modgpu_verify_table_summary_t (include/modgpu.h) in its first 32 bytes; one line of the workspace
 struct VerifyTableSummary {
@@ -31,6 +33,19 @@ struct VerifyTableSummary {
     unsigned long long pad[4];
 };
 static_assert(sizeof(VerifyTableSummary) == 64, "one line");
+
+// The DIGEST TABLE mode of the same three kernels (modgpu_digest_table_device): for entry i the record of
+//   out[j] = src_i[j] ^ ks(key_i)[off_i + j]:  s1 = sum of out[j], s2 = sum of j * out[j] (both in pieces, each reduced mod 65521 by
+// whoever sends it: only the residues mean anything), n, 0 -- modgpu_digest_result_t, closed on the host (modgpu_digest_adler32).
+// `dst` of an entry is never looked at: the plan launch lays the entry on the chunk grid of its SOURCE (the body's source is then
+// 16-byte aligned: no funnel), the finish launch sums the < 16 bytes at either end and stores the record whole, the stream kernel's
+// second loop (one uniform branch on `mode`) sums the bodies and adds to the records with non-returning 64-bit atomic adds.
+// The workspace is the table call's own (no summary line: `sum` is null).
+struct DigestTableRecord {
+    unsigned long long s1, s2, n, reserved;
+};
+constexpr uint32_t kDigestTableMod = 65521u; // the largest prime below 2^16 (Adler-32)
+enum VerifyTableMode : uint32_t { VERIFY_TABLE_COMPARE = 0u, VERIFY_TABLE_DIGEST = 1u };
 
 struct VerifyTableArgs {
     const CycleTableEntry *entries;
@@ -44,6 +59,8 @@ struct VerifyTableArgs {
     uint64_t level_n[kTableLevels];
     uint32_t top;                  // highest level (<= 16 keys)
     uint32_t n_blk;                // ceil(n / 1024)
+    uint32_t mode;                 // VERIFY_TABLE_COMPARE, or VERIFY_TABLE_DIGEST: `records` in place of `results`, `sum` null
+    DigestTableRecord *records;    // n records in the caller's device memory: stored whole by finish, added to by stream
 };
 
 uint32_t modgpu_verify_table_chunk_bytes();
@@ -53,3 +70,7 @@ const char *modgpu_verify_table_kernel_name();
 hipError_t modgpu_launch_verify_table_plan(const VerifyTableArgs &a, hipStream_t stream);
 hipError_t modgpu_launch_verify_table_finish(const VerifyTableArgs &a, hipStream_t stream);
 hipError_t modgpu_launch_verify_table_stream(const VerifyTableArgs &a, uint32_t grid, hipStream_t stream);
+// The same three kernels with a.mode = VERIFY_TABLE_DIGEST: the three launches of a digest table call (any grid >= 1 gives the same sums)
+hipError_t modgpu_launch_digest_table_plan(const VerifyTableArgs &a, hipStream_t stream);
+hipError_t modgpu_launch_digest_table_finish(const VerifyTableArgs &a, hipStream_t stream);
+hipError_t modgpu_launch_digest_table_stream(const VerifyTableArgs &a, uint32_t grid, hipStream_t stream);

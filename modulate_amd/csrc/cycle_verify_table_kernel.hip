@@ -28,11 +28,95 @@
 // result and the same pair (the count; the entry's index) to the summary.  No LDS is allocated for it and NO barrier is added: the test
 // on clean data is one ballot per change of entry, so a table of 100 000 one-chunk entries pays a compare and a branch per chunk, and a
 // clean table of any size issues no atomic but the ticket fetches.  The stream kernel contains no store of any kind.
+//
+// The DIGEST mode (cycle_verify_table_kernel.h: VERIFY_TABLE_DIGEST; modgpu_digest_table_device) runs the same three kernels over the
+// same kind of table with `dst` ignored: plan lays the grid on the SOURCE, finish sums the ragged edges and stores every record whole,
+// and the stream kernel takes its second loop -- one uniform branch apart, with registers, views and LDS of its own scope -- which
+// reads one side, sums what the cipher makes of it and adds to the entry's record.  Its protocol is written where the loop is.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
 #include "cycle_table_impl.h"
 #include "cycle_verify_table_kernel.h"
+
+// ---- the digest mode's arithmetic (cycle_verify_table_kernel.h: DigestTableRecord) -------------------------------------------------
+namespace {
+// byte sum and position sum (byte i of the word weighs i) of one 16-byte word: one v_dot4_u32_u8 per dword and weight.  The five
+// weights live in VGPRs: v_dot4 takes no literal, and as hoisted scalar constants they cost the stream kernel an SGPR spill.
+struct DotWeights {
+    uint32_t ones, p0, p1, p2, p3;
+};
+__device__ __forceinline__ DotWeights dot_weights()
+{
+    DotWeights k;
+    asm("v_mov_b32 %0, 0x01010101" : "=v"(k.ones));
+    asm("v_mov_b32 %0, 0x03020100" : "=v"(k.p0));
+    asm("v_mov_b32 %0, 0x07060504" : "=v"(k.p1));
+    asm("v_mov_b32 %0, 0x0B0A0908" : "=v"(k.p2));
+    asm("v_mov_b32 %0, 0x0F0E0D0C" : "=v"(k.p3));
+    return k;
+}
+__device__ __forceinline__ void word_sums(const u32x4 &d, const DotWeights &k, uint32_t &b, uint32_t &w)
+{
+    b = __builtin_amdgcn_udot4(d.x, k.ones, 0u, false);
+    b = __builtin_amdgcn_udot4(d.y, k.ones, b, false);
+    b = __builtin_amdgcn_udot4(d.z, k.ones, b, false);
+    b = __builtin_amdgcn_udot4(d.w, k.ones, b, false);
+    w = __builtin_amdgcn_udot4(d.x, k.p0, 0u, false);
+    w = __builtin_amdgcn_udot4(d.y, k.p1, w, false);
+    w = __builtin_amdgcn_udot4(d.z, k.p2, w, false);
+    w = __builtin_amdgcn_udot4(d.w, k.p3, w, false);
+}
+// x mod 65521 for any 64-bit x, without a 64-bit division: 2^16 = 15 (mod 65521), so the four 16-bit pieces of x weigh 1, 15, 225 and
+// 3375 -- their weighted sum is below 65536 * 3616 < 2^28 and one 32-bit remainder finishes it
+__device__ __forceinline__ uint32_t digest_red(unsigned long long x)
+{
+    const uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
+    return ((lo & 0xFFFFu) + 15u * (lo >> 16) + 225u * (hi & 0xFFFFu) + 3375u * (hi >> 16)) % kDigestTableMod;
+}
+// The sum of x over the wave's 64 lanes, in lane 63 (other lanes hold partial sums): the row_shr / row_bcast DPP ladder, so that no
+// lane index is needed (v_mbcnt is what this TU's guard reads as a rewritten ticket atomic).  A lane the control leaves without a
+// source adds 0 (old = 0, bound_ctrl off).  x < 2^26 in every lane: no carry is lost.
+__device__ __forceinline__ uint32_t wave_sum_lane63(uint32_t x)
+{
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, false); // row_shr:1
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, false); // row_shr:2
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, false); // row_shr:4
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, false); // row_shr:8: lane 15 of a row has the row's sum
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false); // row_bcast:15 into rows 1 and 3
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false); // row_bcast:31 into rows 2 and 3
+    return x;
+}
+// The < 16 bytes in front of an entry's body and behind it, summed bytewise; byte j of the entry weighs j mod 65521.  Each sum is
+// below 30 * 255 * 65521 < 2^29.  The record is whole: s1, s2 reduced, the entry's n, 0.
+__device__ __forceinline__ DigestTableRecord digest_edges(const CycleTablePlan &P)
+{
+    const uint8_t *sb = P.src_origin + P.lead;
+    const uint64_t body = P.end - P.lead;
+    const bool plain = P.base_head == 0;
+    const uint32_t after = (uint32_t)(((unsigned long long)P.head_n + body) % kDigestTableMod);
+    uint32_t s1 = 0u, s2 = 0u;
+#pragma unroll
+    for (uint32_t j = 0; j < 15; ++j) {
+        if (j < P.tail_n) {
+            const uint8_t s = sb[body + j];
+            const uint32_t out = plain ? s : cycle_byte(s, mulmod_canon(P.base_tail, c_pow_b0.v[j]));
+            s1 += out;
+            s2 += (after + j) % kDigestTableMod * out;
+        }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < 15; ++j) {
+        if (j < P.head_n) {
+            const uint8_t s = sb[(int64_t)j - P.head_n];
+            const uint32_t out = plain ? s : cycle_byte(s, mulmod_canon(P.base_head, c_pow_b0.v[j]));
+            s1 += out;
+            s2 += j * out;
+        }
+    }
+    return DigestTableRecord{s1, s2 % kDigestTableMod, (unsigned long long)P.head_n + body + P.tail_n, 0ull};
+}
+} // namespace
 
 // ---- plan: one thread per entry ----------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_verify_table_plan(VerifyTableArgs a)
@@ -43,15 +127,19 @@ __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_verify_table_plan(Ve
         a.hdr->ticket = 0;
         a.hdr->first_bad = kTableNoBad;
         a.hdr->total = 0;
-        a.sum->mismatches = 0ull;
-        a.sum->first_bad_entry = kVerifyNone;
-        a.sum->entries = a.n;
-        a.sum->reserved = 0ull;
+        if (a.mode == VERIFY_TABLE_COMPARE) { // (a digest call has no summary line)
+            a.sum->mismatches = 0ull;
+            a.sum->first_bad_entry = kVerifyNone;
+            a.sum->entries = a.n;
+            a.sum->reserved = 0ull;
+        }
     }
     uint64_t cnt = 0;
     uint32_t bad = 0;
     if (i < a.n) {
-        const CycleTableEntry E = a.entries[i];
+        CycleTableEntry E = a.entries[i];
+        // a digest entry's dst is not looked at: the source takes its place, and the chunk grid is laid on the source
+        if (a.mode != VERIFY_TABLE_COMPARE) E.dst = const_cast<uint8_t *>(E.src);
         const TableGrid g = table_grid(E, E.flags); // (dst is the comparand: the chunk grid is laid on it)
         cnt = g.cnt;
         bad = g.bad;
@@ -80,39 +168,43 @@ __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_verify_table_finish(
         } else {
             a.plan[i].start = start;
             for (uint32_t k = 0; k < kTableLevels; ++k) table_set_level(a.level[k], k, a.top, i, start);
-            // the < 16 bytes in front of the body and behind it, compared bytewise; the index counts from the entry's first byte
-            const uint8_t *sb = P.src_origin + P.lead;
-            const uint8_t *eb = P.dst_origin + P.lead;
-            const uint64_t body = P.end - P.lead;
-            const bool plain = P.base_head == 0;
-            unsigned long long cnt = 0ull, first = kVerifyNone;
+            if (a.mode != VERIFY_TABLE_COMPARE) {
+                a.records[i] = digest_edges(P); // the < 16 bytes at either end summed, the record stored whole: nothing needs clearing
+            } else {
+                // the < 16 bytes in front of the body and behind it, compared bytewise; the index counts from the entry's first byte
+                const uint8_t *sb = P.src_origin + P.lead;
+                const uint8_t *eb = P.dst_origin + P.lead;
+                const uint64_t body = P.end - P.lead;
+                const bool plain = P.base_head == 0;
+                unsigned long long cnt = 0ull, first = kVerifyNone;
 #pragma unroll
-            for (uint32_t j = 0; j < 15; ++j) {
-                if (j < P.tail_n) {
-                    const uint8_t s = sb[body + j];
-                    const uint8_t want = plain ? s : cycle_byte(s, mulmod_canon(P.base_tail, c_pow_b0.v[j]));
-                    if (eb[body + j] != want) {
-                        ++cnt;
-                        const unsigned long long at = (unsigned long long)P.head_n + body + j;
-                        first = at < first ? at : first;
+                for (uint32_t j = 0; j < 15; ++j) {
+                    if (j < P.tail_n) {
+                        const uint8_t s = sb[body + j];
+                        const uint8_t want = plain ? s : cycle_byte(s, mulmod_canon(P.base_tail, c_pow_b0.v[j]));
+                        if (eb[body + j] != want) {
+                            ++cnt;
+                            const unsigned long long at = (unsigned long long)P.head_n + body + j;
+                            first = at < first ? at : first;
+                        }
                     }
                 }
-            }
 #pragma unroll
-            for (uint32_t j = 0; j < 15; ++j) {
-                if (j < P.head_n) {
-                    const uint8_t s = sb[(int64_t)j - P.head_n];
-                    const uint8_t want = plain ? s : cycle_byte(s, mulmod_canon(P.base_head, c_pow_b0.v[j]));
-                    if (eb[(int64_t)j - P.head_n] != want) {
-                        ++cnt;
-                        first = j < first ? j : first;
+                for (uint32_t j = 0; j < 15; ++j) {
+                    if (j < P.head_n) {
+                        const uint8_t s = sb[(int64_t)j - P.head_n];
+                        const uint8_t want = plain ? s : cycle_byte(s, mulmod_canon(P.base_head, c_pow_b0.v[j]));
+                        if (eb[(int64_t)j - P.head_n] != want) {
+                            ++cnt;
+                            first = j < first ? j : first;
+                        }
                     }
                 }
-            }
-            a.results[i] = CycleVerifyResult{cnt, first, (unsigned long long)P.head_n + body + P.tail_n, 0ull};
-            if (cnt != 0ull) {
-                __hip_atomic_fetch_add(&a.sum->mismatches, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_fetch_min(&a.sum->first_bad_entry, (unsigned long long)i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                a.results[i] = CycleVerifyResult{cnt, first, (unsigned long long)P.head_n + body + P.tail_n, 0ull};
+                if (cnt != 0ull) {
+                    __hip_atomic_fetch_add(&a.sum->mismatches, cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_fetch_min(&a.sum->first_bad_entry, (unsigned long long)i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
             }
         }
     }
@@ -139,6 +231,163 @@ __global__ __launch_bounds__(BLOCK) MODGPU_KEEP_OFF_THE_FIXED_TEMPORARIES void m
     __shared__ uint32_t q_next[2];
     const uint32_t voff = tid * lcg::WORD;
     const uint32_t lane_mul = mulmod_canon(c_tile_lo.v[tid >> 8], c_lane_pow.v[tid & 255]);
+
+    // ---- the digest loop (cycle_verify_table_kernel.h: VERIFY_TABLE_DIGEST): the loop below with ONE load stream and sums in place of
+    // the compare.  One uniform branch; the verify loop is not entered, and this scope's registers and LDS are its own.
+    // Widths (cycle_to_kernel.hip's digest loop has the same sums).  Per lane-word b = sum of bytes <= 4 080 and w = sum of i * byte_i <=
+    // 30 600.  Per chunk a lane adds, in 32 bits, c1 = sum of b <= 16 320 and c2 = sum of (q * b + w), q < 65 536 the word's offset from
+    // the chunk origin: < 1.07e9.  The chunk origin's index in the entry enters reduced (bm < 65 521): bm * c1 + c2 < 2^32.  Across
+    // chunks the lane keeps 64-bit sums that grow by < 2^32 per chunk, and an entry has fewer than 2^24 chunks.
+    // Leaving an entry (or ending), the lanes' sums are reduced mod 65 521, folded per wave by DPP, and lane 63 of each wave adds the
+    // wave's pair into the LDS slot of the trip's parity (< 16 * 64 * 65 521 < 2^26) BEFORE the barrier the trip has anyway; behind it
+    // thread 0 reduces the slot, sends ONE pair of non-returning 64-bit adds to the entry's record and clears the slot.  The slot of the
+    // other parity is the next trip's: a wave that runs ahead into a trip that flushes too (a table of one-chunk entries flushes at
+    // every chunk) does not meet thread 0's read, and the trip after that is two barriers away.  No barrier is added.
+    if (__builtin_expect(a.mode != VERIFY_TABLE_COMPARE, 0)) { // (laid out behind the verify loop, whose code stays where it was)
+        __shared__ uint32_t dg_slot[4]; // [parity][s1, s2]
+        struct DView {
+            const uint8_t *src0; // the source's chunk origin of the entry
+            uint32_t lo, hi;     // global chunks [lo, hi)
+            uint32_t lead_rem;   // as the verify loop's
+            uint32_t entry;      // bits 0..23: index in the table; bits 24..27: head_n
+            uint32_t lane_base;  // per lane; 0 in every lane = the identity keystream
+        };
+        auto in = [](uint32_t g, const DView &v) { return g - v.lo < v.hi - v.lo; };
+        auto search = [&](uint32_t g, DView &v) {
+            uint32_t j = 0;
+            int k = (int)a.top;
+#pragma unroll 1
+            do j = table_descend(a.level[k], j, g);
+            while (--k >= 0);
+            const CycleTablePlan P = *as_const(a.plan + j);
+            v.src0 = P.src_origin;
+            v.lead_rem = table_lead_rem(P);
+            v.lo = (uint32_t)P.start;
+            v.hi = (uint32_t)P.start + P.chunks;
+            v.entry = j | (P.head_n << 24);
+            v.lane_base = mulmod_canon(P.base, lane_mul);
+        };
+        auto span = [&](uint32_t g, const DView &v) { return table_span_packed<CHUNK>(g, total, v); };
+        DView vb[NB];
+#pragma unroll
+        for (int i = 0; i < NB; ++i) vb[i] = DView{nullptr, 0, 0, 0, ~0u, 1};
+        // chunk g into one buffer of the ping-pong.  The body's source is 16-byte aligned (the plan laid the grid on it): no funnel.
+        // Lanes in front of a cut first chunk's body wrap past num_records: dropped, and masked in the sums.
+        auto load = [&](u32x4(&w)[U], DView &v, const DView &prev, uint32_t g) {
+            if (g < total && !in(g, v)) {
+                if (in(g, prev)) v = prev;
+                else search(g, v);
+            }
+            const Span s = span(g, v);
+            const auto r = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(v.src0 + s.off + s.cut), 0, (int)s.bytes, 0x00020000);
+#pragma unroll
+            for (int u = 0; u < U; ++u) w[u] = __builtin_amdgcn_raw_buffer_load_b128(r, voff + u * SUB - s.cut, 0, AUX_NT);
+        };
+
+        unsigned long long a1 = 0ull, a2 = 0ull; // the lane's sums over the entry its workgroup is in
+        const DotWeights wt = dot_weights();
+        uint32_t pending = 0;
+        const uint32_t q_next_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)&q_next[0];
+        const uint32_t slot_lds = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint32_t *)&dg_slot[0];
+        const uint32_t one = 1u, zero = 0u;
+        if (tid == 0) // both slots start clean; the first trip's barrier lies between this and their first use
+            asm volatile("ds_write_b32 %0, %1\n\tds_write_b32 %0, %1 offset:4\n\tds_write_b32 %0, %1 offset:8\n\tds_write_b32 %0, %1 offset:12\n\t"
+                         "s_waitcnt lgkmcnt(0)"
+                         :
+                         : "v"(slot_lds), "v"(zero)
+                         : "memory");
+        // chunk g of view v; g_next (view `next`) is the chunk the workgroup sums after it; `par` = trip & 1
+        auto sum = [&](u32x4(&w)[U], const DView &v, uint32_t g, const DView &next, uint32_t g_next, uint32_t par) {
+            const Span s = span(g, v);
+            const uint32_t c = g - v.lo; // < 2^24
+            u32x4 d[U];
+            if (__builtin_amdgcn_readfirstlane((int)v.lane_base) != 0) {
+                uint32_t p = mulmod_canon(c_chunk_pow0<CHUNK>.v[c & 255], c_chunk_pow1<CHUNK>.v[(c >> 8) & 255]);
+                p = mulmod_canon(p, c_chunk_pow2<CHUNK>.v[(c >> 16) & 255]);
+                uint32_t st = mulmod_canon(v.lane_base, p);
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    d[u] = cycle_word<ALG>(w[u], st);
+                    if (u + 1 < U) st = mulmod_canon(st, lcg::kTileLo.v[BLOCK / 256]);
+                }
+            } else {
+#pragma unroll
+                for (int u = 0; u < U; ++u) d[u] = w[u];
+            }
+            // index in the entry of the byte at the chunk's origin, mod 65 521: head_n - lead + CHUNK * c, CHUNK mod 65 521 = 15
+            const uint32_t lead = v.lead_rem & 0xFFFFu;
+            const uint32_t idxm = ((v.entry >> 24) + 2u * kDigestTableMod - lead) % kDigestTableMod;
+            const uint32_t bm = (idxm + (CHUNK % kDigestTableMod) * c) % kDigestTableMod;
+            uint32_t c1 = 0u, c2 = 0u;
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const uint32_t q = voff + (uint32_t)u * SUB;
+                uint32_t b, ws;
+                word_sums(d[u], wt, b, ws);
+                // a lane outside the chunk's bytes read zeros: its d is the keystream, not output
+                const bool inside = q - s.cut < s.bytes;
+                b = inside ? b : 0u;
+                ws = inside ? ws : 0u;
+                c1 += b;
+                c2 += q * b + ws;
+            }
+            a1 += c1;
+            a2 += (unsigned long long)(bm * c1 + c2);
+            const bool leaving = g_next >= total || next.entry != v.entry; // (uniform) the workgroup leaves the entry, or ends
+            if (leaving) {
+                const uint32_t r1 = wave_sum_lane63(digest_red(a1)), r2 = wave_sum_lane63(digest_red(a2));
+                a1 = a2 = 0ull;
+                if ((tid & 63u) == 63u)
+                    asm volatile("ds_add_u32 %0, %1\n\tds_add_u32 %0, %2 offset:4\n\ts_waitcnt lgkmcnt(0)" : : "v"(slot_lds + 8u * par), "v"(r1), "v"(r2) : "memory");
+            }
+            if (tid == 0)
+                asm volatile("ds_write_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : : "v"(q_next_lds + 4u * par), "v"(pending) : "memory");
+            __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_s_barrier();
+            if (leaving && tid == 0) {
+                uint32_t t1, t2;
+                asm volatile("ds_read_b32 %0, %2\n\tds_read_b32 %1, %2 offset:4\n\ts_waitcnt lgkmcnt(0)\n\t"
+                             "ds_write_b32 %2, %3\n\tds_write_b32 %2, %3 offset:4\n\ts_waitcnt lgkmcnt(0)"
+                             : "=&v"(t1), "=&v"(t2)
+                             : "v"(slot_lds + 8u * par), "v"(zero)
+                             : "memory");
+                DigestTableRecord *rec = a.records + (v.entry & 0xFFFFFFu);
+                __hip_atomic_fetch_add(&rec->s1, (unsigned long long)(t1 % kDigestTableMod), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_add(&rec->s2, (unsigned long long)(t2 % kDigestTableMod), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        };
+        auto take_published = [&](uint32_t par) {
+            uint32_t t;
+            asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(t) : "v"(q_next_lds + 4u * par) : "memory");
+            return (uint32_t)PREFIX * G + (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
+        };
+        uint32_t cq[NB];
+        static_assert(NB == 2 && DEPTH == 1 && PREFIX == NB, "the unrolled trip's position is the mailbox slot's and the sums' slot's parity");
+#pragma unroll
+        for (int i = 0; i < NB; ++i) cq[i] = blk + (uint32_t)i * G;
+        if (cq[0] < total) {
+            u32x4 w[NB][U];
+            load(w[0], vb[0], vb[1], cq[0]);
+            bool finished = false;
+            while (!finished) {
+#pragma unroll
+                for (int p = 0; p < NB; ++p) {
+                    __builtin_amdgcn_s_barrier();
+                    if (tid == 0) pending = __hip_atomic_fetch_add(&a.hdr->ticket, one, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    load(w[(p + DEPTH) % NB], vb[(p + DEPTH) % NB], vb[p], cq[DEPTH]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    sum(w[p], vb[p], cq[0], vb[(p + DEPTH) % NB], cq[DEPTH], (uint32_t)p);
+                    cq[0] = cq[1];
+                    cq[DEPTH] = take_published((uint32_t)p);
+                    if (cq[0] >= total) {
+                        finished = true;
+                        break;
+                    }
+                }
+            }
+        }
+        return;
+    }
 
     struct View {
         const uint8_t *exp0; // the comparand's chunk origin of the entry
@@ -343,4 +592,19 @@ hipError_t modgpu_launch_verify_table_stream(const VerifyTableArgs &a, uint32_t 
 {
     VerifyTableStream::launch(a, grid, stream);
     return hipGetLastError();
+}
+// the digest table call: the same kernels, the mode set
+namespace {
+VerifyTableArgs digest_mode(const VerifyTableArgs &a)
+{
+    VerifyTableArgs d = a;
+    d.mode = VERIFY_TABLE_DIGEST;
+    return d;
+}
+} // namespace
+hipError_t modgpu_launch_digest_table_plan(const VerifyTableArgs &a, hipStream_t stream) { return modgpu_launch_verify_table_plan(digest_mode(a), stream); }
+hipError_t modgpu_launch_digest_table_finish(const VerifyTableArgs &a, hipStream_t stream) { return modgpu_launch_verify_table_finish(digest_mode(a), stream); }
+hipError_t modgpu_launch_digest_table_stream(const VerifyTableArgs &a, uint32_t grid, hipStream_t stream)
+{
+    return modgpu_launch_verify_table_stream(digest_mode(a), grid, stream);
 }

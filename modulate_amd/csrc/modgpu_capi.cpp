@@ -1578,8 +1578,9 @@ void store_le32(uint8_t *p, uint32_t v)
 }
 
 } // namespace
-// ---- the five calls over a table in device memory: modgpu_cycle_table_device, modgpu_rekey_table_device, modgpu_verify_table_device,
-// modgpu_verify_rekey_table_device (three launches: plan, finish, stream) and modgpu_rekey_move_table_device (five).
+// ---- the six calls over a table in device memory: modgpu_cycle_table_device, modgpu_rekey_table_device, modgpu_verify_table_device,
+// modgpu_verify_rekey_table_device, modgpu_digest_table_device (three launches: plan, finish, stream) and modgpu_rekey_move_table_device
+// (five).
 // One workspace walk, one set of grid hooks and one call body (table_call); a call is its layout, its launches and its names. --------
 namespace {
 static_assert(sizeof(modgpu_table_entry_t) == sizeof(CycleTableEntry) && offsetof(modgpu_table_entry_t, key) == offsetof(CycleTableEntry, key) &&
@@ -1672,7 +1673,7 @@ bool move_table_sizes_ok(uint64_t n, uint64_t total_bytes)
 // The grid of a call's stream (move) launch.  The out-of-place table takes the out-of-place kernel's (25 workgroups per 32 CUs;
 // DESIGN.md 4.8 has the A/B against one per CU); the others one workgroup per CU on every CU, as the rekey and verify kernels
 // (the move launch never gets more than the device holds at once).  modgpu_debug_set_*_table_grid forces one.
-enum TableCall { kCycleTable, kRekeyTable, kVerifyTable, kRekeyVerifyTable, kMoveTable, kTableCalls };
+enum TableCall { kCycleTable, kRekeyTable, kVerifyTable, kRekeyVerifyTable, kMoveTable, kDigestTable, kTableCalls };
 #ifdef MODGPU_TESTING_HOOKS
 std::atomic<uint32_t> g_table_grid[kTableCalls] = {};
 uint32_t table_grid_forced(TableCall c) { return g_table_grid[c].load(std::memory_order_relaxed); }
@@ -1689,11 +1690,12 @@ uint32_t table_grid(TableCall c)
     return (uint32_t)std::max<uint64_t>(1, cap);
 }
 
-// What a call is: which of the five (its grid), whether it verifies (it then writes `results`, which no other call looks at), and what
-// it is called -- in tier 1's words for a short workspace, and in modgpu_last_launch's report of its stream (move) launch
+// What a call is: which of the six (its grid), the size of the record it writes per entry into `results` (the verifying calls' result,
+// the digest call's record; 0: the call has no `results`, and nothing looks at that argument), and what it is called -- in tier 1's
+// words for a short workspace, and in modgpu_last_launch's report of its stream (move) launch
 struct TableKind {
     TableCall call;
-    bool verifies;
+    uint32_t result_bytes;
     const char *short_workspace;
     const char *(*kernel)();
     int variant;
@@ -1713,16 +1715,16 @@ template <class Args, hipError_t (*F)(const Args &, uint32_t, hipStream_t)> hipE
 // `refused`: a refusal of the call's own, made right behind the limit (the move call's total_bytes), or nullptr;
 // `layout()` plans the workspace once the pointers are known to be sound; `bind(a, w, L)` puts the call's own sections into a.
 template <class Args, class Entry, size_t N, class Layout, class Bind>
-int table_call(const TableKind &kind, const TableLaunch<Args> (&launches)[N], const Entry *entries, uint64_t n, modgpu_verify_result_t *results,
+int table_call(const TableKind &kind, const TableLaunch<Args> (&launches)[N], const Entry *entries, uint64_t n, const void *results,
                const char *refused, void *ws, uint64_t ws_bytes, int device, hipStream_t stream, Layout layout, Bind bind)
 {
     if (n == 0) return MODGPU_OK;
     if (n > kTableMaxEntries) return fail(MODGPU_ERR_INVALID, "more than 4194304 entries (the table call's limit)");
     if (refused) return fail(MODGPU_ERR_INVALID, refused);
     if (!entries || !ws) return fail(MODGPU_ERR_INVALID, "null table or workspace");
-    if (kind.verifies && !results) return fail(MODGPU_ERR_INVALID, "null results");
+    if (kind.result_bytes && !results) return fail(MODGPU_ERR_INVALID, "null results");
     if ((reinterpret_cast<uintptr_t>(entries) | reinterpret_cast<uintptr_t>(ws)) & 7) return fail(MODGPU_ERR_INVALID, "table or workspace not 8-byte aligned");
-    if (kind.verifies && (reinterpret_cast<uintptr_t>(results) & 7)) return fail(MODGPU_ERR_INVALID, "results not 8-byte aligned");
+    if (kind.result_bytes && (reinterpret_cast<uintptr_t>(results) & 7)) return fail(MODGPU_ERR_INVALID, "results not 8-byte aligned");
     const TableLayout L = layout();
     if (ws_bytes < L.bytes) return fail(MODGPU_ERR_INVALID, kind.short_workspace);
     DeviceScope scope(device);
@@ -1731,7 +1733,7 @@ int table_call(const TableKind &kind, const TableLaunch<Args> (&launches)[N], co
     HIP_TRY(hipGetDevice(&phys));
     if (modgpu_xfer_device_of(entries, n * sizeof(Entry)) != phys || modgpu_xfer_device_of(ws, L.bytes) != phys)
         return fail(MODGPU_ERR_INVALID, "the table or the workspace is not device memory of the call's device");
-    if (kind.verifies && modgpu_xfer_device_of(results, n * sizeof(modgpu_verify_result_t)) != phys)
+    if (kind.result_bytes && modgpu_xfer_device_of(results, n * kind.result_bytes) != phys)
         return fail(MODGPU_ERR_INVALID, "the results are not device memory of the call's device");
     uint8_t *const w = static_cast<uint8_t *>(ws);
     Args a{};
@@ -1761,7 +1763,7 @@ int table_call(const TableKind &kind, const TableLaunch<Args> (&launches)[N], co
 int table_impl(const modgpu_table_entry_t *entries, uint64_t n, void *ws, uint64_t ws_bytes, int device, hipStream_t stream)
 {
     using A = CycleTableArgs;
-    static constexpr TableKind kind = {kCycleTable, false, "workspace smaller than modgpu_table_workspace_bytes(n_entries)", modgpu_table_kernel_name, CYCLE_TABLE,
+    static constexpr TableKind kind = {kCycleTable, 0, "workspace smaller than modgpu_table_workspace_bytes(n_entries)", modgpu_table_kernel_name, CYCLE_TABLE,
                                          modgpu_table_block, modgpu_table_chunk_bytes, MODGPU_TABLE_KERNEL_SOURCE_HASH};
     static constexpr TableLaunch<A> launches[] = {{"table plan launch", no_grid<A, modgpu_launch_table_plan>},
                                                   {"table finish launch", no_grid<A, modgpu_launch_table_finish>},
@@ -1773,7 +1775,7 @@ int table_impl(const modgpu_table_entry_t *entries, uint64_t n, void *ws, uint64
 int rekey_table_impl(const modgpu_rekey_table_entry_t *entries, uint64_t n, void *ws, uint64_t ws_bytes, int device, hipStream_t stream)
 {
     using A = RekeyTableArgs;
-    static constexpr TableKind kind = {kRekeyTable, false, "workspace smaller than modgpu_rekey_table_workspace_bytes(n_entries)", modgpu_rekey_table_kernel_name,
+    static constexpr TableKind kind = {kRekeyTable, 0, "workspace smaller than modgpu_rekey_table_workspace_bytes(n_entries)", modgpu_rekey_table_kernel_name,
                                          CYCLE_REKEY_TABLE, modgpu_rekey_table_block, modgpu_rekey_table_chunk_bytes, MODGPU_REKEY_TABLE_KERNEL_SOURCE_HASH};
     static constexpr TableLaunch<A> launches[] = {{"rekey table plan launch", no_grid<A, modgpu_launch_rekey_table_plan>},
                                                   {"rekey table finish launch", no_grid<A, modgpu_launch_rekey_table_finish>},
@@ -1786,7 +1788,7 @@ int verify_table_impl(const modgpu_table_entry_t *entries, uint64_t n, modgpu_ve
                       hipStream_t stream)
 {
     using A = VerifyTableArgs;
-    static constexpr TableKind kind = {kVerifyTable, true, "workspace smaller than modgpu_verify_table_workspace_bytes(n_entries)", modgpu_verify_table_kernel_name,
+    static constexpr TableKind kind = {kVerifyTable, sizeof(modgpu_verify_result_t), "workspace smaller than modgpu_verify_table_workspace_bytes(n_entries)", modgpu_verify_table_kernel_name,
                                          CYCLE_VERIFY_TABLE, modgpu_verify_table_block, modgpu_verify_table_chunk_bytes, MODGPU_VERIFY_TABLE_KERNEL_SOURCE_HASH};
     static constexpr TableLaunch<A> launches[] = {{"verify table plan launch", no_grid<A, modgpu_launch_verify_table_plan>},
                                                   {"verify table finish launch", no_grid<A, modgpu_launch_verify_table_finish>},
@@ -1798,11 +1800,31 @@ int verify_table_impl(const modgpu_table_entry_t *entries, uint64_t n, modgpu_ve
                       });
 }
 
+// The digest table call: the verify table TU's three kernels in their digest mode, on the out-of-place table call's workspace (no
+// summary line).  `dst` of an entry is never looked at.
+static_assert(sizeof(modgpu_digest_result_t) == sizeof(DigestTableRecord) && offsetof(modgpu_digest_result_t, s2) == offsetof(DigestTableRecord, s2) &&
+                  offsetof(modgpu_digest_result_t, n) == offsetof(DigestTableRecord, n) && offsetof(modgpu_digest_result_t, reserved) == offsetof(DigestTableRecord, reserved) &&
+                  kDigestTableMod == kDigestMod,
+              "the digest table kernels write the public record");
+int digest_table_impl(const modgpu_table_entry_t *entries, uint64_t n, modgpu_digest_result_t *records, void *ws, uint64_t ws_bytes, int device,
+                      hipStream_t stream)
+{
+    using A = VerifyTableArgs;
+    static constexpr TableKind kind = {kDigestTable, sizeof(modgpu_digest_result_t), "workspace smaller than modgpu_digest_table_workspace_bytes(n_entries)",
+                                         modgpu_verify_table_kernel_name, CYCLE_DIGEST_TABLE, modgpu_verify_table_block, modgpu_verify_table_chunk_bytes,
+                                         MODGPU_VERIFY_TABLE_KERNEL_SOURCE_HASH};
+    static constexpr TableLaunch<A> launches[] = {{"digest table plan launch", no_grid<A, modgpu_launch_digest_table_plan>},
+                                                  {"digest table finish launch", no_grid<A, modgpu_launch_digest_table_finish>},
+                                                  {"digest table stream launch", on_grid<A, modgpu_launch_digest_table_stream>}};
+    return table_call(kind, launches, entries, n, records, nullptr, ws, ws_bytes, device, stream, [&] { return table_layout(n); },
+                      [&](A &a, uint8_t *, const TableLayout &) { a.records = reinterpret_cast<DigestTableRecord *>(records); });
+}
+
 int verify_rekey_table_impl(const modgpu_rekey_table_entry_t *entries, uint64_t n, modgpu_verify_result_t *results, void *ws, uint64_t ws_bytes,
                             int device, hipStream_t stream)
 {
     using A = RekeyVerifyTableArgs;
-    static constexpr TableKind kind = {kRekeyVerifyTable, true, "workspace smaller than modgpu_verify_rekey_table_workspace_bytes(n_entries)",
+    static constexpr TableKind kind = {kRekeyVerifyTable, sizeof(modgpu_verify_result_t), "workspace smaller than modgpu_verify_rekey_table_workspace_bytes(n_entries)",
                                          modgpu_rekey_verify_table_kernel_name, CYCLE_REKEY_VERIFY_TABLE, modgpu_rekey_verify_table_block,
                                          modgpu_rekey_verify_table_chunk_bytes, MODGPU_REKEY_VERIFY_TABLE_KERNEL_SOURCE_HASH};
     static constexpr TableLaunch<A> launches[] = {{"verify rekey table plan launch", no_grid<A, modgpu_launch_rekey_verify_table_plan>},
@@ -1821,7 +1843,7 @@ int rekey_move_table_impl(const modgpu_rekey_table_entry_t *entries, uint64_t n,
                           hipStream_t stream)
 {
     using A = MoveTableArgs;
-    static constexpr TableKind kind = {kMoveTable, false, "workspace smaller than modgpu_rekey_move_table_workspace_bytes(n_entries, total_bytes)",
+    static constexpr TableKind kind = {kMoveTable, 0, "workspace smaller than modgpu_rekey_move_table_workspace_bytes(n_entries, total_bytes)",
                                          modgpu_rekey_move_table_kernel_name, CYCLE_REKEY_MOVE_TABLE, modgpu_rekey_move_table_block,
                                          modgpu_rekey_move_table_chunk_bytes, MODGPU_REKEY_MOVE_TABLE_KERNEL_SOURCE_HASH};
     static constexpr TableLaunch<A> launches[] = {{"rekey move table plan launch", no_grid<A, modgpu_launch_rekey_move_table_plan>},
@@ -2294,6 +2316,19 @@ int modgpu_verify_table_device(const modgpu_table_entry_t *dev_entries, uint64_t
 {
     return guarded([&]() -> int {
         return verify_table_impl(dev_entries, n_entries, dev_results, dev_workspace, workspace_bytes, device, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+uint64_t modgpu_digest_table_workspace_bytes(uint64_t n_entries)
+{
+    return n_entries == 0 || n_entries > kTableMaxEntries ? 0 : table_layout(n_entries).bytes;
+}
+
+int modgpu_digest_table_device(const modgpu_table_entry_t *dev_entries, uint64_t n_entries, modgpu_digest_result_t *dev_results, void *dev_workspace,
+                               uint64_t workspace_bytes, int device, void *hip_stream)
+{
+    return guarded([&]() -> int {
+        return digest_table_impl(dev_entries, n_entries, dev_results, dev_workspace, workspace_bytes, device, static_cast<hipStream_t>(hip_stream));
     });
 }
 
@@ -3063,6 +3098,16 @@ int modgpu_time_verify_table_device(const void *dev_entries, uint64_t n_entries,
     });
 }
 
+int modgpu_time_digest_table_device(const void *dev_entries, uint64_t n_entries, void *dev_results, void *dev_workspace, uint64_t workspace_bytes,
+                                    int device, void *hip_stream, int iters, float *ms_per_call)
+{
+    return guarded([&]() -> int {
+        return time_calls(device, hip_stream, iters, ms_per_call, [&](hipStream_t st) {
+            return digest_table_impl(static_cast<const modgpu_table_entry_t *>(dev_entries), n_entries, static_cast<modgpu_digest_result_t *>(dev_results), dev_workspace, workspace_bytes, -1, st);
+        });
+    });
+}
+
 int modgpu_time_verify_rekey_table_device(const void *dev_entries, uint64_t n_entries, void *dev_results, void *dev_workspace, uint64_t workspace_bytes,
                                           int device, void *hip_stream, int iters, float *ms_per_call)
 {
@@ -3113,6 +3158,7 @@ void modgpu_debug_set_rekey_table_grid(uint32_t grid) { force_table_grid(kRekeyT
 
 void modgpu_debug_set_verify_table_grid(uint32_t grid) { force_table_grid(kVerifyTable, grid); }
 void modgpu_debug_set_rekey_verify_table_grid(uint32_t grid) { force_table_grid(kRekeyVerifyTable, grid); }
+void modgpu_debug_set_digest_table_grid(uint32_t grid) { force_table_grid(kDigestTable, grid); }
 
 // (caps the compare launches of the verify call and of the rekey verify call alike)
 void modgpu_debug_set_verify_form(int grid) { g_verify_grid.store(grid <= 0 ? 0u : std::min<uint32_t>((uint32_t)grid, 4096u), std::memory_order_relaxed); }
