@@ -768,77 +768,160 @@ void entry_bases(const EntryGeom &g, uint32_t key_res, uint64_t o, uint32_t &hea
     tail = lcg::state_residue(key_res, o + g.head + (g.words * 16) % lcg::PERIOD);
 }
 
-// The next run of up to kCycleBatchMax non-empty entries from *i on that `keep` accepts (indices into the caller's arrays); 0: none left.
-template <class Keep> int next_run(const uint64_t *sizes, int n, int &i, int (&idx)[kCycleBatchMax], Keep keep)
-{
-    int g = 0;
-    for (; i < n && g < kCycleBatchMax; ++i)
-        if (sizes[i] && keep(i)) idx[g++] = i;
-    return g;
-}
+// One run of an entry-list call: up to kCycleBatchMax non-empty entries of the current device, gathered from the caller's arrays.
+// `role` is the pointer the chunk grid lies on: the destination (out of place, rekey), expect (the verifying calls), and for a digest
+// entry its destination if it has one, else its source.  Offsets are as the caller gave them (no list: 0); plan_entries' binders reduce them.
+struct EntryRun {
+    int n = 0;
+    int idx[kCycleBatchMax]; // where each entry stands in the caller's arrays
+    uint8_t *role[kCycleBatchMax];
+    const uint8_t *src[kCycleBatchMax];
+    uint64_t size[kCycleBatchMax], off[2][kCycleBatchMax];
+};
 
-// One launch of the out-of-place kernel over 1..kCycleBatchMax non-empty entries of the current device.  MODGPU_OK, an error, or 1:
-// no ticket pair to be had right now (or an entry beyond the three-byte chunk jump tables): the caller copies and cycles in place.
-int launch_to(uint8_t *const *dst, const uint8_t *const *src, const uint64_t *sizes, const uint64_t *offs, int n, uint32_t key_res,
-              hipStream_t stream)
+// The run loop of the five entry-list calls: fn(run) for each run of up to kCycleBatchMax non-empty entries that `keep` accepts, in the
+// caller's order, until one fails.  `role` may be null, and so may its entries, only where the check let that pass (digest): the source
+// stands in (it is never stored through).
+template <class Keep, class Fn>
+int for_each_run(const void *const *role, const void *const *src, const uint64_t *sizes, const uint64_t *offs_a, const uint64_t *offs_b, int n,
+                 Keep keep, Fn fn)
 {
-    CycleToArgs a{};
-    const uint64_t chunk = modgpu_to_chunk_bytes();
+    EntryRun r;
+    for (int i = 0; i < n;) {
+        for (r.n = 0; i < n && r.n < kCycleBatchMax; ++i) {
+            if (!sizes[i] || !keep(i)) continue;
+            const int k = r.n++;
+            r.idx[k] = i;
+            r.role[k] = const_cast<uint8_t *>(static_cast<const uint8_t *>(role && role[i] ? role[i] : src[i]));
+            r.src[k] = static_cast<const uint8_t *>(src[i]);
+            r.size[k] = sizes[i];
+            r.off[0][k] = offs_a ? offs_a[i] : 0;
+            r.off[1][k] = offs_b ? offs_b[i] : 0;
+        }
+        if (r.n == 0) break;
+        if (const int rc = fn(r)) return rc;
+    }
+    return MODGPU_OK;
+}
+constexpr auto every_entry = [](int) { return true; };
+
+// The entry planner: every part's geometry on the chunk grid of its role pointer, the chunk index space start[] with its padding, and
+// n_parts.  bind(P, k, g) fills what only that call has: the role pointer's field, its base states (entry_bases, one set or two, or none
+// for an identity keystream: the zeroes stay), its result.  `oversized`: an entry beyond the kernels' three-byte chunk jump tables.
+struct EntryPlan {
     uint64_t total = 0, bytes = 0;
-    bool misaligned = false;
-    for (int k = 0; k < n; ++k) {
-        CycleToPart &P = a.part[k];
-        const EntryGeom g = entry_geom(dst[k], sizes[k], chunk);
-        P.dst_body = dst[k] + g.head;
-        P.src_body = src[k] + g.head;
+    bool misaligned = false, oversized = false;
+};
+template <class Args, class Bind> EntryPlan plan_entries(Args &a, const EntryRun &r, uint64_t chunk, Bind bind)
+{
+    EntryPlan p;
+    for (int k = 0; k < r.n; ++k) {
+        auto &P = a.part[k];
+        const EntryGeom g = entry_geom(r.role[k], r.size[k], chunk);
+        P.src_body = r.src[k] + g.head;
         P.head_n = (uint32_t)g.head;
         P.tail_n = (uint32_t)g.tail;
         P.lead = g.lead;
         P.end = g.end;
-        entry_bases(g, key_res, offs[k] % lcg::PERIOD, P.base_head, P.base_body, P.base_tail);
-        if (g.n_chunks >= (1ull << 24)) return 1;
-        a.start[k] = (uint32_t)total;
-        total += g.n_chunks > g.first ? g.n_chunks - g.first : 0;
-        bytes += sizes[k];
-        misaligned |= g.words != 0 && ((reinterpret_cast<uintptr_t>(src[k]) - reinterpret_cast<uintptr_t>(dst[k])) & 3) != 0;
+        bind(P, k, g);
+        a.start[k] = (uint32_t)p.total;
+        p.total += g.n_chunks > g.first ? g.n_chunks - g.first : 0;
+        p.bytes += r.size[k];
+        // a source whose phase differs from the role pointer's by a whole number of dwords needs no funnel: dword-aligned dwordx4 loads
+        p.misaligned |= g.words != 0 && ((reinterpret_cast<uintptr_t>(r.src[k]) - reinterpret_cast<uintptr_t>(r.role[k])) & 3) != 0;
+        p.oversized |= g.n_chunks >= (1ull << 24);
     }
-    for (int k = n; k <= kCycleBatchMax; ++k) a.start[k] = (uint32_t)total;
-    a.n_parts = (uint32_t)n;
+    for (int k = r.n; k <= kCycleBatchMax; ++k) a.start[k] = (uint32_t)p.total;
+    a.n_parts = (uint32_t)r.n;
+    return p;
+}
+// The work-queue kernel's grid cap, main workgroups only: 25 per 32 CUs (cycle_kernel.hip)
+uint64_t queue_cap(uint64_t total)
+{
+    uint64_t cap = 0, helpers = 0;
+    queue_grid(total, large_grid(), &cap, &helpers);
+    return cap;
+}
+// ... and no grid has more workgroups than there are chunks
+uint32_t entry_grid(uint64_t total, uint64_t cap) { return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(total, cap)); }
+// After an entry launch: its error (`ticket`: the ring line a ticketed kernel drew and nobody will sign off), or the count and the report.
+int entry_launched(hipError_t e, const char *what, const QueuePair *ticket, const char *kernel, int variant, uint32_t grid, uint32_t block,
+                   uint64_t chunk, uint64_t bytes, const char *source_hash)
+{
+    if (e != hipSuccess) {
+        if (ticket) queue_pair_unused(*ticket);
+        return fail_hip(e, what);
+    }
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    t_last_launch = {kernel, variant, grid, block, (uint32_t)chunk, bytes, grid, source_hash};
+    return MODGPU_OK;
+}
+
+// One launch of the out-of-place kernel over a run.  MODGPU_OK, an error, or 1: no ticket pair to be had right now (or an entry beyond
+// the three-byte chunk jump tables): the caller copies and cycles in place.
+int launch_to(const EntryRun &r, uint32_t key_res, hipStream_t stream)
+{
+    CycleToArgs a{};
+    const uint64_t chunk = modgpu_to_chunk_bytes();
+    const EntryPlan p = plan_entries(a, r, chunk, [&](CycleToPart &P, int k, const EntryGeom &g) {
+        P.dst_body = r.role[k] + g.head;
+        entry_bases(g, key_res, r.off[0][k] % lcg::PERIOD, P.base_head, P.base_body, P.base_tail);
+    });
+    if (p.oversized) return 1;
     const QueuePair q = queue_pair(stream);
     if (!q.pair) return 1;
     a.queue = q.pair;
     a.queue_done = q.done;
     a.queue_seq = q.seq;
-    // the work-queue kernel's grid, main workgroups only: 25 per 32 CUs (cycle_kernel.hip), never more than there are chunks
-    uint64_t cap = 0, helpers = 0;
-    queue_grid(total, large_grid(), &cap, &helpers);
-    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(total, cap));
-    // a source whose phase differs from the destination's by a whole number of dwords needs no funnel: dword-aligned dwordx4 loads
-    const int form = misaligned ? to_form() : CYCLE_TO_PLAIN;
-    hipError_t e = modgpu_launch_cycle_to(a, form, grid, stream);
-    if (e != hipSuccess) {
-        queue_pair_unused(q);
-        return fail_hip(e, "cycle kernel launch (out of place)");
-    }
-    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    t_last_launch = {modgpu_to_kernel_name(form), CYCLE_TO, grid, modgpu_to_block(), (uint32_t)chunk, bytes, grid, MODGPU_TO_KERNEL_SOURCE_HASH};
-    return MODGPU_OK;
+    const uint32_t grid = entry_grid(p.total, queue_cap(p.total));
+    const int form = p.misaligned ? to_form() : CYCLE_TO_PLAIN;
+    return entry_launched(modgpu_launch_cycle_to(a, form, grid, stream), "cycle kernel launch (out of place)", &q, modgpu_to_kernel_name(form), CYCLE_TO,
+                          grid, modgpu_to_block(), chunk, p.bytes, MODGPU_TO_KERNEL_SOURCE_HASH);
 }
 
-// The checks that come before any device work: a null pointer with bytes to move, a destination that partly overlaps its own source,
-// or one that meets any OTHER entry's source or destination (sources may overlap each other: they are only read).
-int check_to_entries(void *const *dst, const void *const *src, const uint64_t *sizes, int n)
+// The rules of one entry that writes: a source, and a destination that is its source or lies clear of it.  (No destination at all -- d
+// null -- is the digest call's entry that only reads.)
+int check_to_entry(const void *d, const void *s, uint64_t size)
 {
-    for (int i = 0; i < n; ++i) {
-        if (!sizes[i]) continue;
-        if (!dst[i] || !src[i]) return fail(MODGPU_ERR_INVALID, "null buffer");
-        if (dst[i] != src[i] && ranges_meet(dst[i], sizes[i], src[i], sizes[i]))
-            return fail(MODGPU_ERR_INVALID, "destination partly overlaps its source (only dst == src may alias)");
-    }
+    if (!s) return fail(MODGPU_ERR_INVALID, "null buffer");
+    if (d && d != s && ranges_meet(d, size, s, size)) return fail(MODGPU_ERR_INVALID, "destination partly overlaps its source (only dst == src may alias)");
+    return MODGPU_OK;
+}
+// ... and of the entries among each other: no destination meets any OTHER entry's source or destination (sources may overlap each other:
+// they are only read).  `dst` may be null, and so may its entries, where the caller let that pass.
+int check_to_meetings(void *const *dst, const void *const *src, const uint64_t *sizes, int n)
+{
+    auto d = [&](int i) -> const void * { return dst && sizes[i] ? dst[i] : nullptr; };
     for (int i = 0; i < n; ++i)
         for (int j = 0; j < n; ++j)
-            if (i != j && (ranges_meet(dst[i], sizes[i], src[j], sizes[j]) || ranges_meet(dst[i], sizes[i], dst[j], sizes[j])))
+            if (i != j && d(i) && (ranges_meet(d(i), sizes[i], src[j], sizes[j]) || (d(j) && ranges_meet(d(i), sizes[i], d(j), sizes[j]))))
                 return fail(MODGPU_ERR_INVALID, "a destination meets another entry's source or destination");
+    return MODGPU_OK;
+}
+// The checks of the out-of-place and the rekey calls, before any device work: the lists, a null pointer with bytes to move, and the two
+// rules above.
+int check_to_entries(void *const *dst, const void *const *src, const uint64_t *sizes, int n)
+{
+    if (n < 0 || (n > 0 && (!dst || !src || !sizes))) return fail(MODGPU_ERR_INVALID, "bad entry list");
+    for (int i = 0; i < n; ++i) {
+        if (!sizes[i]) continue;
+        if (!dst[i]) return fail(MODGPU_ERR_INVALID, "null buffer");
+        if (int rc = check_to_entry(dst[i], src[i], sizes[i])) return rc;
+    }
+    return check_to_meetings(dst, src, sizes, n);
+}
+// What the calls with results check of them, and of an entry's span: their kernels have no second route for an entry beyond the chunk
+// jump tables (the kernel jumps to a chunk's keystream state by the three bytes of its index in the entry).
+int check_results(int n, const void *results)
+{
+    if (n > 0 && !results) return fail(MODGPU_ERR_INVALID, "null result");
+    if (reinterpret_cast<uintptr_t>(results) & 7) return fail(MODGPU_ERR_INVALID, "result not 8-byte aligned");
+    return MODGPU_OK;
+}
+int check_entry_span(const void *role, uint64_t size, uint64_t chunk)
+{
+    if (size >= (1ull << 41) || entry_geom(static_cast<const uint8_t *>(role), size, chunk).n_chunks >= (1ull << 24))
+        return fail(MODGPU_ERR_INVALID, "an entry that spans 2^24 chunks of 64 KiB or more (1 TiB)");
     return MODGPU_OK;
 }
 
@@ -848,31 +931,20 @@ int check_to_entries(void *const *dst, const void *const *src, const uint64_t *s
 int cycle_to_impl(void *const *dst, const void *const *src, const uint64_t *sizes, const uint64_t *offs, int n, int32_t key, hipStream_t stream)
 {
     const uint32_t key_res = lcg::key_residue(key);
-    int i = 0, idx[kCycleBatchMax];
-    while (const int g = next_run(sizes, n, i, idx, [](int) { return true; })) {
-        uint8_t *gd[kCycleBatchMax];
-        const uint8_t *gs[kCycleBatchMax];
-        uint64_t gn[kCycleBatchMax], go[kCycleBatchMax];
-        for (int k = 0; k < g; ++k) {
-            gd[k] = static_cast<uint8_t *>(dst[idx[k]]);
-            gs[k] = static_cast<const uint8_t *>(src[idx[k]]);
-            gn[k] = sizes[idx[k]];
-            go[k] = offs ? offs[idx[k]] : 0;
-        }
-        int rc = key_res ? launch_to(gd, gs, gn, go, g, key_res, stream) : 1;
+    return for_each_run(dst, src, sizes, offs, nullptr, n, every_entry, [&](const EntryRun &r) {
+        int rc = key_res ? launch_to(r, key_res, stream) : 1;
         if (rc == 1) {
             rc = MODGPU_OK;
-            for (int k = 0; k < g && rc == MODGPU_OK; ++k) {
-                if (gd[k] != gs[k]) {
-                    const hipError_t e = hipMemcpyAsync(gd[k], gs[k], gn[k], hipMemcpyDefault, stream);
+            for (int k = 0; k < r.n && rc == MODGPU_OK; ++k) {
+                if (r.role[k] != r.src[k]) {
+                    const hipError_t e = hipMemcpyAsync(r.role[k], r.src[k], r.size[k], hipMemcpyDefault, stream);
                     if (e != hipSuccess) return fail_hip(e, "hipMemcpyAsync (out of place)");
                 }
-                if (key_res) rc = cycle_device_impl(gd[k], gn[k], key, go[k], stream);
+                if (key_res) rc = cycle_device_impl(r.role[k], r.size[k], key, r.off[0][k], stream);
             }
         }
-        if (rc != MODGPU_OK) return rc;
-    }
-    return MODGPU_OK;
+        return rc;
+    });
 }
 
 // ---- rekey: dst = src ^ ks(key_from)[off_from + j] ^ ks(key_to)[off_to + j] (modgpu_rekey_device_to / modgpu_rekey_batch_device_to) ----
@@ -887,36 +959,20 @@ int rekey_shape() { return g_rekey_shape.load(std::memory_order_relaxed); }
 constexpr int rekey_shape() { return kRekeyShapeShipped; }
 #endif
 
-// One launch of the rekey kernel over 1..kCycleBatchMax non-empty entries of the current device, both keys non-zero residues.
-// MODGPU_OK, an error, or 1: no ticket pair to be had right now (or an entry beyond the three-byte chunk jump tables).
+// One launch of the rekey kernel over a run, both keys non-zero residues.  MODGPU_OK, an error, or 1: no ticket pair to be had right
+// now (or an entry beyond the three-byte chunk jump tables).
 // `own_pair`: a clean ticket pair of the caller's (the move call's workspace header) instead of one of the ring's.
-int launch_rekey(uint8_t *const *dst, const uint8_t *const *src, const uint64_t *sizes, const uint64_t *offs_from, const uint64_t *offs_to,
-                 int n, uint32_t key_from, uint32_t key_to, hipStream_t stream, uint32_t *own_pair = nullptr)
+int launch_rekey(const EntryRun &r, uint32_t key_from, uint32_t key_to, hipStream_t stream, uint32_t *own_pair = nullptr)
 {
     CycleRekeyArgs a{};
     const uint64_t chunk = modgpu_rekey_chunk_bytes();
-    uint64_t total = 0, bytes = 0;
-    bool misaligned = false;
-    for (int k = 0; k < n; ++k) {
-        CycleRekeyPart &P = a.part[k];
-        const EntryGeom g = entry_geom(dst[k], sizes[k], chunk);
-        P.dst_body = dst[k] + g.head;
-        P.src_body = src[k] + g.head;
-        P.head_n = (uint32_t)g.head;
-        P.tail_n = (uint32_t)g.tail;
-        P.lead = g.lead;
-        P.end = g.end;
+    const EntryPlan p = plan_entries(a, r, chunk, [&](CycleRekeyPart &P, int k, const EntryGeom &g) {
+        P.dst_body = r.role[k] + g.head;
         // two keystreams, two sets of bases on the same positions: differing offsets change nothing else
-        entry_bases(g, key_from, offs_from[k] % lcg::PERIOD, P.base_head[0], P.base_body[0], P.base_tail[0]);
-        entry_bases(g, key_to, offs_to[k] % lcg::PERIOD, P.base_head[1], P.base_body[1], P.base_tail[1]);
-        if (g.n_chunks >= (1ull << 24)) return 1;
-        a.start[k] = (uint32_t)total;
-        total += g.n_chunks > g.first ? g.n_chunks - g.first : 0;
-        bytes += sizes[k];
-        misaligned |= g.words != 0 && ((reinterpret_cast<uintptr_t>(src[k]) - reinterpret_cast<uintptr_t>(dst[k])) & 3) != 0;
-    }
-    for (int k = n; k <= kCycleBatchMax; ++k) a.start[k] = (uint32_t)total;
-    a.n_parts = (uint32_t)n;
+        entry_bases(g, key_from, r.off[0][k] % lcg::PERIOD, P.base_head[0], P.base_body[0], P.base_tail[0]);
+        entry_bases(g, key_to, r.off[1][k] % lcg::PERIOD, P.base_head[1], P.base_body[1], P.base_tail[1]);
+    });
+    if (p.oversized) return 1;
     QueuePair q;
     if (own_pair) {
         q.pair = own_pair;
@@ -927,20 +983,19 @@ int launch_rekey(uint8_t *const *dst, const uint8_t *const *src, const uint64_t 
     a.queue = q.pair;
     a.queue_done = q.done;
     a.queue_seq = q.seq;
-    uint64_t cap = 0, helpers = 0;
-    queue_grid(total, large_grid(), &cap, &helpers);
-    if (rekey_shape() == CYCLE_REKEY_SHAPE_ALL) cap = large_grid();
-    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(total, cap));
-    const int form = misaligned ? CYCLE_REKEY_FUNNEL : CYCLE_REKEY_PLAIN;
-    hipError_t e = modgpu_launch_cycle_rekey(a, form, grid, stream);
-    if (e != hipSuccess) {
-        queue_pair_unused(q);
-        return fail_hip(e, "cycle kernel launch (rekey)");
-    }
-    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    t_last_launch = {modgpu_rekey_kernel_name(form), CYCLE_REKEY, grid, modgpu_rekey_block(), (uint32_t)chunk, bytes, grid, MODGPU_REKEY_KERNEL_SOURCE_HASH};
-    return MODGPU_OK;
+    const uint32_t grid = entry_grid(p.total, rekey_shape() == CYCLE_REKEY_SHAPE_ALL ? large_grid() : queue_cap(p.total));
+    const int form = p.misaligned ? CYCLE_REKEY_FUNNEL : CYCLE_REKEY_PLAIN;
+    return entry_launched(modgpu_launch_cycle_rekey(a, form, grid, stream), "cycle kernel launch (rekey)", &q, modgpu_rekey_kernel_name(form), CYCLE_REKEY,
+                          grid, modgpu_rekey_block(), chunk, p.bytes, MODGPU_REKEY_KERNEL_SOURCE_HASH);
 }
+
+// The rekey calls' degenerate keystreams, entry by entry: the same reduced key at the same stream position has ks ^ ks = 0.
+struct SameStream {
+    bool same_key;
+    const uint64_t *offs_from, *offs_to;
+    static uint64_t at(const uint64_t *offs, int i) { return offs ? offs[i] % lcg::PERIOD : 0; }
+    bool operator()(int i) const { return same_key && at(offs_from, i) == at(offs_to, i); }
+};
 
 // Entries already checked (check_to_entries), on the current device, asynchronous on `stream`.  Degenerate keystreams take the
 // out-of-place call: a key == 0 mod m has the identity keystream, so only the other key is left to apply (both zero: a copy); an
@@ -953,37 +1008,25 @@ int rekey_impl(void *const *dst, const void *const *src, const uint64_t *sizes, 
     const uint32_t kf = lcg::key_residue(key_from), kt = lcg::key_residue(key_to);
     if (!kf) return cycle_to_impl(dst, src, sizes, offs_to, n, key_to, stream); // (key_to == 0 too: a copy)
     if (!kt) return cycle_to_impl(dst, src, sizes, offs_from, n, key_from, stream);
-    auto at = [](const uint64_t *offs, int i) { return offs ? offs[i] % lcg::PERIOD : 0; };
-    auto identity = [&](int i) { return kf == kt && at(offs_from, i) == at(offs_to, i); };
+    const SameStream identity{kf == kt, offs_from, offs_to};
     for (int i = 0; i < n; ++i)
         if (sizes[i] && identity(i))
             if (int rc = cycle_to_impl(&dst[i], &src[i], &sizes[i], nullptr, 1, 0, stream)) return rc;
-    int i = 0, idx[kCycleBatchMax];
-    while (const int g = next_run(sizes, n, i, idx, [&](int j) { return !identity(j); })) {
-        uint8_t *gd[kCycleBatchMax];
-        const uint8_t *gs[kCycleBatchMax];
-        uint64_t gn[kCycleBatchMax], gf[kCycleBatchMax], gt[kCycleBatchMax];
-        for (int k = 0; k < g; ++k) {
-            gd[k] = static_cast<uint8_t *>(dst[idx[k]]);
-            gs[k] = static_cast<const uint8_t *>(src[idx[k]]);
-            gn[k] = sizes[idx[k]];
-            gf[k] = at(offs_from, idx[k]);
-            gt[k] = at(offs_to, idx[k]);
-        }
-        int rc = launch_rekey(gd, gs, gn, gf, gt, g, kf, kt, stream);
+    return for_each_run(dst, src, sizes, offs_from, offs_to, n, [&](int i) { return !identity(i); }, [&](const EntryRun &r) {
+        int rc = launch_rekey(r, kf, kt, stream);
         if (rc == 1) {
             rc = MODGPU_OK;
-            for (int k = 0; k < g && rc == MODGPU_OK; ++k) {
-                void *d = gd[k];
-                const void *s = gs[k];
-                rc = cycle_to_impl(&d, &s, &gn[k], &gf[k], 1, key_from, stream);
-                if (rc == MODGPU_OK) rc = cycle_device_impl(d, gn[k], key_to, gt[k], stream);
+            for (int k = 0; k < r.n && rc == MODGPU_OK; ++k) {
+                void *d = r.role[k];
+                const void *s = r.src[k];
+                rc = cycle_to_impl(&d, &s, &r.size[k], &r.off[0][k], 1, key_from, stream);
+                if (rc == MODGPU_OK) rc = cycle_device_impl(d, r.size[k], key_to, r.off[1][k], stream);
             }
         }
-        if (rc != MODGPU_OK) return rc;
-    }
-    return MODGPU_OK;
+        return rc;
+    });
 }
+
 
 // ---- move: rekey with memmove rules, any overlap of destination and source (modgpu_rekey_move_device) ----
 // The workspace: a header line -- words 0, 1 the ticket pair, word kMoveStatusWord the status (0, or 1 + the stalled chunk) --, one
@@ -1048,13 +1091,14 @@ int move_launches(uint8_t *dst, const uint8_t *src, uint64_t n, uint32_t kf, uin
     HIP_TRY(hipMemsetAsync(ws, 0, L.head, stream)); // header and flags
     // the pieces are READ first: nothing of the source has been written yet
     if (head || tail) {
-        uint8_t *pd[2];
-        const uint8_t *ps[2];
-        uint64_t pn[2], pf[2], pt[2];
-        int k = 0;
-        if (head) pd[k] = ws + L.head, ps[k] = src, pn[k] = head, pf[k] = of, pt[k] = ot, ++k;
-        if (tail) pd[k] = ws + L.tail, ps[k] = src + head + body, pn[k] = tail, pf[k] = of + head + body, pt[k] = ot + head + body, ++k;
-        const int rc = launch_rekey(pd, ps, pn, pf, pt, k, kf, kt, stream, hdr);
+        EntryRun r;
+        auto piece = [&](uint8_t *d, uint64_t at, uint64_t len) {
+            const int k = r.n++;
+            r.role[k] = d, r.src[k] = src + at, r.size[k] = len, r.off[0][k] = of + at, r.off[1][k] = ot + at;
+        };
+        if (head) piece(ws + L.head, 0, head);
+        if (tail) piece(ws + L.tail, head + body, tail);
+        const int rc = launch_rekey(r, kf, kt, stream, hdr);
         if (rc != MODGPU_OK) return rc == 1 ? fail(MODGPU_ERR_INVALID, "move: a ragged piece beyond the chunk tables") : rc;
     }
     if (body) {
@@ -1078,11 +1122,7 @@ int move_launches(uint8_t *dst, const uint8_t *src, uint64_t n, uint32_t kf, uin
             return fail(MODGPU_ERR_INVALID, "move: internal error (a chunk would wait for a later one)");
         // the rekey call's grid; every position is a ticket, so the pass needs no workgroup that is not running, but a grid the
         // device holds at once wastes none (modgpu_launch_cycle_rekey_move caps it)
-        uint64_t cap = 0, helpers = 0;
-        queue_grid(total, large_grid(), &cap, &helpers);
-        if (rekey_shape() == CYCLE_REKEY_SHAPE_ALL) cap = large_grid();
-        if (move_grid_forced()) cap = move_grid_forced();
-        uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(total, cap));
+        uint32_t grid = entry_grid(total, move_grid_forced() ? move_grid_forced() : rekey_shape() == CYCLE_REKEY_SHAPE_ALL ? large_grid() : queue_cap(total));
         const int form = (delta & 3) != 0 ? CYCLE_REKEY_FUNNEL : CYCLE_REKEY_PLAIN;
         const hipError_t e = modgpu_launch_cycle_rekey_move(a, form, &grid, stream);
         if (e != hipSuccess) return fail_hip(e, "cycle kernel launch (move)");
@@ -1149,56 +1189,62 @@ uint32_t verify_grid_forced() { return g_verify_grid.load(std::memory_order_rela
 constexpr uint32_t verify_grid_forced() { return 0; }
 #endif
 
-// One compare launch over 1..kCycleBatchMax non-empty entries of the current device (key_res == 0: the identity forms).
-int launch_verify(const uint8_t *const *expect, const uint8_t *const *src, const uint64_t *sizes, const uint64_t *offs,
-                  modgpu_verify_result_t *const *results, int n, uint32_t key_res, hipStream_t stream)
+// One compare launch over a run (key_res == 0: the identity forms); result r.idx[k] of `results` is entry k's.
+int launch_verify(const EntryRun &r, modgpu_verify_result_t *results, uint32_t key_res, hipStream_t stream)
 {
     CycleVerifyArgs a{};
     const uint64_t chunk = modgpu_verify_chunk_bytes();
-    uint64_t total = 0, bytes = 0;
-    bool misaligned = false;
-    for (int k = 0; k < n; ++k) {
-        CycleVerifyPart &P = a.part[k];
-        const EntryGeom g = entry_geom(expect[k], sizes[k], chunk);
-        P.expect_body = expect[k] + g.head;
-        P.src_body = src[k] + g.head;
-        P.result = reinterpret_cast<CycleVerifyResult *>(results[k]);
-        P.n = sizes[k];
-        P.head_n = (uint32_t)g.head;
-        P.tail_n = (uint32_t)g.tail;
-        P.lead = g.lead;
-        P.end = g.end;
-        if (key_res) entry_bases(g, key_res, offs[k] % lcg::PERIOD, P.base_head, P.base_body, P.base_tail);
-        a.start[k] = (uint32_t)total;
-        total += g.n_chunks > g.first ? g.n_chunks - g.first : 0;
-        bytes += sizes[k];
-        misaligned |= g.words != 0 && ((reinterpret_cast<uintptr_t>(src[k]) - reinterpret_cast<uintptr_t>(expect[k])) & 3) != 0;
-    }
-    for (int k = n; k <= kCycleBatchMax; ++k) a.start[k] = (uint32_t)total;
-    a.n_parts = (uint32_t)n;
-    const uint64_t cap = verify_grid_forced() ? verify_grid_forced() : large_grid();
-    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(total, cap));
-    const int form = (misaligned ? CYCLE_VERIFY_FUNNEL : CYCLE_VERIFY_PLAIN) | (key_res ? 0 : CYCLE_VERIFY_IDENTITY);
-    const hipError_t e = modgpu_launch_cycle_verify(a, form, grid, stream);
-    if (e != hipSuccess) return fail_hip(e, "verify kernel launch");
-    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    t_last_launch = {modgpu_verify_kernel_name(form), CYCLE_VERIFY, grid, modgpu_verify_block(), (uint32_t)chunk, bytes, grid, MODGPU_VERIFY_KERNEL_SOURCE_HASH};
-    return MODGPU_OK;
+    const EntryPlan p = plan_entries(a, r, chunk, [&](CycleVerifyPart &P, int k, const EntryGeom &g) {
+        P.expect_body = r.role[k] + g.head;
+        P.result = reinterpret_cast<CycleVerifyResult *>(results + r.idx[k]);
+        P.n = r.size[k];
+        if (key_res) entry_bases(g, key_res, r.off[0][k] % lcg::PERIOD, P.base_head, P.base_body, P.base_tail);
+    });
+    const uint32_t grid = entry_grid(p.total, verify_grid_forced() ? verify_grid_forced() : large_grid());
+    const int form = (p.misaligned ? CYCLE_VERIFY_FUNNEL : CYCLE_VERIFY_PLAIN) | (key_res ? 0 : CYCLE_VERIFY_IDENTITY);
+    return entry_launched(modgpu_launch_cycle_verify(a, form, grid, stream), "verify kernel launch", nullptr, modgpu_verify_kernel_name(form), CYCLE_VERIFY,
+                          grid, modgpu_verify_block(), chunk, p.bytes, MODGPU_VERIFY_KERNEL_SOURCE_HASH);
 }
 
 // Everything that is checked before a device is looked at.
 int check_verify_entries(const void *const *expect, const void *const *src, const uint64_t *sizes, int n, const modgpu_verify_result_t *results)
 {
     if (n < 0 || (n > 0 && (!expect || !src || !sizes))) return fail(MODGPU_ERR_INVALID, "bad entry list");
-    if (n > 0 && !results) return fail(MODGPU_ERR_INVALID, "null result");
-    if (reinterpret_cast<uintptr_t>(results) & 7) return fail(MODGPU_ERR_INVALID, "result not 8-byte aligned");
+    if (int rc = check_results(n, results)) return rc;
     for (int i = 0; i < n; ++i) {
         if (!sizes[i]) continue;
         if (!expect[i] || !src[i]) return fail(MODGPU_ERR_INVALID, "null buffer");
-        // (the kernel jumps to a chunk's keystream state by the three bytes of its index in the entry)
-        if (sizes[i] >= (1ull << 41) || entry_geom(static_cast<const uint8_t *>(expect[i]), sizes[i], modgpu_verify_chunk_bytes()).n_chunks >= (1ull << 24))
-            return fail(MODGPU_ERR_INVALID, "an entry that spans 2^24 chunks of 64 KiB or more (1 TiB)");
+        if (int rc = check_entry_span(expect[i], sizes[i], modgpu_verify_chunk_bytes())) return rc;
     }
+    return MODGPU_OK;
+}
+
+// What the calls with results do before their first launch, n > 0: the records are device memory of the call's device, an earlier
+// call's error is cleared (the launches report hipGetLastError: it must not be taken for theirs), and the records are made clean on the
+// call's own stream -- the verify record by a launch (first_mismatch starts at all ones) ...
+int results_on_device(const void *results, uint64_t bytes)
+{
+    int phys = -1;
+    HIP_TRY(hipGetDevice(&phys));
+    if (modgpu_xfer_device_of(results, bytes) != phys) return fail(MODGPU_ERR_INVALID, "the result is not device memory of the call's device");
+    return MODGPU_OK;
+}
+int prepare_results(modgpu_verify_result_t *results, int n, hipStream_t stream)
+{
+    if (int rc = results_on_device(results, (uint64_t)n * sizeof *results)) return rc;
+    (void)hipGetLastError();
+    const hipError_t e = modgpu_launch_verify_init(reinterpret_cast<CycleVerifyResult *>(results), (uint64_t)n, stream);
+    if (e != hipSuccess) return fail_hip(e, "verify init launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    t_last_launch = {"modgpu_cycle_verify_init", CYCLE_VERIFY, (uint32_t)(((uint64_t)n + 255) / 256), 256u, 0u, 0, 0u, MODGPU_VERIFY_KERNEL_SOURCE_HASH};
+    return MODGPU_OK;
+}
+// ... and the digest record by a memset (a node of a capture, so a replay starts clean), which comes before the clearing.
+int prepare_results(modgpu_digest_result_t *results, int n, hipStream_t stream)
+{
+    if (int rc = results_on_device(results, (uint64_t)n * sizeof *results)) return rc;
+    HIP_TRY(hipMemsetAsync(results, 0, (size_t)n * sizeof *results, stream));
+    (void)hipGetLastError();
     return MODGPU_OK;
 }
 
@@ -1208,31 +1254,9 @@ int verify_impl(const void *const *expect, const void *const *src, const uint64_
                 modgpu_verify_result_t *results, hipStream_t stream)
 {
     if (n == 0) return MODGPU_OK;
-    int phys = -1;
-    HIP_TRY(hipGetDevice(&phys));
-    if (modgpu_xfer_device_of(results, (uint64_t)n * sizeof(modgpu_verify_result_t)) != phys)
-        return fail(MODGPU_ERR_INVALID, "the result is not device memory of the call's device");
+    if (int rc = prepare_results(results, n, stream)) return rc;
     const uint32_t key_res = lcg::key_residue(key);
-    (void)hipGetLastError(); // (the launches report hipGetLastError: an earlier call's error must not be taken for theirs)
-    const hipError_t e = modgpu_launch_verify_init(reinterpret_cast<CycleVerifyResult *>(results), (uint64_t)n, stream);
-    if (e != hipSuccess) return fail_hip(e, "verify init launch");
-    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    t_last_launch = {"modgpu_cycle_verify_init", CYCLE_VERIFY, (uint32_t)(((uint64_t)n + 255) / 256), 256u, 0u, 0, 0u, MODGPU_VERIFY_KERNEL_SOURCE_HASH};
-    int i = 0, idx[kCycleBatchMax];
-    while (const int g = next_run(sizes, n, i, idx, [](int) { return true; })) {
-        const uint8_t *ge[kCycleBatchMax], *gs[kCycleBatchMax];
-        uint64_t gn[kCycleBatchMax], go[kCycleBatchMax];
-        modgpu_verify_result_t *gr[kCycleBatchMax];
-        for (int k = 0; k < g; ++k) {
-            ge[k] = static_cast<const uint8_t *>(expect[idx[k]]);
-            gs[k] = static_cast<const uint8_t *>(src[idx[k]]);
-            gn[k] = sizes[idx[k]];
-            go[k] = offs ? offs[idx[k]] : 0;
-            gr[k] = results + idx[k];
-        }
-        if (const int rc = launch_verify(ge, gs, gn, go, gr, g, key_res, stream)) return rc;
-    }
-    return MODGPU_OK;
+    return for_each_run(expect, src, sizes, offs, nullptr, n, every_entry, [&](const EntryRun &r) { return launch_verify(r, results, key_res, stream); });
 }
 
 // ---- digest: Adler-32 of out[j] = src[j] ^ ks(key)[off + j], with or without storing out (modgpu_digest_device / modgpu_digest_batch_device) ----
@@ -1250,148 +1274,75 @@ uint32_t digest_grid_forced() { return g_digest_grid.load(std::memory_order_rela
 constexpr uint32_t digest_grid_forced() { return 0; }
 #endif
 
-// One digest launch over 1..kCycleBatchMax non-empty entries of the current device (key_res == 0: out = src).  An entry without a
-// destination is planned with its source in the destination's role: the chunk grid lies on the source, whose phase against itself is 0.
-int launch_digest(uint8_t *const *dst, const uint8_t *const *src, const uint64_t *sizes, const uint64_t *offs,
-                  modgpu_digest_result_t *const *results, int n, uint32_t key_res, hipStream_t stream)
+// One digest launch over a run (key_res == 0: out = src); record r.idx[k] of `results` is entry k's.  An entry without a destination
+// (`dst` null, or its entry) is planned with its source in the destination's role: the chunk grid lies on the source, whose phase
+// against itself is 0.
+int launch_digest(const EntryRun &r, void *const *dst, modgpu_digest_result_t *results, uint32_t key_res, hipStream_t stream)
 {
     CycleToArgs a{};
     const uint64_t chunk = modgpu_to_chunk_bytes();
-    uint64_t total = 0, bytes = 0;
-    bool misaligned = false;
-    for (int k = 0; k < n; ++k) {
-        CycleToPart &P = a.part[k];
-        uint8_t *const role = dst[k] ? dst[k] : const_cast<uint8_t *>(src[k]); // (never stored through when it is the source)
-        const EntryGeom g = entry_geom(role, sizes[k], chunk);
-        P.dst_body = role + g.head;
-        P.src_body = src[k] + g.head;
-        P.head_n = (uint32_t)g.head;
-        P.tail_n = (uint32_t)g.tail;
-        P.lead = g.lead;
-        P.end = g.end;
-        if (key_res) entry_bases(g, key_res, offs[k] % lcg::PERIOD, P.base_head, P.base_body, P.base_tail);
-        a.result[k] = reinterpret_cast<CycleToDigest *>(results[k]);
-        if (dst[k]) a.store_mask |= 1u << k;
-        a.start[k] = (uint32_t)total;
-        total += g.n_chunks > g.first ? g.n_chunks - g.first : 0;
-        bytes += sizes[k];
-        misaligned |= g.words != 0 && ((reinterpret_cast<uintptr_t>(src[k]) - reinterpret_cast<uintptr_t>(role)) & 3) != 0;
-    }
-    for (int k = n; k <= kCycleBatchMax; ++k) a.start[k] = (uint32_t)total;
-    a.n_parts = (uint32_t)n;
+    const EntryPlan p = plan_entries(a, r, chunk, [&](CycleToPart &P, int k, const EntryGeom &g) {
+        P.dst_body = r.role[k] + g.head;
+        if (key_res) entry_bases(g, key_res, r.off[0][k] % lcg::PERIOD, P.base_head, P.base_body, P.base_tail);
+        a.result[k] = reinterpret_cast<CycleToDigest *>(results + r.idx[k]);
+        if (dst && dst[r.idx[k]]) a.store_mask |= 1u << k;
+    });
     a.digest = CYCLE_TO_DIGEST_ON | (key_res ? 0u : CYCLE_TO_DIGEST_IDENTITY);
     // digest only: one workgroup per CU, as verify (a read-only stream).  A launch that stores takes the out-of-place kernel's grid,
     // 25 workgroups per 32 CUs (cycle_kernel.hip: the memory system does best with fewer read/write streams than CUs)
-    uint64_t cap = large_grid(), helpers = 0;
-    if (a.store_mask) queue_grid(total, large_grid(), &cap, &helpers);
-    if (digest_grid_forced()) cap = digest_grid_forced();
-    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(total, cap));
-    const int form = misaligned ? to_form() : CYCLE_TO_PLAIN;
-    const hipError_t e = modgpu_launch_cycle_to_digest(a, form, grid, stream);
-    if (e != hipSuccess) return fail_hip(e, "digest kernel launch");
-    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    t_last_launch = {modgpu_to_kernel_name(form), CYCLE_TO_DIGEST, grid, modgpu_to_block(), (uint32_t)chunk, bytes, grid, MODGPU_TO_KERNEL_SOURCE_HASH};
-    return MODGPU_OK;
+    const uint32_t grid = entry_grid(p.total, digest_grid_forced() ? digest_grid_forced() : a.store_mask ? queue_cap(p.total) : large_grid());
+    const int form = p.misaligned ? to_form() : CYCLE_TO_PLAIN;
+    return entry_launched(modgpu_launch_cycle_to_digest(a, form, grid, stream), "digest kernel launch", nullptr, modgpu_to_kernel_name(form), CYCLE_TO_DIGEST,
+                          grid, modgpu_to_block(), chunk, p.bytes, MODGPU_TO_KERNEL_SOURCE_HASH);
 }
 
 // Everything that is checked before a device is looked at.  `dst` may be null (digest only), and so may any of its entries; an entry
-// that has a destination keeps the out-of-place rules (check_to_entries).
+// that has a destination keeps the out-of-place rules (check_to_entry, check_to_meetings).
 int check_digest_entries(void *const *dst, const void *const *src, const uint64_t *sizes, int n, const modgpu_digest_result_t *results)
 {
     if (n < 0 || (n > 0 && (!src || !sizes))) return fail(MODGPU_ERR_INVALID, "bad entry list");
-    if (n > 0 && !results) return fail(MODGPU_ERR_INVALID, "null result");
-    if (reinterpret_cast<uintptr_t>(results) & 7) return fail(MODGPU_ERR_INVALID, "result not 8-byte aligned");
-    auto dst_of = [&](int i) -> const void * { return dst && sizes[i] ? dst[i] : nullptr; };
+    if (int rc = check_results(n, results)) return rc;
     for (int i = 0; i < n; ++i) {
         if (!sizes[i]) continue;
-        if (!src[i]) return fail(MODGPU_ERR_INVALID, "null buffer");
-        const void *d = dst_of(i);
-        if (d && d != src[i] && ranges_meet(d, sizes[i], src[i], sizes[i]))
-            return fail(MODGPU_ERR_INVALID, "destination partly overlaps its source (only dst == src may alias)");
-        // (the kernel jumps to a chunk's keystream state by the three bytes of its index in the entry)
-        if (sizes[i] >= (1ull << 41) || entry_geom(static_cast<const uint8_t *>(d ? d : src[i]), sizes[i], modgpu_to_chunk_bytes()).n_chunks >= (1ull << 24))
-            return fail(MODGPU_ERR_INVALID, "an entry that spans 2^24 chunks of 64 KiB or more (1 TiB)");
+        const void *const d = dst ? dst[i] : nullptr;
+        if (int rc = check_to_entry(d, src[i], sizes[i])) return rc;
+        if (int rc = check_entry_span(d ? d : src[i], sizes[i], modgpu_to_chunk_bytes())) return rc;
     }
-    for (int i = 0; i < n; ++i)
-        for (int j = 0; j < n; ++j)
-            if (i != j && dst_of(i) && (ranges_meet(dst_of(i), sizes[i], src[j], sizes[j]) || (dst_of(j) && ranges_meet(dst_of(i), sizes[i], dst_of(j), sizes[j]))))
-                return fail(MODGPU_ERR_INVALID, "a destination meets another entry's source or destination");
-    return MODGPU_OK;
+    return check_to_meetings(dst, src, sizes, n);
 }
 
 // Entries already checked (check_digest_entries), on the current device, asynchronous on `stream`: all n records are zeroed on the
-// call's own stream (a node of a capture, so a replay starts clean), then runs of up to kCycleBatchMax non-empty entries share a launch.
+// call's own stream, then runs of up to kCycleBatchMax non-empty entries share a launch.
 int digest_impl(void *const *dst, const void *const *src, const uint64_t *sizes, const uint64_t *offs, int n, int32_t key,
                 modgpu_digest_result_t *results, hipStream_t stream)
 {
     if (n == 0) return MODGPU_OK;
-    int phys = -1;
-    HIP_TRY(hipGetDevice(&phys));
-    if (modgpu_xfer_device_of(results, (uint64_t)n * sizeof(modgpu_digest_result_t)) != phys)
-        return fail(MODGPU_ERR_INVALID, "the result is not device memory of the call's device");
+    if (int rc = prepare_results(results, n, stream)) return rc;
     const uint32_t key_res = lcg::key_residue(key);
-    HIP_TRY(hipMemsetAsync(results, 0, (size_t)n * sizeof(modgpu_digest_result_t), stream));
-    (void)hipGetLastError(); // (the launch reports hipGetLastError: an earlier call's error must not be taken for its own)
-    int i = 0, idx[kCycleBatchMax];
-    while (const int g = next_run(sizes, n, i, idx, [](int) { return true; })) {
-        uint8_t *gd[kCycleBatchMax];
-        const uint8_t *gs[kCycleBatchMax];
-        uint64_t gn[kCycleBatchMax], go[kCycleBatchMax];
-        modgpu_digest_result_t *gr[kCycleBatchMax];
-        for (int k = 0; k < g; ++k) {
-            gd[k] = dst ? static_cast<uint8_t *>(dst[idx[k]]) : nullptr;
-            gs[k] = static_cast<const uint8_t *>(src[idx[k]]);
-            gn[k] = sizes[idx[k]];
-            go[k] = offs ? offs[idx[k]] : 0;
-            gr[k] = results + idx[k];
-        }
-        if (const int rc = launch_digest(gd, gs, gn, go, gr, g, key_res, stream)) return rc;
-    }
-    return MODGPU_OK;
+    return for_each_run(dst, src, sizes, offs, nullptr, n, every_entry, [&](const EntryRun &r) { return launch_digest(r, dst, results, key_res, stream); });
 }
+
 
 // ---- rekey verify: count and locate the j with expect[j] != (src[j] ^ ks(key_from)[off_from + j] ^ ks(key_to)[off_to + j])
 // (modgpu_verify_rekey_device / modgpu_verify_rekey_batch_device) ----
 // One two-keystream compare launch over 1..kCycleBatchMax non-empty entries of the current device, both keys non-zero residues:
 // launch_verify's geometry with two sets of bases.
 static_assert(sizeof(CycleRekeyVerifyArgs) <= 4096, "the table of entries travels in the kernel arguments");
-int launch_rekey_verify(const uint8_t *const *expect, const uint8_t *const *src, const uint64_t *sizes, const uint64_t *offs_from,
-                        const uint64_t *offs_to, modgpu_verify_result_t *const *results, int n, uint32_t key_from, uint32_t key_to,
-                        hipStream_t stream)
+int launch_rekey_verify(const EntryRun &r, modgpu_verify_result_t *results, uint32_t key_from, uint32_t key_to, hipStream_t stream)
 {
     CycleRekeyVerifyArgs a{};
     const uint64_t chunk = modgpu_rekey_verify_chunk_bytes();
-    uint64_t total = 0, bytes = 0;
-    bool misaligned = false;
-    for (int k = 0; k < n; ++k) {
-        CycleRekeyVerifyPart &P = a.part[k];
-        const EntryGeom g = entry_geom(expect[k], sizes[k], chunk);
-        P.expect_body = expect[k] + g.head;
-        P.src_body = src[k] + g.head;
-        P.result = reinterpret_cast<CycleVerifyResult *>(results[k]);
-        P.n = sizes[k];
-        P.head_n = (uint32_t)g.head;
-        P.tail_n = (uint32_t)g.tail;
-        P.lead = g.lead;
-        P.end = g.end;
-        entry_bases(g, key_from, offs_from[k] % lcg::PERIOD, P.base_head[0], P.base_body[0], P.base_tail[0]);
-        entry_bases(g, key_to, offs_to[k] % lcg::PERIOD, P.base_head[1], P.base_body[1], P.base_tail[1]);
-        a.start[k] = (uint32_t)total;
-        total += g.n_chunks > g.first ? g.n_chunks - g.first : 0;
-        bytes += sizes[k];
-        misaligned |= g.words != 0 && ((reinterpret_cast<uintptr_t>(src[k]) - reinterpret_cast<uintptr_t>(expect[k])) & 3) != 0;
-    }
-    for (int k = n; k <= kCycleBatchMax; ++k) a.start[k] = (uint32_t)total;
-    a.n_parts = (uint32_t)n;
-    const uint64_t cap = verify_grid_forced() ? verify_grid_forced() : large_grid();
-    const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(total, cap));
-    const int form = misaligned ? CYCLE_REKEY_VERIFY_FUNNEL : CYCLE_REKEY_VERIFY_PLAIN;
-    const hipError_t e = modgpu_launch_cycle_rekey_verify(a, form, grid, stream);
-    if (e != hipSuccess) return fail_hip(e, "rekey verify kernel launch");
-    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    t_last_launch = {modgpu_rekey_verify_kernel_name(form), CYCLE_REKEY_VERIFY, grid, modgpu_rekey_verify_block(), (uint32_t)chunk, bytes, grid,
-                     MODGPU_REKEY_VERIFY_KERNEL_SOURCE_HASH};
-    return MODGPU_OK;
+    const EntryPlan p = plan_entries(a, r, chunk, [&](CycleRekeyVerifyPart &P, int k, const EntryGeom &g) {
+        P.expect_body = r.role[k] + g.head;
+        P.result = reinterpret_cast<CycleVerifyResult *>(results + r.idx[k]);
+        P.n = r.size[k];
+        entry_bases(g, key_from, r.off[0][k] % lcg::PERIOD, P.base_head[0], P.base_body[0], P.base_tail[0]);
+        entry_bases(g, key_to, r.off[1][k] % lcg::PERIOD, P.base_head[1], P.base_body[1], P.base_tail[1]);
+    });
+    const uint32_t grid = entry_grid(p.total, verify_grid_forced() ? verify_grid_forced() : large_grid());
+    const int form = p.misaligned ? CYCLE_REKEY_VERIFY_FUNNEL : CYCLE_REKEY_VERIFY_PLAIN;
+    return entry_launched(modgpu_launch_cycle_rekey_verify(a, form, grid, stream), "rekey verify kernel launch", nullptr, modgpu_rekey_verify_kernel_name(form),
+                          CYCLE_REKEY_VERIFY, grid, modgpu_rekey_verify_block(), chunk, p.bytes, MODGPU_REKEY_VERIFY_KERNEL_SOURCE_HASH);
 }
 
 // Entries already checked (check_verify_entries), on the current device, asynchronous on `stream`.  One launch initialises all n
@@ -1406,36 +1357,12 @@ int verify_rekey_impl(const void *const *expect, const void *const *src, const u
     if (!kf) return verify_impl(expect, src, sizes, offs_to, n, key_to, results, stream); // (key_to == 0 too: a plain compare)
     if (!kt) return verify_impl(expect, src, sizes, offs_from, n, key_from, results, stream);
     if (n == 0) return MODGPU_OK;
-    int phys = -1;
-    HIP_TRY(hipGetDevice(&phys));
-    if (modgpu_xfer_device_of(results, (uint64_t)n * sizeof(modgpu_verify_result_t)) != phys)
-        return fail(MODGPU_ERR_INVALID, "the result is not device memory of the call's device");
-    (void)hipGetLastError(); // (the launches report hipGetLastError: an earlier call's error must not be taken for theirs)
-    const hipError_t e = modgpu_launch_verify_init(reinterpret_cast<CycleVerifyResult *>(results), (uint64_t)n, stream);
-    if (e != hipSuccess) return fail_hip(e, "verify init launch");
-    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    t_last_launch = {"modgpu_cycle_verify_init", CYCLE_VERIFY, (uint32_t)(((uint64_t)n + 255) / 256), 256u, 0u, 0, 0u, MODGPU_VERIFY_KERNEL_SOURCE_HASH};
-    auto at = [](const uint64_t *offs, int i) { return offs ? offs[i] % lcg::PERIOD : 0; };
-    auto identity = [&](int i) { return kf == kt && at(offs_from, i) == at(offs_to, i); };
-    for (int pass = 0; pass < 2; ++pass) { // 0: two streams, 1: coinciding streams
-        int i = 0, idx[kCycleBatchMax];
-        while (const int g = next_run(sizes, n, i, idx, [&](int j) { return identity(j) == (pass == 1); })) {
-            const uint8_t *ge[kCycleBatchMax], *gs[kCycleBatchMax];
-            uint64_t gn[kCycleBatchMax], gf[kCycleBatchMax], gt[kCycleBatchMax];
-            modgpu_verify_result_t *gr[kCycleBatchMax];
-            for (int k = 0; k < g; ++k) {
-                ge[k] = static_cast<const uint8_t *>(expect[idx[k]]);
-                gs[k] = static_cast<const uint8_t *>(src[idx[k]]);
-                gn[k] = sizes[idx[k]];
-                gf[k] = at(offs_from, idx[k]);
-                gt[k] = at(offs_to, idx[k]);
-                gr[k] = results + idx[k];
-            }
-            const int rc = pass == 0 ? launch_rekey_verify(ge, gs, gn, gf, gt, gr, g, kf, kt, stream) : launch_verify(ge, gs, gn, gf, gr, g, 0u, stream);
-            if (rc) return rc;
-        }
-    }
-    return MODGPU_OK;
+    if (int rc = prepare_results(results, n, stream)) return rc;
+    const SameStream identity{kf == kt, offs_from, offs_to};
+    if (int rc = for_each_run(expect, src, sizes, offs_from, offs_to, n, [&](int i) { return !identity(i); },
+                              [&](const EntryRun &r) { return launch_rekey_verify(r, results, kf, kt, stream); }))
+        return rc;
+    return for_each_run(expect, src, sizes, nullptr, nullptr, n, identity, [&](const EntryRun &r) { return launch_verify(r, results, 0u, stream); });
 }
 } // namespace
 
@@ -1990,6 +1917,17 @@ int rekey_move_table_validate_impl(const modgpu_rekey_table_entry_t *t, uint64_t
     }
     return MODGPU_OK;
 }
+
+// The body of the ten exported entry-list calls: the checks that need no device, the call's device, the call on the caller's stream.
+template <class Check, class Impl> int entry_call(int device, void *hip_stream, Check check, Impl impl)
+{
+    return guarded([&]() -> int {
+        if (int rc = check()) return rc;
+        DeviceScope scope(device);
+        if (scope.rc) return scope.rc;
+        return impl(static_cast<hipStream_t>(hip_stream));
+    });
+}
 } // namespace
 
 } // namespace modgpu
@@ -2027,35 +1965,22 @@ int modgpu_cycle_batch_device(void *const *dev_parts, const uint64_t *sizes, con
 
 int modgpu_cycle_device_to(void *dev_dst, const void *dev_src, uint64_t n, int32_t key, uint64_t stream_off, int device, void *hip_stream)
 {
-    return guarded([&]() -> int {
-        if (int rc = check_to_entries(&dev_dst, &dev_src, &n, 1)) return rc;
-        DeviceScope scope(device);
-        if (scope.rc) return scope.rc;
-        return cycle_to_impl(&dev_dst, &dev_src, &n, &stream_off, 1, key, static_cast<hipStream_t>(hip_stream));
-    });
+    return entry_call(device, hip_stream, [&] { return check_to_entries(&dev_dst, &dev_src, &n, 1); },
+                      [&](hipStream_t st) { return cycle_to_impl(&dev_dst, &dev_src, &n, &stream_off, 1, key, st); });
 }
 
 int modgpu_cycle_batch_device_to(void *const *dst_parts, const void *const *src_parts, const uint64_t *sizes, const uint64_t *stream_offs,
                                  int n_parts, int32_t key, int device, void *hip_stream)
 {
-    return guarded([&]() -> int {
-        if (n_parts < 0 || (n_parts > 0 && (!dst_parts || !src_parts || !sizes))) return fail(MODGPU_ERR_INVALID, "bad entry list");
-        if (int rc = check_to_entries(dst_parts, src_parts, sizes, n_parts)) return rc;
-        DeviceScope scope(device);
-        if (scope.rc) return scope.rc;
-        return cycle_to_impl(dst_parts, src_parts, sizes, stream_offs, n_parts, key, static_cast<hipStream_t>(hip_stream));
-    });
+    return entry_call(device, hip_stream, [&] { return check_to_entries(dst_parts, src_parts, sizes, n_parts); },
+                      [&](hipStream_t st) { return cycle_to_impl(dst_parts, src_parts, sizes, stream_offs, n_parts, key, st); });
 }
 
 int modgpu_rekey_device_to(void *dev_dst, const void *dev_src, uint64_t n, int32_t key_from, uint64_t off_from, int32_t key_to, uint64_t off_to,
                            int device, void *hip_stream)
 {
-    return guarded([&]() -> int {
-        if (int rc = check_to_entries(&dev_dst, &dev_src, &n, 1)) return rc;
-        DeviceScope scope(device);
-        if (scope.rc) return scope.rc;
-        return rekey_impl(&dev_dst, &dev_src, &n, &off_from, &off_to, 1, key_from, key_to, static_cast<hipStream_t>(hip_stream));
-    });
+    return entry_call(device, hip_stream, [&] { return check_to_entries(&dev_dst, &dev_src, &n, 1); },
+                      [&](hipStream_t st) { return rekey_impl(&dev_dst, &dev_src, &n, &off_from, &off_to, 1, key_from, key_to, st); });
 }
 
 uint64_t modgpu_move_workspace_bytes(uint64_t n)
@@ -2094,59 +2019,37 @@ int modgpu_move_status(const void *dev_workspace, int device, uint64_t *stalled_
 int modgpu_rekey_batch_device_to(void *const *dst_parts, const void *const *src_parts, const uint64_t *sizes, const uint64_t *offs_from,
                                  const uint64_t *offs_to, int n_parts, int32_t key_from, int32_t key_to, int device, void *hip_stream)
 {
-    return guarded([&]() -> int {
-        if (n_parts < 0 || (n_parts > 0 && (!dst_parts || !src_parts || !sizes))) return fail(MODGPU_ERR_INVALID, "bad entry list");
-        if (int rc = check_to_entries(dst_parts, src_parts, sizes, n_parts)) return rc;
-        DeviceScope scope(device);
-        if (scope.rc) return scope.rc;
-        return rekey_impl(dst_parts, src_parts, sizes, offs_from, offs_to, n_parts, key_from, key_to, static_cast<hipStream_t>(hip_stream));
-    });
+    return entry_call(device, hip_stream, [&] { return check_to_entries(dst_parts, src_parts, sizes, n_parts); },
+                      [&](hipStream_t st) { return rekey_impl(dst_parts, src_parts, sizes, offs_from, offs_to, n_parts, key_from, key_to, st); });
 }
 
 int modgpu_verify_device(const void *dev_expect, const void *dev_src, uint64_t n, int32_t key, uint64_t stream_off,
                          modgpu_verify_result_t *dev_result, int device, void *hip_stream)
 {
-    return guarded([&]() -> int {
-        if (int rc = check_verify_entries(&dev_expect, &dev_src, &n, 1, dev_result)) return rc;
-        DeviceScope scope(device);
-        if (scope.rc) return scope.rc;
-        return verify_impl(&dev_expect, &dev_src, &n, &stream_off, 1, key, dev_result, static_cast<hipStream_t>(hip_stream));
-    });
+    return entry_call(device, hip_stream, [&] { return check_verify_entries(&dev_expect, &dev_src, &n, 1, dev_result); },
+                      [&](hipStream_t st) { return verify_impl(&dev_expect, &dev_src, &n, &stream_off, 1, key, dev_result, st); });
 }
 
 int modgpu_verify_batch_device(const void *const *expect_parts, const void *const *src_parts, const uint64_t *sizes, const uint64_t *stream_offs,
                                int n_parts, int32_t key, modgpu_verify_result_t *dev_results, int device, void *hip_stream)
 {
-    return guarded([&]() -> int {
-        if (int rc = check_verify_entries(expect_parts, src_parts, sizes, n_parts, dev_results)) return rc;
-        DeviceScope scope(device);
-        if (scope.rc) return scope.rc;
-        return verify_impl(expect_parts, src_parts, sizes, stream_offs, n_parts, key, dev_results, static_cast<hipStream_t>(hip_stream));
-    });
+    return entry_call(device, hip_stream, [&] { return check_verify_entries(expect_parts, src_parts, sizes, n_parts, dev_results); },
+                      [&](hipStream_t st) { return verify_impl(expect_parts, src_parts, sizes, stream_offs, n_parts, key, dev_results, st); });
 }
 
 int modgpu_verify_rekey_device(const void *dev_expect, const void *dev_src, uint64_t n, int32_t key_from, uint64_t off_from, int32_t key_to,
                                uint64_t off_to, modgpu_verify_result_t *dev_result, int device, void *hip_stream)
 {
-    return guarded([&]() -> int {
-        if (int rc = check_verify_entries(&dev_expect, &dev_src, &n, 1, dev_result)) return rc;
-        DeviceScope scope(device);
-        if (scope.rc) return scope.rc;
-        return verify_rekey_impl(&dev_expect, &dev_src, &n, &off_from, &off_to, 1, key_from, key_to, dev_result, static_cast<hipStream_t>(hip_stream));
-    });
+    return entry_call(device, hip_stream, [&] { return check_verify_entries(&dev_expect, &dev_src, &n, 1, dev_result); },
+                      [&](hipStream_t st) { return verify_rekey_impl(&dev_expect, &dev_src, &n, &off_from, &off_to, 1, key_from, key_to, dev_result, st); });
 }
 
 int modgpu_verify_rekey_batch_device(const void *const *expect_parts, const void *const *src_parts, const uint64_t *sizes, const uint64_t *offs_from,
                                      const uint64_t *offs_to, int n_parts, int32_t key_from, int32_t key_to, modgpu_verify_result_t *dev_results,
                                      int device, void *hip_stream)
 {
-    return guarded([&]() -> int {
-        if (int rc = check_verify_entries(expect_parts, src_parts, sizes, n_parts, dev_results)) return rc;
-        DeviceScope scope(device);
-        if (scope.rc) return scope.rc;
-        return verify_rekey_impl(expect_parts, src_parts, sizes, offs_from, offs_to, n_parts, key_from, key_to, dev_results,
-                                 static_cast<hipStream_t>(hip_stream));
-    });
+    return entry_call(device, hip_stream, [&] { return check_verify_entries(expect_parts, src_parts, sizes, n_parts, dev_results); },
+                      [&](hipStream_t st) { return verify_rekey_impl(expect_parts, src_parts, sizes, offs_from, offs_to, n_parts, key_from, key_to, dev_results, st); });
 }
 
 int modgpu_verify_results(const modgpu_verify_result_t *dev_results, uint64_t count, int device, modgpu_verify_result_t *host_out)
@@ -2170,23 +2073,15 @@ int modgpu_verify_results(const modgpu_verify_result_t *dev_results, uint64_t co
 int modgpu_digest_device(void *dev_dst, const void *dev_src, uint64_t n, int32_t key, uint64_t stream_off, modgpu_digest_result_t *dev_result,
                          int device, void *hip_stream)
 {
-    return guarded([&]() -> int {
-        if (int rc = check_digest_entries(dev_dst ? &dev_dst : nullptr, &dev_src, &n, 1, dev_result)) return rc;
-        DeviceScope scope(device);
-        if (scope.rc) return scope.rc;
-        return digest_impl(dev_dst ? &dev_dst : nullptr, &dev_src, &n, &stream_off, 1, key, dev_result, static_cast<hipStream_t>(hip_stream));
-    });
+    return entry_call(device, hip_stream, [&] { return check_digest_entries(dev_dst ? &dev_dst : nullptr, &dev_src, &n, 1, dev_result); },
+                      [&](hipStream_t st) { return digest_impl(dev_dst ? &dev_dst : nullptr, &dev_src, &n, &stream_off, 1, key, dev_result, st); });
 }
 
 int modgpu_digest_batch_device(void *const *dst_parts, const void *const *src_parts, const uint64_t *sizes, const uint64_t *stream_offs,
                                int n_parts, int32_t key, modgpu_digest_result_t *dev_results, int device, void *hip_stream)
 {
-    return guarded([&]() -> int {
-        if (int rc = check_digest_entries(dst_parts, src_parts, sizes, n_parts, dev_results)) return rc;
-        DeviceScope scope(device);
-        if (scope.rc) return scope.rc;
-        return digest_impl(dst_parts, src_parts, sizes, stream_offs, n_parts, key, dev_results, static_cast<hipStream_t>(hip_stream));
-    });
+    return entry_call(device, hip_stream, [&] { return check_digest_entries(dst_parts, src_parts, sizes, n_parts, dev_results); },
+                      [&](hipStream_t st) { return digest_impl(dst_parts, src_parts, sizes, stream_offs, n_parts, key, dev_results, st); });
 }
 
 uint32_t modgpu_digest_adler32(const modgpu_digest_result_t *host_result)

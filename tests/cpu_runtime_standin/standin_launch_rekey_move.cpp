@@ -4,25 +4,15 @@
 // GIVES: ascending when the destination lies below the source, descending when above.  A plan with the wrong direction therefore
 // gives wrong bytes here as it would on the device.  The plan is checked on the way: one entry, lead 0, no edges, a chunk-aligned
 // destination, a whole number of words, and a dependence window that is the one the shift implies and looks at lower positions only.
-#include <hip/hip_runtime.h>
-
-#include <atomic>
-
 #include "../../modulate_amd/csrc/cycle_rekey_kernel.h"
-#include "../../modulate_amd/csrc/lcg.h"
+#include "standin_entry.h"
 
 namespace {
+namespace E = standin_entry;
 std::atomic<unsigned long long> g_move_launches[2] = {}, g_move_plan_errors{0};
 
-struct MoveLaunch {
-    CycleRekeyArgs a;
-    int form;
-};
-
-void run_move(void *arg)
+void run_move(CycleRekeyArgs &b, int form)
 {
-    MoveLaunch *l = static_cast<MoveLaunch *>(arg);
-    CycleRekeyArgs &b = l->a;
     const CycleRekeyPart &P = b.part[0];
     const int64_t chunk = modgpu_rekey_chunk_bytes();
     const uint64_t total = (P.end + chunk - 1) / chunk;
@@ -32,7 +22,7 @@ void run_move(void *arg)
     bad += b.start[0] != 0;
     for (int p = 1; p <= kCycleBatchMax; ++p) bad += b.start[p] != total;
     bad += !b.move_flags || !b.move_status || b.queue_done != nullptr || D == S || (b.move_down != 0) != (D > S);
-    bad += (l->form == CYCLE_REKEY_FUNNEL) != (((S - D) & 3) != 0);
+    bad += (form == CYCLE_REKEY_FUNNEL) != (((S - D) & 3) != 0);
     // the window from the addresses themselves: chunk c + m reads the dwords of the source that hold its bytes
     {
         const int64_t delta = (int64_t)(S - D);
@@ -48,8 +38,7 @@ void run_move(void *arg)
         }
         bad += count != (int64_t)b.move_win_n || (count && lo != b.move_win_lo);
     }
-    uint32_t expect = 0;
-    if (!std::atomic_ref<uint32_t>(b.queue[0]).compare_exchange_strong(expect, 1u)) ++bad; // the pair is the workspace's own: always clean
+    bad += !E::take_pair(b); // the pair is the workspace's own: always clean
     if (!bad) {
         uint32_t sa = P.base_body[0], sb = P.base_body[1];
         if (!b.move_down) {
@@ -72,9 +61,8 @@ void run_move(void *arg)
         for (uint64_t c = 0; c < total; ++c) b.move_flags[c] = 1u;
     }
     g_move_plan_errors.fetch_add(bad);
-    std::atomic_ref<uint32_t>(b.queue[0]).store(0u);
-    g_move_launches[l->form == CYCLE_REKEY_FUNNEL ? 1 : 0].fetch_add(1);
-    delete l;
+    E::sign_off_pair(b); // (the workspace's pair has no sign-off word: a plan that carries one counted as an error above)
+    g_move_launches[form == CYCLE_REKEY_FUNNEL ? 1 : 0].fetch_add(1);
 }
 } // namespace
 
@@ -82,8 +70,7 @@ hipError_t modgpu_launch_cycle_rekey_move(const CycleRekeyArgs &a, int form, uin
 {
     if (*grid > 256u) *grid = 256u; // what the stand-in's device "holds at once"
     if (*grid == 0) *grid = 1;
-    shim::enqueue(stream, run_move, new MoveLaunch{a, form});
-    return hipSuccess;
+    return E::enqueue<CycleRekeyArgs, run_move>(a, form, stream);
 }
 
 extern "C" unsigned long long modgpu_shim_move_launches(int form) { return form == 0 || form == 1 ? g_move_launches[form].load() : 0; }

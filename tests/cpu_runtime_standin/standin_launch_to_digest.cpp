@@ -4,20 +4,12 @@
 // states, the store mask and the record pointers), what the kernel would do -- byte by byte with lcg.h.  It reads every source byte,
 // writes a destination only where the store mask says so, and ADDS onto the records (the host zeroed them in stream order), so the
 // sanitizer runs see every byte the plan says the kernel touches.  No ticket pair: the plan must not carry one.
-#include <hip/hip_runtime.h>
-
-#include <atomic>
-
 #include "../../modulate_amd/csrc/cycle_to_kernel.h"
-#include "../../modulate_amd/csrc/lcg.h"
+#include "standin_entry.h"
 
 namespace {
+namespace E = standin_entry;
 std::atomic<unsigned long long> g_digest_launches[2] = {}, g_digest_plan_errors{0}, g_digest_stored{0};
-
-struct DigestLaunch {
-    CycleToArgs a;
-    int form;
-};
 
 // out[i] = src[i] ^ keystream (state = canonical state of src[0]; identity: out = src), stored if `dst`, summed with byte i weighing j0 + i
 void span_digest(uint8_t *dst, const uint8_t *src, uint64_t n, uint32_t state, bool identity, uint64_t j0, uint64_t &s1, uint64_t &s2)
@@ -31,46 +23,31 @@ void span_digest(uint8_t *dst, const uint8_t *src, uint64_t n, uint32_t state, b
     }
 }
 
-void run_digest(void *arg)
+void run_digest(CycleToArgs &b, int form)
 {
-    DigestLaunch *l = static_cast<DigestLaunch *>(arg);
-    const CycleToArgs &b = l->a;
-    const uint64_t chunk = modgpu_to_chunk_bytes();
     const bool identity = (b.digest & CYCLE_TO_DIGEST_IDENTITY) != 0;
     if (!(b.digest & CYCLE_TO_DIGEST_ON) || b.queue || b.queue_done || b.n_parts < 1 || b.n_parts > (uint32_t)kCycleBatchMax || (b.store_mask >> b.n_parts) != 0)
         g_digest_plan_errors.fetch_add(1);
-    uint64_t total = 0;
-    for (uint32_t p = 0; p < b.n_parts; ++p) {
-        const CycleToPart &P = b.part[p];
+    g_digest_plan_errors.fetch_add(E::for_parts(b, [](const CycleToPart &P) { return P.dst_body; }, [&](uint32_t p, const CycleToPart &P, const E::Geom &g) {
         const bool store = ((b.store_mask >> p) & 1u) != 0;
-        const uint64_t body_bytes = P.end - P.lead, n_chunks = (P.end + chunk - 1) / chunk, first = P.lead != 0 ? 1 : 0;
-        if (b.start[p] != total || (reinterpret_cast<uintptr_t>(P.dst_body) & (chunk - 1)) != P.lead || (body_bytes != 0 && (reinterpret_cast<uintptr_t>(P.dst_body) & 15) != 0) || // (an entry that ends before its first aligned byte has no body)
-            !b.result[p] || (reinterpret_cast<uintptr_t>(b.result[p]) & 7) != 0 || (!store && P.dst_body != P.src_body))
-            g_digest_plan_errors.fetch_add(1);
-        total += n_chunks > first ? n_chunks - first : 0;
+        const unsigned bad = !b.result[p] || (E::at(b.result[p]) & 7) != 0 || (!store && P.dst_body != P.src_body);
         uint64_t s1 = 0, s2 = 0;
-        uint8_t *const d = store ? P.dst_body : nullptr;
-        span_digest(d ? d - P.head_n : nullptr, P.src_body - P.head_n, P.head_n, P.base_head, identity, 0, s1, s2);
-        span_digest(d, P.src_body, body_bytes, identity ? 0u : lcg::mulmod(P.base_body, lcg::powmod(lcg::A, P.lead)), identity, P.head_n, s1, s2);
-        span_digest(d ? d + body_bytes : nullptr, P.src_body + body_bytes, P.tail_n, P.base_tail, identity, P.head_n + body_bytes, s1, s2);
+        E::for_spans(P, !identity, [&](int64_t at, uint64_t n, uint64_t j0, E::States st) { span_digest(store ? P.dst_body + at : nullptr, P.src_body + at, n, st.s[0], identity, j0, s1, s2); });
         if (store) g_digest_stored.fetch_add(1);
         std::atomic_ref<unsigned long long>(b.result[p]->s1).fetch_add(s1 % kDigestMod);
         std::atomic_ref<unsigned long long>(b.result[p]->s2).fetch_add(s2);
-        std::atomic_ref<unsigned long long>(b.result[p]->n).fetch_add(P.head_n + body_bytes + P.tail_n);
-    }
-    for (uint32_t p = b.n_parts; p <= (uint32_t)kCycleBatchMax; ++p)
-        if (b.start[p] != total) g_digest_plan_errors.fetch_add(1);
-    g_digest_launches[l->form == CYCLE_TO_FUNNEL ? 1 : 0].fetch_add(1);
-    delete l;
+        std::atomic_ref<unsigned long long>(b.result[p]->n).fetch_add(P.head_n + g.body_bytes + P.tail_n);
+        return bad;
+    }));
+    g_digest_launches[form == CYCLE_TO_FUNNEL ? 1 : 0].fetch_add(1);
 }
 } // namespace
 
 hipError_t modgpu_launch_cycle_to_digest(const CycleToArgs &a, int form, uint32_t, hipStream_t stream)
 {
-    DigestLaunch *l = new DigestLaunch{a, form};
-    l->a.digest |= CYCLE_TO_DIGEST_ON;
-    shim::enqueue(stream, run_digest, l);
-    return hipSuccess;
+    CycleToArgs on = a;
+    on.digest |= CYCLE_TO_DIGEST_ON;
+    return E::enqueue<CycleToArgs, run_digest>(on, form, stream);
 }
 
 extern "C" unsigned long long modgpu_shim_digest_launches(int form) { return form == 0 || form == 1 ? g_digest_launches[form].load() : 0; }

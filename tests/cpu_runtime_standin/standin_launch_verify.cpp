@@ -4,22 +4,13 @@
 // with lcg.h.  It READS both sides where the plan says the kernel reads them and writes only the result, adding the count and taking
 // the minimum of the position as the kernel's atomics do, so the host planning (edges, cut chunk, batch splitting, the order of the
 // initialising launch and the compare launches) is checked on the CPU, and the sanitizer runs see every byte the plan touches.
-#include <hip/hip_runtime.h>
-
-#include <atomic>
-#include <chrono>
-#include <thread>
-
 #include "../../modulate_amd/csrc/cycle_verify_kernel.h"
-#include "../../modulate_amd/csrc/lcg.h"
+#include "standin_entry.h"
 
 namespace {
+namespace E = standin_entry;
 std::atomic<unsigned long long> g_verify_launches[4] = {}, g_verify_inits{0}, g_verify_plan_errors{0};
 
-struct VerifyLaunch {
-    CycleVerifyArgs a;
-    int form;
-};
 struct VerifyInit {
     CycleVerifyResult *results;
     uint64_t count;
@@ -47,39 +38,23 @@ void run_verify_init(void *arg)
     delete l;
 }
 
-void run_verify(void *arg)
+void run_verify(CycleVerifyArgs &b, int form)
 {
-    VerifyLaunch *l = static_cast<VerifyLaunch *>(arg);
-    const CycleVerifyArgs &b = l->a;
-    const bool keyed = !(l->form & CYCLE_VERIFY_IDENTITY);
-    std::this_thread::sleep_for(std::chrono::microseconds(200)); // a launch lasts a while: overlaps become likely
-    const uint64_t chunk = modgpu_verify_chunk_bytes();
-    uint64_t total = 0;
-    for (uint32_t p = 0; p < b.n_parts; ++p) {
-        const CycleVerifyPart &P = b.part[p];
-        const uint64_t body_bytes = P.end - P.lead, n_chunks = (P.end + chunk - 1) / chunk, first = P.lead != 0 ? 1 : 0;
-        // (an entry shorter than its head has an empty body wherever the head ends)
-        if (b.start[p] != total || (reinterpret_cast<uintptr_t>(P.expect_body) & (chunk - 1)) != P.lead ||
-            (body_bytes && (reinterpret_cast<uintptr_t>(P.expect_body) & 15) != 0) || P.head_n + body_bytes + P.tail_n != P.n || n_chunks >= (1u << 24))
-            g_verify_plan_errors.fetch_add(1);
-        const bool funnel = body_bytes && ((reinterpret_cast<uintptr_t>(P.src_body) - reinterpret_cast<uintptr_t>(P.expect_body)) & 3) != 0;
-        if (funnel && !(l->form & CYCLE_VERIFY_FUNNEL)) g_verify_plan_errors.fetch_add(1); // the plain form reads whole dwords
-        total += n_chunks > first ? n_chunks - first : 0;
-        const uint32_t fwd = keyed ? lcg::powmod(lcg::A, P.lead) : 1u;
+    const bool keyed = !(form & CYCLE_VERIFY_IDENTITY);
+    E::last_a_while();
+    g_verify_plan_errors.fetch_add(E::for_parts(b, [](const CycleVerifyPart &P) { return P.expect_body; }, [&](uint32_t, const CycleVerifyPart &P, const E::Geom &g) {
+        unsigned bad = P.head_n + g.body_bytes + P.tail_n != P.n || g.n_chunks >= (1u << 24);
+        bad += E::needs_funnel(P.expect_body, P.src_body, g.body_bytes) && !(form & CYCLE_VERIFY_FUNNEL);
         unsigned long long count = 0, lowest = kVerifyNone;
-        span_verify(P.expect_body - P.head_n, P.src_body - P.head_n, P.head_n, P.base_head, keyed, 0, count, lowest);
-        span_verify(P.expect_body, P.src_body, body_bytes, keyed ? lcg::mulmod(P.base_body, fwd) : 0u, keyed, P.head_n, count, lowest);
-        span_verify(P.expect_body + body_bytes, P.src_body + body_bytes, P.tail_n, P.base_tail, keyed, P.head_n + body_bytes, count, lowest);
+        E::for_spans(P, keyed, [&](int64_t at, uint64_t n, uint64_t j0, E::States st) { span_verify(P.expect_body + at, P.src_body + at, n, st.s[0], keyed, j0, count, lowest); });
         // as the kernel: n stored, count added, position folded in with a minimum -- on a result the init launch has made clean
-        if (P.result->mismatches != 0 || P.result->first_mismatch != kVerifyNone || P.result->reserved != 0) g_verify_plan_errors.fetch_add(1);
+        bad += P.result->mismatches != 0 || P.result->first_mismatch != kVerifyNone || P.result->reserved != 0;
         P.result->n = P.n;
         P.result->mismatches += count;
         if (lowest < P.result->first_mismatch) P.result->first_mismatch = lowest;
-    }
-    for (uint32_t p = b.n_parts; p <= (uint32_t)kCycleBatchMax; ++p)
-        if (b.start[p] != total) g_verify_plan_errors.fetch_add(1);
-    g_verify_launches[l->form & 3].fetch_add(1);
-    delete l;
+        return bad;
+    }));
+    g_verify_launches[form & 3].fetch_add(1);
 }
 } // namespace
 
@@ -95,11 +70,7 @@ hipError_t modgpu_launch_verify_init(CycleVerifyResult *results, uint64_t count,
     shim::enqueue(stream, run_verify_init, new VerifyInit{results, count});
     return hipSuccess;
 }
-hipError_t modgpu_launch_cycle_verify(const CycleVerifyArgs &a, int form, uint32_t, hipStream_t stream)
-{
-    shim::enqueue(stream, run_verify, new VerifyLaunch{a, form});
-    return hipSuccess;
-}
+hipError_t modgpu_launch_cycle_verify(const CycleVerifyArgs &a, int form, uint32_t, hipStream_t stream) { return E::enqueue<CycleVerifyArgs, run_verify>(a, form, stream); }
 
 extern "C" unsigned long long modgpu_shim_verify_launches(int form) { return form >= 0 && form < 4 ? g_verify_launches[form].load() : 0; }
 extern "C" unsigned long long modgpu_shim_verify_inits(void) { return g_verify_inits.load(); }
