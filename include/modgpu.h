@@ -616,6 +616,43 @@ uint64_t modgpu_digest_table_workspace_bytes(uint64_t n_entries);
 int modgpu_digest_table_device(const modgpu_table_entry_t *dev_entries, uint64_t n_entries, modgpu_digest_result_t *dev_results,
                                void *dev_workspace, uint64_t workspace_bytes, int device, void *hip_stream);
 
+/* ---- CYCLE DIGEST TABLE: modgpu_cycle_table_device and one digest record per entry, in the same pass and the same three launches -------
+ * "Decrypt the 100 000 files of this part and tell me that they are the files that were packed", or "encrypt them and give me one
+ * plaintext checksum per file": the source is read once (2n bytes of traffic, where modgpu_cycle_table_device followed by
+ * modgpu_digest_table_device moves 3n).  Per entry
+ *   * `dst` receives, byte for byte, what modgpu_cycle_table_device writes for the same table -- and nothing next to it is touched;
+ *   * dev_records[i] receives {s1, s2, n, 0} as modgpu_digest_device defines it (only the residues mod 65521 of s1 and s2 specified),
+ *     of one side of the XOR: */
+#define MODGPU_DIGEST_OUTPUT 0u /* records are of out[j] = src[j] ^ ks(key)[stream_off + j]: what is stored */
+#define MODGPU_DIGEST_INPUT 1u  /* records are of src[j] as read: what the cipher was applied to */
+/* The ciphertext's checksum depends on the stream offset, so a packer asks for MODGPU_DIGEST_INPUT (the plaintext it read), an
+ * extractor for MODGPU_DIGEST_OUTPUT (the plaintext it wrote).  Records are read back and closed with modgpu_digest_results /
+ * modgpu_digest_adler32.  An empty entry gives {0, 0, 0, 0}; a key == 0 mod 2^31-1 is a copy with a checksum; dst == src cycles in
+ * place, and with MODGPU_DIGEST_INPUT the record is then of the bytes as they were before the call.  The bytes of workspace a call
+ * over n_entries needs (0 for none, or above MODGPU_TABLE_MAX_ENTRIES) -- modgpu_table_workspace_bytes(n_entries), the same layout: */
+uint64_t modgpu_cycle_digest_table_workspace_bytes(uint64_t n_entries);
+
+/* The contract is modgpu_cycle_table_device's for the data and modgpu_digest_table_device's for the records, word for word where each
+ * applies: THREE launches (plan, finish, stream) whatever the count -- path_stats().gpu_launches counts 3, modgpu_last_launch reports
+ * the stream launch as variant 18 with `bytes` = 0 and modgpu_table_kernel_source_hash() --; asynchronous on `hip_stream`,
+ * allocation-free, capturable into a hipGraph; the table is read when the call RUNS on the device, so a replay picks up rewritten
+ * entries; the workspace (8-byte aligned device memory of `device`) is the caller's, reset by the plan launch in stream order, and two
+ * calls on one workspace must not overlap in time.  modgpu_table_status reports this call too.
+ *   * dev_records: n_entries records in device memory of `device`, 8-byte aligned, the caller's.  THE CALL INITIALISES THEM ITSELF, AND
+ *     WITHOUT A MEMSET NODE: the finish launch stores every entry's record whole (the sums of the < 16 ragged bytes at either end of
+ *     the entry, and n), the stream launch then only adds to valid records (non-returning 64-bit atomic adds).  A replayed graph
+ *     starts clean.
+ *   * Tier 1 (host, MODGPU_ERR_INVALID before anything is queued): modgpu_digest_table_device's tier 1 with this call's workspace
+ *     size, and a `side` that is neither of the two constants (refused whatever n_entries is).  n_entries == 0 queues nothing.
+ *   * Tier 2 (device, by the plan launch): modgpu_cycle_table_device's -- a NULL dst or src with n > 0 (a NULL dst is a refusal here:
+ *     modgpu_digest_table_device is the call that only reads), nonzero flags, an entry of 1 TiB or more, more than 2^31 chunks of
+ *     64 KiB together.  Any of these makes the whole call write NOTHING AT ALL -- no byte of any destination and no record -- and
+ *     modgpu_table_status names the lowest such entry.
+ *   * Tier 3: overlaps follow modgpu_cycle_table_device's rule (modgpu_table_validate checks it on a host copy), unchecked on the
+ *     device.  Records that overlap an entry's range are the caller's error. */
+int modgpu_cycle_digest_table_device(const modgpu_table_entry_t *dev_entries, uint64_t n_entries, modgpu_digest_result_t *dev_records,
+                                     uint32_t side, void *dev_workspace, uint64_t workspace_bytes, int device, void *hip_stream);
+
 /* Replaces CEncryptionCycler::Cycle (CEncryptionCycler.cpp:4-14) for a caller-owned HOST buffer,
  * on the GPU.  Pageable memory is staged through page-locked slots owned by this library (memcpy ->
  * slot -> kernel across PCIe on the slot -> memcpy back, chunked over several host threads and

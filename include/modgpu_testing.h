@@ -65,6 +65,10 @@ int modgpu_time_verify_rekey_table_device(const void *dev_entries, uint64_t n_en
  * records array. */
 int modgpu_time_digest_table_device(const void *dev_entries, uint64_t n_entries, void *dev_results, void *dev_workspace,
                                     uint64_t workspace_bytes, int device, void *hip_stream, int iters, float *ms_per_call);
+/* The same for modgpu_cycle_digest_table_device: `iters` back-to-back cycle digest table calls (three launches each) on one workspace
+ * and one records array, `side` as the call's. */
+int modgpu_time_cycle_digest_table_device(const void *dev_entries, uint64_t n_entries, void *dev_records, uint32_t side, void *dev_workspace,
+                                          uint64_t workspace_bytes, int device, void *hip_stream, int iters, float *ms_per_call);
 
 /* The launch the calling thread made last (any entry point), as the library planned it. */
 typedef struct modgpu_launch_info {
@@ -92,7 +96,9 @@ typedef struct modgpu_launch_info {
                              16 = the digest loop of the out-of-place kernel (modgpu_digest_device / _batch_device; `bytes` = all
                                   entries of the launch; `source_hash` = modgpu_to_kernel_source_hash()),
                              17 = the digest table call's stream launch (modgpu_digest_table_device: the verify table call's stream
-                                  kernel in its digest loop; `bytes` = 0, as for 8) */
+                                  kernel in its digest loop; `bytes` = 0, as for 8),
+                             18 = the cycle digest table call's stream launch (modgpu_cycle_digest_table_device: the table call's
+                                  stream kernel in its digesting loop; `bytes` = 0, as for 8) */
     uint32_t grid;        /* workgroups launched                                                  */
     uint32_t block;       /* threads per workgroup                                                */
     uint32_t chunk_bytes; /* bytes one workgroup trip covers                                      */
@@ -112,7 +118,8 @@ typedef struct modgpu_launch_info {
                                 modgpu_rekey_verify_table_kernel_source_hash() for variant 13,
                                 modgpu_rekey_move_table_kernel_source_hash() for variant 15,
                                 modgpu_to_kernel_source_hash() for variant 16,
-                                modgpu_verify_table_kernel_source_hash() for variant 17; static storage */
+                                modgpu_verify_table_kernel_source_hash() for variant 17,
+                                modgpu_table_kernel_source_hash() for variant 18; static storage */
 } modgpu_launch_info_t;
 int modgpu_last_launch(modgpu_launch_info_t *out);
 
@@ -284,6 +291,11 @@ void modgpu_debug_set_rekey_verify_table_grid(uint32_t grid);
  * Measurement (tools/bench_digest_table.py) and parity tests of small grids, where one workgroup passes several entries and a wave
  * folds its sums at every change of entry.  Any grid gives the same residues. */
 void modgpu_debug_set_digest_table_grid(uint32_t grid);
+
+/* The cycle digest table call's stream launch: `grid` workgroups (1..4096), 0 = the shipped grid (one workgroup per CU: faster than the
+ * out-of-place table call's 25 per 32 CUs at 4 GiB).  Measurement (tools/bench_cycle_digest_table.py) and parity tests of small grids, where one
+ * workgroup passes several entries and folds its sums at every change of entry.  Any grid gives the same bytes and the same residues. */
+void modgpu_debug_set_cycle_digest_table_grid(uint32_t grid);
 
 /* The resident slice of a single in-place buffer's work-queue launch: every such launch of `min_bytes` bytes or more takes the keep
  * kernel with exactly this `mask` (a power of two minus one) and `run` (run = 0: no chunk is kept; mask = 0, run = 1: every chunk),

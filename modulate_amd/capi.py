@@ -102,6 +102,8 @@ EXPORTS = {
                                           _vp, _int, _vp]),
     "modgpu_digest_table_workspace_bytes": (_u64, [_u64]),
     "modgpu_digest_table_device": (_int, [_vp, _u64, _vp, _vp, _u64, _int, _vp]),
+    "modgpu_cycle_digest_table_workspace_bytes": (_u64, [_u64]),
+    "modgpu_cycle_digest_table_device": (_int, [_vp, _u64, _vp, ctypes.c_uint32, _vp, _u64, _int, _vp]),
     "modgpu_digest_results": (_int, [_vp, _u64, _int, _vp, ctypes.POINTER(ctypes.c_uint32)]),
     "modgpu_digest_adler32": (ctypes.c_uint32, [_vp]),
 }
@@ -132,6 +134,7 @@ assert REKEY_TABLE_DTYPE.itemsize == ctypes.sizeof(RekeyTableEntry) == 56
 VERIFY_RESULT_DTYPE = np.dtype([("mismatches", "<u8"), ("first_mismatch", "<u8"), ("n", "<u8"), ("reserved", "<u8")])
 VERIFY_NONE = 0xFFFFFFFFFFFFFFFF  # first_mismatch of a clean entry
 # modgpu_digest_result_t (include/modgpu.h): 32 bytes; only the residues mod 65521 of s1 and s2 are specified
+DIGEST_OUTPUT, DIGEST_INPUT = 0, 1  # MODGPU_DIGEST_OUTPUT / _INPUT: which side of the XOR a cycle digest table call's records are of
 DIGEST_RESULT_DTYPE = np.dtype([("s1", "<u8"), ("s2", "<u8"), ("n", "<u8"), ("reserved", "<u8")])
 # modgpu_verify_table_summary_t (include/modgpu.h): 32 bytes
 VERIFY_TABLE_SUMMARY_DTYPE = np.dtype([("mismatches", "<u8"), ("first_bad_entry", "<u8"), ("entries", "<u8"), ("reserved", "<u8")])
@@ -192,6 +195,7 @@ TESTING_EXPORTS = {
     "modgpu_time_verify_table_device": (_int, [_vp, _u64, _vp, _vp, _u64, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
     "modgpu_verify_table_kernel_source_hash": (ctypes.c_char_p, []),
     "modgpu_time_digest_table_device": (_int, [_vp, _u64, _vp, _vp, _u64, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
+    "modgpu_time_cycle_digest_table_device": (_int, [_vp, _u64, _vp, ctypes.c_uint32, _vp, _u64, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
     "modgpu_time_verify_rekey_device": (_int, [_vp, _vp, _u64, _i32, _u64, _i32, _u64, _vp, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
     "modgpu_rekey_verify_kernel_source_hash": (ctypes.c_char_p, []),
     "modgpu_keep_kernel_source_hash": (ctypes.c_char_p, []),
@@ -228,6 +232,7 @@ DEBUG_EXPORTS = {
     "modgpu_debug_set_verify_table_grid": (None, [ctypes.c_uint32]),
     "modgpu_debug_set_rekey_verify_table_grid": (None, [ctypes.c_uint32]),
     "modgpu_debug_set_digest_table_grid": (None, [ctypes.c_uint32]),
+    "modgpu_debug_set_cycle_digest_table_grid": (None, [ctypes.c_uint32]),
     "modgpu_debug_set_keep": (None, [_u64, ctypes.c_uint32, ctypes.c_uint32]),
     "modgpu_debug_set_digest_grid": (None, [_int]),
 }
@@ -1350,6 +1355,58 @@ def debug_set_digest_table_grid(grid=0):
     _debug_lib().modgpu_debug_set_digest_table_grid(grid)
 
 
+def cycle_digest_table_workspace_bytes(n_entries):
+    """bytes of device workspace a cycle digest table call over n_entries needs (0 for none, or above the limit): table_workspace_bytes(n)"""
+    return lib().modgpu_cycle_digest_table_workspace_bytes(n_entries)
+
+
+def cycle_digest_table_device(entries, records=None, side=DIGEST_OUTPUT, workspace=None, device=-1, stream=None, *, n=None):
+    """Cycles a TABLE of out-of-place entries as cycle_table_device does AND digests every entry in the same pass, three launches
+    whatever the length: record i is of what was stored (side=DIGEST_OUTPUT) or of the source bytes as read (DIGEST_INPUT).  `entries`
+    is a host table (a TABLE_DTYPE array: uploaded) or a table already in device memory (a DeviceBuffer or an address; then n, the
+    entry count, is needed).  `records` is a DeviceBuffer or address of 32 * n bytes, `workspace` one of at least
+    cycle_digest_table_workspace_bytes(n) bytes; None makes one.  When this function made a buffer itself it waits for the call, raises
+    ModGpuError if the device refused an entry (nothing was written, no byte and no record) and returns (the records as a
+    DIGEST_RESULT_DTYPE array, their Adler-32 values as a uint32 array); otherwise the call is asynchronous on `stream`, returns None,
+    and table_status(workspace) and digest_results(records, n) tell the outcome after a synchronise."""
+    own = []
+    try:
+        addr, n, t = _table_arg(entries, TABLE_DTYPE, n, device, own)
+        if t is not None and t.size == 0:
+            return np.zeros(0, dtype=DIGEST_RESULT_DTYPE), np.zeros(0, dtype=np.uint32)
+        if records is None and n:
+            records = DeviceBuffer(n * DIGEST_RESULT_DTYPE.itemsize, device)
+            own.append(records)
+        ws, ws_bytes = _workspace_arg(workspace, n, lambda: cycle_digest_table_workspace_bytes(n), device, own)
+        rec = _dev_addr(records) if records is not None else 0
+        _check(lib().modgpu_cycle_digest_table_device(_vp(addr), n, _vp(rec), side, _vp(ws), ws_bytes, device, _vp(stream or 0)))
+        if not own:
+            return None
+        _check(lib().modgpu_sync(device, _vp(stream or 0)))
+        bad = table_status(ws, device) if n else None
+        if bad is not None:
+            raise ModGpuError(1, f"the device refused cycle digest table entry {bad}; nothing was written")
+        return digest_results(rec, n, device)
+    finally:
+        for b in own:
+            b.free()
+
+
+def time_cycle_digest_table_device(entries, n, records, workspace, side=DIGEST_OUTPUT, device=-1, stream=None, iters=2):
+    """Mean ms per cycle digest table call (three launches) over `iters` calls, HIP events on the launch stream; table, records and
+    workspace resident."""
+    ms = ctypes.c_float(0)
+    ws_bytes = workspace.nbytes if isinstance(workspace, DeviceBuffer) else cycle_digest_table_workspace_bytes(n)
+    _check(lib().modgpu_time_cycle_digest_table_device(_vp(_dev_addr(entries)), n, _vp(_dev_addr(records)), side, _vp(_dev_addr(workspace)), ws_bytes,
+                                                       device, _vp(stream or 0), iters, ctypes.byref(ms)))
+    return ms.value
+
+
+def debug_set_cycle_digest_table_grid(grid=0):
+    """Testing flavour: the cycle digest table call's stream grid (0 = shipped).  Every grid gives the same bytes and residues."""
+    _debug_lib().modgpu_debug_set_cycle_digest_table_grid(grid)
+
+
 def verify_rekey_table_workspace_bytes(n_entries):
     """bytes of device workspace a rekey verify table call over n_entries needs (0 for none, or above the limit)"""
     return lib().modgpu_verify_rekey_table_workspace_bytes(n_entries)
@@ -1526,6 +1583,22 @@ class DeviceBuffer:
         for i, (o, n) in enumerate(ranges):
             t[i]["src"], t[i]["n"], t[i]["stream_off"], t[i]["key"] = self.ptr + o, n, part_off + o, as_int32(key)
         return digest_table_device(t, None, workspace, self.device, stream)[1]
+
+    def extract(self, ranges, key, out, part_off=0, side=DIGEST_OUTPUT, workspace=None, stream=None):
+        """Cycles every range of `ranges` -- a list of (offset, n) -- of the part this buffer holds, each from stream offset part_off +
+        offset, into `out` (another DeviceBuffer), packed end to end from offset 0, and returns one Adler-32 per range -- of what was
+        stored, or with side=DIGEST_INPUT of what was read -- as a uint32 array: one cycle_digest_table_device call.  With `out is self`
+        each range is cycled in place."""
+        ranges = [(int(o), int(n)) for o, n in ranges]
+        assert all(o >= 0 and n >= 0 and o + n <= self.nbytes for o, n in ranges)
+        assert out is self or (out.device == self.device and sum(n for _, n in ranges) <= out.nbytes)
+        t = table(len(ranges))
+        at = 0
+        for i, (o, n) in enumerate(ranges):
+            t[i]["dst"], t[i]["src"] = (self.ptr + o if out is self else out.ptr + at), self.ptr + o
+            t[i]["n"], t[i]["stream_off"], t[i]["key"] = n, part_off + o, as_int32(key)
+            at += n
+        return cycle_digest_table_device(t, None, side, workspace, self.device, stream)[1]
 
     def move(self, dst_offset, src_offset, n, key_from=0, key_to=0, off_from=0, off_to=0, workspace=None, stream=None):
         """Moves n bytes inside the buffer from src_offset to dst_offset, the ranges overlapping in any way (memmove rules), rekeying

@@ -452,6 +452,39 @@ def digest_table_loop(k):
     return bad
 
 
+def cycle_digest_table_loop(k):
+    """the out-of-place table kernel's second loop (cycle_table_kernel.h: CYCLE_TABLE_DIGEST, one uniform branch apart from the plain
+    loop).  It cycles as the plain loop does and sums what it stores, or what it read: the sums are taken with v_dot4_u32_u8; every
+    64-bit atomic of the kernel is a non-returning add (the pair per unrolled trip that goes onto the entry's record: 4; the loop would
+    wait for a value that came back); the fold that precedes them goes through LDS (ds_add_u32) and not through memory; both loops
+    draw one plain returning 32-bit ticket per unrolled trip (4); and every store of the kernel is a whole word through a buffer
+    descriptor with the streaming policy -- 4 words x 2 unrolled trips in each loop, nt sc1 -- and nothing through a pointer"""
+    bad = []
+    if "v_dot4_u32_u8" not in k.fn:
+        bad.append("%s: no v_dot4_u32_u8 (the cycle digest loop's byte and position sums)" % k.name)
+    atomics = [(m.group(1), m.group(2)) for m in re.finditer(r"^\s+(global_atomic_\w+)\b([^;\n]*)", k.fn, re.M)]
+    wide = [(op, args) for op, args in atomics if op.endswith("_x2")]
+    if any(" sc0" in args for _, args in wide):
+        bad.append("%s: a 64-bit atomic returns its value (sc0): the cycle digest loop's sums are non-returning global_atomic_add_x2" % k.name)
+    if len(wide) != 4 or any(op != "global_atomic_add_x2" for op, _ in wide):
+        bad.append("%s: 64-bit atomics %s, expected 4 global_atomic_add_x2 (a pair per unrolled trip of the cycle digest loop) and nothing else"
+                   % (k.name, [op for op, _ in wide]))
+    fetches = [args for op, args in atomics if op == "global_atomic_add"]
+    if len(fetches) != 4 or not all(args.rstrip().endswith(" sc0") for args in fetches) or len(atomics) != len(wide) + len(fetches):
+        bad.append("%s: %d 32-bit global_atomic_add among %d atomics, expected the ticket fetch of each unrolled trip of both loops (4), each "
+                   "returning (sc0), and the 64-bit adds" % (k.name, len(fetches), len(atomics)))
+    if not code_lines(k.fn, "ds_add_u32"):
+        bad.append("%s: no ds_add_u32 (the cycle digest loop folds a workgroup's sums in LDS, one pair per wave)" % k.name)
+    data = code_lines(k.fn, "buffer_store_")
+    if len(data) != 16 or any(not ln.lstrip().startswith("buffer_store_dwordx4") or not ln.endswith(" nt sc1") for ln in data):
+        bad.append("%s: a store of the cycle digest loop is not nt sc1 (%d buffer stores, expected 16 whole words, all nt sc1: %s in each loop)"
+                   % (k.name, len(data), TRIPS))
+    if re.search(r"^\s+(global|flat|scratch)_store", k.fn, re.M):
+        bad.append("%s: a store through a pointer in the kernel of the cycle digest loop (records take 64-bit atomic adds, data goes through "
+                   "the destination's descriptor)" % k.name)
+    return bad
+
+
 def digest_loop(k):
     """the out-of-place kernel's second loop (cycle_to_kernel.h: the pass whose destination is a sum).  Everything it sends to memory
     besides an entry's own output is a 64-bit atomic add onto a record the host zeroed: the kernel's 64-bit atomics are
@@ -632,9 +665,11 @@ TUS = (
     TU("cycle_rekey_kernel.s", "the rekey kernel's TU",
        (Kind("modgpu_cycle_rekey_kernel", BUDGET + [rekey_blocks, (block_count, TWO_KEYSTREAM, 17, TRIPS + " in the stream and in the move loop + the cut first chunk"),
                                                    TICKET, loads_nt, (stores, "nt sc1"), move_loop]),)),
-    # table of out-of-place entries
+    # table of out-of-place entries.  The stream kernel has two loops, the plain one and the cycle digest loop (one uniform branch
+    # chooses): twice the blocks, the ticket fetches and the stores, and the second loop's pair of 64-bit adds per unrolled trip
     table_tu("cycle_table_kernel.s", "the table kernels' TU", "modgpu_cycle_table", PLANNING,
-             [keystream_blocks, (block_count, KEYSTREAM, 8, TRIPS), loads_nt, (stores, "nt sc1"), scalar_entry_search]),
+             [keystream_blocks, (block_count, KEYSTREAM, 16, TRIPS + " in the plain and in the cycle digest loop"), loads_nt, (stores, "nt sc1"),
+              cycle_digest_table_loop, scalar_entry_search]),
     # table of rekey entries
     table_tu("cycle_rekey_table_kernel.s", "the rekey table kernels' TU", "modgpu_cycle_rekey_table", REKEY_PLANNING,
              [rekey_blocks, (block_count, TWO_KEYSTREAM, 8, TRIPS), loads_nt, (stores, "nt sc1"), scalar_entry_search]),

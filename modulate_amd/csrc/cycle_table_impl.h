@@ -2,7 +2,8 @@
 // cycle_verify_table_kernel.hip, cycle_rekey_verify_table_kernel.hip, cycle_rekey_move_table_kernel.hip): the state of any stream
 // position by four byte tables, an entry laid on the chunk grid and the refusal rule, the plan launch's scan, the finish launch's totals
 // and search levels, one level of the 16-ary descent, a chunk's span, the funnel; what the two-keystream tables add (the identity kept
-// as 2^31-1, the six states of an entry); what the verifying tables add (a lane's findings).  Each of those TUs includes it and names
+// as 2^31-1, the six states of an entry); what the verifying tables add (a lane's findings); what the two digesting loops add (a word's sums, the reduction mod 65521, the wave
+// fold).  Each of those TUs includes it and names
 // it in its source list, so each keeps a hash of its own.  A TU keeps its __global__ kernels, its View, its load / store / compare /
 // move code, its edge treatment and its launch wrappers; the two verifying stream kernels also keep their per-wave flush, and the
 // descent's loop stays with its caller (two of them enter it without the test for level 0): as functions here they changed those
@@ -310,5 +311,54 @@ __device__ __forceinline__ void note_word(uint32_t &cnt, uint32_t &low, u32x4 x,
     low = pos + b < low ? pos + b : low;
 }
 __device__ __forceinline__ uint32_t any_bits(u32x4 x) { return x.x | x.y | x.z | x.w; }
+
+// ---- digesting ----------------------------------------------------------------------------------------------------------------------
+// (the verify table TU's digest loop and the out-of-place table TU's cycle digest loop; cycle_table_kernel.h: DigestTableRecord)
+// byte sum and position sum (byte i of the word weighs i) of one 16-byte word: one v_dot4_u32_u8 per dword and weight.  The five
+// weights live in VGPRs: v_dot4 takes no literal, and as hoisted scalar constants they cost the stream kernel an SGPR spill.
+struct DotWeights {
+    uint32_t ones, p0, p1, p2, p3;
+};
+__device__ __forceinline__ DotWeights dot_weights()
+{
+    DotWeights k;
+    asm("v_mov_b32 %0, 0x01010101" : "=v"(k.ones));
+    asm("v_mov_b32 %0, 0x03020100" : "=v"(k.p0));
+    asm("v_mov_b32 %0, 0x07060504" : "=v"(k.p1));
+    asm("v_mov_b32 %0, 0x0B0A0908" : "=v"(k.p2));
+    asm("v_mov_b32 %0, 0x0F0E0D0C" : "=v"(k.p3));
+    return k;
+}
+__device__ __forceinline__ void word_sums(const u32x4 &d, const DotWeights &k, uint32_t &b, uint32_t &w)
+{
+    b = __builtin_amdgcn_udot4(d.x, k.ones, 0u, false);
+    b = __builtin_amdgcn_udot4(d.y, k.ones, b, false);
+    b = __builtin_amdgcn_udot4(d.z, k.ones, b, false);
+    b = __builtin_amdgcn_udot4(d.w, k.ones, b, false);
+    w = __builtin_amdgcn_udot4(d.x, k.p0, 0u, false);
+    w = __builtin_amdgcn_udot4(d.y, k.p1, w, false);
+    w = __builtin_amdgcn_udot4(d.z, k.p2, w, false);
+    w = __builtin_amdgcn_udot4(d.w, k.p3, w, false);
+}
+// x mod 65521 for any 64-bit x, without a 64-bit division: 2^16 = 15 (mod 65521), so the four 16-bit pieces of x weigh 1, 15, 225 and
+// 3375 -- their weighted sum is below 65536 * 3616 < 2^28 and one 32-bit remainder finishes it
+__device__ __forceinline__ uint32_t digest_red(unsigned long long x)
+{
+    const uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
+    return ((lo & 0xFFFFu) + 15u * (lo >> 16) + 225u * (hi & 0xFFFFu) + 3375u * (hi >> 16)) % kDigestTableMod;
+}
+// The sum of x over the wave's 64 lanes, in lane 63 (other lanes hold partial sums): the row_shr / row_bcast DPP ladder, so that no
+// lane index is needed (v_mbcnt is what this TU's guard reads as a rewritten ticket atomic).  A lane the control leaves without a
+// source adds 0 (old = 0, bound_ctrl off).  x < 2^26 in every lane: no carry is lost.
+__device__ __forceinline__ uint32_t wave_sum_lane63(uint32_t x)
+{
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, false); // row_shr:1
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, false); // row_shr:2
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, false); // row_shr:4
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, false); // row_shr:8: lane 15 of a row has the row's sum
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false); // row_bcast:15 into rows 1 and 3
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false); // row_bcast:31 into rows 2 and 3
+    return x;
+}
 
 } // namespace

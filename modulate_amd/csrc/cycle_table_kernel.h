@@ -65,6 +65,23 @@ struct CycleTablePlan {
 };
 static_assert(sizeof(CycleTablePlan) == 64, "one s_load_dwordx16");
 
+// The record of a digesting table call (modgpu_digest_result_t): s1 = sum of byte[j], s2 = sum of j * byte[j], both in pieces, each
+// reduced mod 65521 by whoever sends it (only the residues mean anything), n, 0.  Closed on the host (modgpu_digest_adler32).
+struct DigestTableRecord {
+    unsigned long long s1, s2, n, reserved;
+};
+constexpr uint32_t kDigestTableMod = 65521u; // the largest prime below 2^16 (Adler-32)
+
+// The CYCLE DIGEST mode of the same three kernels (modgpu_cycle_digest_table_device): every entry is cycled as in the plain mode --
+// plan is the plain mode's, the grid on the DESTINATION -- and record i receives the digest of the entry's stored bytes
+// (CYCLE_TABLE_SIDE_OUTPUT) or of its source bytes as read (CYCLE_TABLE_SIDE_INPUT).  The finish launch sums the < 16 bytes at either
+// end while it cycles them and stores the record whole; the stream kernel's second loop (one uniform branch on `mode`) sums each word
+// it stores, or the funnelled word it read, and adds to the records with non-returning 64-bit atomic adds.
+enum CycleTableMode : uint32_t { CYCLE_TABLE_PLAIN = 0u, CYCLE_TABLE_DIGEST = 1u };
+enum CycleTableSide : uint32_t { CYCLE_TABLE_SIDE_OUTPUT = 0u, CYCLE_TABLE_SIDE_INPUT = 1u };
+// reporting only (modgpu_last_launch): the stream launch of a cycle digest table call
+constexpr int CYCLE_DIGEST_CYCLE_TABLE = 18;
+
 struct CycleTableArgs {
     const CycleTableEntry *entries;
     uint64_t n;
@@ -75,6 +92,9 @@ struct CycleTableArgs {
     uint64_t level_n[kTableLevels];
     uint32_t top;                  // highest level (<= 16 keys)
     uint32_t n_blk;                // ceil(n / 1024)
+    uint32_t mode;                 // CYCLE_TABLE_PLAIN (side 0, records null), or CYCLE_TABLE_DIGEST
+    uint32_t side;                 // CYCLE_TABLE_SIDE_OUTPUT / _INPUT: which side of the XOR the records are of
+    DigestTableRecord *records;    // n records in the caller's device memory: stored whole by finish, added to by stream
 };
 
 uint32_t modgpu_table_chunk_bytes();
@@ -84,3 +104,8 @@ const char *modgpu_table_kernel_name();
 hipError_t modgpu_launch_table_plan(const CycleTableArgs &a, hipStream_t stream);
 hipError_t modgpu_launch_table_finish(const CycleTableArgs &a, hipStream_t stream);
 hipError_t modgpu_launch_table_stream(const CycleTableArgs &a, uint32_t grid, hipStream_t stream);
+// The same three kernels with a.mode = CYCLE_TABLE_DIGEST (a.side and a.records are the caller's): the three launches of a cycle digest
+// table call (any grid >= 1 gives the same bytes and the same residues)
+hipError_t modgpu_launch_cycle_digest_table_plan(const CycleTableArgs &a, hipStream_t stream);
+hipError_t modgpu_launch_cycle_digest_table_finish(const CycleTableArgs &a, hipStream_t stream);
+hipError_t modgpu_launch_cycle_digest_table_stream(const CycleTableArgs &a, uint32_t grid, hipStream_t stream);

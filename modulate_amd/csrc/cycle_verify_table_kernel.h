@@ -41,10 +41,7 @@ static_assert(sizeof(VerifyTableSummary) == 64, "one line");
 // 16-byte aligned: no funnel), the finish launch sums the < 16 bytes at either end and stores the record whole, the stream kernel's
 // second loop (one uniform branch on `mode`) sums the bodies and adds to the records with non-returning 64-bit atomic adds.
 // The workspace is the table call's own (no summary line: `sum` is null).
-struct DigestTableRecord {
-    unsigned long long s1, s2, n, reserved;
-};
-constexpr uint32_t kDigestTableMod = 65521u; // the largest prime below 2^16 (Adler-32)
+// (DigestTableRecord and kDigestTableMod: cycle_table_kernel.h)
 enum VerifyTableMode : uint32_t { VERIFY_TABLE_COMPARE = 0u, VERIFY_TABLE_DIGEST = 1u };
 
 struct VerifyTableArgs {
