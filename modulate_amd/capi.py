@@ -317,6 +317,38 @@ def _check(rc):
         raise ModGpuError(rc, lib().modgpu_last_error().decode())
 
 
+def _ptr_array(xs):
+    """the void* array of a batch call: the device addresses of `xs` (addresses or DeviceBuffers; a None entry is NULL); None stays None"""
+    return (_vp * len(xs))(*[_dev_addr(x) if x is not None else 0 for x in xs]) if xs is not None else None
+
+
+def _u64_array(xs):
+    """the uint64_t array of a batch call (sizes, stream offsets); None stays None"""
+    return (_u64 * len(xs))(*xs) if xs is not None else None
+
+
+def _own_result_call(call, first, src, n, scalars, result, device, stream, fetch, needed="both sides are", first_optional=False):
+    """The single-entry calls that write one 32-byte record: library function `call` gets (first, src, n, *scalars, record, device,
+    stream).  `first` (the comparand, or the destination, which may be None if `first_optional`) and `src` are addresses or
+    DeviceBuffers, and n defaults to the smaller DeviceBuffer's size.  With result=None a record is made, the stream synchronised and
+    fetch(record, 1, device) returned (the record is freed whatever happened); otherwise the call is asynchronous and returns None."""
+    if n is None:
+        if not isinstance(src, DeviceBuffer) or not (isinstance(first, DeviceBuffer) or (first_optional and first is None)):
+            raise TypeError(f"n is needed unless {needed} DeviceBuffer")
+        n = src.nbytes if first is None else min(first.nbytes, src.nbytes)
+    own = DeviceBuffer(32, device) if result is None else None
+    try:
+        _check(getattr(lib(), call)(_vp(_dev_addr(first) if first is not None else 0), _vp(_dev_addr(src)), n, *scalars,
+                                    _vp(_dev_addr(own if own is not None else result)), device, _vp(stream or 0)))
+        if own is None:
+            return None
+        _check(lib().modgpu_sync(device, _vp(stream or 0)))
+        return fetch(own, 1, device)
+    finally:
+        if own is not None:
+            own.free()
+
+
 def _host_ptr(a):
     if not (isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.flags["C_CONTIGUOUS"] and a.flags["WRITEABLE"]):
         raise TypeError("need a writable C-contiguous uint8 ndarray")
@@ -637,11 +669,8 @@ def cycle_host_split(buf, key, stream_off=0, n_devices=0):
 def cycle_batch_device(ptrs, sizes, key, stream_offs=None, device=-1, stream=None):
     """Raw device addresses of ONE device, each its own Cycle call (from stream_offs[i] or 0); asynchronous on `stream`.
     Runs of up to 16 parts share one kernel launch when together they are beyond 256 MiB or small on average."""
-    n = len(ptrs)
-    p = (_vp * n)(*ptrs)
-    z = (_u64 * n)(*sizes)
-    o = (_u64 * n)(*stream_offs) if stream_offs is not None else None
-    _check(lib().modgpu_cycle_batch_device(p, z, o, n, as_int32(key), device, _vp(stream or 0)))
+    _check(lib().modgpu_cycle_batch_device(_ptr_array(ptrs), _u64_array(sizes), _u64_array(stream_offs), len(ptrs), as_int32(key), device,
+                                           _vp(stream or 0)))
 
 
 def cycle_file(src_path, dst_path, key, stream_off=0, device=-1):
@@ -672,10 +701,7 @@ def cycle_device(dev_ptr, n, key, stream_off=0, device=-1, stream=None):
 
 def time_cycle_device(dev_ptr, n, key, stream_off=0, device=-1, stream=None, iters=2):
     """Mean ms per launch over `iters` launches, HIP events on the launch stream."""
-    ms = ctypes.c_float(0)
-    _check(lib().modgpu_time_cycle_device(_vp(dev_ptr), n, as_int32(key), stream_off, device, _vp(stream or 0),
-                                          iters, ctypes.byref(ms)))
-    return ms.value
+    return _time_call("modgpu_time_cycle_device", (_vp(dev_ptr), n, as_int32(key), stream_off), device, stream, iters)
 
 
 def cycle_device_to(dst_ptr, src_ptr, n, key, stream_off=0, device=-1, stream=None):
@@ -689,19 +715,13 @@ def cycle_batch_device_to(dst_ptrs, src_ptrs, sizes, key, stream_offs=None, devi
     destination may meet no other entry's range.  Up to 16 non-empty entries share a launch."""
     n = len(dst_ptrs)
     assert len(src_ptrs) == n and len(sizes) == n
-    d = (_vp * n)(*dst_ptrs)
-    s = (_vp * n)(*src_ptrs)
-    z = (_u64 * n)(*sizes)
-    o = (_u64 * n)(*stream_offs) if stream_offs is not None else None
-    _check(lib().modgpu_cycle_batch_device_to(d, s, z, o, n, as_int32(key), device, _vp(stream or 0)))
+    _check(lib().modgpu_cycle_batch_device_to(_ptr_array(dst_ptrs), _ptr_array(src_ptrs), _u64_array(sizes), _u64_array(stream_offs), n,
+                                              as_int32(key), device, _vp(stream or 0)))
 
 
 def time_cycle_device_to(dst_ptr, src_ptr, n, key, stream_off=0, device=-1, stream=None, iters=2):
     """Mean ms per out-of-place launch over `iters` launches, HIP events on the launch stream."""
-    ms = ctypes.c_float(0)
-    _check(lib().modgpu_time_cycle_device_to(_vp(dst_ptr), _vp(src_ptr), n, as_int32(key), stream_off, device, _vp(stream or 0),
-                                             iters, ctypes.byref(ms)))
-    return ms.value
+    return _time_call("modgpu_time_cycle_device_to", (_vp(dst_ptr), _vp(src_ptr), n, as_int32(key), stream_off), device, stream, iters)
 
 
 def rekey_device_to(dst, src, key_from, key_to, off_from=0, off_to=0, device=-1, stream=None, *, n=None):
@@ -721,20 +741,14 @@ def rekey_batch_device_to(dst_ptrs, src_ptrs, sizes, key_from, key_to, offs_from
     may meet no other entry's range.  Up to 16 non-empty entries share a launch."""
     n = len(dst_ptrs)
     assert len(src_ptrs) == n and len(sizes) == n
-    d = (_vp * n)(*[_dev_addr(x) for x in dst_ptrs])
-    s = (_vp * n)(*[_dev_addr(x) for x in src_ptrs])
-    z = (_u64 * n)(*sizes)
-    of = (_u64 * n)(*offs_from) if offs_from is not None else None
-    ot = (_u64 * n)(*offs_to) if offs_to is not None else None
-    _check(lib().modgpu_rekey_batch_device_to(d, s, z, of, ot, n, as_int32(key_from), as_int32(key_to), device, _vp(stream or 0)))
+    _check(lib().modgpu_rekey_batch_device_to(_ptr_array(dst_ptrs), _ptr_array(src_ptrs), _u64_array(sizes), _u64_array(offs_from),
+                                              _u64_array(offs_to), n, as_int32(key_from), as_int32(key_to), device, _vp(stream or 0)))
 
 
 def time_rekey_device_to(dst, src, n, key_from, key_to, off_from=0, off_to=0, device=-1, stream=None, iters=2):
     """Mean ms per rekey launch over `iters` launches, HIP events on the launch stream."""
-    ms = ctypes.c_float(0)
-    _check(lib().modgpu_time_rekey_device_to(_vp(_dev_addr(dst)), _vp(_dev_addr(src)), n, as_int32(key_from), off_from, as_int32(key_to),
-                                             off_to, device, _vp(stream or 0), iters, ctypes.byref(ms)))
-    return ms.value
+    return _time_call("modgpu_time_rekey_device_to", (_vp(_dev_addr(dst)), _vp(_dev_addr(src)), n, as_int32(key_from), off_from, as_int32(key_to),
+                                                      off_to), device, stream, iters)
 
 
 def move_workspace_bytes(n):
@@ -817,32 +831,68 @@ def table_status(workspace, device=-1):
     return None
 
 
-def _table_arg(entries, dtype, n, device, own, validate=None, needed="n (the entry count) is", known=True):
-    """The table of a *_table_device call, as (address, n, host array or None): a host array is checked with `validate` and uploaded
-    (the buffer joins `own`; an empty one is not, and has no address: the caller returns); a table already in device memory needs n,
-    and whatever else the caller says is `known` -- its address goes to the library as it is, which refuses a NULL one."""
-    if isinstance(entries, np.ndarray):
-        t = np.ascontiguousarray(entries, dtype=dtype)
-        if validate:
-            validate(t)
-        if t.size == 0:
-            return None, 0, t
-        buf = DeviceBuffer(t.nbytes, device)
-        own.append(buf)
-        buf.upload(t.view(np.uint8))
-        return buf.ptr, t.size, t
-    if n is None or not known:
-        raise TypeError(f"{needed} needed for a table in device memory")
-    return _dev_addr(entries), n, None
+def _no_verify_results():
+    return np.zeros(0, dtype=VERIFY_RESULT_DTYPE)
 
 
-def _workspace_arg(workspace, n, need, device, own):
-    """The workspace of a *_table_device call, as (address, bytes): None makes one of need() bytes (it joins `own`)."""
-    if workspace is None and n:
-        workspace = DeviceBuffer(need(), device)
-        own.append(workspace)
-    ws = _dev_addr(workspace) if workspace is not None else 0
-    return ws, workspace.nbytes if isinstance(workspace, DeviceBuffer) else need()
+def _no_digest_results():
+    return np.zeros(0, dtype=DIGEST_RESULT_DTYPE), np.zeros(0, dtype=np.uint32)
+
+
+def _table_call(call, entries, dtype, n, workspace, need, device, stream, refused, *, validate=None, needed="n (the entry count) is",
+                known=True, extra=(), fetch=None, results=None, empty=None, status=table_status, gave_up=None):
+    """Every *_table_device call: library function `call` gets (table, n, [results], *extra, workspace, its bytes, device, stream).
+    The table `entries` is a host array of `dtype` -- checked with `validate`, uploaded; an empty one makes no call and returns
+    empty(), or None -- or is in device memory already: then n is needed, and whatever else the caller says is `known`, and its
+    address goes to the library as it is, which refuses a NULL one.  `results`, the buffer of 32-byte records, is an argument only of
+    the calls that have a `fetch` (verify_results or digest_results); None makes one, as workspace=None makes one of need(n) bytes.
+    When a buffer was made here the call is waited for, `status` is read -- table_status's one outcome, or rekey_move_table_status's
+    pair -- and ModGpuError raised with the text `refused` (code 1) or `gave_up` (code 3); then the results are fetched and returned,
+    and every buffer made here is freed, whatever happened.  Otherwise the call is asynchronous and None is returned."""
+    own = []
+    try:
+        if isinstance(entries, np.ndarray):
+            t = np.ascontiguousarray(entries, dtype=dtype)
+            if validate:
+                validate(t)
+            if t.size == 0:
+                return empty() if empty else None
+            entries, n = DeviceBuffer(t.nbytes, device), t.size
+            own.append(entries)
+            entries.upload(t.view(np.uint8))
+        elif n is None or not known:
+            raise TypeError(f"{needed} needed for a table in device memory")
+        if fetch and results is None and n:
+            results = DeviceBuffer(n * 32, device)
+            own.append(results)
+        res = _dev_addr(results) if results is not None else 0
+        if workspace is None and n:
+            workspace = DeviceBuffer(need(n), device)
+            own.append(workspace)
+        ws = _dev_addr(workspace) if workspace is not None else 0
+        ws_bytes = workspace.nbytes if isinstance(workspace, DeviceBuffer) else need(n)
+        stv = _vp(stream or 0)
+        _check(getattr(lib(), call)(_vp(_dev_addr(entries)), n, *((_vp(res),) if fetch else ()), *extra, _vp(ws), ws_bytes, device, stv))
+        if not own:
+            return None
+        _check(lib().modgpu_sync(device, stv))
+        outcome = status(ws, device)
+        bad, stalled = outcome if isinstance(outcome, tuple) else (outcome, None)
+        if bad is not None:
+            raise ModGpuError(1, refused.format(bad))
+        if stalled is not None:
+            raise ModGpuError(3, gave_up.format(stalled))
+        return fetch(res, n, device) if fetch else None
+    finally:
+        for b in own:
+            b.free()
+
+
+def _time_call(call, args, device, stream, iters):
+    """Every time_* call: library function `call` with `args`, then device, stream, iters and the float it stores its mean ms in."""
+    ms = ctypes.c_float(0)
+    _check(getattr(lib(), call)(*args, device, _vp(stream or 0), iters, ctypes.byref(ms)))
+    return ms.value
 
 
 def cycle_table_device(entries, workspace=None, device=-1, stream=None, check=True, *, n=None):
@@ -852,30 +902,14 @@ def cycle_table_device(entries, workspace=None, device=-1, stream=None, check=Tr
     or address of at least table_workspace_bytes(n) bytes; None makes one.  When this function made a buffer itself (an uploaded
     table, a workspace) it waits for the call before freeing it and raises ModGpuError if the device refused an entry; otherwise the
     call is asynchronous on `stream` and table_status(workspace) tells the outcome after a synchronise."""
-    own = []
-    try:
-        addr, n, t = _table_arg(entries, TABLE_DTYPE, n, device, own, table_validate if check else None)
-        if t is not None and t.size == 0:
-            return
-        ws, ws_bytes = _workspace_arg(workspace, n, lambda: table_workspace_bytes(n), device, own)
-        _check(lib().modgpu_cycle_table_device(_vp(addr), n, _vp(ws), ws_bytes, device, _vp(stream or 0)))
-        if own:
-            _check(lib().modgpu_sync(device, _vp(stream or 0)))
-            bad = table_status(ws, device)
-            if bad is not None:
-                raise ModGpuError(1, f"the device refused table entry {bad}; nothing was written")
-    finally:
-        for b in own:
-            b.free()
+    _table_call("modgpu_cycle_table_device", entries, TABLE_DTYPE, n, workspace, table_workspace_bytes, device, stream,
+                "the device refused table entry {}; nothing was written", validate=table_validate if check else None)
 
 
 def time_cycle_table_device(entries, n, workspace, device=-1, stream=None, iters=2):
     """Mean ms per table call (three launches) over `iters` calls, HIP events on the launch stream; table and workspace resident."""
-    ms = ctypes.c_float(0)
     ws_bytes = workspace.nbytes if isinstance(workspace, DeviceBuffer) else table_workspace_bytes(n)
-    _check(lib().modgpu_time_cycle_table_device(_vp(_dev_addr(entries)), n, _vp(_dev_addr(workspace)), ws_bytes, device, _vp(stream or 0),
-                                                iters, ctypes.byref(ms)))
-    return ms.value
+    return _time_call("modgpu_time_cycle_table_device", (_vp(_dev_addr(entries)), n, _vp(_dev_addr(workspace)), ws_bytes), device, stream, iters)
 
 
 def table_kernel_source_hash():
@@ -913,31 +947,15 @@ def rekey_table_device(entries, workspace=None, device=-1, stream=None, check=Tr
     count, is needed).  `workspace` is a DeviceBuffer or address of at least rekey_table_workspace_bytes(n) bytes; None makes one.
     When this function made a buffer itself it waits for the call before freeing it and raises ModGpuError if the device refused an
     entry; otherwise the call is asynchronous on `stream` and table_status(workspace) tells the outcome after a synchronise."""
-    own = []
-    try:
-        addr, n, t = _table_arg(entries, REKEY_TABLE_DTYPE, n, device, own, rekey_table_validate if check else None)
-        if t is not None and t.size == 0:
-            return
-        ws, ws_bytes = _workspace_arg(workspace, n, lambda: rekey_table_workspace_bytes(n), device, own)
-        _check(lib().modgpu_rekey_table_device(_vp(addr), n, _vp(ws), ws_bytes, device, _vp(stream or 0)))
-        if own:
-            _check(lib().modgpu_sync(device, _vp(stream or 0)))
-            bad = table_status(ws, device)
-            if bad is not None:
-                raise ModGpuError(1, f"the device refused rekey table entry {bad}; nothing was written")
-    finally:
-        for b in own:
-            b.free()
+    _table_call("modgpu_rekey_table_device", entries, REKEY_TABLE_DTYPE, n, workspace, rekey_table_workspace_bytes, device, stream,
+                "the device refused rekey table entry {}; nothing was written", validate=rekey_table_validate if check else None)
 
 
 def time_rekey_table_device(entries, n, workspace, device=-1, stream=None, iters=2):
     """Mean ms per rekey table call (three launches) over `iters` calls, HIP events on the launch stream; table and workspace
     resident."""
-    ms = ctypes.c_float(0)
     ws_bytes = workspace.nbytes if isinstance(workspace, DeviceBuffer) else rekey_table_workspace_bytes(n)
-    _check(lib().modgpu_time_rekey_table_device(_vp(_dev_addr(entries)), n, _vp(_dev_addr(workspace)), ws_bytes, device, _vp(stream or 0),
-                                                iters, ctypes.byref(ms)))
-    return ms.value
+    return _time_call("modgpu_time_rekey_table_device", (_vp(_dev_addr(entries)), n, _vp(_dev_addr(workspace)), ws_bytes), device, stream, iters)
 
 
 def rekey_table_kernel_source_hash():
@@ -988,26 +1006,15 @@ def rekey_move_table_device(entries, total_bytes=None, workspace=None, device=-1
     rekey_move_table_workspace_bytes(n, total_bytes) bytes; None makes one.  When this function made a buffer itself it waits for the
     call before freeing it and raises ModGpuError if the device refused an entry or the pass gave up; otherwise the call is
     asynchronous on `stream` and rekey_move_table_status(workspace) tells the outcome after a synchronise."""
-    own = []
-    try:
-        addr, n, t = _table_arg(entries, REKEY_TABLE_DTYPE, n, device, own, rekey_move_table_validate if check else None,
-                                "n (the entry count) and total_bytes are", total_bytes is not None)
-        if t is not None and t.size == 0:
-            return
-        if total_bytes is None:
-            total_bytes = int(t["n"].sum(dtype=np.uint64))
-        ws, ws_bytes = _workspace_arg(workspace, n, lambda: rekey_move_table_workspace_bytes(n, total_bytes), device, own)
-        _check(lib().modgpu_rekey_move_table_device(_vp(addr), n, total_bytes, _vp(ws), ws_bytes, device, _vp(stream or 0)))
-        if own:
-            _check(lib().modgpu_sync(device, _vp(stream or 0)))
-            bad, stalled = rekey_move_table_status(ws, device)
-            if bad is not None:
-                raise ModGpuError(1, f"the device refused move table entry {bad}; nothing was written")
-            if stalled is not None:
-                raise ModGpuError(3, f"the move table pass gave up waiting at chunk {stalled}")
-    finally:
-        for b in own:
-            b.free()
+    known = total_bytes is not None
+    if not known and isinstance(entries, np.ndarray):
+        entries = np.ascontiguousarray(entries, dtype=REKEY_TABLE_DTYPE)
+        total_bytes = int(entries["n"].sum(dtype=np.uint64))
+    _table_call("modgpu_rekey_move_table_device", entries, REKEY_TABLE_DTYPE, n, workspace,
+                lambda k: rekey_move_table_workspace_bytes(k, total_bytes), device, stream,
+                "the device refused move table entry {}; nothing was written", gave_up="the move table pass gave up waiting at chunk {}",
+                validate=rekey_move_table_validate if check else None, needed="n (the entry count) and total_bytes are", known=known,
+                extra=(total_bytes,), status=rekey_move_table_status)
 
 
 def compaction_table(base_ptr, keep, key, part_off=0):
@@ -1042,21 +1049,8 @@ def verify_device(expect, src, key, stream_off=0, result=None, device=-1, stream
     finds the lowest, in one read-only pass; only the 32-byte result (device memory: a DeviceBuffer or an address) is written.
     `expect` / `src` are addresses or DeviceBuffer; n defaults to the smaller buffer's size when both are DeviceBuffer.  With
     result=None a result buffer is made, the stream synchronised and the result returned as a VERIFY_RESULT_DTYPE record."""
-    if n is None:
-        if not (isinstance(expect, DeviceBuffer) and isinstance(src, DeviceBuffer)):
-            raise TypeError("n is needed unless both sides are DeviceBuffer")
-        n = min(expect.nbytes, src.nbytes)
-    own = DeviceBuffer(VERIFY_RESULT_DTYPE.itemsize, device) if result is None else None
-    try:
-        _check(lib().modgpu_verify_device(_vp(_dev_addr(expect)), _vp(_dev_addr(src)), n, as_int32(key), stream_off,
-                                          _vp(_dev_addr(own if own is not None else result)), device, _vp(stream or 0)))
-        if own is None:
-            return None
-        _check(lib().modgpu_sync(device, _vp(stream or 0)))
-        return verify_results(own, 1, device)[0]
-    finally:
-        if own is not None:
-            own.free()
+    r = _own_result_call("modgpu_verify_device", expect, src, n, (as_int32(key), stream_off), result, device, stream, verify_results)
+    return r if r is None else r[0]
 
 
 def verify_batch_device(expect_ptrs, src_ptrs, sizes, key, results, stream_offs=None, device=-1, stream=None):
@@ -1064,11 +1058,8 @@ def verify_batch_device(expect_ptrs, src_ptrs, sizes, key, results, stream_offs=
     read, so anything may overlap anything.  One launch initialises the results, up to 16 non-empty entries share a compare launch."""
     n = len(expect_ptrs)
     assert len(src_ptrs) == n and len(sizes) == n
-    e = (_vp * n)(*[_dev_addr(x) for x in expect_ptrs])
-    s = (_vp * n)(*[_dev_addr(x) for x in src_ptrs])
-    z = (_u64 * n)(*sizes)
-    o = (_u64 * n)(*stream_offs) if stream_offs is not None else None
-    _check(lib().modgpu_verify_batch_device(e, s, z, o, n, as_int32(key), _vp(_dev_addr(results)), device, _vp(stream or 0)))
+    _check(lib().modgpu_verify_batch_device(_ptr_array(expect_ptrs), _ptr_array(src_ptrs), _u64_array(sizes), _u64_array(stream_offs), n,
+                                            as_int32(key), _vp(_dev_addr(results)), device, _vp(stream or 0)))
 
 
 def verify_results(results, count=1, device=-1):
@@ -1081,10 +1072,8 @@ def verify_results(results, count=1, device=-1):
 
 def time_verify_device(expect, src, n, key, result, stream_off=0, device=-1, stream=None, iters=2):
     """Mean ms per verify call (two launches) over `iters` calls, HIP events on the launch stream."""
-    ms = ctypes.c_float(0)
-    _check(lib().modgpu_time_verify_device(_vp(_dev_addr(expect)), _vp(_dev_addr(src)), n, as_int32(key), stream_off, _vp(_dev_addr(result)),
-                                           device, _vp(stream or 0), iters, ctypes.byref(ms)))
-    return ms.value
+    return _time_call("modgpu_time_verify_device", (_vp(_dev_addr(expect)), _vp(_dev_addr(src)), n, as_int32(key), stream_off,
+                                                    _vp(_dev_addr(result))), device, stream, iters)
 
 
 def verify_kernel_source_hash():
@@ -1103,21 +1092,9 @@ def digest_device(src, key, stream_off=0, dst=None, result=None, device=-1, stre
     `dst` are addresses or DeviceBuffer; n defaults to the source's size (the smaller one's with a DeviceBuffer dst).  The 32-byte record
     `result` is device memory (a DeviceBuffer or an address).  With result=None a record is made, the stream synchronised and the
     Adler-32 returned as an int."""
-    if n is None:
-        if not isinstance(src, DeviceBuffer) or not (dst is None or isinstance(dst, DeviceBuffer)):
-            raise TypeError("n is needed unless the buffers are DeviceBuffer")
-        n = src.nbytes if dst is None else min(src.nbytes, dst.nbytes)
-    own = DeviceBuffer(DIGEST_RESULT_DTYPE.itemsize, device) if result is None else None
-    try:
-        _check(lib().modgpu_digest_device(_vp(_dev_addr(dst) if dst is not None else 0), _vp(_dev_addr(src)), n, as_int32(key), stream_off,
-                                          _vp(_dev_addr(own if own is not None else result)), device, _vp(stream or 0)))
-        if own is None:
-            return None
-        _check(lib().modgpu_sync(device, _vp(stream or 0)))
-        return int(digest_results(own, 1, device)[1][0])
-    finally:
-        if own is not None:
-            own.free()
+    r = _own_result_call("modgpu_digest_device", dst, src, n, (as_int32(key), stream_off), result, device, stream, digest_results,
+                         "the buffers are", True)
+    return r if r is None else int(r[1][0])
 
 
 def digest_batch_device(src_ptrs, sizes, key, results, dst_ptrs=None, stream_offs=None, device=-1, stream=None):
@@ -1125,11 +1102,8 @@ def digest_batch_device(src_ptrs, sizes, key, results, dst_ptrs=None, stream_off
     0 entry: that entry is digest only.  One memset zeroes the records, up to 16 non-empty entries share a launch."""
     n = len(src_ptrs)
     assert len(sizes) == n and (dst_ptrs is None or len(dst_ptrs) == n)
-    d = (_vp * n)(*[_dev_addr(x) if x is not None else 0 for x in dst_ptrs]) if dst_ptrs is not None else None
-    s = (_vp * n)(*[_dev_addr(x) for x in src_ptrs])
-    z = (_u64 * n)(*sizes)
-    o = (_u64 * n)(*stream_offs) if stream_offs is not None else None
-    _check(lib().modgpu_digest_batch_device(d, s, z, o, n, as_int32(key), _vp(_dev_addr(results)), device, _vp(stream or 0)))
+    _check(lib().modgpu_digest_batch_device(_ptr_array(dst_ptrs), _ptr_array(src_ptrs), _u64_array(sizes), _u64_array(stream_offs), n,
+                                            as_int32(key), _vp(_dev_addr(results)), device, _vp(stream or 0)))
 
 
 def digest_results(results, count=1, device=-1):
@@ -1154,10 +1128,8 @@ def digest_adler32(record):
 
 def time_digest_device(src, n, key, result, dst=None, stream_off=0, device=-1, stream=None, iters=2):
     """Mean ms per digest call (the memset node and one launch) over `iters` calls, HIP events on the launch stream."""
-    ms = ctypes.c_float(0)
-    _check(lib().modgpu_time_digest_device(_vp(_dev_addr(dst) if dst is not None else 0), _vp(_dev_addr(src)), n, as_int32(key), stream_off,
-                                           _vp(_dev_addr(result)), device, _vp(stream or 0), iters, ctypes.byref(ms)))
-    return ms.value
+    return _time_call("modgpu_time_digest_device", (_vp(_dev_addr(dst) if dst is not None else 0), _vp(_dev_addr(src)), n, as_int32(key), stream_off,
+                                                    _vp(_dev_addr(result))), device, stream, iters)
 
 
 def debug_set_digest_grid(grid=0):
@@ -1170,21 +1142,9 @@ def verify_rekey_device(expect, src, key_from, key_to, off_from=0, off_to=0, res
     ^ ks(key_to)[off_to + j]) -- the bytes rekey_device_to would have written -- and finds the lowest, in one read-only pass; only the
     32-byte result (device memory: a DeviceBuffer or an address) is written.  Arguments and the result=None convenience as
     verify_device."""
-    if n is None:
-        if not (isinstance(expect, DeviceBuffer) and isinstance(src, DeviceBuffer)):
-            raise TypeError("n is needed unless both sides are DeviceBuffer")
-        n = min(expect.nbytes, src.nbytes)
-    own = DeviceBuffer(VERIFY_RESULT_DTYPE.itemsize, device) if result is None else None
-    try:
-        _check(lib().modgpu_verify_rekey_device(_vp(_dev_addr(expect)), _vp(_dev_addr(src)), n, as_int32(key_from), off_from, as_int32(key_to), off_to,
-                                                _vp(_dev_addr(own if own is not None else result)), device, _vp(stream or 0)))
-        if own is None:
-            return None
-        _check(lib().modgpu_sync(device, _vp(stream or 0)))
-        return verify_results(own, 1, device)[0]
-    finally:
-        if own is not None:
-            own.free()
+    r = _own_result_call("modgpu_verify_rekey_device", expect, src, n, (as_int32(key_from), off_from, as_int32(key_to), off_to), result, device,
+                         stream, verify_results)
+    return r if r is None else r[0]
 
 
 def verify_rekey_batch_device(expect_ptrs, src_ptrs, sizes, key_from, key_to, results, offs_from=None, offs_to=None, device=-1, stream=None):
@@ -1193,21 +1153,15 @@ def verify_rekey_batch_device(expect_ptrs, src_ptrs, sizes, key_from, key_to, re
     non-empty entries whose two streams differ share a compare launch, and so do up to 16 whose streams coincide."""
     n = len(expect_ptrs)
     assert len(src_ptrs) == n and len(sizes) == n
-    e = (_vp * n)(*[_dev_addr(x) for x in expect_ptrs])
-    s = (_vp * n)(*[_dev_addr(x) for x in src_ptrs])
-    z = (_u64 * n)(*sizes)
-    f = (_u64 * n)(*offs_from) if offs_from is not None else None
-    t = (_u64 * n)(*offs_to) if offs_to is not None else None
-    _check(lib().modgpu_verify_rekey_batch_device(e, s, z, f, t, n, as_int32(key_from), as_int32(key_to), _vp(_dev_addr(results)), device,
-                                                  _vp(stream or 0)))
+    _check(lib().modgpu_verify_rekey_batch_device(_ptr_array(expect_ptrs), _ptr_array(src_ptrs), _u64_array(sizes), _u64_array(offs_from),
+                                                  _u64_array(offs_to), n, as_int32(key_from), as_int32(key_to), _vp(_dev_addr(results)),
+                                                  device, _vp(stream or 0)))
 
 
 def time_verify_rekey_device(expect, src, n, key_from, key_to, result, off_from=0, off_to=0, device=-1, stream=None, iters=2):
     """Mean ms per rekey verify call (two launches) over `iters` calls, HIP events on the launch stream."""
-    ms = ctypes.c_float(0)
-    _check(lib().modgpu_time_verify_rekey_device(_vp(_dev_addr(expect)), _vp(_dev_addr(src)), n, as_int32(key_from), off_from, as_int32(key_to), off_to,
-                                                 _vp(_dev_addr(result)), device, _vp(stream or 0), iters, ctypes.byref(ms)))
-    return ms.value
+    return _time_call("modgpu_time_verify_rekey_device", (_vp(_dev_addr(expect)), _vp(_dev_addr(src)), n, as_int32(key_from), off_from,
+                                                          as_int32(key_to), off_to, _vp(_dev_addr(result))), device, stream, iters)
 
 
 def keep_kernel_source_hash():
@@ -1260,37 +1214,17 @@ def verify_table_device(entries, results=None, workspace=None, device=-1, stream
     waits for the call, raises ModGpuError if the device refused an entry (no result was written) and returns the results as a
     VERIFY_RESULT_DTYPE array; otherwise the call is asynchronous on `stream`, returns None, and table_status(workspace),
     verify_table_summary(workspace) and verify_results(results, n) tell the outcome after a synchronise."""
-    own = []
-    try:
-        addr, n, t = _table_arg(entries, TABLE_DTYPE, n, device, own)
-        if t is not None and t.size == 0:
-            return np.zeros(0, dtype=VERIFY_RESULT_DTYPE)
-        if results is None and n:
-            results = DeviceBuffer(n * VERIFY_RESULT_DTYPE.itemsize, device)
-            own.append(results)
-        ws, ws_bytes = _workspace_arg(workspace, n, lambda: verify_table_workspace_bytes(n), device, own)
-        res = _dev_addr(results) if results is not None else 0
-        _check(lib().modgpu_verify_table_device(_vp(addr), n, _vp(res), _vp(ws), ws_bytes, device, _vp(stream or 0)))
-        if not own:
-            return None
-        _check(lib().modgpu_sync(device, _vp(stream or 0)))
-        bad = table_status(ws, device) if n else None
-        if bad is not None:
-            raise ModGpuError(1, f"the device refused verify table entry {bad}; no result was written")
-        return verify_results(res, n, device)
-    finally:
-        for b in own:
-            b.free()
+    return _table_call("modgpu_verify_table_device", entries, TABLE_DTYPE, n, workspace, verify_table_workspace_bytes, device, stream,
+                       "the device refused verify table entry {}; no result was written", fetch=verify_results, results=results,
+                       empty=_no_verify_results)
 
 
 def time_verify_table_device(entries, n, results, workspace, device=-1, stream=None, iters=2):
     """Mean ms per verify table call (three launches) over `iters` calls, HIP events on the launch stream; table, results and
     workspace resident."""
-    ms = ctypes.c_float(0)
     ws_bytes = workspace.nbytes if isinstance(workspace, DeviceBuffer) else verify_table_workspace_bytes(n)
-    _check(lib().modgpu_time_verify_table_device(_vp(_dev_addr(entries)), n, _vp(_dev_addr(results)), _vp(_dev_addr(workspace)), ws_bytes, device,
-                                                 _vp(stream or 0), iters, ctypes.byref(ms)))
-    return ms.value
+    return _time_call("modgpu_time_verify_table_device", (_vp(_dev_addr(entries)), n, _vp(_dev_addr(results)), _vp(_dev_addr(workspace)), ws_bytes), device,
+                      stream, iters)
 
 
 def verify_table_kernel_source_hash():
@@ -1317,37 +1251,17 @@ def digest_table_device(entries, results=None, workspace=None, device=-1, stream
     ModGpuError if the device refused an entry (no record was written) and returns (the records as a DIGEST_RESULT_DTYPE array, their
     Adler-32 values as a uint32 array); otherwise the call is asynchronous on `stream`, returns None, and table_status(workspace) and
     digest_results(results, n) tell the outcome after a synchronise."""
-    own = []
-    try:
-        addr, n, t = _table_arg(entries, TABLE_DTYPE, n, device, own)
-        if t is not None and t.size == 0:
-            return np.zeros(0, dtype=DIGEST_RESULT_DTYPE), np.zeros(0, dtype=np.uint32)
-        if results is None and n:
-            results = DeviceBuffer(n * DIGEST_RESULT_DTYPE.itemsize, device)
-            own.append(results)
-        ws, ws_bytes = _workspace_arg(workspace, n, lambda: digest_table_workspace_bytes(n), device, own)
-        res = _dev_addr(results) if results is not None else 0
-        _check(lib().modgpu_digest_table_device(_vp(addr), n, _vp(res), _vp(ws), ws_bytes, device, _vp(stream or 0)))
-        if not own:
-            return None
-        _check(lib().modgpu_sync(device, _vp(stream or 0)))
-        bad = table_status(ws, device) if n else None
-        if bad is not None:
-            raise ModGpuError(1, f"the device refused digest table entry {bad}; no record was written")
-        return digest_results(res, n, device)
-    finally:
-        for b in own:
-            b.free()
+    return _table_call("modgpu_digest_table_device", entries, TABLE_DTYPE, n, workspace, digest_table_workspace_bytes, device, stream,
+                       "the device refused digest table entry {}; no record was written", fetch=digest_results, results=results,
+                       empty=_no_digest_results)
 
 
 def time_digest_table_device(entries, n, results, workspace, device=-1, stream=None, iters=2):
     """Mean ms per digest table call (three launches) over `iters` calls, HIP events on the launch stream; table, records and
     workspace resident."""
-    ms = ctypes.c_float(0)
     ws_bytes = workspace.nbytes if isinstance(workspace, DeviceBuffer) else digest_table_workspace_bytes(n)
-    _check(lib().modgpu_time_digest_table_device(_vp(_dev_addr(entries)), n, _vp(_dev_addr(results)), _vp(_dev_addr(workspace)), ws_bytes, device,
-                                                 _vp(stream or 0), iters, ctypes.byref(ms)))
-    return ms.value
+    return _time_call("modgpu_time_digest_table_device", (_vp(_dev_addr(entries)), n, _vp(_dev_addr(results)), _vp(_dev_addr(workspace)), ws_bytes), device,
+                      stream, iters)
 
 
 def debug_set_digest_table_grid(grid=0):
@@ -1369,37 +1283,17 @@ def cycle_digest_table_device(entries, records=None, side=DIGEST_OUTPUT, workspa
     ModGpuError if the device refused an entry (nothing was written, no byte and no record) and returns (the records as a
     DIGEST_RESULT_DTYPE array, their Adler-32 values as a uint32 array); otherwise the call is asynchronous on `stream`, returns None,
     and table_status(workspace) and digest_results(records, n) tell the outcome after a synchronise."""
-    own = []
-    try:
-        addr, n, t = _table_arg(entries, TABLE_DTYPE, n, device, own)
-        if t is not None and t.size == 0:
-            return np.zeros(0, dtype=DIGEST_RESULT_DTYPE), np.zeros(0, dtype=np.uint32)
-        if records is None and n:
-            records = DeviceBuffer(n * DIGEST_RESULT_DTYPE.itemsize, device)
-            own.append(records)
-        ws, ws_bytes = _workspace_arg(workspace, n, lambda: cycle_digest_table_workspace_bytes(n), device, own)
-        rec = _dev_addr(records) if records is not None else 0
-        _check(lib().modgpu_cycle_digest_table_device(_vp(addr), n, _vp(rec), side, _vp(ws), ws_bytes, device, _vp(stream or 0)))
-        if not own:
-            return None
-        _check(lib().modgpu_sync(device, _vp(stream or 0)))
-        bad = table_status(ws, device) if n else None
-        if bad is not None:
-            raise ModGpuError(1, f"the device refused cycle digest table entry {bad}; nothing was written")
-        return digest_results(rec, n, device)
-    finally:
-        for b in own:
-            b.free()
+    return _table_call("modgpu_cycle_digest_table_device", entries, TABLE_DTYPE, n, workspace, cycle_digest_table_workspace_bytes, device,
+                       stream, "the device refused cycle digest table entry {}; nothing was written", extra=(side,), fetch=digest_results,
+                       results=records, empty=_no_digest_results)
 
 
 def time_cycle_digest_table_device(entries, n, records, workspace, side=DIGEST_OUTPUT, device=-1, stream=None, iters=2):
     """Mean ms per cycle digest table call (three launches) over `iters` calls, HIP events on the launch stream; table, records and
     workspace resident."""
-    ms = ctypes.c_float(0)
     ws_bytes = workspace.nbytes if isinstance(workspace, DeviceBuffer) else cycle_digest_table_workspace_bytes(n)
-    _check(lib().modgpu_time_cycle_digest_table_device(_vp(_dev_addr(entries)), n, _vp(_dev_addr(records)), side, _vp(_dev_addr(workspace)), ws_bytes,
-                                                       device, _vp(stream or 0), iters, ctypes.byref(ms)))
-    return ms.value
+    return _time_call("modgpu_time_cycle_digest_table_device", (_vp(_dev_addr(entries)), n, _vp(_dev_addr(records)), side, _vp(_dev_addr(workspace)),
+                                                                ws_bytes), device, stream, iters)
 
 
 def debug_set_cycle_digest_table_grid(grid=0):
@@ -1422,37 +1316,17 @@ def verify_rekey_table_device(entries, results=None, workspace=None, device=-1, 
     entry (no result was written) and returns the results as a VERIFY_RESULT_DTYPE array; otherwise the call is asynchronous on
     `stream`, returns None, and table_status(workspace), verify_table_summary(workspace) and verify_results(results, n) tell the
     outcome after a synchronise."""
-    own = []
-    try:
-        addr, n, t = _table_arg(entries, REKEY_TABLE_DTYPE, n, device, own)
-        if t is not None and t.size == 0:
-            return np.zeros(0, dtype=VERIFY_RESULT_DTYPE)
-        if results is None and n:
-            results = DeviceBuffer(n * VERIFY_RESULT_DTYPE.itemsize, device)
-            own.append(results)
-        ws, ws_bytes = _workspace_arg(workspace, n, lambda: verify_rekey_table_workspace_bytes(n), device, own)
-        res = _dev_addr(results) if results is not None else 0
-        _check(lib().modgpu_verify_rekey_table_device(_vp(addr), n, _vp(res), _vp(ws), ws_bytes, device, _vp(stream or 0)))
-        if not own:
-            return None
-        _check(lib().modgpu_sync(device, _vp(stream or 0)))
-        bad = table_status(ws, device) if n else None
-        if bad is not None:
-            raise ModGpuError(1, f"the device refused rekey verify table entry {bad}; no result was written")
-        return verify_results(res, n, device)
-    finally:
-        for b in own:
-            b.free()
+    return _table_call("modgpu_verify_rekey_table_device", entries, REKEY_TABLE_DTYPE, n, workspace, verify_rekey_table_workspace_bytes,
+                       device, stream, "the device refused rekey verify table entry {}; no result was written", fetch=verify_results,
+                       results=results, empty=_no_verify_results)
 
 
 def time_verify_rekey_table_device(entries, n, results, workspace, device=-1, stream=None, iters=2):
     """Mean ms per rekey verify table call (three launches) over `iters` calls, HIP events on the launch stream; table, results and
     workspace resident."""
-    ms = ctypes.c_float(0)
     ws_bytes = workspace.nbytes if isinstance(workspace, DeviceBuffer) else verify_rekey_table_workspace_bytes(n)
-    _check(lib().modgpu_time_verify_rekey_table_device(_vp(_dev_addr(entries)), n, _vp(_dev_addr(results)), _vp(_dev_addr(workspace)), ws_bytes,
-                                                       device, _vp(stream or 0), iters, ctypes.byref(ms)))
-    return ms.value
+    return _time_call("modgpu_time_verify_rekey_table_device", (_vp(_dev_addr(entries)), n, _vp(_dev_addr(results)), _vp(_dev_addr(workspace)), ws_bytes), device,
+                      stream, iters)
 
 
 def rekey_verify_table_kernel_source_hash():

@@ -71,3 +71,133 @@ def test_kernel_trace_summary_by_kernel_and_grid(tmp_path):
     big = out["by_kernel_and_grid"][0]
     assert big["workgroups"] == 256 and big["dispatches"] == 2 and big["median_us"] == 8100.0 and big["total_us"] == 16200.0
     assert out["by_kernel_and_grid"][1]["workgroups"] == 2048 and out["by_kernel_and_grid"][1]["median_us"] == 5.5
+
+
+# ---- tools/bench_common.py: the harness of the fourteen event-timed bench tools
+
+TOOLS = os.path.join(ROOT, "tools")
+# tool -> (factor of the rate, its key): what each tool passes to bench_common.stats
+BENCH_RATES = {"bench_cycle_to": (2, "TBps_2n"), "bench_rekey": (2, "TBps_2n"), "bench_table": (2, "TBps_2n"), "bench_rekey_table": (2, "TBps_2n"),
+               "bench_verify": (2, "TBps_2n"), "bench_verify_table": (2, "TBps_2n"), "bench_keep": (2, "TBps_2n"), "bench_verify_rekey": (2, "TBps_2n"),
+               "bench_verify_rekey_table": (2, "TBps_2n"), "bench_rekey_move": (1, "TBps"), "bench_rekey_move_table": (1, "TBps"),
+               "bench_digest": (1, "TBps_n"), "bench_digest_table": (1, "TBps"), "bench_cycle_digest_table": (1, "TBps")}
+
+
+def _bench_common():
+    if TOOLS not in sys.path:
+        sys.path.insert(0, TOOLS)
+    import bench_common
+    return bench_common
+
+
+def _profiles():
+    """(tool name, document) of every committed profile one of the fourteen tools wrote"""
+    import glob
+    for path in sorted(glob.glob(os.path.join(ROOT, "profiles", "*.json"))):
+        with open(path) as f:
+            doc = json.load(f)
+        tool = os.path.basename(str(doc.get("tool", "")) if isinstance(doc, dict) else "").replace(".py", "")
+        if tool in BENCH_RATES:
+            yield tool, doc
+
+
+def test_bench_common_import_has_no_side_effects():
+    """Importing the harness writes no environment variable and loads neither the HIP runtime nor libmodgpu: setup() does, when a tool
+    asks for it.  In a child process, so that nothing this test process loaded counts."""
+    code = "\n".join([
+        "import os, sys",
+        "before = dict(os.environ)",
+        f"sys.path.insert(0, {TOOLS!r})",
+        "import bench_common",
+        "assert dict(os.environ) == before, 'the import changed os.environ'",
+        "assert 'modulate_amd' not in sys.modules and 'hip_rt' not in sys.modules, sorted(m for m in sys.modules if 'mod' in m or 'hip' in m)",
+        "import modulate_amd.capi as capi",
+        "import hip_rt",
+        "assert capi._libs == {} and hip_rt._hip is None",
+        "maps = open('/proc/self/maps').read()",
+        "assert 'libamdhip64' not in maps and 'libmodgpu' not in maps",
+        "assert 'MODGPU_REQUIRE_GPU' not in os.environ or before.get('MODGPU_REQUIRE_GPU') == os.environ['MODGPU_REQUIRE_GPU']",
+        "print('clean')"])
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True)
+    assert r.returncode == 0 and r.stdout.strip() == "clean", r.stderr
+
+
+def test_bench_stats_reproduces_the_recorded_rates():
+    """Every (row, variant) of the committed profiles: the rate of the recorded bytes at the recorded median, with the tool's factor,
+    is the recorded rate -- within rate x 5.1e-6 / median_ms + 5.1e-5, the worst case of the recorded median's rounding to 5 places
+    plus the recorded rate's own rounding to 4 (derived, not measured) -- and bench_common.stats gives that rate, rounded."""
+    H = _bench_common()
+    pairs = 0
+
+    def variants(node, key):
+        if isinstance(node, dict):
+            if "median_ms" in node and key in node:
+                yield node
+            else:
+                for child in node.values():
+                    yield from variants(child, key)
+
+    def rows(node):
+        if isinstance(node, dict):
+            if "bytes" in node:
+                yield node
+            else:
+                for child in node.values():
+                    yield from rows(child)
+
+    for tool, doc in _profiles():
+        factor, key = BENCH_RATES[tool]
+        for row in rows(doc):
+            for v in variants(row, key):
+                rate = factor * row["bytes"] / (v["median_ms"] * 1e-3) / 1e12
+                assert abs(rate - v[key]) <= v[key] * 5.1e-6 / v["median_ms"] + 5.1e-5, (tool, row["bytes"], v)
+                assert H.stats([v["median_ms"]], row["bytes"], factor, key)[key] == round(rate, 4)  # stats is that formula, rounded
+                pairs += 1
+    assert pairs >= 300, pairs
+
+
+def test_bench_stats_on_fixed_times():
+    H = _bench_common()
+    assert H.stats([3.0, 1.0, 2.0], 1 << 30, 2, "TBps_2n") == {"median_ms": 2.0, "min_ms": 1.0, "max_ms": 3.0, "TBps_2n": 1.0737}
+    # an even count: the upper of the two middle times
+    assert H.stats([4.0, 1.0, 0.123456789, 2.0], 10 ** 9, 1, "TBps") == {"median_ms": 2.0, "min_ms": 0.12346, "max_ms": 4.0, "TBps": 0.5}
+    assert H.stats([0.02], 65536, 1, "TBps_n") == {"median_ms": 0.02, "min_ms": 0.02, "max_ms": 0.02, "TBps_n": 0.0033}
+    row = {"base": {"median_ms": 3.0}, "table": {"median_ms": 1.5}, "table2": {"median_ms": 1.6}}
+    H.add_speedups(row, ["table", "base"])
+    assert row["table_speedup_over_base"] == 2.0 and H.aa_spread(row, "table") == 0.06667
+    H.add_speedups(row, ["table2"])
+    assert "table2_speedup_over_base" not in row
+
+
+def test_bench_table_layouts_are_the_recorded_ones():
+    """bench_common.table_layout against tests/bench_layouts.json -- the SHA-256 of every array each tool's own layout() returned
+    before the harness took them over, with its entry count and byte total -- and against the entries and bytes of the committed
+    profiles, which were taken on those tables."""
+    import hashlib
+    H = _bench_common()
+    with open(os.path.join(ROOT, "tests", "bench_layouts.json")) as f:
+        want = json.load(f)
+    assert sorted(want) == sorted(t + "/" + s for t, shapes in H.LAYOUT_SHAPES.items() for s in shapes)
+    for name, w in want.items():
+        tool, shape = name.split("/")
+        got = H.table_layout(tool, shape)
+        parts = [hashlib.sha256(x.tobytes()).hexdigest() + ":" + str(x.dtype) if hasattr(x, "tobytes") else int(x) for x in got]
+        assert parts == w["parts"], name
+        assert (int(got[0].size), int(got[0].sum())) == (w["entries"], w["bytes"]), name
+    assert (want["table/config4"]["entries"], want["table/config4"]["bytes"]) == (100000, 3278797672)
+    assert (want["digest_table/16kx64k"]["entries"], want["digest_table/16kx64k"]["bytes"]) == (16384, 1073741824)
+    seen = 0
+    for tool, doc in _profiles():
+        layout = tool[len("bench_"):]
+        for shape, row in doc.get("shapes", {}).items():
+            if layout in H.LAYOUT_SHAPES and shape in H.LAYOUT_SHAPES[layout]:
+                assert (row["entries"], row["bytes"]) == (want[layout + "/" + shape]["entries"], want[layout + "/" + shape]["bytes"]), (tool, shape)
+                seen += 1
+    assert seen >= 20, seen
+    for tool in H.LAYOUT_SHAPES:
+        for shape in ("nonsense",) + tuple(s for s in H.SINGLE_ENTRY if s not in H.LAYOUT_SHAPES[tool]):
+            try:
+                H.table_layout(tool, shape)
+            except ValueError:
+                continue
+            raise AssertionError((tool, shape))

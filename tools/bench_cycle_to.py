@@ -12,40 +12,15 @@ single pass; the variants alternate step by step so drift hits all of them alike
 
     python tools/bench_cycle_to.py [--sizes-mib 64,256,1024,4096] [--warmup 3] [--steps 20] [--out profiles/r07_cycle_to.json]
 """
-import argparse
 import ctypes
-import json
-import os
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-os.environ["MODGPU_REQUIRE_GPU"] = "1"
-import numpy as np  # noqa: E402
-import modulate_amd as M  # noqa: E402
-from hip_rt import Stream, hip, _ok  # noqa: E402  (tests/hip_rt.py: streams over the HIP runtime libmodgpu.so brought in)
+import bench_common as H
+
+M, Stream, hip, _ok = H.setup()
 
 VARIANTS = ("inplace", "to_aligned", "to_mis_a", "to_mis_b", "copy_inplace")
 KEY = M.KEY_PS4
 D2D = 3  # hipMemcpyDeviceToDevice
-
-
-class Event:
-    def __init__(self):
-        self.h = ctypes.c_void_p()
-        _ok(hip().hipEventCreate(ctypes.byref(self.h)), "hipEventCreate")
-
-    def record(self, stream):
-        _ok(hip().hipEventRecord(self.h, ctypes.c_void_p(stream.handle)), "hipEventRecord")
-
-
-def elapsed_ms(e0, e1):
-    _ok(hip().hipEventSynchronize(e1.h), "hipEventSynchronize")
-    ms = ctypes.c_float()
-    _ok(hip().hipEventElapsedTime(ctypes.byref(ms), e0.h, e1.h), "hipEventElapsedTime")
-    return ms.value
 
 
 def one_pass(v, src, dst, n, st):
@@ -64,43 +39,21 @@ def one_pass(v, src, dst, n, st):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--sizes-mib", default="64,256,1024,4096")
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r07_cycle_to.json"))
-    a = ap.parse_args()
+    a = H.arguments("r07_cycle_to.json", sizes_mib="64,256,1024,4096").parse_args()
     assert a.warmup >= 3 and a.steps >= 20, "at least 3 warm-ups and 20 timed steps"
     M.use_testing_flavour()  # the same device code as libmodgpu.so, plus the switch between the two source forms
     st = Stream()
-    e0, e1 = Event(), Event()
     rows = {}
-    tile = np.random.default_rng(1).integers(0, 256, size=1 << 24, dtype=np.uint8)
     for mib in [int(x) for x in a.sizes_mib.split(",")]:
         n = mib << 20
         sbuf, dbuf = M.DeviceBuffer(n + 64), M.DeviceBuffer(n + 64)
-        for off in range(0, n + 64, tile.size):
-            sbuf.upload(tile[:min(tile.size, n + 64 - off)], offset=off)
+        H.fill(sbuf, n + 64)
         src, dst = sbuf.ptr, dbuf.ptr  # hipMalloc: 256-byte aligned, phase 0
-        kernels = {}
-        for v in VARIANTS:
-            for _ in range(a.warmup):
-                kernels[v] = one_pass(v, src, dst, n, st)["kernel"]
-        st.sync()
-        times = {v: [] for v in VARIANTS}
-        for _ in range(a.steps):
-            for v in VARIANTS:
-                e0.record(st)
-                one_pass(v, src, dst, n, st)
-                e1.record(st)
-                times[v].append(elapsed_ms(e0, e1))
+        times, info, _ = H.measure(st, VARIANTS, lambda v: one_pass(v, src, dst, n, st), a.warmup, a.steps)
         M.debug_set_to_form(None)
-        row = {"bytes": n, "kernel": kernels}
+        row = {"bytes": n, "kernel": {v: info[v]["kernel"] for v in VARIANTS}}
         for v in VARIANTS:
-            t = sorted(times[v])
-            med = t[len(t) // 2]
-            row[v] = {"median_ms": round(med, 5), "min_ms": round(t[0], 5), "max_ms": round(t[-1], 5),
-                      "TBps_2n": round(2 * n / (med * 1e-3) / 1e12, 4)}
+            row[v] = H.stats(times[v], n, 2, "TBps_2n")
         row["to_aligned_over_inplace"] = round(row["inplace"]["median_ms"] / row["to_aligned"]["median_ms"], 4)
         row["to_aligned_over_copy_inplace"] = round(row["copy_inplace"]["median_ms"] / row["to_aligned"]["median_ms"], 4)
         row["mis_a_over_mis_b"] = round(row["to_mis_b"]["median_ms"] / row["to_mis_a"]["median_ms"], 4)
@@ -109,14 +62,9 @@ def main():
         sbuf.free()
         dbuf.free()
     st.destroy()
-    out = {"tool": "tools/bench_cycle_to.py", "unit": "TB/s of 2n algorithmic bytes per pass (n read + n written)",
-           "when": time.strftime("%Y-%m-%dT%H:%M:%S"), "warmup": a.warmup, "steps": a.steps, "key": KEY,
-           "to_kernel_source_hash": M.to_kernel_source_hash(), "kernel_source_hash": M.kernel_source_hash(),
-           "misaligned": "src phase 5, dst phase 0", "sizes": rows}
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1)
-    print("wrote", a.out)
+    H.write_profile(a.out, {**H.profile_head("bench_cycle_to.py", "TB/s of 2n algorithmic bytes per pass (n read + n written)", a),
+                            "key": KEY, "to_kernel_source_hash": M.to_kernel_source_hash(), "kernel_source_hash": M.kernel_source_hash(),
+                            "misaligned": "src phase 5, dst phase 0", "sizes": rows})
 
 
 if __name__ == "__main__":

@@ -20,42 +20,20 @@ alternate step by step so drift hits all of them alike; 3 warm-ups, median of 20
 
     python tools/bench_digest.py [--sizes-kib 64,1024,16384,4194304] [--warmup 3] [--steps 20] [--parent-lib PATH] [--out profiles/r16_digest.json]
 """
-import argparse
 import ctypes
-import json
-import os
-import sys
 import time
 import zlib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-os.environ["MODGPU_REQUIRE_GPU"] = "1"
-import numpy as np  # noqa: E402
-import modulate_amd as M  # noqa: E402
-from hip_rt import Stream, hip, _ok  # noqa: E402  (tests/hip_rt.py: streams over the HIP runtime libmodgpu.so brought in)
+import numpy as np
+
+import bench_common as H
+
+M, Stream, hip, _ok = H.setup()
 
 SINGLE = ("digest", "digest_g200", "digest_p5", "verify", "verify_p5", "fused", "fused_g256", "fused_p5", "to", "to_again", "to_p5")
 GRID = {"digest_g200": 200, "fused_g256": 256}  # the grid A/B: each mode on the other's shipped grid
 KEY = M.KEY_PS4
 _vp = ctypes.c_void_p
-
-
-class Event:
-    def __init__(self):
-        self.h = _vp()
-        _ok(hip().hipEventCreate(ctypes.byref(self.h)), "hipEventCreate")
-
-    def record(self, stream):
-        _ok(hip().hipEventRecord(self.h, _vp(stream.handle)), "hipEventRecord")
-
-
-def elapsed_ms(e0, e1):
-    _ok(hip().hipEventSynchronize(e1.h), "hipEventSynchronize")
-    ms = ctypes.c_float()
-    _ok(hip().hipEventElapsedTime(ctypes.byref(ms), e0.h, e1.h), "hipEventElapsedTime")
-    return ms.value
 
 
 def one_pass(v, B, n, st, parent):
@@ -82,43 +60,26 @@ def one_pass(v, B, n, st, parent):
     return M.last_launch()
 
 
-def stats(ts, n):
-    t = sorted(ts)
-    med = t[len(t) // 2]
-    return {"median_ms": round(med, 5), "min_ms": round(t[0], 5), "max_ms": round(t[-1], 5), "TBps_n": round(n / (med * 1e-3) / 1e12, 4)}
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--sizes-kib", default="64,1024,16384,4194304")
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--steps", type=int, default=20)
+    ap = H.arguments("r16_digest.json", sizes_kib="64,1024,16384,4194304")
     ap.add_argument("--parent-lib", default=None, help="libmodgpu.so built from the parent commit: modgpu_cycle_device_to before / after")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r16_digest.json"))
     a = ap.parse_args()
     assert a.warmup >= 3 and a.steps >= 20, "at least 3 warm-ups and 20 timed steps"
     parent = ctypes.CDLL(a.parent_lib) if a.parent_lib else None
     M.use_testing_flavour()  # the same device code as libmodgpu.so, plus the grid switch
     st = Stream()
-    e0, e1 = Event(), Event()
     rows = {}
-    tile = np.random.default_rng(1).integers(0, 256, size=1 << 24, dtype=np.uint8)
     sizes = [int(x) << 10 for x in a.sizes_kib.split(",")]
     for n in sizes:
         sbuf, dbuf, mbuf, rbuf, vbuf = M.DeviceBuffer(n + 64), M.DeviceBuffer(n + 64), M.DeviceBuffer(n + 64), M.DeviceBuffer(32 * 16), M.DeviceBuffer(32)
-        for off in range(0, n + 64, tile.size):
-            sbuf.upload(tile[:min(tile.size, n + 64 - off)], offset=off)
+        H.fill(sbuf, n + 64)
         B = {"src": sbuf.ptr, "dst": dbuf.ptr, "dst_p5": mbuf.ptr, "res": rbuf.ptr, "vres": vbuf.ptr}  # hipMalloc: 256-byte aligned, phase 0
         largest = n == max(sizes) and n % 16 == 0
         variants = SINGLE + (("to_parent",) if parent else ()) + (("digest_batch",) if largest else ())
         order = [v for v in variants if v.startswith("to")] + [v for v in variants if not v.startswith("to")]  # the `to` passes make `expect`
-        launch, seen = {}, {}
-        for v in order:
-            for _ in range(a.warmup):
-                info = one_pass(v, B, n, st, parent)
-            if info:
-                launch[v] = {"kernel": info["kernel"], "variant": info["variant"], "grid": info["grid"]}
-            st.sync()
+        seen = {}
+
+        def checked(v, info):
             if v.startswith("verify"):
                 r = M.verify_results(vbuf, 1)
                 assert int(r["mismatches"][0]) == 0 and int(r["n"][0]) == n, (v, r)
@@ -126,19 +87,15 @@ def main():
                 recs, adlers = M.digest_results(rbuf, 16 if v == "digest_batch" else 1)
                 assert int(recs["n"].sum()) == n, (v, recs)
                 seen[v] = [int(x) for x in adlers]
-        assert seen["digest"] == seen["fused"] and seen["digest_p5"] == seen["fused_p5"], seen
-        times = {v: [] for v in variants}
-        for _ in range(a.steps):
-            for v in variants:
-                e0.record(st)
-                one_pass(v, B, n, st, parent)
-                e1.record(st)
-                times[v].append(elapsed_ms(e0, e1))
-        row = {"bytes": n, "launch": launch, "adler32": seen}
+            if v == order[-1]:
+                assert seen["digest"] == seen["fused"] and seen["digest_p5"] == seen["fused_p5"], seen
+
+        times, info, _ = H.measure(st, variants, lambda v: one_pass(v, B, n, st, parent), a.warmup, a.steps, warm_order=order, after_warmup=checked)
+        row = {"bytes": n, "launch": {v: H.launch_row(info[v]) for v in order if info[v]}, "adler32": seen}
         for v in variants:
-            row[v] = stats(times[v], n)
+            row[v] = H.stats(times[v], n, 1, "TBps_n")
         med = {v: row[v]["median_ms"] for v in variants}
-        spread = abs(med["to"] - med["to_again"]) / min(med["to"], med["to_again"])
+        spread = H.spread(med["to"], med["to_again"])
         row["aa_spread_of_to"] = round(spread, 5)
         row["digest_over_verify"] = round(med["digest"] / med["verify"], 4)
         row["digest_p5_over_verify_p5"] = round(med["digest_p5"] / med["verify_p5"], 4)
@@ -177,17 +134,14 @@ def main():
         for b in (sbuf, dbuf, mbuf, rbuf, vbuf):
             b.free()
     st.destroy()
-    out = {"tool": "tools/bench_digest.py", "unit": "TB/s of n bytes per pass (digest only reads n; fused and out of place read n and write n; verify reads 2n)",
-           "when": time.strftime("%Y-%m-%dT%H:%M:%S"), "warmup": a.warmup, "steps": a.steps, "key": KEY,
-           "rules": {"digest only": "median <= verify's median x 1.05 on the same source in the same run",
-                     "fused": "median <= the out-of-place median x (1.05 + A/A spread of the out-of-place pass in the same run)",
-                     "to before / after": "to_over_to_parent within the A/A spread"},
-           "to_kernel_source_hash": M.to_kernel_source_hash(), "verify_kernel_source_hash": M.verify_kernel_source_hash(),
-           "parent_lib": bool(parent), "p5": "source at phase 5, destination / expect at phase 0", "sizes": rows}
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1)
-    print("wrote", a.out)
+    H.write_profile(a.out, {
+        **H.profile_head("bench_digest.py", "TB/s of n bytes per pass (digest only reads n; fused and out of place read n and write n; verify reads 2n)", a),
+        "key": KEY,
+        "rules": {"digest only": "median <= verify's median x 1.05 on the same source in the same run",
+                  "fused": "median <= the out-of-place median x (1.05 + A/A spread of the out-of-place pass in the same run)",
+                  "to before / after": "to_over_to_parent within the A/A spread"},
+        "to_kernel_source_hash": M.to_kernel_source_hash(), "verify_kernel_source_hash": M.verify_kernel_source_hash(),
+        "parent_lib": bool(parent), "p5": "source at phase 5, destination / expect at phase 0", "sizes": rows})
 
 
 if __name__ == "__main__":

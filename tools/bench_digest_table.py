@@ -17,88 +17,37 @@ timed every value of the table call is compared -- with zlib.adler32 of the host
 
     python tools/bench_digest_table.py [--shapes 64k,1m,16m,4g,4g_p5,16kx64k,config4] [--warmup 3] [--steps 20] [--out profiles/r17_digest_table.json]
 """
-import argparse
 import ctypes
-import json
-import os
-import sys
-import time
 import zlib
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-os.environ["MODGPU_REQUIRE_GPU"] = "1"
-import numpy as np  # noqa: E402
-import modulate_amd as M  # noqa: E402
-from hip_rt import Stream, hip, _ok  # noqa: E402  (tests/hip_rt.py: streams over the HIP runtime libmodgpu.so brought in)
+import numpy as np
+
+import bench_common as H
+
+M, Stream, hip, _ok = H.setup()
 
 KEY = M.KEY_PS3
 VARIANTS = ("table", "grid200", "base")
 GRIDS = {"table": 0, "grid200": 200}
-SINGLE = {"64k": 64 << 10, "1m": 1 << 20, "16m": 16 << 20, "4g": 4 << 30, "4g_p5": 4 << 30}
 _vp, _u64 = ctypes.c_void_p, ctypes.c_uint64
 
 
-class Event:
-    def __init__(self):
-        self.h = ctypes.c_void_p()
-        _ok(hip().hipEventCreate(ctypes.byref(self.h)), "hipEventCreate")
-
-    def record(self, stream):
-        _ok(hip().hipEventRecord(self.h, ctypes.c_void_p(stream.handle)), "hipEventRecord")
-
-
-def elapsed_ms(e0, e1):
-    _ok(hip().hipEventSynchronize(e1.h), "hipEventSynchronize")
-    ms = ctypes.c_float()
-    _ok(hip().hipEventElapsedTime(ctypes.byref(ms), e0.h, e1.h), "hipEventElapsedTime")
-    return ms.value
-
-
-def layout(shape):
-    """(sizes, source offsets from a chunk-aligned base, stream offsets, source bytes)"""
-    rng = np.random.default_rng(0x4D6F6475)
-    if shape in SINGLE:
-        sz = np.array([SINGLE[shape]], np.int64)
-        z = np.zeros(1, np.int64)
-        return sz, z + (5 if shape == "4g_p5" else 0), z + 12345, int(sz[0]) + 64
-    if shape == "16kx64k":
-        sz = np.full(16384, 65536, np.int64)
-        so = np.arange(16384, dtype=np.int64) * (65536 + 16) + rng.integers(0, 16, size=16384)
-        return sz, so, so, int(so[-1]) + 65536 + 64
-    if shape == "config4":
-        sz = rng.integers(0, 65537, size=100000).astype(np.int64)
-        o = np.concatenate([[0], np.cumsum(sz)[:-1]]).astype(np.int64)
-        return sz, o, o, int(sz.sum()) + 64
-    raise ValueError(shape)
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--shapes", default="64k,1m,16m,4g,4g_p5,16kx64k,config4")
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--variants", default=",".join(VARIANTS))
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r17_digest_table.json"))
-    a = ap.parse_args()
+    a = H.arguments("r17_digest_table.json", shapes="64k,1m,16m,4g,4g_p5,16kx64k,config4", variants=",".join(VARIANTS)).parse_args()
     variants = a.variants.split(",")
     assert a.warmup >= 1 and a.steps >= 1
     M.use_testing_flavour()  # the same device code as libmodgpu.so, plus the switch of the stream grid
     M.debug_set_digest_table_grid(0)
     L = M.lib()
     st = Stream()
-    e0, e1 = Event(), Event()
     rows = {}
     shipped = None
-    tile = np.random.default_rng(1).integers(0, 256, size=1 << 24, dtype=np.uint8)
     for shape in a.shapes.split(","):
-        sz, so, offs, sn = layout(shape)
+        sz, so, offs, sn = H.table_layout("digest_table", shape)
         n_bytes, k = int(sz.sum()), sz.size
         sbuf = M.DeviceBuffer(sn + 65536)
         base = -sbuf.ptr % 65536  # the layout's offsets count from a chunk edge
-        for off in range(0, sn, tile.size):
-            sbuf.upload(tile[:min(tile.size, sn - off)], offset=base + off)
+        H.fill(sbuf, sn, offset=base)
         t = M.table(k)
         t["src"] = sbuf.ptr + base + so
         t["n"], t["stream_off"], t["key"] = sz, offs, M.as_int32(KEY)
@@ -123,14 +72,8 @@ def main():
             return M.last_launch()
 
         # every value, before anything is timed
-        launch = {}
-        for v in variants:
-            before = M.path_stats()["gpu_launches"]
-            for _ in range(a.warmup):
-                info = one_pass(v)
-            launch[v] = {"kernel": info["kernel"], "variant": info["variant"], "grid": info["grid"],
-                         "launches_per_pass": (M.path_stats()["gpu_launches"] - before) // a.warmup}
-            st.sync()
+        def checked(v, info):
+            nonlocal shipped
             if v in GRIDS:
                 assert M.table_status(ws) is None and info["variant"] == 17, (shape, v, info)
                 if v == "table" and shipped is None:
@@ -147,35 +90,21 @@ def main():
                     one_pass("base")
                     st.sync()
                     assert np.array_equal(got, M.digest_results(res_base, k)[1]), (shape, v, "the table call and the existing call disagree")
-        times = {v: [] for v in variants}
-        for _ in range(a.steps):
-            for v in variants:
-                e0.record(st)
-                one_pass(v)
-                e1.record(st)
-                times[v].append(elapsed_ms(e0, e1))
+
+        times, info, launches = H.measure(st, variants, one_pass, a.warmup, a.steps, after_warmup=checked)
         M.debug_set_digest_table_grid(0)
-        row = {"entries": int(k), "bytes": n_bytes, "launch": launch}
+        row = {"entries": int(k), "bytes": n_bytes, "launch": {v: H.launch_row(info[v], launches[v]) for v in variants}}
         for v in variants:
-            tt = sorted(times[v])
-            med = tt[len(tt) // 2]
-            row[v] = {"median_ms": round(med, 5), "min_ms": round(tt[0], 5), "max_ms": round(tt[-1], 5), "TBps": round(n_bytes / (med * 1e-3) / 1e12, 4)}
-        if "base" in variants:
-            for v in variants:
-                if v != "base":
-                    row[v + "_speedup_over_base"] = round(row["base"]["median_ms"] / row[v]["median_ms"], 4)
+            row[v] = H.stats(times[v], n_bytes, 1, "TBps")
+        H.add_speedups(row, variants)
         rows[shape] = row
         print("%-8s %6d entries  " % (shape, k) + "  ".join("%s %.4f ms %.2f TB/s" % (v, row[v]["median_ms"], row[v]["TBps"]) for v in variants), flush=True)
         for b in (sbuf, tb, ws, res, res_base):
             b.free()
     st.destroy()
-    out = {"tool": "tools/bench_digest_table.py", "unit": "TB/s of n bytes read per pass", "when": time.strftime("%Y-%m-%dT%H:%M:%S"), "warmup": a.warmup,
-           "steps": a.steps, "key": KEY, "shipped_grid": shipped, "verify_table_kernel_source_hash": M.verify_table_kernel_source_hash(),
-           "to_kernel_source_hash": M.to_kernel_source_hash(), "shapes": rows}
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1)
-    print("wrote", a.out)
+    H.write_profile(a.out, {**H.profile_head("bench_digest_table.py", "TB/s of n bytes read per pass", a), "key": KEY, "shipped_grid": shipped,
+                            "verify_table_kernel_source_hash": M.verify_table_kernel_source_hash(),
+                            "to_kernel_source_hash": M.to_kernel_source_hash(), "shapes": rows})
 
 
 if __name__ == "__main__":

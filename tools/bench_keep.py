@@ -16,41 +16,18 @@ by step so drift hits all of them alike; 3 warm-ups, the median of 20.  Rate uni
 
     python tools/bench_keep.py [--sizes-mib 4096,1024] [--warmup 3] [--steps 20] [--out profiles/r13_keep.json]
 """
-import argparse
 import ctypes
-import json
-import os
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-os.environ["MODGPU_REQUIRE_GPU"] = "1"
-import numpy as np  # noqa: E402
-import modulate_amd as M  # noqa: E402
-from hip_rt import Stream, hip, _ok  # noqa: E402  (tests/hip_rt.py: streams over the HIP runtime libmodgpu.so brought in)
+import numpy as np
+
+import bench_common as H
+
+M, Stream, hip, _ok = H.setup()
 
 KEY = M.KEY_PS4
 CHUNK = 65536
 STRIDED = (64, 128, 192, 224)
 FLUSH_BYTES = 768 << 20
-
-
-class Event:
-    def __init__(self):
-        self.h = ctypes.c_void_p()
-        _ok(hip().hipEventCreate(ctypes.byref(self.h)), "hipEventCreate")
-
-    def record(self, stream):
-        _ok(hip().hipEventRecord(self.h, ctypes.c_void_p(stream.handle)), "hipEventRecord")
-
-
-def elapsed_ms(e0, e1):
-    _ok(hip().hipEventSynchronize(e1.h), "hipEventSynchronize")
-    ms = ctypes.c_float()
-    _ok(hip().hipEventElapsedTime(ctypes.byref(ms), e0.h, e1.h), "hipEventElapsedTime")
-    return ms.value
 
 
 def policies(n):
@@ -65,30 +42,17 @@ def policies(n):
     return out
 
 
-def stats(ts, n):
-    t = sorted(ts)
-    med = t[len(t) // 2]
-    return {"median_ms": round(med, 5), "min_ms": round(t[0], 5), "max_ms": round(t[-1], 5), "TBps_2n": round(2 * n / (med * 1e-3) / 1e12, 4)}
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--sizes-mib", default="4096,1024")
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r13_keep.json"))
-    a = ap.parse_args()
+    a = H.arguments("r13_keep.json", sizes_mib="4096,1024").parse_args()
     assert a.warmup >= 3 and a.steps >= 20, "at least 3 warm-ups and 20 timed steps"
     M.use_testing_flavour()
     st = Stream()
-    e0, e1 = Event(), Event()
     flush = M.DeviceBuffer(FLUSH_BYTES)
     rows = {}
-    tile = np.random.default_rng(1).integers(0, 256, size=1 << 26, dtype=np.uint8)
+    tile = H.tile(1 << 26)
     for n in [int(x) << 20 for x in a.sizes_mib.split(",")]:
         buf = M.DeviceBuffer(n)
-        for off in range(0, n, tile.size):
-            buf.upload(tile[:min(tile.size, n - off)], offset=off)
+        H.fill(buf, n, tile_bytes=1 << 26)
         pol = policies(n)
         variants = list(pol)
 
@@ -98,10 +62,7 @@ def main():
             return M.last_launch()
 
         def timed(v):
-            e0.record(st)
-            one_pass(v)
-            e1.record(st)
-            return elapsed_ms(e0, e1)
+            return H.timed(st, one_pass, v)
 
         launch = {}
         for v in variants:
@@ -124,12 +85,12 @@ def main():
         assert np.array_equal(buf.download(1 << 20, offset=n - (1 << 20)), tile[(n - (1 << 20)) % tile.size:][:1 << 20]), "the passes did not cancel"
         row = {"bytes": n, "launch": launch, "warm": {}, "cold": {}, "after_other": {}}
         for v in variants:
-            row["warm"][v] = stats(warm[v], n)
-            row["cold"][v] = stats(cold[v], n)
-            row["after_other"][v] = stats(after_other[v], n)
+            row["warm"][v] = H.stats(warm[v], n, 2, "TBps_2n")
+            row["cold"][v] = H.stats(cold[v], n, 2, "TBps_2n")
+            row["after_other"][v] = H.stats(after_other[v], n, 2, "TBps_2n")
         for mode in ("warm", "cold"):
             m = {v: row[mode][v]["median_ms"] for v in variants}
-            row[mode + "_aa_spread_of_main"] = round(abs(m["main"] - m["main_again"]) / min(m["main"], m["main_again"]), 5)
+            row[mode + "_aa_spread_of_main"] = round(H.spread(m["main"], m["main_again"]), 5)
             row[mode + "_over_main"] = {v: round(m[v] / m["main"], 5) for v in variants}
         rows[str(n)] = row
         for mode in ("warm", "cold"):
@@ -139,13 +100,9 @@ def main():
     M.debug_set_keep(0, 0, 0)
     flush.free()
     st.destroy()
-    out = {"tool": "tools/bench_keep.py", "unit": "TB/s of 2n bytes per pass (n read + n written)", "when": time.strftime("%Y-%m-%dT%H:%M:%S"),
-           "warmup": a.warmup, "steps": a.steps, "key": KEY, "flush_bytes_cold": FLUSH_BYTES,
-           "kernel_source_hash": M.kernel_source_hash(), "keep_kernel_source_hash": M.keep_kernel_source_hash(), "sizes": rows}
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1)
-    print("wrote", a.out)
+    H.write_profile(a.out, {**H.profile_head("bench_keep.py", "TB/s of 2n bytes per pass (n read + n written)", a), "key": KEY,
+                            "flush_bytes_cold": FLUSH_BYTES, "kernel_source_hash": M.kernel_source_hash(),
+                            "keep_kernel_source_hash": M.keep_kernel_source_hash(), "sizes": rows})
 
 
 if __name__ == "__main__":

@@ -20,19 +20,13 @@ per pass.  One key, off_to = off_from - the segment's shift: compacting a reside
 
     python tools/bench_rekey_move_table.py [--shapes ...] [--other-lib PATH] [--warmup 2] [--steps 10] [--out profiles/r15_move_table.json]
 """
-import argparse
 import ctypes
-import json
-import os
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "tools"))
-import bench_rekey_move as R  # noqa: E402  (the harness: Event, fill, measure; it also puts the repository and tests/ on sys.path)
-import numpy as np  # noqa: E402
-import modulate_amd as M  # noqa: E402
-from hip_rt import Stream, hip, _ok  # noqa: E402
+import numpy as np
+
+import bench_common as H
+
+M, Stream, hip, _ok = H.setup()
 
 KEY = M.KEY_PS4
 OFF = (1 << 32) + (1 << 28)
@@ -59,10 +53,7 @@ def against_other(L, O, shape, st, stv, a):
     kk, k3 = M.as_int32(KEY), M.as_int32(M.KEY_PS3)
     src, dst = M.DeviceBuffer(n + d + 64), M.DeviceBuffer(n)
     ws = M.DeviceBuffer(M.move_workspace_bytes(n))
-    R.fill(src, n + d)
-    for name in ("modgpu_rekey_device_to", "modgpu_rekey_move_device"):
-        getattr(O, name).restype = ctypes.c_int
-        getattr(O, name).argtypes = getattr(L, name).argtypes
+    H.fill(src, n + d)
 
     def one_pass(v):
         lib = O if v.startswith("other") else L
@@ -74,7 +65,7 @@ def against_other(L, O, shape, st, stv, a):
             raise RuntimeError(shape + " failed")
         return None if lib is O else M.last_launch()
 
-    row = R.measure(["this", "other", "this2", "other2"], one_pass, st, a.warmup, a.steps, n)
+    row = H.measure_with_aa(st, ["this", "other", "this2", "other2"], one_pass, a.warmup, a.steps, n)
     row["this_over_other"] = round(row["this"]["median_ms"] / row["other"]["median_ms"], 5)
     row["bar"] = {"rule": "|this / other - 1| <= the run's A/A spread", "aa_spread": row["aa_spread"], "met": abs(row["this_over_other"] - 1) <= row["aa_spread"]}
     for b in (src, dst, ws):
@@ -83,13 +74,9 @@ def against_other(L, O, shape, st, stv, a):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--shapes", default=ALL_SHAPES)
+    ap = H.arguments("r15_move_table.json", warmup=2, steps=10, shapes=ALL_SHAPES)
     ap.add_argument("--other-lib", default=None, help="another build's libmodgpu.so (the parent commit's) for rekey4g and move4g")
-    ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--singles-steps", type=int, default=3, help="steps of cfg4, whose 99 000 single calls take seconds per pass")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r15_move_table.json"))
     a = ap.parse_args()
     assert a.warmup >= 1 and a.steps >= 1
     L = M.lib()
@@ -102,11 +89,11 @@ def main():
             if not a.other_lib:
                 print(shape, "skipped: no --other-lib")
                 continue
-            row, shown = against_other(L, ctypes.CDLL(a.other_lib), shape, st, stv, a)
+            row, shown = against_other(L, H.other_library(a.other_lib, ["modgpu_rekey_device_to", "modgpu_rekey_move_device"], L), shape, st, stv, a)
         else:
             keep = kept(shape)
             part, other = M.DeviceBuffer(PART + 64), M.DeviceBuffer(PART + 64)
-            R.fill(part, PART)
+            H.fill(part, PART)
             # (compaction_table packs from the first kept range's offset; here the part BEGINS with a removed file, so the ranges are
             # packed from offset 0 and the first segment slides too)
             first = keep[0][0]
@@ -140,7 +127,7 @@ def main():
                 return M.last_launch()
 
             variants = ["table", "singles", "copy", "table2", "singles2", "copy2"]
-            row = R.measure(variants, one_pass, st, 1 if shape == "cfg4" else a.warmup, a.singles_steps if shape == "cfg4" else a.steps, total)
+            row = H.measure_with_aa(st, variants, one_pass, 1 if shape == "cfg4" else a.warmup, a.singles_steps if shape == "cfg4" else a.steps, total)
             st.sync()
             assert M.rekey_move_table_status(ws) == (None, None) and M.move_status(ws_single) is None
             row["entries"] = int(t.size)
@@ -155,14 +142,11 @@ def main():
         print("%-8s " % shape + "  ".join("%s %.3f ms %.2f TB/s" % (v, row[v]["median_ms"], row[v]["TBps"]) for v in shown)
               + "  A/A %.2f %%" % (100 * row["aa_spread"]) + ("  bar %s" % row["bar"] if "bar" in row else ""), flush=True)
     st.destroy()
-    out = {"tool": "tools/bench_rekey_move_table.py", "unit": "TB/s of payload bytes moved per pass", "when": time.strftime("%Y-%m-%dT%H:%M:%S"),
-           "warmup": a.warmup, "steps": a.steps, "singles_steps": a.singles_steps, "key": KEY, "off_from": OFF, "part_bytes": PART, "removed_file_bytes": FILE,
-           "rekey_move_table_kernel_source_hash": M.rekey_move_table_kernel_source_hash(), "rekey_kernel_source_hash": M.rekey_kernel_source_hash(),
-           "rekey_table_kernel_source_hash": M.rekey_table_kernel_source_hash(), "shapes": rows}
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1)
-    print("wrote", a.out)
+    H.write_profile(a.out, {**H.profile_head("bench_rekey_move_table.py", "TB/s of payload bytes moved per pass", a),
+                            "singles_steps": a.singles_steps, "key": KEY, "off_from": OFF, "part_bytes": PART, "removed_file_bytes": FILE,
+                            "rekey_move_table_kernel_source_hash": M.rekey_move_table_kernel_source_hash(),
+                            "rekey_kernel_source_hash": M.rekey_kernel_source_hash(),
+                            "rekey_table_kernel_source_hash": M.rekey_table_kernel_source_hash(), "shapes": rows})
 
 
 if __name__ == "__main__":

@@ -16,40 +16,18 @@ and writes n).
 
     python tools/bench_verify.py [--sizes-kib 64,1024,16384,4194304] [--warmup 3] [--steps 20] [--out profiles/r11_verify.json]
 """
-import argparse
 import ctypes
-import json
-import os
-import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-os.environ["MODGPU_REQUIRE_GPU"] = "1"
-import numpy as np  # noqa: E402
-import modulate_amd as M  # noqa: E402
-from hip_rt import Stream, hip, _ok  # noqa: E402  (tests/hip_rt.py: streams over the HIP runtime libmodgpu.so brought in)
+import numpy as np
+
+import bench_common as H
+
+M, Stream, hip, _ok = H.setup()
 
 SINGLE = ("verify", "verify_200", "to", "to_again", "verify_mis", "to_mis", "verify_wrong")
 BATCH = ("verify_batch", "to_batch")
 KEY, WRONG = M.KEY_PS4, M.KEY_PS3
-
-
-class Event:
-    def __init__(self):
-        self.h = ctypes.c_void_p()
-        _ok(hip().hipEventCreate(ctypes.byref(self.h)), "hipEventCreate")
-
-    def record(self, stream):
-        _ok(hip().hipEventRecord(self.h, ctypes.c_void_p(stream.handle)), "hipEventRecord")
-
-
-def elapsed_ms(e0, e1):
-    _ok(hip().hipEventSynchronize(e1.h), "hipEventSynchronize")
-    ms = ctypes.c_float()
-    _ok(hip().hipEventElapsedTime(ctypes.byref(ms), e0.h, e1.h), "hipEventElapsedTime")
-    return ms.value
 
 
 def one_pass(v, B, n, st):
@@ -78,57 +56,34 @@ def one_pass(v, B, n, st):
     return M.last_launch()
 
 
-def stats(ts, n):
-    t = sorted(ts)
-    med = t[len(t) // 2]
-    return {"median_ms": round(med, 5), "min_ms": round(t[0], 5), "max_ms": round(t[-1], 5), "TBps_2n": round(2 * n / (med * 1e-3) / 1e12, 4)}
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--sizes-kib", default="64,1024,16384,4194304")
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r11_verify.json"))
-    a = ap.parse_args()
+    a = H.arguments("r11_verify.json", sizes_kib="64,1024,16384,4194304").parse_args()
     assert a.warmup >= 3 and a.steps >= 20, "at least 3 warm-ups and 20 timed steps"
     M.use_testing_flavour()  # the same device code as libmodgpu.so, plus the grid switch
     st = Stream()
-    e0, e1 = Event(), Event()
     rows = {}
-    tile = np.random.default_rng(1).integers(0, 256, size=1 << 24, dtype=np.uint8)
     sizes = [int(x) << 10 for x in a.sizes_kib.split(",")]
     for n in sizes:
         sbuf, dbuf, mbuf, rbuf = M.DeviceBuffer(n + 64), M.DeviceBuffer(n + 64), M.DeviceBuffer(n + 64), M.DeviceBuffer(32 * 16)
-        for off in range(0, n + 64, tile.size):
-            sbuf.upload(tile[:min(tile.size, n + 64 - off)], offset=off)
+        H.fill(sbuf, n + 64)
         B = {"src": sbuf.ptr, "dst": dbuf.ptr, "dst_mis": mbuf.ptr, "res": rbuf.ptr}  # hipMalloc: 256-byte aligned, phase 0
         variants = SINGLE + (BATCH if n == max(sizes) and n % 16 == 0 else ())
         order = [v for v in variants if v.startswith("to")] + [v for v in variants if not v.startswith("to")]  # the `to` passes make `expect`
-        launch, seen = {}, {}
-        for v in order:
-            for _ in range(a.warmup):
-                info = one_pass(v, B, n, st)
-            launch[v] = {"kernel": info["kernel"], "variant": info["variant"], "grid": info["grid"]}
+        seen = {}
+
+        def checked(v, info):
             if v.startswith("verify"):
-                st.sync()
                 r = M.verify_results(rbuf, 16 if v == "verify_batch" else 1)
                 seen[v] = {"mismatches": int(r["mismatches"].sum()), "first_mismatch": int(r["first_mismatch"].min()), "n": int(r["n"].sum())}
                 assert seen[v]["n"] == n and (seen[v]["mismatches"] == 0) == (v != "verify_wrong"), (v, seen[v])
-        st.sync()
-        times = {v: [] for v in variants}
-        for _ in range(a.steps):
-            for v in variants:
-                e0.record(st)
-                one_pass(v, B, n, st)
-                e1.record(st)
-                times[v].append(elapsed_ms(e0, e1))
+
+        times, info, _ = H.measure(st, variants, lambda v: one_pass(v, B, n, st), a.warmup, a.steps, warm_order=order, after_warmup=checked)
         M.debug_set_verify_form(0)
-        row = {"bytes": n, "launch": launch, "results": seen}
+        row = {"bytes": n, "launch": {v: H.launch_row(info[v]) for v in order}, "results": seen}
         for v in variants:
-            row[v] = stats(times[v], n)
+            row[v] = H.stats(times[v], n, 2, "TBps_2n")
         med = {v: row[v]["median_ms"] for v in variants}
-        spread = abs(med["to"] - med["to_again"]) / min(med["to"], med["to_again"])
+        spread = H.spread(med["to"], med["to_again"])
         bound = max(1.05, 1 + 2 * spread)
         row["aa_spread_of_to"] = round(spread, 5)
         row["bound"] = round(bound, 5)
@@ -157,15 +112,12 @@ def main():
         for b in (sbuf, dbuf, mbuf, rbuf):
             b.free()
     st.destroy()
-    out = {"tool": "tools/bench_verify.py", "unit": "TB/s of 2n bytes per pass (verify: 2n read; out of place: n read + n written)",
-           "when": time.strftime("%Y-%m-%dT%H:%M:%S"), "warmup": a.warmup, "steps": a.steps, "key": KEY, "wrong_key": WRONG,
-           "rule": "verify's median <= the out-of-place median x max(1.05, 1 + 2 x A/A spread of the out-of-place pass in the same run)",
-           "verify_kernel_source_hash": M.verify_kernel_source_hash(), "to_kernel_source_hash": M.to_kernel_source_hash(),
-           "misaligned": "src phase 5, expect / dst phase 0", "sizes": rows}
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1)
-    print("wrote", a.out)
+    H.write_profile(a.out, {
+        **H.profile_head("bench_verify.py", "TB/s of 2n bytes per pass (verify: 2n read; out of place: n read + n written)", a),
+        "key": KEY, "wrong_key": WRONG,
+        "rule": "verify's median <= the out-of-place median x max(1.05, 1 + 2 x A/A spread of the out-of-place pass in the same run)",
+        "verify_kernel_source_hash": M.verify_kernel_source_hash(), "to_kernel_source_hash": M.to_kernel_source_hash(),
+        "misaligned": "src phase 5, expect / dst phase 0", "sizes": rows})
 
 
 if __name__ == "__main__":

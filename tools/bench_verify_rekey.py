@@ -16,41 +16,14 @@ stream around every single pass; the variants alternate step by step so drift hi
 
     python tools/bench_verify_rekey.py [--sizes-kib 64,1024,16384,4194304] [--warmup 3] [--steps 20] [--out profiles/r13_verify_rekey.json]
 """
-import argparse
-import ctypes
-import json
-import os
-import sys
-import time
+import bench_common as H
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
-os.environ["MODGPU_REQUIRE_GPU"] = "1"
-import numpy as np  # noqa: E402
-import modulate_amd as M  # noqa: E402
-from hip_rt import Stream, hip, _ok  # noqa: E402  (tests/hip_rt.py: streams over the HIP runtime libmodgpu.so brought in)
+M, Stream, hip, _ok = H.setup()
 
 SINGLE = ("vr", "rekey", "rekey_again", "vr_mis", "rekey_mis", "vr_wrong")
 LARGEST = ("vr_batch", "rekey_batch", "route_today")
 KF, KT, WRONG = M.KEY_PS3, M.KEY_PS4, 12345
 OF, OT = 3, (1 << 32) + 11
-
-
-class Event:
-    def __init__(self):
-        self.h = ctypes.c_void_p()
-        _ok(hip().hipEventCreate(ctypes.byref(self.h)), "hipEventCreate")
-
-    def record(self, stream):
-        _ok(hip().hipEventRecord(self.h, ctypes.c_void_p(stream.handle)), "hipEventRecord")
-
-
-def elapsed_ms(e0, e1):
-    _ok(hip().hipEventSynchronize(e1.h), "hipEventSynchronize")
-    ms = ctypes.c_float()
-    _ok(hip().hipEventElapsedTime(ctypes.byref(ms), e0.h, e1.h), "hipEventElapsedTime")
-    return ms.value
 
 
 def one_pass(v, B, n, st):
@@ -79,57 +52,34 @@ def one_pass(v, B, n, st):
     return M.last_launch()
 
 
-def stats(ts, n):
-    t = sorted(ts)
-    med = t[len(t) // 2]
-    return {"median_ms": round(med, 5), "min_ms": round(t[0], 5), "max_ms": round(t[-1], 5), "TBps_2n": round(2 * n / (med * 1e-3) / 1e12, 4)}
-
-
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--sizes-kib", default="64,1024,16384,4194304")
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r13_verify_rekey.json"))
-    a = ap.parse_args()
+    a = H.arguments("r13_verify_rekey.json", sizes_kib="64,1024,16384,4194304").parse_args()
     assert a.warmup >= 3 and a.steps >= 20, "at least 3 warm-ups and 20 timed steps"
     st = Stream()
-    e0, e1 = Event(), Event()
     rows = {}
-    tile = np.random.default_rng(1).integers(0, 256, size=1 << 24, dtype=np.uint8)
     sizes = [int(x) << 10 for x in a.sizes_kib.split(",")]
     for n in sizes:
         largest = n == max(sizes) and n % 16 == 0
         sbuf, dbuf, mbuf, rbuf = M.DeviceBuffer(n + 64), M.DeviceBuffer(n + 64), M.DeviceBuffer(n + 64), M.DeviceBuffer(32 * 16)
         xbuf = M.DeviceBuffer(n + 64) if largest else None
-        for off in range(0, n + 64, tile.size):
-            sbuf.upload(tile[:min(tile.size, n + 64 - off)], offset=off)
+        H.fill(sbuf, n + 64)
         B = {"src": sbuf.ptr, "dst": dbuf.ptr, "dst_mis": mbuf.ptr, "res": rbuf.ptr, "scratch": xbuf.ptr if xbuf else 0}  # hipMalloc: phase 0
         variants = SINGLE + (LARGEST if largest else ())
         order = [v for v in variants if v.startswith("rekey")] + [v for v in variants if not v.startswith("rekey")]  # the rekey passes make `expect`
-        launch, seen = {}, {}
-        for v in order:
-            for _ in range(a.warmup):
-                info = one_pass(v, B, n, st)
-            launch[v] = {"kernel": info["kernel"], "variant": info["variant"], "grid": info["grid"]}
+        seen = {}
+
+        def checked(v, info):
             if not v.startswith("rekey"):
-                st.sync()
                 r = M.verify_results(rbuf, 16 if v == "vr_batch" else 1)
                 seen[v] = {"mismatches": int(r["mismatches"].sum()), "first_mismatch": int(r["first_mismatch"].min()), "n": int(r["n"].sum())}
                 assert seen[v]["n"] == n and (seen[v]["mismatches"] == 0) == (v != "vr_wrong"), (v, seen[v])
-        st.sync()
-        times = {v: [] for v in variants}
-        for _ in range(a.steps):
-            for v in variants:
-                e0.record(st)
-                one_pass(v, B, n, st)
-                e1.record(st)
-                times[v].append(elapsed_ms(e0, e1))
-        row = {"bytes": n, "launch": launch, "results": seen}
+
+        times, info, _ = H.measure(st, variants, lambda v: one_pass(v, B, n, st), a.warmup, a.steps, warm_order=order, after_warmup=checked)
+        row = {"bytes": n, "launch": {v: H.launch_row(info[v]) for v in order}, "results": seen}
         for v in variants:
-            row[v] = stats(times[v], n)
+            row[v] = H.stats(times[v], n, 2, "TBps_2n")
         med = {v: row[v]["median_ms"] for v in variants}
-        spread = abs(med["rekey"] - med["rekey_again"]) / min(med["rekey"], med["rekey_again"])
+        spread = H.spread(med["rekey"], med["rekey_again"])
         bound = max(1.05, 1 + 2 * spread)
         row["aa_spread_of_rekey"] = round(spread, 5)
         row["bound"] = round(bound, 5)
@@ -145,16 +95,12 @@ def main():
         for b in (sbuf, dbuf, mbuf, rbuf) + ((xbuf,) if xbuf else ()):
             b.free()
     st.destroy()
-    out = {"tool": "tools/bench_verify_rekey.py", "unit": "TB/s of 2n bytes per pass (rekey verify: 2n read; rekey: n read + n written)",
-           "when": time.strftime("%Y-%m-%dT%H:%M:%S"), "warmup": a.warmup, "steps": a.steps, "key_from": KF, "key_to": KT, "wrong_key_to": WRONG,
-           "off_from": OF, "off_to": OT,
-           "rule": "the rekey verify's median <= the rekey median x max(1.05, 1 + 2 x A/A spread of the rekey pass in the same run)",
-           "rekey_verify_kernel_source_hash": M.rekey_verify_kernel_source_hash(), "rekey_kernel_source_hash": M.rekey_kernel_source_hash(),
-           "verify_kernel_source_hash": M.verify_kernel_source_hash(), "misaligned": "src phase 5, expect / dst phase 0", "sizes": rows}
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1)
-    print("wrote", a.out)
+    H.write_profile(a.out, {
+        **H.profile_head("bench_verify_rekey.py", "TB/s of 2n bytes per pass (rekey verify: 2n read; rekey: n read + n written)", a),
+        "key_from": KF, "key_to": KT, "wrong_key_to": WRONG, "off_from": OF, "off_to": OT,
+        "rule": "the rekey verify's median <= the rekey median x max(1.05, 1 + 2 x A/A spread of the rekey pass in the same run)",
+        "rekey_verify_kernel_source_hash": M.rekey_verify_kernel_source_hash(), "rekey_kernel_source_hash": M.rekey_kernel_source_hash(),
+        "verify_kernel_source_hash": M.verify_kernel_source_hash(), "misaligned": "src phase 5, expect / dst phase 0", "sizes": rows})
 
 
 if __name__ == "__main__":
