@@ -653,6 +653,55 @@ uint64_t modgpu_cycle_digest_table_workspace_bytes(uint64_t n_entries);
 int modgpu_cycle_digest_table_device(const modgpu_table_entry_t *dev_entries, uint64_t n_entries, modgpu_digest_result_t *dev_records,
                                      uint32_t side, void *dev_workspace, uint64_t workspace_bytes, int device, void *hip_stream);
 
+/* ---- DIGEST CHECK: are these records the checksums of my manifest, and if not, which entry first?  On the device, in two launches ------
+ * The digest calls leave one record per entry in device memory; the caller holds a manifest of Adler-32 values.  This call closes every
+ * record where it lies and compares it with the manifest, so that nobody downloads 32 bytes per entry, finalises them on the host and
+ * compares in a loop -- and so that a captured graph that digests a part can decide without the host.  It takes the records of every
+ * digest producer: modgpu_digest_device / _batch_device, modgpu_digest_table_device, modgpu_cycle_digest_table_device.
+ * Entry i is BAD when the Adler-32 of dev_records[i] differs from dev_expect[i]; the Adler-32 is exactly what modgpu_digest_adler32
+ * computes (the residues of s1, s2 and n mod 65521 first; A = (1 + s1) % m, B = (n + n * s1 - s2) % m; B << 16 | A; s1 and s2 may hold
+ * any 64-bit value), and both halves are compared.
+ * The whole check in 32 bytes.  The layout is pinned (8-byte aligned). */
+typedef struct modgpu_digest_check_summary {
+    uint64_t bad_entries;     /* entries whose record does not close to expect[i] */
+    uint64_t first_bad_entry; /* the lowest such i; UINT64_MAX if none */
+    uint64_t entries;         /* n_entries of the call that ran */
+    uint64_t refused;         /* 1: the table call that produced the records was refused (see below); else 0 */
+} modgpu_digest_check_summary_t;
+
+/* The bytes of a bitmap over n_entries: 8 * ceil(n_entries / 64); 0 for 0 or above MODGPU_TABLE_MAX_ENTRIES. */
+uint64_t modgpu_digest_check_bits_bytes(uint64_t n_entries);
+
+/* dev_records: n_entries records; dev_expect: n_entries Adler-32 values; dev_summary: the 32 bytes above; all device memory of `device`.
+ *   * dev_bad_bits, when not NULL: modgpu_digest_check_bits_bytes(n_entries) bytes.  Word w holds bit b set exactly when entry
+ *     64 * w + b is bad; every word of ceil(n_entries / 64) is stored whole and the tail bits are 0, so nothing needs clearing
+ *     beforehand.  A caller who wants to know which entries are bad downloads n / 8 bytes instead of 32 n.
+ *   * dev_table_workspace, when not NULL: the workspace of the modgpu_digest_table_device or modgpu_cycle_digest_table_device call
+ *     that produced the records (only its first 64 bytes, the table call's header, are looked at).  The check reads the header's
+ *     status ON THE DEVICE WHEN IT RUNS: if that table call was refused -- its records are then whatever the caller left there -- the
+ *     check compares nothing, writes {0, UINT64_MAX, n_entries, 1} and leaves dev_bad_bits untouched.  A captured "digest table + check"
+ *     graph is so honest on every replay, with no host in between.  With NULL the records are taken as they are: use NULL for the
+ *     records of modgpu_digest_device / _batch_device.
+ *   * Asynchronous on `hip_stream`; `device` -1 = the current device, an explicit device leaves the thread's current device as it was;
+ *     allocation-free; capturable into a hipGraph.  THE CALL INITIALISES ITS SUMMARY ITSELF, IN STREAM ORDER, so a replay starts clean.
+ *     It draws no ticket and has no degraded route.  EVERYTHING BUT THE SUMMARY AND THE BITS IS READ-ONLY.  The caller orders the call
+ *     behind the producer: the same stream, or an event.
+ *   * TWO launches whatever n_entries is (the init, then the check): path_stats().gpu_launches counts 2, modgpu_last_launch reports
+ *     the check launch as variant 19 with `bytes` = 0 and modgpu_verify_table_kernel_source_hash().
+ *   * Tier 1 (host, MODGPU_ERR_INVALID before anything is queued, with a text in modgpu_last_error()): NULL records, expect or summary
+ *     with n_entries > 0; records, summary, bits or the table workspace not 8-byte aligned; expect not 4-byte aligned; more than
+ *     MODGPU_TABLE_MAX_ENTRIES entries; summary or bits overlapping the records, expect or each other; any of the given ranges (of
+ *     the table workspace its first 64 bytes) not reported as device memory of `device` (both ends of a range are asked about, as
+ *     modgpu_digest_results does).  n_entries == 0 queues nothing and touches nothing. */
+int modgpu_digest_check_device(const modgpu_digest_result_t *dev_records, const uint32_t *dev_expect, uint64_t n_entries,
+                               const void *dev_table_workspace, modgpu_digest_check_summary_t *dev_summary, uint64_t *dev_bad_bits,
+                               int device, void *hip_stream);
+
+/* The summary from device memory of `device` into host_out.  Synchronous (a small copy from the device, like
+ * modgpu_verify_table_summary): call it after the caller has synchronised the stream the check ran on.  MODGPU_ERR_INVALID when
+ * refused != 0 (host_out is filled all the same). */
+int modgpu_digest_check_summary(const modgpu_digest_check_summary_t *dev_summary, int device, modgpu_digest_check_summary_t *host_out);
+
 /* Replaces CEncryptionCycler::Cycle (CEncryptionCycler.cpp:4-14) for a caller-owned HOST buffer,
  * on the GPU.  Pageable memory is staged through page-locked slots owned by this library (memcpy ->
  * slot -> kernel across PCIe on the slot -> memcpy back, chunked over several host threads and

@@ -69,6 +69,10 @@ int modgpu_time_digest_table_device(const void *dev_entries, uint64_t n_entries,
  * and one records array, `side` as the call's. */
 int modgpu_time_cycle_digest_table_device(const void *dev_entries, uint64_t n_entries, void *dev_records, uint32_t side, void *dev_workspace,
                                           uint64_t workspace_bytes, int device, void *hip_stream, int iters, float *ms_per_call);
+/* The same for modgpu_digest_check_device: `iters` back-to-back digest checks (two launches each) on one summary and one bitmap;
+ * dev_table_workspace and dev_bad_bits may be NULL, as the call's. */
+int modgpu_time_digest_check_device(const void *dev_records, const void *dev_expect, uint64_t n_entries, const void *dev_table_workspace,
+                                    void *dev_summary, void *dev_bad_bits, int device, void *hip_stream, int iters, float *ms_per_call);
 
 /* The launch the calling thread made last (any entry point), as the library planned it. */
 typedef struct modgpu_launch_info {
@@ -98,7 +102,9 @@ typedef struct modgpu_launch_info {
                              17 = the digest table call's stream launch (modgpu_digest_table_device: the verify table call's stream
                                   kernel in its digest loop; `bytes` = 0, as for 8),
                              18 = the cycle digest table call's stream launch (modgpu_cycle_digest_table_device: the table call's
-                                  stream kernel in its digesting loop; `bytes` = 0, as for 8) */
+                                  stream kernel in its digesting loop; `bytes` = 0, as for 8),
+                             19 = the check launch of modgpu_digest_check_device (the verify table call's finish kernel in its check
+                                  mode, "modgpu_cycle_verify_table_finish"; `bytes` = 0, `chunk_bytes` = 0) */
     uint32_t grid;        /* workgroups launched                                                  */
     uint32_t block;       /* threads per workgroup                                                */
     uint32_t chunk_bytes; /* bytes one workgroup trip covers                                      */
@@ -119,7 +125,8 @@ typedef struct modgpu_launch_info {
                                 modgpu_rekey_move_table_kernel_source_hash() for variant 15,
                                 modgpu_to_kernel_source_hash() for variant 16,
                                 modgpu_verify_table_kernel_source_hash() for variant 17,
-                                modgpu_table_kernel_source_hash() for variant 18; static storage */
+                                modgpu_table_kernel_source_hash() for variant 18,
+                                modgpu_verify_table_kernel_source_hash() for variant 19; static storage */
 } modgpu_launch_info_t;
 int modgpu_last_launch(modgpu_launch_info_t *out);
 

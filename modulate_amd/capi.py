@@ -106,6 +106,9 @@ EXPORTS = {
     "modgpu_cycle_digest_table_device": (_int, [_vp, _u64, _vp, ctypes.c_uint32, _vp, _u64, _int, _vp]),
     "modgpu_digest_results": (_int, [_vp, _u64, _int, _vp, ctypes.POINTER(ctypes.c_uint32)]),
     "modgpu_digest_adler32": (ctypes.c_uint32, [_vp]),
+    "modgpu_digest_check_bits_bytes": (_u64, [_u64]),
+    "modgpu_digest_check_device": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _int, _vp]),
+    "modgpu_digest_check_summary": (_int, [_vp, _int, _vp]),
 }
 
 
@@ -138,6 +141,8 @@ DIGEST_OUTPUT, DIGEST_INPUT = 0, 1  # MODGPU_DIGEST_OUTPUT / _INPUT: which side 
 DIGEST_RESULT_DTYPE = np.dtype([("s1", "<u8"), ("s2", "<u8"), ("n", "<u8"), ("reserved", "<u8")])
 # modgpu_verify_table_summary_t (include/modgpu.h): 32 bytes
 VERIFY_TABLE_SUMMARY_DTYPE = np.dtype([("mismatches", "<u8"), ("first_bad_entry", "<u8"), ("entries", "<u8"), ("reserved", "<u8")])
+# modgpu_digest_check_summary_t (include/modgpu.h): 32 bytes
+DIGEST_CHECK_SUMMARY_DTYPE = np.dtype([("bad_entries", "<u8"), ("first_bad_entry", "<u8"), ("entries", "<u8"), ("refused", "<u8")])
 
 
 class PathStats(ctypes.Structure):
@@ -204,6 +209,7 @@ TESTING_EXPORTS = {
     "modgpu_rekey_move_table_kernel_source_hash": (ctypes.c_char_p, []),
     "modgpu_keep_policy": (_int, [_u64, ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_uint32)]),
     "modgpu_time_digest_device": (_int, [_vp, _vp, _u64, _i32, _u64, _vp, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
+    "modgpu_time_digest_check_device": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
 }
 # include/modgpu_testing.h, modgpu_debug_* group: ONLY in libmodgpu_testing.so
 DEBUG_EXPORTS = {
@@ -840,7 +846,7 @@ def _no_digest_results():
 
 
 def _table_call(call, entries, dtype, n, workspace, need, device, stream, refused, *, validate=None, needed="n (the entry count) is",
-                known=True, extra=(), fetch=None, results=None, empty=None, status=table_status, gave_up=None):
+                known=True, extra=(), fetch=None, results=None, empty=None, status=table_status, gave_up=None, then=None):
     """Every *_table_device call: library function `call` gets (table, n, [results], *extra, workspace, its bytes, device, stream).
     The table `entries` is a host array of `dtype` -- checked with `validate`, uploaded; an empty one makes no call and returns
     empty(), or None -- or is in device memory already: then n is needed, and whatever else the caller says is `known`, and its
@@ -848,7 +854,10 @@ def _table_call(call, entries, dtype, n, workspace, need, device, stream, refuse
     the calls that have a `fetch` (verify_results or digest_results); None makes one, as workspace=None makes one of need(n) bytes.
     When a buffer was made here the call is waited for, `status` is read -- table_status's one outcome, or rekey_move_table_status's
     pair -- and ModGpuError raised with the text `refused` (code 1) or `gave_up` (code 3); then the results are fetched and returned,
-    and every buffer made here is freed, whatever happened.  Otherwise the call is asynchronous and None is returned."""
+    and every buffer made here is freed, whatever happened.  Otherwise the call is asynchronous and None is returned.
+    `then(res, n, ws, stv, own)`, for a table that was uploaded here, queues more work behind the call on the same stream -- the buffers
+    it makes go into `own` -- and returns what reads that work's outcome once the stream has been waited for and the status was clean:
+    the wrapper then returns the pair (what it returns without `then`, that outcome)."""
     own = []
     try:
         if isinstance(entries, np.ndarray):
@@ -875,6 +884,7 @@ def _table_call(call, entries, dtype, n, workspace, need, device, stream, refuse
         _check(getattr(lib(), call)(_vp(_dev_addr(entries)), n, *((_vp(res),) if fetch else ()), *extra, _vp(ws), ws_bytes, device, stv))
         if not own:
             return None
+        after = then(res, n, ws, stv, own) if then else None
         _check(lib().modgpu_sync(device, stv))
         outcome = status(ws, device)
         bad, stalled = outcome if isinstance(outcome, tuple) else (outcome, None)
@@ -882,7 +892,8 @@ def _table_call(call, entries, dtype, n, workspace, need, device, stream, refuse
             raise ModGpuError(1, refused.format(bad))
         if stalled is not None:
             raise ModGpuError(3, gave_up.format(stalled))
-        return fetch(res, n, device) if fetch else None
+        fetched = fetch(res, n, device) if fetch else None
+        return (fetched, after()) if then else fetched
     finally:
         for b in own:
             b.free()
@@ -1301,6 +1312,106 @@ def debug_set_cycle_digest_table_grid(grid=0):
     _debug_lib().modgpu_debug_set_cycle_digest_table_grid(grid)
 
 
+def digest_check_bits_bytes(n_entries):
+    """bytes of a digest check's bitmap over n_entries: 8 * ceil(n / 64) (0 for none, or above the table calls' limit)"""
+    return lib().modgpu_digest_check_bits_bytes(n_entries)
+
+
+def _no_bad_entries():
+    return 0, None, np.zeros(0, dtype=np.uint64)
+
+
+def digest_check_result(summary, n, bad_bits=None, device=-1):
+    """What a digest check left in `summary` (and `bad_bits`; DeviceBuffer or address each): (bad entries, the lowest bad entry or
+    None, the bad indices as a uint64 array -- None without a bitmap).  Synchronous small copies (32 bytes, and n / 8 only if an entry
+    is bad): synchronise the stream the check ran on first.  Raises ModGpuError if the table call that produced the records had been
+    refused (nothing was compared)."""
+    out = np.zeros(1, dtype=DIGEST_CHECK_SUMMARY_DTYPE)
+    _check(lib().modgpu_digest_check_summary(_vp(_dev_addr(summary)), device, _vp(out.ctypes.data)))
+    bad, first = int(out["bad_entries"][0]), int(out["first_bad_entry"][0])
+    if bad_bits is None:
+        return bad, None if first == VERIFY_NONE else first, None
+    if not bad:
+        return _no_bad_entries()
+    words = np.zeros((n + 63) // 64, dtype="<u8")
+    _check(lib().modgpu_d2h(_vp(words.ctypes.data), _vp(_dev_addr(bad_bits)), words.nbytes, device))
+    return bad, first, np.flatnonzero(np.unpackbits(words.view(np.uint8), bitorder="little")[:n]).astype(np.uint64)
+
+
+def _queue_digest_check(records, expect, n, table_workspace, summary, bad_bits, device, stv, own):
+    """One modgpu_digest_check_device call queued on stream `stv`; a host manifest is uploaded, and a missing bitmap made, into
+    buffers appended to `own` (the caller frees them).  Returns the bitmap."""
+    if isinstance(expect, np.ndarray):
+        e = np.ascontiguousarray(expect, dtype=np.uint32)
+        if e.size < n:
+            raise ValueError(f"a manifest of {e.size} values for {n} entries")
+        expect = DeviceBuffer(max(4 * n, 4), device)
+        own.append(expect)
+        expect.upload(e[:n].view(np.uint8))
+    if bad_bits is None:
+        bad_bits = DeviceBuffer(max(digest_check_bits_bytes(n), 8), device)
+        own.append(bad_bits)
+    _check(lib().modgpu_digest_check_device(_vp(_dev_addr(records)), _vp(_dev_addr(expect)), n,
+                                            _vp(_dev_addr(table_workspace) if table_workspace is not None else 0), _vp(_dev_addr(summary)),
+                                            _vp(_dev_addr(bad_bits)), device, stv))
+    return bad_bits
+
+
+def digest_check_device(records, expect, n, table_workspace=None, summary=None, bad_bits=None, device=-1, stream=None):
+    """CHECKS n digest records in device memory (a DeviceBuffer or an address: what digest_device, digest_batch_device,
+    digest_table_device or cycle_digest_table_device left there) against a manifest of Adler-32 values, on the device, in two
+    launches: entry i is bad when its record does not close to expect[i].  `expect` is a device address, a DeviceBuffer or a host
+    uint32 array (uploaded).  `table_workspace`, when given, is the workspace of the table call that produced the records: had the
+    device refused that call nothing is compared and ModGpuError is raised.  `summary` (32 bytes) and `bad_bits`
+    (digest_check_bits_bytes(n) bytes) are device memory.  With summary=None one is made (and a bitmap, unless given), the stream
+    synchronised and (bad entries, the lowest bad entry or None, the bad indices as a uint64 array) returned after reading back 32
+    bytes, and n / 8 more only if an entry is bad.  With a summary of the caller's the call is asynchronous on `stream` -- it can be
+    captured into a graph --, returns None, and digest_check_result(summary, n, bad_bits) tells the outcome after a synchronise; no
+    bitmap is written unless one is given."""
+    if not n:
+        return _no_bad_entries() if summary is None else None
+    stv = _vp(stream or 0)
+    own = []
+    try:
+        if summary is not None:
+            if isinstance(expect, np.ndarray):
+                raise TypeError("an asynchronous check needs its manifest in device memory")
+            _check(lib().modgpu_digest_check_device(_vp(_dev_addr(records)), _vp(_dev_addr(expect)), n,
+                                                    _vp(_dev_addr(table_workspace) if table_workspace is not None else 0), _vp(_dev_addr(summary)),
+                                                    _vp(_dev_addr(bad_bits) if bad_bits is not None else 0), device, stv))
+            return None
+        summary = DeviceBuffer(32, device)
+        own.append(summary)
+        bad_bits = _queue_digest_check(records, expect, n, table_workspace, summary, bad_bits, device, stv, own)
+        _check(lib().modgpu_sync(device, stv))
+        return digest_check_result(summary, n, bad_bits, device)
+    finally:
+        for b in own:
+            b.free()
+
+
+def time_digest_check_device(records, expect, n, summary, bad_bits=None, table_workspace=None, device=-1, stream=None, iters=2):
+    """Mean ms per digest check (two launches) over `iters` calls, HIP events on the launch stream; everything resident."""
+    return _time_call("modgpu_time_digest_check_device", (_vp(_dev_addr(records)), _vp(_dev_addr(expect)), n,
+                                                          _vp(_dev_addr(table_workspace) if table_workspace is not None else 0), _vp(_dev_addr(summary)),
+                                                          _vp(_dev_addr(bad_bits) if bad_bits is not None else 0)), device, stream, iters)
+
+
+def _check_behind(expect, device):
+    """`then` of a digest producing table call (_table_call): a digest check of its records against `expect`, queued behind it"""
+    def then(res, n, ws, stv, own):
+        summary = DeviceBuffer(32, device)
+        own.append(summary)
+        bad_bits = _queue_digest_check(res, expect, n, ws, summary, None, device, stv, own)
+        return lambda: digest_check_result(summary, n, bad_bits, device)
+    return then
+
+
+def _keep_on_device(res, n, device):
+    """the `fetch` of a table call whose records stay where they are"""
+    return None
+
+
 def verify_rekey_table_workspace_bytes(n_entries):
     """bytes of device workspace a rekey verify table call over n_entries needs (0 for none, or above the limit)"""
     return lib().modgpu_verify_rekey_table_workspace_bytes(n_entries)
@@ -1458,11 +1569,25 @@ class DeviceBuffer:
             t[i]["src"], t[i]["n"], t[i]["stream_off"], t[i]["key"] = self.ptr + o, n, part_off + o, as_int32(key)
         return digest_table_device(t, None, workspace, self.device, stream)[1]
 
-    def extract(self, ranges, key, out, part_off=0, side=DIGEST_OUTPUT, workspace=None, stream=None):
-        """Cycles every range of `ranges` -- a list of (offset, n) -- of the part this buffer holds, each from stream offset part_off +
-        offset, into `out` (another DeviceBuffer), packed end to end from offset 0, and returns one Adler-32 per range -- of what was
-        stored, or with side=DIGEST_INPUT of what was read -- as a uint32 array: one cycle_digest_table_device call.  With `out is self`
-        each range is cycled in place."""
+    def check(self, ranges, key, adlers, part_off=0, workspace=None, stream=None):
+        """"Is this part the part I packed, and if not, which file first?": the ranges of `digests` against `adlers`, one Adler-32 per
+        range (a host uint32 array, uploaded) -- one digest_table_device call and one digest check on the same stream, one synchronise,
+        and the records never leave the device: 32 bytes come back, and n / 8 more only if a range is bad.  Returns (bad ranges, the
+        lowest bad range or None, the bad ranges' indices as a uint64 array)."""
+        ranges = [(int(o), int(n)) for o, n in ranges]
+        assert all(o >= 0 and n >= 0 and o + n <= self.nbytes for o, n in ranges)
+        adlers = np.ascontiguousarray(adlers, dtype=np.uint32)
+        assert adlers.size == len(ranges)
+        if not ranges:
+            return _no_bad_entries()
+        t = table(len(ranges))
+        for i, (o, n) in enumerate(ranges):
+            t[i]["src"], t[i]["n"], t[i]["stream_off"], t[i]["key"] = self.ptr + o, n, part_off + o, as_int32(key)
+        return _table_call("modgpu_digest_table_device", t, TABLE_DTYPE, None, workspace, digest_table_workspace_bytes, self.device, stream,
+                           "the device refused digest table entry {}; no record was written", fetch=_keep_on_device,
+                           then=_check_behind(adlers, self.device))[1]
+
+    def _extract_table(self, ranges, key, out, part_off):
         ranges = [(int(o), int(n)) for o, n in ranges]
         assert all(o >= 0 and n >= 0 and o + n <= self.nbytes for o, n in ranges)
         assert out is self or (out.device == self.device and sum(n for _, n in ranges) <= out.nbytes)
@@ -1472,7 +1597,28 @@ class DeviceBuffer:
             t[i]["dst"], t[i]["src"] = (self.ptr + o if out is self else out.ptr + at), self.ptr + o
             t[i]["n"], t[i]["stream_off"], t[i]["key"] = n, part_off + o, as_int32(key)
             at += n
-        return cycle_digest_table_device(t, None, side, workspace, self.device, stream)[1]
+        return t
+
+    def extract(self, ranges, key, out, part_off=0, side=DIGEST_OUTPUT, workspace=None, stream=None):
+        """Cycles every range of `ranges` -- a list of (offset, n) -- of the part this buffer holds, each from stream offset part_off +
+        offset, into `out` (another DeviceBuffer), packed end to end from offset 0, and returns one Adler-32 per range -- of what was
+        stored, or with side=DIGEST_INPUT of what was read -- as a uint32 array: one cycle_digest_table_device call.  With `out is self`
+        each range is cycled in place."""
+        return cycle_digest_table_device(self._extract_table(ranges, key, out, part_off), None, side, workspace, self.device, stream)[1]
+
+    def extract_checked(self, ranges, key, out, expect, part_off=0, side=DIGEST_OUTPUT, workspace=None, stream=None):
+        """`extract`, and the call's records checked against `expect` -- one Adler-32 per range, a host uint32 array -- on the device,
+        in the same stream: (the Adler-32 values as extract returns them, (bad ranges, the lowest bad range or None, the bad ranges'
+        indices as a uint64 array))."""
+        expect = np.ascontiguousarray(expect, dtype=np.uint32)
+        t = self._extract_table(ranges, key, out, part_off)
+        assert expect.size == t.size
+        if not t.size:
+            return _no_digest_results()[1], _no_bad_entries()
+        (_, adlers), outcome = _table_call("modgpu_cycle_digest_table_device", t, TABLE_DTYPE, None, workspace, cycle_digest_table_workspace_bytes,
+                                           self.device, stream, "the device refused cycle digest table entry {}; nothing was written", extra=(side,),
+                                           fetch=digest_results, then=_check_behind(expect, self.device))
+        return adlers, outcome
 
     def move(self, dst_offset, src_offset, n, key_from=0, key_to=0, off_from=0, off_to=0, workspace=None, stream=None):
         """Moves n bytes inside the buffer from src_offset to dst_offset, the ranges overlapping in any way (memmove rules), rekeying

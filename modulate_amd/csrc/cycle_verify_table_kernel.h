@@ -42,7 +42,17 @@ static_assert(sizeof(VerifyTableSummary) == 64, "one line");
 // second loop (one uniform branch on `mode`) sums the bodies and adds to the records with non-returning 64-bit atomic adds.
 // The workspace is the table call's own (no summary line: `sum` is null).
 // (DigestTableRecord and kDigestTableMod: cycle_table_kernel.h)
-enum VerifyTableMode : uint32_t { VERIFY_TABLE_COMPARE = 0u, VERIFY_TABLE_DIGEST = 1u };
+//
+// The CHECK mode of the finish kernel alone (modgpu_digest_check_device): no table, no workspace of its own.  One thread per RECORD of a
+// digest producer (this TU's digest mode, the out-of-place table TU's, or the digest call's): the record is closed as
+// modgpu_digest_adler32 closes it and compared with expect[i].  One ballot per wave is the wave's word of the bitmap (stored whole where
+// a bitmap is given); only a wave whose ballot is nonzero sends one 64-bit add (its popcount) and one 64-bit unsigned min (its lowest
+// bad index) to the 32-byte summary `check`, which modgpu_launch_verify_init has made {0, kVerifyNone, 0, 0} earlier on the stream.
+// `producer`, when given, is the header of the table call that wrote the records: if that call was refused (first_bad set) nothing is
+// compared, the summary becomes {0, kVerifyNone, n, 1} and the bitmap is not touched.  One uniform branch at the top of the kernel.
+enum VerifyTableMode : uint32_t { VERIFY_TABLE_COMPARE = 0u, VERIFY_TABLE_DIGEST = 1u, VERIFY_TABLE_CHECK = 2u };
+// reporting only (modgpu_last_launch): the check launch of modgpu_digest_check_device
+constexpr int CYCLE_DIGEST_CHECK = 19;
 
 struct VerifyTableArgs {
     const CycleTableEntry *entries;
@@ -58,6 +68,11 @@ struct VerifyTableArgs {
     uint32_t n_blk;                // ceil(n / 1024)
     uint32_t mode;                 // VERIFY_TABLE_COMPARE, or VERIFY_TABLE_DIGEST: `records` in place of `results`, `sum` null
     DigestTableRecord *records;    // n records in the caller's device memory: stored whole by finish, added to by stream
+    // VERIFY_TABLE_CHECK only (everything above but n, mode and records -- which are only read -- is unused then):
+    const uint32_t *expect;         // n expected Adler-32 values
+    unsigned long long *bad_bits;   // ceil(n / 64) words, bit b of word w = entry 64 w + b is bad; nullptr: no bitmap wanted
+    const CycleTableHdr *producer;  // the header of the table call that wrote the records; nullptr: the records are taken as they are
+    CycleVerifyResult *check;       // the summary: {bad entries, lowest bad entry, n, 1 if the producer was refused}
 };
 
 uint32_t modgpu_verify_table_chunk_bytes();
@@ -71,3 +86,7 @@ hipError_t modgpu_launch_verify_table_stream(const VerifyTableArgs &a, uint32_t 
 hipError_t modgpu_launch_digest_table_plan(const VerifyTableArgs &a, hipStream_t stream);
 hipError_t modgpu_launch_digest_table_finish(const VerifyTableArgs &a, hipStream_t stream);
 hipError_t modgpu_launch_digest_table_stream(const VerifyTableArgs &a, uint32_t grid, hipStream_t stream);
+// The finish kernel with mode = VERIFY_TABLE_CHECK on ceil(n / 1024) workgroups, n > 0: `summary` initialised by
+// modgpu_launch_verify_init(summary, 1, stream) earlier on the same stream.  bad_bits and producer may be nullptr.
+hipError_t modgpu_launch_digest_check(const DigestTableRecord *records, const uint32_t *expect, uint64_t n, const CycleTableHdr *producer,
+                                      CycleVerifyResult *summary, unsigned long long *bad_bits, hipStream_t stream);

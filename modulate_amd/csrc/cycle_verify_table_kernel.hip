@@ -33,6 +33,10 @@
 // same kind of table with `dst` ignored: plan lays the grid on the SOURCE, finish sums the ragged edges and stores every record whole,
 // and the stream kernel takes its second loop -- one uniform branch apart, with registers, views and LDS of its own scope -- which
 // reads one side, sums what the cipher makes of it and adds to the entry's record.  Its protocol is written where the loop is.
+//
+// The CHECK mode (VERIFY_TABLE_CHECK; modgpu_digest_check_device) is the finish kernel alone, launched without a table: one thread per
+// digest RECORD, closed and compared with a manifest of Adler-32 values.  One uniform branch at the top of finish; written where the
+// digest mode's arithmetic is.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
@@ -70,6 +74,51 @@ __device__ __forceinline__ DigestTableRecord digest_edges(const CycleTablePlan &
         }
     }
     return DigestTableRecord{s1, s2 % kDigestTableMod, (unsigned long long)P.head_n + body + P.tail_n, 0ull};
+}
+
+// ---- the check mode (cycle_verify_table_kernel.h: VERIFY_TABLE_CHECK; modgpu_digest_check_device) ----------------------------------
+// A record closed as modgpu_digest_adler32 closes it: the residues first, then A = (1 + s1) % m, B = (n + n * s1 - s2) % m.  In 32 bits:
+// n * s1 <= 65520^2 < 2^32, and the sum behind it is below 3 m.
+__device__ __forceinline__ uint32_t digest_close(const DigestTableRecord &r)
+{
+    constexpr uint32_t m = kDigestTableMod;
+    const uint32_t s1 = (uint32_t)(r.s1 % m), s2 = (uint32_t)(r.s2 % m), n = (uint32_t)(r.n % m);
+    const uint32_t A = (1u + s1) % m;
+    const uint32_t B = (n + n * s1 % m + m - s2) % m;
+    return B << 16 | A;
+}
+// One thread per record.  No LDS, no barrier; a clean manifest sends no atomic.  Workgroups are whole waves (kTableBlock % 64 == 0), so
+// a wave's 64 entries are one word of the bitmap; a wave none of whose entries exists (its first is >= n) stores nothing.
+__device__ __forceinline__ void digest_check(const VerifyTableArgs &a)
+{
+    static_assert(kTableBlock % 64 == 0, "a wave's entries are one word of the bitmap");
+    const uint32_t tid = threadIdx.x;
+    const uint64_t i = (uint64_t)blockIdx.x * kTableBlock + tid;
+    const bool first = blockIdx.x == 0 && tid == 0;
+    // the producer was refused (one scalar load, uniform for the grid): its records are whatever the caller left there
+    if (a.producer && *as_const(&a.producer->first_bad) != kTableNoBad) {
+        if (first) {
+            a.check->n = a.n;
+            a.check->reserved = 1ull;
+        }
+        return;
+    }
+    bool bad = false;
+    if (i < a.n) {
+        const DigestTableRecord r = a.records[i];
+        bad = digest_close(r) != a.expect[i];
+    }
+    const unsigned long long word = __builtin_amdgcn_ballot_w64(bad);
+    const uint64_t i0 = i & ~63ull; // the wave's first entry
+    if ((tid & 63u) == 0u && i0 < a.n) {
+        if (a.bad_bits) a.bad_bits[i0 >> 6] = word;
+        if (word != 0ull) {
+            __hip_atomic_fetch_add(&a.check->mismatches, (unsigned long long)__builtin_popcountll(word), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_min(&a.check->first_mismatch, (unsigned long long)(i0 + (uint64_t)__builtin_ctzll(word)), __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    if (first) a.check->n = a.n; // (a field no atomic touches)
 }
 } // namespace
 
@@ -111,6 +160,10 @@ __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_verify_table_finish(
     const uint32_t tid = threadIdx.x;
     const uint32_t b = blockIdx.x;
     const uint64_t i = (uint64_t)b * kTableBlock + tid;
+    if (__builtin_expect(a.mode == VERIFY_TABLE_CHECK, 0)) { // (uniform) modgpu_digest_check_device: records against a manifest, no table
+        digest_check(a);
+        return;
+    }
     const TableTotals T = table_totals(a.blk, a.n_blk, b, tid);
     const bool ok = T.bad == 0 && T.total <= kTableMaxChunks;
     if (b == 0 && tid == 0) a.hdr->total = ok ? T.total : 0;
@@ -562,4 +615,20 @@ hipError_t modgpu_launch_digest_table_finish(const VerifyTableArgs &a, hipStream
 hipError_t modgpu_launch_digest_table_stream(const VerifyTableArgs &a, uint32_t grid, hipStream_t stream)
 {
     return modgpu_launch_verify_table_stream(digest_mode(a), grid, stream);
+}
+// the digest check: the finish kernel alone, in its check mode
+hipError_t modgpu_launch_digest_check(const DigestTableRecord *records, const uint32_t *expect, uint64_t n, const CycleTableHdr *producer,
+                                      CycleVerifyResult *summary, unsigned long long *bad_bits, hipStream_t stream)
+{
+    VerifyTableArgs a{};
+    a.n = n;
+    a.n_blk = (uint32_t)((n + kTableBlock - 1) / kTableBlock);
+    a.mode = VERIFY_TABLE_CHECK;
+    a.records = const_cast<DigestTableRecord *>(records); // (only read)
+    a.expect = expect;
+    a.bad_bits = bad_bits;
+    a.producer = producer;
+    a.check = summary;
+    hipLaunchKernelGGL(modgpu_cycle_verify_table_finish, dim3(a.n_blk), dim3(kTableBlock), 0, stream, a);
+    return hipGetLastError();
 }

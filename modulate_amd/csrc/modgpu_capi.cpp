@@ -1817,15 +1817,69 @@ int rekey_move_table_impl(const modgpu_rekey_table_entry_t *entries, uint64_t n,
 // The first `bytes` of a table call's workspace (its header[, its summary line]) read back for modgpu_table_status and
 // modgpu_verify_table_summary: synchronous.  (modgpu_rekey_move_table_status keeps these steps written out: folded in as well, the
 // libraries' lists of exported symbols are no longer the ones they had -- a weak std::to_string instance drops out.)
-int read_workspace_top(const void *dev_workspace, bool out_pointers, int device, void *top, size_t bytes)
+// modgpu_digest_check_summary reads its 32 bytes the same way, with words of its own for the two refusals.
+int read_workspace_top(const void *dev_workspace, bool out_pointers, int device, void *top, size_t bytes,
+                       const char *null_text = "null workspace or out pointer",
+                       const char *foreign_text = "the workspace is not device memory of the call's device")
 {
-    if (!dev_workspace || !out_pointers) return fail(MODGPU_ERR_INVALID, "null workspace or out pointer");
+    if (!dev_workspace || !out_pointers) return fail(MODGPU_ERR_INVALID, null_text);
     DeviceScope scope(device);
     if (scope.rc) return scope.rc;
     int phys = -1;
     HIP_TRY(hipGetDevice(&phys));
-    if (modgpu_xfer_device_of(dev_workspace, bytes) != phys) return fail(MODGPU_ERR_INVALID, "the workspace is not device memory of the call's device");
+    if (modgpu_xfer_device_of(dev_workspace, bytes) != phys) return fail(MODGPU_ERR_INVALID, foreign_text);
     HIP_TRY(hipMemcpy(top, dev_workspace, bytes, hipMemcpyDeviceToHost));
+    return MODGPU_OK;
+}
+
+// The digest check: records of any digest producer against a manifest of Adler-32 values, on the device.  Tier 1 (include/modgpu.h), then
+// two launches on `stream`: the verify call's init launch on the one summary ({0, none, 0, 0} is its starting value too), then the verify
+// table TU's finish kernel in its check mode.  No workspace of its own, no ticket, nothing that can run out.
+static_assert(sizeof(modgpu_digest_check_summary_t) == 32 && sizeof(CycleVerifyResult) == 32 &&
+                  offsetof(modgpu_digest_check_summary_t, bad_entries) == offsetof(CycleVerifyResult, mismatches) &&
+                  offsetof(modgpu_digest_check_summary_t, first_bad_entry) == offsetof(CycleVerifyResult, first_mismatch) &&
+                  offsetof(modgpu_digest_check_summary_t, entries) == offsetof(CycleVerifyResult, n) &&
+                  offsetof(modgpu_digest_check_summary_t, refused) == offsetof(CycleVerifyResult, reserved),
+              "the check kernel writes the public summary, and the verify call's init launch starts it");
+uint64_t digest_check_bits_bytes(uint64_t n) { return n == 0 || n > kTableMaxEntries ? 0 : 8 * ((n + 63) / 64); }
+int digest_check_impl(const modgpu_digest_result_t *records, const uint32_t *expect, uint64_t n, const void *table_ws,
+                      modgpu_digest_check_summary_t *summary, uint64_t *bits, int device, hipStream_t stream)
+{
+    if (n == 0) return MODGPU_OK;
+    if (n > kTableMaxEntries) return fail(MODGPU_ERR_INVALID, "more entries than a table call takes (4194304)");
+    if (!records || !expect || !summary) return fail(MODGPU_ERR_INVALID, "null records, manifest or summary");
+    if ((reinterpret_cast<uintptr_t>(records) | reinterpret_cast<uintptr_t>(summary) | reinterpret_cast<uintptr_t>(bits)) & 7)
+        return fail(MODGPU_ERR_INVALID, "records, summary or bits not 8-byte aligned");
+    if (reinterpret_cast<uintptr_t>(expect) & 3) return fail(MODGPU_ERR_INVALID, "manifest not 4-byte aligned");
+    if (reinterpret_cast<uintptr_t>(table_ws) & 7) return fail(MODGPU_ERR_INVALID, "table workspace not 8-byte aligned");
+    const uint64_t records_bytes = n * sizeof *records, expect_bytes = n * sizeof *expect, bits_bytes = bits ? digest_check_bits_bytes(n) : 0;
+    auto meet = [](const void *p, uint64_t pn, const void *q, uint64_t qn) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+        return pn && qn && a < b + qn && b < a + pn;
+    };
+    if (meet(summary, sizeof *summary, records, records_bytes) || meet(summary, sizeof *summary, expect, expect_bytes) ||
+        meet(bits, bits_bytes, records, records_bytes) || meet(bits, bits_bytes, expect, expect_bytes) || meet(bits, bits_bytes, summary, sizeof *summary))
+        return fail(MODGPU_ERR_INVALID, "the summary or the bits overlap the records, the manifest or each other");
+    DeviceScope scope(device);
+    if (scope.rc) return scope.rc;
+    int phys = -1;
+    HIP_TRY(hipGetDevice(&phys));
+    if (modgpu_xfer_device_of(records, records_bytes) != phys || modgpu_xfer_device_of(expect, expect_bytes) != phys ||
+        modgpu_xfer_device_of(summary, sizeof *summary) != phys || (bits && modgpu_xfer_device_of(bits, bits_bytes) != phys))
+        return fail(MODGPU_ERR_INVALID, "the records, the manifest, the summary or the bits are not device memory of the call's device");
+    if (table_ws && modgpu_xfer_device_of(table_ws, sizeof(CycleTableHdr)) != phys)
+        return fail(MODGPU_ERR_INVALID, "the table workspace is not device memory of the call's device");
+    CycleVerifyResult *const sum = reinterpret_cast<CycleVerifyResult *>(summary);
+    (void)hipGetLastError(); // (the launches report hipGetLastError: an earlier call's error must not be taken for theirs)
+    hipError_t e = modgpu_launch_verify_init(sum, 1, stream);
+    if (e != hipSuccess) return fail_hip(e, "digest check init launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    e = modgpu_launch_digest_check(reinterpret_cast<const DigestTableRecord *>(records), expect, n, static_cast<const CycleTableHdr *>(table_ws), sum,
+                                   reinterpret_cast<unsigned long long *>(bits), stream);
+    if (e != hipSuccess) return fail_hip(e, "digest check launch");
+    g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
+    const uint32_t grid = (uint32_t)((n + kTableBlock - 1) / kTableBlock);
+    t_last_launch = {"modgpu_cycle_verify_table_finish", CYCLE_DIGEST_CHECK, grid, kTableBlock, 0u, 0, grid, MODGPU_VERIFY_TABLE_KERNEL_SOURCE_HASH};
     return MODGPU_OK;
 }
 
@@ -2134,6 +2188,30 @@ int modgpu_digest_results(const modgpu_digest_result_t *dev_results, uint64_t co
         HIP_TRY(hipMemcpy(host_out, dev_results, count * sizeof(modgpu_digest_result_t), hipMemcpyDeviceToHost));
         if (adler32_out)
             for (uint64_t i = 0; i < count; ++i) adler32_out[i] = modgpu_digest_adler32(host_out + i);
+        return MODGPU_OK;
+    });
+}
+
+uint64_t modgpu_digest_check_bits_bytes(uint64_t n_entries) { return digest_check_bits_bytes(n_entries); }
+
+int modgpu_digest_check_device(const modgpu_digest_result_t *dev_records, const uint32_t *dev_expect, uint64_t n_entries, const void *dev_table_workspace,
+                               modgpu_digest_check_summary_t *dev_summary, uint64_t *dev_bad_bits, int device, void *hip_stream)
+{
+    return guarded([&]() -> int {
+        return digest_check_impl(dev_records, dev_expect, n_entries, dev_table_workspace, dev_summary, dev_bad_bits, device, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int modgpu_digest_check_summary(const modgpu_digest_check_summary_t *dev_summary, int device, modgpu_digest_check_summary_t *host_out)
+{
+    return guarded([&]() -> int {
+        modgpu_digest_check_summary_t s;
+        if (int rc = read_workspace_top(dev_summary, host_out != nullptr, device, &s, sizeof s, "null summary or out pointer",
+                                        "the summary is not device memory of the call's device"))
+            return rc;
+        *host_out = s;
+        if (s.refused != 0)
+            return fail(MODGPU_ERR_INVALID, "the table call that produced the records was refused (nothing was compared; modgpu_table_status names the entry)");
         return MODGPU_OK;
     });
 }
@@ -3047,6 +3125,16 @@ int modgpu_time_digest_table_device(const void *dev_entries, uint64_t n_entries,
     return guarded([&]() -> int {
         return time_calls(device, hip_stream, iters, ms_per_call, [&](hipStream_t st) {
             return digest_table_impl(static_cast<const modgpu_table_entry_t *>(dev_entries), n_entries, static_cast<modgpu_digest_result_t *>(dev_results), dev_workspace, workspace_bytes, -1, st);
+        });
+    });
+}
+
+int modgpu_time_digest_check_device(const void *dev_records, const void *dev_expect, uint64_t n_entries, const void *dev_table_workspace, void *dev_summary,
+                                    void *dev_bad_bits, int device, void *hip_stream, int iters, float *ms_per_call)
+{
+    return guarded([&]() -> int {
+        return time_calls(device, hip_stream, iters, ms_per_call, [&](hipStream_t st) {
+            return digest_check_impl(static_cast<const modgpu_digest_result_t *>(dev_records), static_cast<const uint32_t *>(dev_expect), n_entries, dev_table_workspace, static_cast<modgpu_digest_check_summary_t *>(dev_summary), static_cast<uint64_t *>(dev_bad_bits), -1, st);
         });
     });
 }
