@@ -386,6 +386,36 @@ int modgpu_rekey_move_table_device(const modgpu_rekey_table_entry_t *dev_entries
 int modgpu_rekey_move_table_validate(const modgpu_rekey_table_entry_t *host_entries, uint64_t n_entries);
 int modgpu_rekey_move_table_status(const void *dev_workspace, int device, uint64_t *first_bad_entry, uint64_t *stalled_chunk);
 
+/* ---- a table of rekey entries RELAID OUT: segments that slide BOTH ways, a splice of a resident part in one pass, ten launches ------
+ * Putting changed files into a resident part is a splice: some files grow, some shrink, some go away, and every surviving segment
+ * slides by the running sum of the size changes before it -- some up and some down in the same table, which the move table call above
+ * refuses.  This call takes such a table.  Its semantics are the move table call's, word for word, with these differences:
+ *   SAME WHERE IT APPLIES: dst_i[j] = SRC0_i[j] ^ ks(key_from_i)[off_from_i + j] ^ ks(key_to_i)[off_to_i + j] with SRC0 device memory
+ *   as the call found it; every degenerate key pair in the pass; asynchronous on `hip_stream`; allocation-free; capturable into a
+ *   hipGraph; the table read when the call runs on the device, so a replayed graph picks up rewritten entries; tier 1 on the host
+ *   before anything is queued; page-locked host memory anywhere in a table is not supported.
+ *   THE RULE.  After dropping empty entries: src_i + n_i <= src_{i+1} and dst_i + n_i <= dst_{i+1} -- the entries are listed by rising
+ *   address, sources pairwise disjoint, destinations pairwise disjoint.  Each non-empty entry is checked against the non-empty entry
+ *   before it, whatever the direction of either: there is no direction clause.  (Under that rule an entry with dst <= src and one with
+ *   dst > src never meet, destination on source, so the table is two one-way tables interleaved: DESIGN.md 4.20.)
+ *   LAUNCHES.  Exactly TEN kernel launches whatever n_entries is and whatever the mix: two sweeps of plan, finish, window, move, place
+ *   on the one stream, sweep 0 over the entries with dst <= src, sweep 1 over those with dst > src.  No memset and no copy; each byte
+ *   of each entry is read once and written once.  modgpu_last_launch reports the second move launch, as variant 15.
+ *   ALL OR NOTHING.  Anything the device refuses makes the WHOLE CALL write nothing, in either sweep: a NULL dst or src with n > 0,
+ *   nonzero flags or reserved, an entry of 1 TiB or more, the rule above, or more chunks than the workspace was sized for -- counted
+ *   over ALL entries, not per sweep.  Both sweeps decide on the same quantities and reach the same verdict; the table must not
+ *   change between them, so, as above, it must not lie in memory the call writes.
+ *   WORKSPACE AND STATUS are the move table call's: modgpu_rekey_move_table_workspace_bytes(n_entries, total_bytes) and
+ *   modgpu_rekey_move_table_status; sweep 1 reuses the workspace in stream order.  A wait that runs out in sweep 0 stays in the status,
+ *   and sweep 1 then stores nothing.  *stalled_chunk is a chunk number in the numbering of the sweep that stalled (each sweep numbers
+ *   the chunks of its own entries from 0): diagnostic only.
+ * modgpu_rekey_relayout_table_validate checks a host copy against tier 1 and the rule above in O(n) and names the entry at fault in
+ * modgpu_last_error().  No device is touched.  (A table the move table call takes is taken here too, at the price of the idle sweep's
+ * five small launches.) */
+int modgpu_rekey_relayout_table_device(const modgpu_rekey_table_entry_t *dev_entries, uint64_t n_entries, uint64_t total_bytes,
+                                       void *dev_workspace, uint64_t workspace_bytes, int device, void *hip_stream);
+int modgpu_rekey_relayout_table_validate(const modgpu_rekey_table_entry_t *host_entries, uint64_t n_entries);
+
 /* ---- VERIFY: is this buffer what the cipher would have produced from that one?  One read-only pass, two numbers -------------------
  * The result of one entry, in device memory.  The layout is pinned (32 bytes, 8-byte aligned). */
 typedef struct modgpu_verify_result {

@@ -19,6 +19,7 @@ from .capi import (  # noqa: F401
     rekey_move_device, move_workspace_bytes, move_status, debug_set_move_grid,
     rekey_move_table_device, rekey_move_table_workspace_bytes, rekey_move_table_validate, rekey_move_table_status, compaction_table,
     rekey_move_table_kernel_source_hash, debug_set_move_table_grid,
+    rekey_relayout_table_device, rekey_relayout_table_validate, relayout_table, splice_moves,
     cycle_table_device, time_cycle_table_device, table, table_workspace_bytes, table_status, table_validate, table_kernel_source_hash,
     debug_set_table_grid, TableEntry, TABLE_DTYPE,
     rekey_table_device, time_rekey_table_device, rekey_table, rekey_table_workspace_bytes, rekey_table_validate,

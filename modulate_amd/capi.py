@@ -85,6 +85,8 @@ EXPORTS = {
     "modgpu_rekey_move_table_device": (_int, [_vp, _u64, _u64, _vp, _u64, _int, _vp]),
     "modgpu_rekey_move_table_validate": (_int, [_vp, _u64]),
     "modgpu_rekey_move_table_status": (_int, [_vp, _int, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
+    "modgpu_rekey_relayout_table_device": (_int, [_vp, _u64, _u64, _vp, _u64, _int, _vp]),
+    "modgpu_rekey_relayout_table_validate": (_int, [_vp, _u64]),
     "modgpu_verify_device": (_int, [_vp, _vp, _u64, _i32, _u64, _vp, _int, _vp]),
     "modgpu_verify_batch_device": (_int, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_u64), ctypes.POINTER(_u64), _int, _i32,
                                           _vp, _int, _vp]),
@@ -1045,6 +1047,65 @@ def compaction_table(base_ptr, keep, key, part_off=0):
     return t
 
 
+def rekey_relayout_table_validate(entries):
+    """the pointer / flags / order rules of rekey_relayout_table_device over a host table (REKEY_TABLE_DTYPE array) -- the move table
+    call's without the direction clause; raises ModGpuError naming an entry at fault"""
+    t = np.ascontiguousarray(entries, dtype=REKEY_TABLE_DTYPE)
+    _check(lib().modgpu_rekey_relayout_table_validate(_vp(t.ctypes.data if t.size else 0), t.size))
+
+
+def rekey_relayout_table_device(entries, total_bytes=None, workspace=None, device=-1, stream=None, check=True, *, n=None):
+    """rekey_move_table_device for a table whose entries slide BOTH ways -- listed by rising address, sources pairwise disjoint,
+    destinations pairwise disjoint, no direction clause (include/modgpu.h) -- in one pass, ten launches whatever its length: the
+    entries with dst <= src in a first sweep, those with dst > src in a second.  Arguments, workspace
+    (rekey_move_table_workspace_bytes) and status (rekey_move_table_status) are rekey_move_table_device's; a host table is checked
+    with rekey_relayout_table_validate first unless check=False."""
+    known = total_bytes is not None
+    if not known and isinstance(entries, np.ndarray):
+        entries = np.ascontiguousarray(entries, dtype=REKEY_TABLE_DTYPE)
+        total_bytes = int(entries["n"].sum(dtype=np.uint64))
+    _table_call("modgpu_rekey_relayout_table_device", entries, REKEY_TABLE_DTYPE, n, workspace,
+                lambda k: rekey_move_table_workspace_bytes(k, total_bytes), device, stream,
+                "the device refused relayout table entry {}; nothing was written", gave_up="the relayout pass gave up waiting at chunk {}",
+                validate=rekey_relayout_table_validate if check else None, needed="n (the entry count) and total_bytes are", known=known,
+                extra=(total_bytes,), status=rekey_move_table_status)
+
+
+def relayout_table(base_ptr, moves, key, key_to=None, part_off=0):
+    """The table that relays out a resident part: `moves` is a list of (src_off, dst_off, n) segments of the part at device address
+    base_ptr, rising and disjoint on both sides, sliding either way; the result (REKEY_TABLE_DTYPE) moves each from stream offset
+    part_off + src_off under `key` to part_off + dst_off under key_to (None: `key`)."""
+    moves = [(int(s), int(d), int(n)) for s, d, n in moves]
+    t = rekey_table(len(moves))
+    for i, (s, d, n) in enumerate(moves):
+        t[i]["dst"], t[i]["src"], t[i]["n"] = base_ptr + d, base_ptr + s, n
+        t[i]["off_from"], t[i]["off_to"] = part_off + s, part_off + d
+        t[i]["key_from"], t[i]["key_to"] = as_int32(key), as_int32(key if key_to is None else key_to)
+    return t
+
+
+def splice_moves(size, edits):
+    """The arithmetic of a splice: `edits` is a list of (offset, old_len, new_len) with rising, disjoint [offset, offset + old_len) inside
+    a part of `size` bytes -- old_len bytes at offset give way to new_len bytes.  Returns (moves, new_size, holes): `moves` the
+    surviving segments between the edits as (src_off, dst_off, n), each slid by the sum of the size changes before it (empty ones
+    left out); `holes` the (new_offset, new_len) of every edit with new_len > 0, for the caller to fill.  ValueError on overlapping
+    or falling edits, or one that passes the end of the part."""
+    moves, holes = [], []
+    at, shift = 0, 0  # the end of the last edit in the old part; new offset - old offset from there on
+    for i, (off, old, new) in enumerate((int(o), int(a), int(b)) for o, a, b in edits):
+        if off < at or old < 0 or new < 0 or off + old > size:
+            raise ValueError(f"edit {i} ({off}, {old}, {new}) starts below the end of the one before it ({at}) or passes the part's size ({size})")
+        if off > at:
+            moves.append((at, at + shift, off - at))
+        if new:
+            holes.append((off + shift, new))
+        shift += new - old
+        at = off + old
+    if size > at:
+        moves.append((at, at + shift, size - at))
+    return moves, size + shift, holes
+
+
 def rekey_move_table_kernel_source_hash():
     """identity of the rekey move table kernels' TU (cycle_rekey_move_table_kernel.hip and what it includes)"""
     return lib().modgpu_rekey_move_table_kernel_source_hash().decode()
@@ -1636,6 +1697,27 @@ class DeviceBuffer:
         t = compaction_table(self.ptr, keep, key, part_off)
         rekey_move_table_device(t, None, workspace, self.device, stream)
         return keep[0][0] + sum(n for _, n in keep) if keep else 0
+
+    def relayout(self, moves, key, key_to=None, part_off=0, workspace=None, stream=None):
+        """Moves the segments `moves` -- a list of (src_off, dst_off, n), rising and disjoint on both sides, sliding either way -- of
+        the part this buffer holds in one pass (relayout_table, rekey_relayout_table_device), each rekeyed from stream offset part_off
+        + src_off under `key` to part_off + dst_off under key_to (None: `key`)."""
+        moves = [(int(s), int(d), int(n)) for s, d, n in moves]
+        assert all(min(s, d) >= 0 and max(s, d) + n <= self.nbytes for s, d, n in moves)
+        rekey_relayout_table_device(relayout_table(self.ptr, moves, key, key_to, part_off), None, workspace, self.device, stream)
+
+    def splice(self, edits, key, used, part_off=0, workspace=None, stream=None, *, key_to=None):
+        """Splices the part this buffer holds in its first `used` bytes: for every (offset, old_len, new_len) of `edits` -- rising,
+        disjoint -- old_len bytes at offset give way to a hole of new_len bytes, and every surviving segment slides by the sum of the
+        size changes before it, up or down, in one pass under `key` -- or rekeyed to key_to on the way (splice_moves, relayout).  Returns
+        (new_used, holes), `holes` the (new_offset, new_len) of every edit with new_len > 0; raises ValueError if new_used exceeds the
+        buffer.  The caller then fills each hole with modgpu_cycle_host_to_device (cycle_host_to_device) at stream offset part_off +
+        new_offset, under the key the part now has."""
+        moves, new_used, holes = splice_moves(used, edits)
+        if new_used > self.nbytes:
+            raise ValueError(f"the spliced part needs {new_used} bytes, the buffer has {self.nbytes}")
+        self.relayout(moves, key, key_to, part_off, workspace, stream)
+        return new_used, holes
 
     def sync(self, stream=None):
         _check(self._lib.modgpu_sync(self.device, _vp(stream or 0)))

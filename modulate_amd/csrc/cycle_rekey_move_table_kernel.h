@@ -52,7 +52,7 @@ struct MoveTableBlk {
     uint32_t last;       // 1 + the last non-empty entry among them (global index), 0 if all are empty
     uint32_t first_down; // the first entry among them with dst < src, ~0 if none
     uint32_t first_up;   // ... with dst > src
-    uint32_t pad[2];
+    uint32_t pad[2];     // a sweep of a relayout call: the chunk count of the 1024 entries with no entry filtered, low word first; else 0
 };
 static_assert(sizeof(MoveTableBlk) == 32, "two per line");
 
@@ -94,7 +94,20 @@ struct MoveTableArgs {
     uint64_t level_n[kTableLevels];
     uint32_t top;
     uint32_t n_blk;
+    uint32_t sweep; // 0: the move table call; 1, 2: sweep 0 (dst <= src) and sweep 1 (dst > src) of a relayout call, see below
 };
+
+// The RELAYOUT call (modgpu_rekey_relayout_table_device): a table whose entries slide BOTH ways, as two sweeps of the
+// five launches above on one stream and one workspace.  An entry that slides down or stays never meets one that slides up (the lemma
+// of 4.20), so the table is two same-direction tables interleaved; `sweep` is a mode of the plan and finish kernels that picks one:
+//   plan    an entry of the other direction is FILTERED: planned as an empty entry -- no chunks, no ragged ends, nothing placed --
+//           but it still counts as non-empty for the prev / last links the order check follows, it is still refused for what an
+//           entry is refused for, and its chunks still count toward MoveTableBlk.pad, the UNFILTERED chunk sum of the record.
+//           Sweep 1 keeps the header's `stalled` word as sweep 0 left it, and if it is set filters every entry: nothing more is stored.
+//   finish  no direction clause: each non-empty entry against the non-empty one before it, whatever the direction of either; the
+//           capacity check is made on the unfiltered sum, so both sweeps reach the same verdict; hdr->up = sweep - 1.
+// Window, move and place run as they are: to them a filtered entry is an empty one.
+constexpr uint32_t kRelayoutSweepDown = 1, kRelayoutSweepUp = 2;
 
 uint32_t modgpu_rekey_move_table_chunk_bytes();
 uint32_t modgpu_rekey_move_table_block();
@@ -106,3 +119,7 @@ hipError_t modgpu_launch_rekey_move_table_window(const MoveTableArgs &a, hipStre
 // *grid comes in as the grid asked for and goes out as the grid launched: never more workgroups than the device holds at once
 hipError_t modgpu_launch_rekey_move_table_move(const MoveTableArgs &a, uint32_t *grid, hipStream_t stream);
 hipError_t modgpu_launch_rekey_move_table_place(const MoveTableArgs &a, hipStream_t stream);
+// The plan and finish launches of one sweep of a relayout call (sweep = kRelayoutSweepDown or kRelayoutSweepUp; a.sweep is not looked
+// at); the window, move and place launches above follow each pair.
+hipError_t modgpu_launch_rekey_relayout_plan(const MoveTableArgs &a, uint32_t sweep, hipStream_t stream);
+hipError_t modgpu_launch_rekey_relayout_finish(const MoveTableArgs &a, uint32_t sweep, hipStream_t stream);

@@ -18,6 +18,11 @@
 // rounding that start down to a source dword cannot pass the 16-byte aligned destination address paired with it.  Upward: the mirror
 // image, walked from the last chunk down.  Positions are tickets only, so whoever holds a position is running, and the lowest
 // unfinished position is never blocked -- whether or not the whole grid is resident.
+//
+// A table whose entries slide BOTH ways (modgpu_rekey_relayout_table_device) is two such tables interleaved: under the
+// order rule a downward or stationary entry and an upward one never meet, destination on source.  The call runs the five launches
+// twice; `sweep` in the arguments makes the plan kernel lay the entries of the other direction as empty ones and the finish kernel drop
+// the direction clause and decide on unfiltered chunk counts.  The window, move and place kernels do not know of it.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
@@ -40,11 +45,15 @@ __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_rekey_move_table_pla
     __shared__ uint64_t sc[kTableBlock];
     __shared__ uint32_t sl[kTableBlock];
     __shared__ uint32_t sbad, sdown, sup;
+    __shared__ unsigned long long sall; // a relayout sweep: the record's chunk count with no entry filtered
     const uint32_t tid = threadIdx.x;
     const uint64_t i = (uint64_t)blockIdx.x * kTableBlock + tid;
+    // sweep 1 of a relayout call keeps the stalled word of sweep 0 (no thread of this launch writes it then), and behind a stalled
+    // sweep 0 it filters every entry: no chunks, nothing placed
+    const bool halted = a.sweep == kRelayoutSweepUp && a.hdr->stalled != 0;
     if (blockIdx.x == 0 && tid == 0) {
         a.hdr->ticket = 0;
-        a.hdr->stalled = 0;
+        if (a.sweep != kRelayoutSweepUp) a.hdr->stalled = 0;
         a.hdr->first_bad = kTableNoBad;
         a.hdr->total = 0;
         a.hdr->up = 0;
@@ -54,16 +63,25 @@ __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_rekey_move_table_pla
         sbad = 0;
         sdown = kNone;
         sup = kNone;
+        sall = 0;
     }
-    uint64_t cnt = 0;
+    uint64_t cnt = 0, all = 0;
     uint32_t bad = 0, full = 0, way = 0; // way: 1 dst < src, 2 dst > src
     if (i < a.n) {
         const RekeyTableEntry E = a.entries[i];
-        const TableGrid g = table_grid(E, E.flags | E.reserved);
-        cnt = g.cnt;
+        TableGrid g = table_grid(E, E.flags | E.reserved);
         bad = g.bad;
         full = E.n != 0 ? 1u : 0u;
         way = !full ? 0u : at(E.dst) < at(E.src) ? 1u : at(E.dst) > at(E.src) ? 2u : 0u;
+        all = g.cnt;
+        // a relayout sweep filters the entries of the other direction: laid as an empty entry, whose refusal, links and unfiltered
+        // chunk count stay what they are
+        if (a.sweep != 0 && (halted || (way == 2) != (a.sweep == kRelayoutSweepUp))) {
+            g.head = g.words = g.tail = 0;
+            g.end = g.lead;
+            g.cnt = 0;
+        }
+        cnt = g.cnt;
         MoveTablePlan P;
         RekeyTableEdge X;
         rekey_table_plan_entry(P, X, E, g);
@@ -77,6 +95,7 @@ __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_rekey_move_table_pla
     if (bad) atomicOr(&sbad, 1u);
     if (way == 1) atomicMin(&sdown, (uint32_t)i);
     if (way == 2) atomicMin(&sup, (uint32_t)i);
+    if (a.sweep != 0 && all) atomicAdd(&sall, (unsigned long long)all);
     // inclusive scans over the 1024 entries (Hillis-Steele; every thread reaches every barrier): the sum of the chunk counts, and the
     // last non-empty entry at or before each
     for (uint32_t s = 1; s < kTableBlock; s <<= 1) {
@@ -98,7 +117,8 @@ __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_rekey_move_table_pla
         B.last = sl[tid] ? blockIdx.x * kTableBlock + sl[tid] : 0;
         B.first_down = sdown;
         B.first_up = sup;
-        B.pad[0] = B.pad[1] = 0;
+        B.pad[0] = (uint32_t)sall;
+        B.pad[1] = (uint32_t)(sall >> 32);
         a.blk[blockIdx.x] = B;
     }
 }
@@ -107,6 +127,10 @@ __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_rekey_move_table_pla
 __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_rekey_move_table_finish(MoveTableArgs a)
 {
     __shared__ uint32_t sprev, sdown, sup;
+    // a relayout sweep decides on UNFILTERED chunk counts, so that both sweeps reach one verdict: those of the records before this
+    // workgroup's and of all records, and this workgroup's own entries' (read only when the call is refused, to name the entry)
+    __shared__ unsigned long long sall_before, sall_total;
+    __shared__ uint64_t sa[kTableBlock];
     const uint32_t tid = threadIdx.x;
     const uint32_t b = blockIdx.x;
     const uint64_t i = (uint64_t)b * kTableBlock + tid;
@@ -114,24 +138,41 @@ __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_rekey_move_table_fin
         sprev = 0;
         sdown = kNone;
         sup = kNone;
+        sall_before = 0;
+        sall_total = 0;
+    }
+    if (a.sweep != 0) {
+        uint64_t all = 0;
+        if (i < a.n) {
+            const RekeyTableEntry E = a.entries[i];
+            all = table_grid(E, E.flags | E.reserved).cnt;
+        }
+        sa[tid] = all; // (table_totals' barriers stand between this store and the reads below)
     }
     // beside the totals: the last non-empty entry before this workgroup's, and the first entry that moves down / up
     uint32_t prev = 0, down = kNone, up = kNone;
+    unsigned long long all_before = 0, all_total = 0;
     const TableTotals T = table_totals(
         a.blk, a.n_blk, b, tid,
         [&](uint32_t k, const MoveTableBlk &B) {
             if (k < b && B.last > prev) prev = B.last;
             down = B.first_down < down ? B.first_down : down;
             up = B.first_up < up ? B.first_up : up;
+            const unsigned long long all = (unsigned long long)B.pad[0] | (unsigned long long)B.pad[1] << 32;
+            all_total += all;
+            all_before += k < b ? all : 0;
         },
         [&] {
             if (prev) atomicMax(&sprev, prev);
             if (down != kNone) atomicMin(&sdown, down);
             if (up != kNone) atomicMin(&sup, up);
+            if (all_total) atomicAdd(&sall_total, all_total);
+            if (all_before) atomicAdd(&sall_before, all_before);
         });
     const uint64_t room = a.cap < kTableMaxChunks ? a.cap : kTableMaxChunks;
-    const bool ok = T.bad == 0 && T.total <= room;
-    const bool upward = sup < sdown; // the first entry with dst != src says which way the table slides
+    const bool ok = T.bad == 0 && (a.sweep != 0 ? (uint64_t)sall_total : T.total) <= room;
+    // the first entry with dst != src says which way the table slides; a relayout sweep says it itself
+    const bool upward = a.sweep != 0 ? a.sweep == kRelayoutSweepUp : sup < sdown;
     if (b == 0 && tid == 0) {
         a.hdr->total = ok ? T.total : 0;
         a.hdr->up = upward ? 1u : 0u;
@@ -139,13 +180,19 @@ __global__ __launch_bounds__(kTableBlock) void modgpu_cycle_rekey_move_table_fin
     if (i < a.n) {
         const MoveTablePlan P = a.plan[i];
         const uint64_t start = T.before + P.start;
-        // refused by the plan, or the first whose chunks pass what the workspace was sized for
-        if (!ok && (P.bad || start + P.chunks > room)) atomicMin((unsigned long long *)&a.hdr->first_bad, (unsigned long long)i);
+        // refused by the plan, or the first whose chunks pass what the workspace was sized for -- in a relayout sweep, counted with no
+        // entry filtered
+        uint64_t upto = start + P.chunks;
+        if (a.sweep != 0 && !ok) {
+            upto = sall_before;
+            for (uint32_t t = 0; t <= tid; ++t) upto += sa[t];
+        }
+        if (!ok && (P.bad || upto > room)) atomicMin((unsigned long long *)&a.hdr->first_bad, (unsigned long long)i);
         // the direction and order rule: this entry against the non-empty entry before it
         const RekeyTableEntry E = a.entries[i];
         if (E.n != 0 && !P.bad) {
             const uint64_t d = at(E.dst), s = at(E.src);
-            bool breaks = upward ? d < s : d > s;
+            bool breaks = a.sweep != 0 ? false : upward ? d < s : d > s; // (a relayout has no direction clause)
             const uint64_t q = P.prev ? (uint64_t)b * kTableBlock + P.prev - 1 : sprev ? (uint64_t)sprev - 1 : kTableNoBad;
             if (q != kTableNoBad) {
                 const RekeyTableEntry Q = a.entries[q];
@@ -472,6 +519,20 @@ hipError_t modgpu_launch_rekey_move_table_plan(const MoveTableArgs &a, hipStream
 hipError_t modgpu_launch_rekey_move_table_finish(const MoveTableArgs &a, hipStream_t stream)
 {
     hipLaunchKernelGGL(modgpu_cycle_rekey_move_table_finish, dim3(a.n_blk), dim3(kTableBlock), 0, stream, a);
+    return hipGetLastError();
+}
+hipError_t modgpu_launch_rekey_relayout_plan(const MoveTableArgs &a, uint32_t sweep, hipStream_t stream)
+{
+    MoveTableArgs s = a;
+    s.sweep = sweep;
+    hipLaunchKernelGGL(modgpu_cycle_rekey_move_table_plan, dim3(s.n_blk), dim3(kTableBlock), 0, stream, s);
+    return hipGetLastError();
+}
+hipError_t modgpu_launch_rekey_relayout_finish(const MoveTableArgs &a, uint32_t sweep, hipStream_t stream)
+{
+    MoveTableArgs s = a;
+    s.sweep = sweep;
+    hipLaunchKernelGGL(modgpu_cycle_rekey_move_table_finish, dim3(s.n_blk), dim3(kTableBlock), 0, stream, s);
     return hipGetLastError();
 }
 hipError_t modgpu_launch_rekey_move_table_window(const MoveTableArgs &a, hipStream_t stream)

@@ -1507,7 +1507,7 @@ void store_le32(uint8_t *p, uint32_t v)
 } // namespace
 // ---- the seven calls over a table in device memory: modgpu_cycle_table_device, modgpu_rekey_table_device, modgpu_verify_table_device,
 // modgpu_verify_rekey_table_device, modgpu_digest_table_device, modgpu_cycle_digest_table_device (three launches: plan, finish, stream) and modgpu_rekey_move_table_device
-// (five).
+// (five) -- and modgpu_rekey_relayout_table_device, the move call's launches twice (ten).
 // One workspace walk, one set of grid hooks and one call body (table_call); a call is its layout, its launches and its names. --------
 namespace {
 static_assert(sizeof(modgpu_table_entry_t) == sizeof(CycleTableEntry) && offsetof(modgpu_table_entry_t, key) == offsetof(CycleTableEntry, key) &&
@@ -1791,8 +1791,13 @@ int verify_rekey_table_impl(const modgpu_rekey_table_entry_t *entries, uint64_t 
 }
 
 hipError_t move_table_move(const MoveTableArgs &a, uint32_t &grid, hipStream_t s) { return modgpu_launch_rekey_move_table_move(a, &grid, s); }
+template <uint32_t Sweep> hipError_t relayout_plan(const MoveTableArgs &a, uint32_t &, hipStream_t s) { return modgpu_launch_rekey_relayout_plan(a, Sweep, s); }
+template <uint32_t Sweep> hipError_t relayout_finish(const MoveTableArgs &a, uint32_t &, hipStream_t s) { return modgpu_launch_rekey_relayout_finish(a, Sweep, s); }
+// The move table call, and (relayout) the relayout call: the same layout, workspace and tier 1, and the five launches
+// twice on the one stream -- sweep 0 over the entries with dst <= src, sweep 1 over those with dst > src, the sweep a mode of the plan
+// and finish kernels.
 int rekey_move_table_impl(const modgpu_rekey_table_entry_t *entries, uint64_t n, uint64_t total_bytes, void *ws, uint64_t ws_bytes, int device,
-                          hipStream_t stream)
+                          hipStream_t stream, bool relayout = false)
 {
     using A = MoveTableArgs;
     static constexpr TableKind kind = {kMoveTable, 0, "workspace smaller than modgpu_rekey_move_table_workspace_bytes(n_entries, total_bytes)",
@@ -1803,15 +1808,28 @@ int rekey_move_table_impl(const modgpu_rekey_table_entry_t *entries, uint64_t n,
                                                   {"rekey move table window launch", no_grid<A, modgpu_launch_rekey_move_table_window>},
                                                   {"rekey move table move launch", move_table_move},
                                                   {"rekey move table place launch", no_grid<A, modgpu_launch_rekey_move_table_place>}};
+    static constexpr TableLaunch<A> sweeps[] = {{"rekey relayout plan launch of sweep 0", relayout_plan<kRelayoutSweepDown>},
+                                                {"rekey relayout finish launch of sweep 0", relayout_finish<kRelayoutSweepDown>},
+                                                {"rekey relayout window launch of sweep 0", no_grid<A, modgpu_launch_rekey_move_table_window>},
+                                                {"rekey relayout move launch of sweep 0", move_table_move},
+                                                {"rekey relayout place launch of sweep 0", no_grid<A, modgpu_launch_rekey_move_table_place>},
+                                                {"rekey relayout plan launch of sweep 1", relayout_plan<kRelayoutSweepUp>},
+                                                {"rekey relayout finish launch of sweep 1", relayout_finish<kRelayoutSweepUp>},
+                                                {"rekey relayout window launch of sweep 1", no_grid<A, modgpu_launch_rekey_move_table_window>},
+                                                {"rekey relayout move launch of sweep 1", move_table_move},
+                                                {"rekey relayout place launch of sweep 1", no_grid<A, modgpu_launch_rekey_move_table_place>}};
     const char *refused = move_table_sizes_ok(n, total_bytes) ? nullptr : "total_bytes beyond 2^31 chunks of 64 KiB";
-    return table_call(kind, launches, entries, n, nullptr, refused, ws, ws_bytes, device, stream, [&] { return move_table_layout(n, total_bytes); },
-                      [](A &a, uint8_t *w, const TableLayout &L) {
-                          a.cap = L.cap;
-                          a.edge = reinterpret_cast<RekeyTableEdge *>(w + L.edge);
-                          a.scratch = w + L.scratch;
-                          a.flags = reinterpret_cast<uint32_t *>(w + L.flags);
-                          a.win = reinterpret_cast<MoveTableWin *>(w + L.win);
-                      });
+    auto call = [&](const auto &list) {
+        return table_call(kind, list, entries, n, nullptr, refused, ws, ws_bytes, device, stream, [&] { return move_table_layout(n, total_bytes); },
+                          [](A &a, uint8_t *w, const TableLayout &L) {
+                              a.cap = L.cap;
+                              a.edge = reinterpret_cast<RekeyTableEdge *>(w + L.edge);
+                              a.scratch = w + L.scratch;
+                              a.flags = reinterpret_cast<uint32_t *>(w + L.flags);
+                              a.win = reinterpret_cast<MoveTableWin *>(w + L.win);
+                          });
+    };
+    return relayout ? call(sweeps) : call(launches);
 }
 
 // The first `bytes` of a table call's workspace (its header[, its summary line]) read back for modgpu_table_status and
@@ -1968,8 +1986,8 @@ template <class Entry> int table_validate_impl(const Entry *t, uint64_t n)
 
 // Tiers 1 and 2 over a host copy, in O(n), as the device decides them: the direction is that of the first entry with dst != src, and
 // every non-empty entry is compared with the non-empty entry before it.  (The chunk count against the workspace is the one check that
-// needs total_bytes: it is not made here.)
-int rekey_move_table_validate_impl(const modgpu_rekey_table_entry_t *t, uint64_t n)
+// needs total_bytes: it is not made here.)  one_way = false: the relayout call's rule, the same without the direction clause.
+int rekey_move_table_validate_impl(const modgpu_rekey_table_entry_t *t, uint64_t n, bool one_way = true)
 {
     if (n > kTableMaxEntries) return fail(MODGPU_ERR_INVALID, "more than 4194304 entries (the table call's limit)");
     if (n && !t) return fail(MODGPU_ERR_INVALID, "null table");
@@ -1977,7 +1995,7 @@ int rekey_move_table_validate_impl(const modgpu_rekey_table_entry_t *t, uint64_t
     auto entry = [](uint64_t i, const char *what) { return fail(MODGPU_ERR_INVALID, "entry " + std::to_string(i) + ": " + what); };
     const uint64_t chunk = modgpu_rekey_move_table_chunk_bytes();
     int way = 0; // -1 downward, +1 upward
-    for (uint64_t i = 0; i < n && !way; ++i)
+    for (uint64_t i = 0; i < n && !way && one_way; ++i)
         if (t[i].n) way = at(t[i].dst) < at(t[i].src) ? -1 : at(t[i].dst) > at(t[i].src) ? 1 : 0;
     uint64_t prev = UINT64_MAX;
     for (uint64_t i = 0; i < n; ++i) {
@@ -1986,7 +2004,7 @@ int rekey_move_table_validate_impl(const modgpu_rekey_table_entry_t *t, uint64_t
         if (!t[i].dst || !t[i].src) return entry(i, "null buffer");
         const uint64_t d = at(t[i].dst), s = at(t[i].src);
         if (t[i].n >= kTableMaxEntryChunks * chunk) return entry(i, "1 TiB or more");
-        if (way > 0 ? d < s : d > s) return entry(i, way > 0 ? "slides down in an upward table" : "slides up in a downward table");
+        if (one_way && (way > 0 ? d < s : d > s)) return entry(i, way > 0 ? "slides down in an upward table" : "slides up in a downward table");
         if (prev != UINT64_MAX) {
             const uint64_t ps = at(t[prev].src), pd = at(t[prev].dst), pn = t[prev].n;
             if (s < ps || s - ps < pn) return entry(i, "source below the end of the previous entry's source (entries are listed by rising address, sources disjoint)");
@@ -2293,6 +2311,19 @@ int modgpu_rekey_move_table_device(const modgpu_rekey_table_entry_t *dev_entries
 int modgpu_rekey_move_table_validate(const modgpu_rekey_table_entry_t *host_entries, uint64_t n_entries)
 {
     return guarded([&]() -> int { return rekey_move_table_validate_impl(host_entries, n_entries); });
+}
+
+int modgpu_rekey_relayout_table_device(const modgpu_rekey_table_entry_t *dev_entries, uint64_t n_entries, uint64_t total_bytes, void *dev_workspace,
+                                       uint64_t workspace_bytes, int device, void *hip_stream)
+{
+    return guarded([&]() -> int {
+        return rekey_move_table_impl(dev_entries, n_entries, total_bytes, dev_workspace, workspace_bytes, device, static_cast<hipStream_t>(hip_stream), true);
+    });
+}
+
+int modgpu_rekey_relayout_table_validate(const modgpu_rekey_table_entry_t *host_entries, uint64_t n_entries)
+{
+    return guarded([&]() -> int { return rekey_move_table_validate_impl(host_entries, n_entries, false); });
 }
 
 int modgpu_rekey_move_table_status(const void *dev_workspace, int device, uint64_t *first_bad_entry, uint64_t *stalled_chunk)
