@@ -683,11 +683,50 @@ uint64_t modgpu_cycle_digest_table_workspace_bytes(uint64_t n_entries);
 int modgpu_cycle_digest_table_device(const modgpu_table_entry_t *dev_entries, uint64_t n_entries, modgpu_digest_result_t *dev_records,
                                      uint32_t side, void *dev_workspace, uint64_t workspace_bytes, int device, void *hip_stream);
 
+/* ---- REKEY DIGEST TABLE: modgpu_rekey_table_device and one digest record per entry, in the same pass and the same three launches ------
+ * "Convert the 100 000 files of this part PS3 -> PS4 and tell me that they are the files of my manifest": the manifest holds plaintext
+ * Adler-32 values, and the plaintext of a rekey pass lies between the two keystreams, in registers only -- so this call is the one way
+ * to checksum it in the pass that handles it (2n bytes of traffic, where modgpu_rekey_table_device followed by
+ * modgpu_digest_table_device over a second table of 40-byte entries moves 3n in six launches).  Per entry
+ *   * `dst` receives, byte for byte, what modgpu_rekey_table_device writes for the same table -- and nothing next to it is touched;
+ *   * dev_records[i] receives {s1, s2, n, 0} as modgpu_digest_device defines it (only the residues mod 65521 of s1 and s2 specified),
+ *     of the side asked for: MODGPU_DIGEST_OUTPUT (the bytes stored), MODGPU_DIGEST_INPUT (the source bytes as read; with dst == src
+ *     the bytes as they were before the call), or */
+#define MODGPU_DIGEST_PLAIN 2u  /* records are of src[j] ^ ks(key_from)[off_from + j]: the plaintext between the two keystreams */
+/* Records are read back and closed with modgpu_digest_results / modgpu_digest_adler32, or checked where they lie with
+ * modgpu_digest_check_device.  An empty entry gives {0, 0, 0, 0}.  modgpu_cycle_digest_table_device has one keystream and keeps refusing
+ * side 2.  The bytes of workspace a call over n_entries needs (0 for none, or above MODGPU_TABLE_MAX_ENTRIES) --
+ * modgpu_rekey_table_workspace_bytes(n_entries), the same layout: */
+uint64_t modgpu_rekey_digest_table_workspace_bytes(uint64_t n_entries);
+
+/* The contract is modgpu_rekey_table_device's for the data and modgpu_cycle_digest_table_device's for the records, word for word where
+ * each applies: the 56-byte entry as it stands; every degenerate key pair (a key == 0 mod 2^31-1 on either side or both, one key at
+ * offsets equal mod 2^31-2) handled in the same pass; dst == src rekeys in place; THREE launches (plan, finish, stream) whatever the
+ * count -- path_stats().gpu_launches counts 3, modgpu_last_launch reports the stream launch as variant 20 with `bytes` = 0 and
+ * modgpu_rekey_table_kernel_source_hash() --; asynchronous on `hip_stream`, allocation-free, capturable into a hipGraph; the table is
+ * read when the call RUNS on the device, so a replay picks up rewritten entries; the workspace (8-byte aligned device memory of
+ * `device`) is the caller's, reset by the plan launch in stream order, and two calls on one workspace must not overlap in time.
+ * modgpu_table_status reports this call too.
+ *   * dev_records: n_entries records in device memory of `device`, 8-byte aligned, the caller's.  THE CALL INITIALISES THEM ITSELF, AND
+ *     WITHOUT A MEMSET NODE: the finish launch stores every entry's record whole (the sums of the < 16 ragged bytes at either end of
+ *     the entry, and n), the stream launch then only adds to valid records (non-returning 64-bit atomic adds).  A replayed graph
+ *     starts clean.
+ *   * Tier 1 (host, MODGPU_ERR_INVALID before anything is queued): modgpu_cycle_digest_table_device's tier 1 with this call's
+ *     workspace size, and a `side` that is none of the three constants (refused whatever n_entries is).  n_entries == 0 queues nothing.
+ *   * Tier 2 (device, by the plan launch): modgpu_rekey_table_device's -- a NULL dst or src with n > 0, nonzero flags or reserved, an
+ *     entry of 1 TiB or more, more than 2^31 chunks of 64 KiB together.  Any of these makes the whole call write NOTHING AT ALL -- no
+ *     byte of any destination and no record -- and modgpu_table_status names the lowest such entry.
+ *   * Tier 3: overlaps follow modgpu_rekey_table_device's rule (modgpu_rekey_table_validate checks it on a host copy), unchecked on
+ *     the device.  Records that overlap an entry's range are the caller's error. */
+int modgpu_rekey_digest_table_device(const modgpu_rekey_table_entry_t *dev_entries, uint64_t n_entries, modgpu_digest_result_t *dev_records,
+                                     uint32_t side, void *dev_workspace, uint64_t workspace_bytes, int device, void *hip_stream);
+
 /* ---- DIGEST CHECK: are these records the checksums of my manifest, and if not, which entry first?  On the device, in two launches ------
  * The digest calls leave one record per entry in device memory; the caller holds a manifest of Adler-32 values.  This call closes every
  * record where it lies and compares it with the manifest, so that nobody downloads 32 bytes per entry, finalises them on the host and
  * compares in a loop -- and so that a captured graph that digests a part can decide without the host.  It takes the records of every
- * digest producer: modgpu_digest_device / _batch_device, modgpu_digest_table_device, modgpu_cycle_digest_table_device.
+ * digest producer: modgpu_digest_device / _batch_device, modgpu_digest_table_device, modgpu_cycle_digest_table_device,
+ * modgpu_rekey_digest_table_device.
  * Entry i is BAD when the Adler-32 of dev_records[i] differs from dev_expect[i]; the Adler-32 is exactly what modgpu_digest_adler32
  * computes (the residues of s1, s2 and n mod 65521 first; A = (1 + s1) % m, B = (n + n * s1 - s2) % m; B << 16 | A; s1 and s2 may hold
  * any 64-bit value), and both halves are compared.
@@ -706,8 +745,9 @@ uint64_t modgpu_digest_check_bits_bytes(uint64_t n_entries);
  *   * dev_bad_bits, when not NULL: modgpu_digest_check_bits_bytes(n_entries) bytes.  Word w holds bit b set exactly when entry
  *     64 * w + b is bad; every word of ceil(n_entries / 64) is stored whole and the tail bits are 0, so nothing needs clearing
  *     beforehand.  A caller who wants to know which entries are bad downloads n / 8 bytes instead of 32 n.
- *   * dev_table_workspace, when not NULL: the workspace of the modgpu_digest_table_device or modgpu_cycle_digest_table_device call
- *     that produced the records (only its first 64 bytes, the table call's header, are looked at).  The check reads the header's
+ *   * dev_table_workspace, when not NULL: the workspace of the modgpu_digest_table_device, modgpu_cycle_digest_table_device or
+ *     modgpu_rekey_digest_table_device call that produced the records (only its first 64 bytes, the table call's header, which all
+ *     three kinds of workspace start with, are looked at).  The check reads the header's
  *     status ON THE DEVICE WHEN IT RUNS: if that table call was refused -- its records are then whatever the caller left there -- the
  *     check compares nothing, writes {0, UINT64_MAX, n_entries, 1} and leaves dev_bad_bits untouched.  A captured "digest table + check"
  *     graph is so honest on every replay, with no host in between.  With NULL the records are taken as they are: use NULL for the

@@ -69,6 +69,10 @@ int modgpu_time_digest_table_device(const void *dev_entries, uint64_t n_entries,
  * and one records array, `side` as the call's. */
 int modgpu_time_cycle_digest_table_device(const void *dev_entries, uint64_t n_entries, void *dev_records, uint32_t side, void *dev_workspace,
                                           uint64_t workspace_bytes, int device, void *hip_stream, int iters, float *ms_per_call);
+/* The same for modgpu_rekey_digest_table_device: `iters` back-to-back rekey digest table calls (three launches each) on one workspace
+ * and one records array, `side` as the call's. */
+int modgpu_time_rekey_digest_table_device(const void *dev_entries, uint64_t n_entries, void *dev_records, uint32_t side, void *dev_workspace,
+                                          uint64_t workspace_bytes, int device, void *hip_stream, int iters, float *ms_per_call);
 /* The same for modgpu_digest_check_device: `iters` back-to-back digest checks (two launches each) on one summary and one bitmap;
  * dev_table_workspace and dev_bad_bits may be NULL, as the call's. */
 int modgpu_time_digest_check_device(const void *dev_records, const void *dev_expect, uint64_t n_entries, const void *dev_table_workspace,
@@ -104,7 +108,9 @@ typedef struct modgpu_launch_info {
                              18 = the cycle digest table call's stream launch (modgpu_cycle_digest_table_device: the table call's
                                   stream kernel in its digesting loop; `bytes` = 0, as for 8),
                              19 = the check launch of modgpu_digest_check_device (the verify table call's finish kernel in its check
-                                  mode, "modgpu_cycle_verify_table_finish"; `bytes` = 0, `chunk_bytes` = 0) */
+                                  mode, "modgpu_cycle_verify_table_finish"; `bytes` = 0, `chunk_bytes` = 0),
+                             20 = the rekey digest table call's stream launch (modgpu_rekey_digest_table_device: the rekey table
+                                  call's stream kernel in its digesting loop; `bytes` = 0, as for 8) */
     uint32_t grid;        /* workgroups launched                                                  */
     uint32_t block;       /* threads per workgroup                                                */
     uint32_t chunk_bytes; /* bytes one workgroup trip covers                                      */
@@ -126,7 +132,8 @@ typedef struct modgpu_launch_info {
                                 modgpu_to_kernel_source_hash() for variant 16,
                                 modgpu_verify_table_kernel_source_hash() for variant 17,
                                 modgpu_table_kernel_source_hash() for variant 18,
-                                modgpu_verify_table_kernel_source_hash() for variant 19; static storage */
+                                modgpu_verify_table_kernel_source_hash() for variant 19,
+                                modgpu_rekey_table_kernel_source_hash() for variant 20; static storage */
 } modgpu_launch_info_t;
 int modgpu_last_launch(modgpu_launch_info_t *out);
 
@@ -303,6 +310,11 @@ void modgpu_debug_set_digest_table_grid(uint32_t grid);
  * out-of-place table call's 25 per 32 CUs at 4 GiB).  Measurement (tools/bench_cycle_digest_table.py) and parity tests of small grids, where one
  * workgroup passes several entries and folds its sums at every change of entry.  Any grid gives the same bytes and the same residues. */
 void modgpu_debug_set_cycle_digest_table_grid(uint32_t grid);
+
+/* The rekey digest table call's stream launch: `grid` workgroups (1..4096), 0 = the shipped grid (one workgroup per CU, as the rekey
+ * table call's).  Measurement (tools/bench_rekey_digest_table.py) and parity tests of small grids, where one workgroup
+ * passes several entries and folds its sums at every change of entry.  Any grid gives the same bytes and the same residues. */
+void modgpu_debug_set_rekey_digest_table_grid(uint32_t grid);
 
 /* The resident slice of a single in-place buffer's work-queue launch: every such launch of `min_bytes` bytes or more takes the keep
  * kernel with exactly this `mask` (a power of two minus one) and `run` (run = 0: no chunk is kept; mask = 0, run = 1: every chunk),

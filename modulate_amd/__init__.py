@@ -32,6 +32,8 @@ from .capi import (  # noqa: F401
     digest_table_device, digest_table_workspace_bytes, time_digest_table_device, debug_set_digest_table_grid,
     cycle_digest_table_device, cycle_digest_table_workspace_bytes, time_cycle_digest_table_device, debug_set_cycle_digest_table_grid,
     DIGEST_OUTPUT, DIGEST_INPUT,
+    rekey_digest_table_device, rekey_digest_table_workspace_bytes, time_rekey_digest_table_device, debug_set_rekey_digest_table_grid,
+    DIGEST_PLAIN,
     digest_check_device, digest_check_result, digest_check_bits_bytes, time_digest_check_device, DIGEST_CHECK_SUMMARY_DTYPE,
     verify_rekey_table_device, verify_rekey_table_workspace_bytes, time_verify_rekey_table_device, rekey_verify_table_kernel_source_hash,
     debug_set_rekey_verify_table_grid,

@@ -106,6 +106,8 @@ EXPORTS = {
     "modgpu_digest_table_device": (_int, [_vp, _u64, _vp, _vp, _u64, _int, _vp]),
     "modgpu_cycle_digest_table_workspace_bytes": (_u64, [_u64]),
     "modgpu_cycle_digest_table_device": (_int, [_vp, _u64, _vp, ctypes.c_uint32, _vp, _u64, _int, _vp]),
+    "modgpu_rekey_digest_table_workspace_bytes": (_u64, [_u64]),
+    "modgpu_rekey_digest_table_device": (_int, [_vp, _u64, _vp, ctypes.c_uint32, _vp, _u64, _int, _vp]),
     "modgpu_digest_results": (_int, [_vp, _u64, _int, _vp, ctypes.POINTER(ctypes.c_uint32)]),
     "modgpu_digest_adler32": (ctypes.c_uint32, [_vp]),
     "modgpu_digest_check_bits_bytes": (_u64, [_u64]),
@@ -140,6 +142,7 @@ VERIFY_RESULT_DTYPE = np.dtype([("mismatches", "<u8"), ("first_mismatch", "<u8")
 VERIFY_NONE = 0xFFFFFFFFFFFFFFFF  # first_mismatch of a clean entry
 # modgpu_digest_result_t (include/modgpu.h): 32 bytes; only the residues mod 65521 of s1 and s2 are specified
 DIGEST_OUTPUT, DIGEST_INPUT = 0, 1  # MODGPU_DIGEST_OUTPUT / _INPUT: which side of the XOR a cycle digest table call's records are of
+DIGEST_PLAIN = 2  # MODGPU_DIGEST_PLAIN: a rekey digest table call's records are of the plaintext between the two keystreams
 DIGEST_RESULT_DTYPE = np.dtype([("s1", "<u8"), ("s2", "<u8"), ("n", "<u8"), ("reserved", "<u8")])
 # modgpu_verify_table_summary_t (include/modgpu.h): 32 bytes
 VERIFY_TABLE_SUMMARY_DTYPE = np.dtype([("mismatches", "<u8"), ("first_bad_entry", "<u8"), ("entries", "<u8"), ("reserved", "<u8")])
@@ -203,6 +206,7 @@ TESTING_EXPORTS = {
     "modgpu_verify_table_kernel_source_hash": (ctypes.c_char_p, []),
     "modgpu_time_digest_table_device": (_int, [_vp, _u64, _vp, _vp, _u64, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
     "modgpu_time_cycle_digest_table_device": (_int, [_vp, _u64, _vp, ctypes.c_uint32, _vp, _u64, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
+    "modgpu_time_rekey_digest_table_device": (_int, [_vp, _u64, _vp, ctypes.c_uint32, _vp, _u64, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
     "modgpu_time_verify_rekey_device": (_int, [_vp, _vp, _u64, _i32, _u64, _i32, _u64, _vp, _int, _vp, _int, ctypes.POINTER(ctypes.c_float)]),
     "modgpu_rekey_verify_kernel_source_hash": (ctypes.c_char_p, []),
     "modgpu_keep_kernel_source_hash": (ctypes.c_char_p, []),
@@ -241,6 +245,7 @@ DEBUG_EXPORTS = {
     "modgpu_debug_set_rekey_verify_table_grid": (None, [ctypes.c_uint32]),
     "modgpu_debug_set_digest_table_grid": (None, [ctypes.c_uint32]),
     "modgpu_debug_set_cycle_digest_table_grid": (None, [ctypes.c_uint32]),
+    "modgpu_debug_set_rekey_digest_table_grid": (None, [ctypes.c_uint32]),
     "modgpu_debug_set_keep": (None, [_u64, ctypes.c_uint32, ctypes.c_uint32]),
     "modgpu_debug_set_digest_grid": (None, [_int]),
 }
@@ -1373,6 +1378,40 @@ def debug_set_cycle_digest_table_grid(grid=0):
     _debug_lib().modgpu_debug_set_cycle_digest_table_grid(grid)
 
 
+def rekey_digest_table_workspace_bytes(n_entries):
+    """bytes of device workspace a rekey digest table call over n_entries needs (0 for none, or above the limit):
+    rekey_table_workspace_bytes(n)"""
+    return lib().modgpu_rekey_digest_table_workspace_bytes(n_entries)
+
+
+def rekey_digest_table_device(entries, records=None, side=DIGEST_PLAIN, workspace=None, device=-1, stream=None, *, n=None):
+    """Rekeys a TABLE of rekey entries as rekey_table_device does AND digests every entry in the same pass, three launches whatever the
+    length: record i is of src ^ ks(key_from), the plaintext between the two keystreams (side=DIGEST_PLAIN), of what was stored
+    (DIGEST_OUTPUT) or of the source bytes as read (DIGEST_INPUT).  `entries` is a host table (a REKEY_TABLE_DTYPE array: uploaded) or a
+    table already in device memory (a DeviceBuffer or an address; then n, the entry count, is needed).  `records` is a DeviceBuffer or
+    address of 32 * n bytes, `workspace` one of at least rekey_digest_table_workspace_bytes(n) bytes; None makes one.  When this function
+    made a buffer itself it waits for the call, raises ModGpuError if the device refused an entry (nothing was written, no byte and no
+    record) and returns (the records as a DIGEST_RESULT_DTYPE array, their Adler-32 values as a uint32 array); otherwise the call is
+    asynchronous on `stream`, returns None, and table_status(workspace) and digest_results(records, n) tell the outcome after a
+    synchronise."""
+    return _table_call("modgpu_rekey_digest_table_device", entries, REKEY_TABLE_DTYPE, n, workspace, rekey_digest_table_workspace_bytes, device,
+                       stream, "the device refused rekey digest table entry {}; nothing was written", extra=(side,), fetch=digest_results,
+                       results=records, empty=_no_digest_results)
+
+
+def time_rekey_digest_table_device(entries, n, records, workspace, side=DIGEST_PLAIN, device=-1, stream=None, iters=2):
+    """Mean ms per rekey digest table call (three launches) over `iters` calls, HIP events on the launch stream; table, records and
+    workspace resident."""
+    ws_bytes = workspace.nbytes if isinstance(workspace, DeviceBuffer) else rekey_digest_table_workspace_bytes(n)
+    return _time_call("modgpu_time_rekey_digest_table_device", (_vp(_dev_addr(entries)), n, _vp(_dev_addr(records)), side, _vp(_dev_addr(workspace)),
+                                                                ws_bytes), device, stream, iters)
+
+
+def debug_set_rekey_digest_table_grid(grid=0):
+    """Testing flavour: the rekey digest table call's stream grid (0 = shipped).  Every grid gives the same bytes and residues."""
+    _debug_lib().modgpu_debug_set_rekey_digest_table_grid(grid)
+
+
 def digest_check_bits_bytes(n_entries):
     """bytes of a digest check's bitmap over n_entries: 8 * ceil(n / 64) (0 for none, or above the table calls' limit)"""
     return lib().modgpu_digest_check_bits_bytes(n_entries)
@@ -1678,6 +1717,38 @@ class DeviceBuffer:
             return _no_digest_results()[1], _no_bad_entries()
         (_, adlers), outcome = _table_call("modgpu_cycle_digest_table_device", t, TABLE_DTYPE, None, workspace, cycle_digest_table_workspace_bytes,
                                            self.device, stream, "the device refused cycle digest table entry {}; nothing was written", extra=(side,),
+                                           fetch=digest_results, then=_check_behind(expect, self.device))
+        return adlers, outcome
+
+    def _convert_table(self, ranges, key_from, key_to, out, part_off):
+        ranges = [(int(o), int(n)) for o, n in ranges]
+        assert all(o >= 0 and n >= 0 and o + n <= self.nbytes for o, n in ranges)
+        assert out is self or (out.device == self.device and all(o + n <= out.nbytes for o, n in ranges))
+        t = rekey_table(len(ranges))
+        for i, (o, n) in enumerate(ranges):
+            t[i]["dst"], t[i]["src"], t[i]["n"] = out.ptr + o, self.ptr + o, n
+            t[i]["off_from"] = t[i]["off_to"] = part_off + o
+            t[i]["key_from"], t[i]["key_to"] = as_int32(key_from), as_int32(key_to)
+        return t
+
+    def convert(self, ranges, key_from, key_to, out, part_off=0, side=DIGEST_PLAIN, workspace=None, stream=None):
+        """Converts every range of `ranges` -- a list of (offset, n) -- of the part this buffer holds from key_from to key_to, each at
+        stream offset part_off + offset under both keys, into the same offset of `out` (another DeviceBuffer, or `self`: in place), and
+        returns one Adler-32 per range -- of the plaintext between the two keystreams, or by `side` of what was stored or read -- as a
+        uint32 array: one rekey_digest_table_device call."""
+        return rekey_digest_table_device(self._convert_table(ranges, key_from, key_to, out, part_off), None, side, workspace, self.device, stream)[1]
+
+    def convert_checked(self, ranges, key_from, key_to, out, expect, part_off=0, side=DIGEST_PLAIN, workspace=None, stream=None):
+        """`convert`, and the call's records checked against `expect` -- one Adler-32 per range, a host uint32 array -- on the device,
+        in the same stream: (the Adler-32 values as convert returns them, (bad ranges, the lowest bad range or None, the bad ranges'
+        indices as a uint64 array))."""
+        expect = np.ascontiguousarray(expect, dtype=np.uint32)
+        t = self._convert_table(ranges, key_from, key_to, out, part_off)
+        assert expect.size == t.size
+        if not t.size:
+            return _no_digest_results()[1], _no_bad_entries()
+        (_, adlers), outcome = _table_call("modgpu_rekey_digest_table_device", t, REKEY_TABLE_DTYPE, None, workspace, rekey_digest_table_workspace_bytes,
+                                           self.device, stream, "the device refused rekey digest table entry {}; nothing was written", extra=(side,),
                                            fetch=digest_results, then=_check_behind(expect, self.device))
         return adlers, outcome
 

@@ -452,37 +452,46 @@ def digest_table_loop(k):
     return bad
 
 
-def cycle_digest_table_loop(k):
+def cycle_digest_table_loop(k, loop="cycle digest"):
     """the out-of-place table kernel's second loop (cycle_table_kernel.h: CYCLE_TABLE_DIGEST, one uniform branch apart from the plain
     loop).  It cycles as the plain loop does and sums what it stores, or what it read: the sums are taken with v_dot4_u32_u8; every
     64-bit atomic of the kernel is a non-returning add (the pair per unrolled trip that goes onto the entry's record: 4; the loop would
     wait for a value that came back); the fold that precedes them goes through LDS (ds_add_u32) and not through memory; both loops
     draw one plain returning 32-bit ticket per unrolled trip (4); and every store of the kernel is a whole word through a buffer
-    descriptor with the streaming policy -- 4 words x 2 unrolled trips in each loop, nt sc1 -- and nothing through a pointer"""
+    descriptor with the streaming policy -- 4 words x 2 unrolled trips in each loop, nt sc1 -- and nothing through a pointer.  `loop`: what
+    the findings call it (the rekey table kernel's second loop is held to the same rules)"""
     bad = []
     if "v_dot4_u32_u8" not in k.fn:
-        bad.append("%s: no v_dot4_u32_u8 (the cycle digest loop's byte and position sums)" % k.name)
+        bad.append("%s: no v_dot4_u32_u8 (the %s loop's byte and position sums)" % (k.name, loop))
     atomics = [(m.group(1), m.group(2)) for m in re.finditer(r"^\s+(global_atomic_\w+)\b([^;\n]*)", k.fn, re.M)]
     wide = [(op, args) for op, args in atomics if op.endswith("_x2")]
     if any(" sc0" in args for _, args in wide):
-        bad.append("%s: a 64-bit atomic returns its value (sc0): the cycle digest loop's sums are non-returning global_atomic_add_x2" % k.name)
+        bad.append("%s: a 64-bit atomic returns its value (sc0): the %s loop's sums are non-returning global_atomic_add_x2" % (k.name, loop))
     if len(wide) != 4 or any(op != "global_atomic_add_x2" for op, _ in wide):
-        bad.append("%s: 64-bit atomics %s, expected 4 global_atomic_add_x2 (a pair per unrolled trip of the cycle digest loop) and nothing else"
-                   % (k.name, [op for op, _ in wide]))
+        bad.append("%s: 64-bit atomics %s, expected 4 global_atomic_add_x2 (a pair per unrolled trip of the %s loop) and nothing else"
+                   % (k.name, [op for op, _ in wide], loop))
     fetches = [args for op, args in atomics if op == "global_atomic_add"]
     if len(fetches) != 4 or not all(args.rstrip().endswith(" sc0") for args in fetches) or len(atomics) != len(wide) + len(fetches):
         bad.append("%s: %d 32-bit global_atomic_add among %d atomics, expected the ticket fetch of each unrolled trip of both loops (4), each "
                    "returning (sc0), and the 64-bit adds" % (k.name, len(fetches), len(atomics)))
     if not code_lines(k.fn, "ds_add_u32"):
-        bad.append("%s: no ds_add_u32 (the cycle digest loop folds a workgroup's sums in LDS, one pair per wave)" % k.name)
+        bad.append("%s: no ds_add_u32 (the %s loop folds a workgroup's sums in LDS, one pair per wave)" % (k.name, loop))
     data = code_lines(k.fn, "buffer_store_")
     if len(data) != 16 or any(not ln.lstrip().startswith("buffer_store_dwordx4") or not ln.endswith(" nt sc1") for ln in data):
-        bad.append("%s: a store of the cycle digest loop is not nt sc1 (%d buffer stores, expected 16 whole words, all nt sc1: %s in each loop)"
-                   % (k.name, len(data), TRIPS))
+        bad.append("%s: a store of the %s loop is not nt sc1 (%d buffer stores, expected 16 whole words, all nt sc1: %s in each loop)"
+                   % (k.name, loop, len(data), TRIPS))
     if re.search(r"^\s+(global|flat|scratch)_store", k.fn, re.M):
-        bad.append("%s: a store through a pointer in the kernel of the cycle digest loop (records take 64-bit atomic adds, data goes through "
-                   "the destination's descriptor)" % k.name)
+        bad.append("%s: a store through a pointer in the kernel of the %s loop (records take 64-bit atomic adds, data goes through "
+                   "the destination's descriptor)" % (k.name, loop))
     return bad
+
+
+def rekey_digest_table_loop(k):
+    """the rekey table kernel's second loop (cycle_rekey_table_kernel.h: REKEY_TABLE_DIGEST, one uniform branch apart from the plain
+    loop).  It rekeys as the plain loop does and sums the word it stores, the word it read or the plaintext between the two keystreams;
+    what it sends to memory and how is the cycle digest loop's, rule for rule.  (The summed word's own v_bitop3_b32 carry the truth
+    table 0x78, p ^ (q & r): rekey_blocks' count of 0x96 stays one per dword of a block.)"""
+    return cycle_digest_table_loop(k, "rekey digest")
 
 
 def digest_loop(k):
@@ -670,9 +679,11 @@ TUS = (
     table_tu("cycle_table_kernel.s", "the table kernels' TU", "modgpu_cycle_table", PLANNING,
              [keystream_blocks, (block_count, KEYSTREAM, 16, TRIPS + " in the plain and in the cycle digest loop"), loads_nt, (stores, "nt sc1"),
               cycle_digest_table_loop, scalar_entry_search]),
-    # table of rekey entries
+    # table of rekey entries.  The stream kernel has two loops, the plain one and the rekey digest loop (one uniform branch chooses):
+    # twice the blocks, the ticket fetches and the stores, and the second loop's pair of 64-bit adds per unrolled trip
     table_tu("cycle_rekey_table_kernel.s", "the rekey table kernels' TU", "modgpu_cycle_rekey_table", REKEY_PLANNING,
-             [rekey_blocks, (block_count, TWO_KEYSTREAM, 8, TRIPS), loads_nt, (stores, "nt sc1"), scalar_entry_search]),
+             [rekey_blocks, (block_count, TWO_KEYSTREAM, 16, TRIPS + " in the plain and in the rekey digest loop"), loads_nt, (stores, "nt sc1"),
+              rekey_digest_table_loop, scalar_entry_search]),
     # verify: the init kernel and the stream kernel plain / funnel x keyed <..., true> (compares with src ^ keystream) / identity (compares
     # the buffers as they are: no block).  Chunks are assigned statically: no ticket, nothing for the atomic optimizer to rewrite
     TU("cycle_verify_kernel.s", "the verify kernels' TU",

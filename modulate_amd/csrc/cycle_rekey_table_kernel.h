@@ -59,6 +59,18 @@ struct RekeyTableEdge {
 };
 static_assert(sizeof(RekeyTableEdge) == 16, "four states");
 
+// The REKEY DIGEST mode of the same three kernels (modgpu_rekey_digest_table_device): every entry is rekeyed as in the plain mode -- plan
+// is the plain mode's, the grid on the DESTINATION -- and record i receives the digest of the entry's stored bytes
+// (REKEY_TABLE_SIDE_OUTPUT), of its source bytes as read (REKEY_TABLE_SIDE_INPUT), or of src ^ ks(key_from), the plaintext between the
+// two keystreams that exists in registers only (REKEY_TABLE_SIDE_PLAIN).  The finish launch sums the < 16 bytes at either end while it
+// rekeys them and stores the record whole; the stream kernel's second loop (one uniform branch on `mode`) sums one word per word it
+// stores and adds to the records with non-returning 64-bit atomic adds.  The record and its protocol are the cycle digest table
+// call's (cycle_table_kernel.h: DigestTableRecord).
+enum RekeyTableMode : uint32_t { REKEY_TABLE_PLAIN = 0u, REKEY_TABLE_DIGEST = 1u };
+enum RekeyTableSide : uint32_t { REKEY_TABLE_SIDE_OUTPUT = 0u, REKEY_TABLE_SIDE_INPUT = 1u, REKEY_TABLE_SIDE_PLAIN = 2u };
+// reporting only (modgpu_last_launch): the stream launch of a rekey digest table call
+constexpr int CYCLE_REKEY_DIGEST_TABLE = 20;
+
 struct RekeyTableArgs {
     const RekeyTableEntry *entries;
     uint64_t n;
@@ -70,6 +82,9 @@ struct RekeyTableArgs {
     uint64_t level_n[kTableLevels];
     uint32_t top;                  // highest level (<= 16 keys)
     uint32_t n_blk;                // ceil(n / 1024)
+    uint32_t mode;                 // REKEY_TABLE_PLAIN (side 0, records null), or REKEY_TABLE_DIGEST
+    uint32_t side;                 // REKEY_TABLE_SIDE_OUTPUT / _INPUT / _PLAIN: which bytes the records are of
+    DigestTableRecord *records;    // n records in the caller's device memory: stored whole by finish, added to by stream
 };
 
 uint32_t modgpu_rekey_table_chunk_bytes();
@@ -79,3 +94,8 @@ const char *modgpu_rekey_table_kernel_name();
 hipError_t modgpu_launch_rekey_table_plan(const RekeyTableArgs &a, hipStream_t stream);
 hipError_t modgpu_launch_rekey_table_finish(const RekeyTableArgs &a, hipStream_t stream);
 hipError_t modgpu_launch_rekey_table_stream(const RekeyTableArgs &a, uint32_t grid, hipStream_t stream);
+// The same three kernels with a.mode = REKEY_TABLE_DIGEST (a.side and a.records are the caller's): the three launches of a rekey digest
+// table call (any grid >= 1 gives the same bytes and the same residues)
+hipError_t modgpu_launch_rekey_digest_table_plan(const RekeyTableArgs &a, hipStream_t stream);
+hipError_t modgpu_launch_rekey_digest_table_finish(const RekeyTableArgs &a, hipStream_t stream);
+hipError_t modgpu_launch_rekey_digest_table_stream(const RekeyTableArgs &a, uint32_t grid, hipStream_t stream);

@@ -1505,8 +1505,8 @@ void store_le32(uint8_t *p, uint32_t v)
 }
 
 } // namespace
-// ---- the seven calls over a table in device memory: modgpu_cycle_table_device, modgpu_rekey_table_device, modgpu_verify_table_device,
-// modgpu_verify_rekey_table_device, modgpu_digest_table_device, modgpu_cycle_digest_table_device (three launches: plan, finish, stream) and modgpu_rekey_move_table_device
+// ---- the eight calls over a table in device memory: modgpu_cycle_table_device, modgpu_rekey_table_device, modgpu_verify_table_device,
+// modgpu_verify_rekey_table_device, modgpu_digest_table_device, modgpu_cycle_digest_table_device, modgpu_rekey_digest_table_device (three launches: plan, finish, stream) and modgpu_rekey_move_table_device
 // (five) -- and modgpu_rekey_relayout_table_device, the move call's launches twice (ten).
 // One workspace walk, one set of grid hooks and one call body (table_call); a call is its layout, its launches and its names. --------
 namespace {
@@ -1600,7 +1600,7 @@ bool move_table_sizes_ok(uint64_t n, uint64_t total_bytes)
 // The grid of a call's stream (move) launch.  The out-of-place table takes the out-of-place kernel's (25 workgroups per 32 CUs;
 // DESIGN.md 4.8 has the A/B against one per CU); its digesting mode measured the other way round and, like the
 // others, takes one workgroup per CU on every CU, as the rekey and verify kernels (the move launch never gets more than the device holds at once).  modgpu_debug_set_*_table_grid forces one.
-enum TableCall { kCycleTable, kRekeyTable, kVerifyTable, kRekeyVerifyTable, kMoveTable, kDigestTable, kCycleDigestTable, kTableCalls };
+enum TableCall { kCycleTable, kRekeyTable, kVerifyTable, kRekeyVerifyTable, kMoveTable, kDigestTable, kCycleDigestTable, kRekeyDigestTable, kTableCalls };
 #ifdef MODGPU_TESTING_HOOKS
 std::atomic<uint32_t> g_table_grid[kTableCalls] = {};
 uint32_t table_grid_forced(TableCall c) { return g_table_grid[c].load(std::memory_order_relaxed); }
@@ -1617,7 +1617,7 @@ uint32_t table_grid(TableCall c)
     return (uint32_t)std::max<uint64_t>(1, cap);
 }
 
-// What a call is: which of the seven (its grid), the size of the record it writes per entry into `results` (the verifying calls' result,
+// What a call is: which of the eight (its grid), the size of the record it writes per entry into `results` (the verifying calls' result,
 // the digest call's record; 0: the call has no `results`, and nothing looks at that argument), and what it is called -- in tier 1's
 // words for a short workspace, and in modgpu_last_launch's report of its stream (move) launch
 struct TableKind {
@@ -1724,7 +1724,11 @@ int cycle_digest_table_impl(const modgpu_table_entry_t *entries, uint64_t n, mod
     return table_impl(entries, n, records, side, ws, ws_bytes, device, stream);
 }
 
-int rekey_table_impl(const modgpu_rekey_table_entry_t *entries, uint64_t n, void *ws, uint64_t ws_bytes, int device, hipStream_t stream)
+// The rekey table call (records == nullptr: nothing looks at `side`), and the rekey digest table call: the same TU's three kernels in
+// their digest mode, on the same workspace, writing one digest record per entry -- of the stored bytes, of the source bytes or of the
+// plaintext between the two keystreams, by `side`.
+int rekey_table_impl(const modgpu_rekey_table_entry_t *entries, uint64_t n, modgpu_digest_result_t *records, uint32_t side, void *ws, uint64_t ws_bytes,
+                     int device, hipStream_t stream)
 {
     using A = RekeyTableArgs;
     static constexpr TableKind kind = {kRekeyTable, 0, "workspace smaller than modgpu_rekey_table_workspace_bytes(n_entries)", modgpu_rekey_table_kernel_name,
@@ -1732,8 +1736,32 @@ int rekey_table_impl(const modgpu_rekey_table_entry_t *entries, uint64_t n, void
     static constexpr TableLaunch<A> launches[] = {{"rekey table plan launch", no_grid<A, modgpu_launch_rekey_table_plan>},
                                                   {"rekey table finish launch", no_grid<A, modgpu_launch_rekey_table_finish>},
                                                   {"rekey table stream launch", on_grid<A, modgpu_launch_rekey_table_stream>}};
-    return table_call(kind, launches, entries, n, nullptr, nullptr, ws, ws_bytes, device, stream, [&] { return rekey_table_layout(n); },
-                      [](A &a, uint8_t *w, const TableLayout &L) { a.edge = reinterpret_cast<RekeyTableEdge *>(w + L.edge); });
+    static constexpr TableKind digest_kind = {kRekeyDigestTable, sizeof(modgpu_digest_result_t), "workspace smaller than modgpu_rekey_digest_table_workspace_bytes(n_entries)",
+                                                modgpu_rekey_table_kernel_name, CYCLE_REKEY_DIGEST_TABLE, modgpu_rekey_table_block, modgpu_rekey_table_chunk_bytes,
+                                                MODGPU_REKEY_TABLE_KERNEL_SOURCE_HASH};
+    static constexpr TableLaunch<A> digest_launches[] = {{"rekey digest table plan launch", no_grid<A, modgpu_launch_rekey_digest_table_plan>},
+                                                         {"rekey digest table finish launch", no_grid<A, modgpu_launch_rekey_digest_table_finish>},
+                                                         {"rekey digest table stream launch", on_grid<A, modgpu_launch_rekey_digest_table_stream>}};
+    return table_call(records ? digest_kind : kind, records ? digest_launches : launches, entries, n, records, nullptr, ws, ws_bytes, device, stream,
+                      [&] { return rekey_table_layout(n); },
+                      [&](A &a, uint8_t *w, const TableLayout &L) {
+                          a.edge = reinterpret_cast<RekeyTableEdge *>(w + L.edge);
+                          a.side = records ? side : 0u;
+                          a.records = reinterpret_cast<DigestTableRecord *>(records);
+                      });
+}
+
+// modgpu_rekey_digest_table_device's own part of tier 1, in front of rekey_table_impl (where a null `records` means the plain call): the
+// side, and a null `records` refused where the digest table call refuses it -- behind the count, the table and the workspace
+static_assert(MODGPU_DIGEST_OUTPUT == REKEY_TABLE_SIDE_OUTPUT && MODGPU_DIGEST_INPUT == REKEY_TABLE_SIDE_INPUT && MODGPU_DIGEST_PLAIN == REKEY_TABLE_SIDE_PLAIN,
+              "the kernels read the public side");
+int rekey_digest_table_impl(const modgpu_rekey_table_entry_t *entries, uint64_t n, modgpu_digest_result_t *records, uint32_t side, void *ws,
+                            uint64_t ws_bytes, int device, hipStream_t stream)
+{
+    if (side != MODGPU_DIGEST_OUTPUT && side != MODGPU_DIGEST_INPUT && side != MODGPU_DIGEST_PLAIN)
+        return fail(MODGPU_ERR_INVALID, "side is neither the output side (0), the input side (1) nor the plaintext between the keystreams (2)");
+    if (n != 0 && n <= kTableMaxEntries && entries && ws && !records) return fail(MODGPU_ERR_INVALID, "null results");
+    return rekey_table_impl(entries, n, records, side, ws, ws_bytes, device, stream);
 }
 
 int verify_table_impl(const modgpu_table_entry_t *entries, uint64_t n, modgpu_verify_result_t *results, void *ws, uint64_t ws_bytes, int device,
@@ -2286,7 +2314,17 @@ int modgpu_rekey_table_device(const modgpu_rekey_table_entry_t *dev_entries, uin
                               int device, void *hip_stream)
 {
     return guarded([&]() -> int {
-        return rekey_table_impl(dev_entries, n_entries, dev_workspace, workspace_bytes, device, static_cast<hipStream_t>(hip_stream));
+        return rekey_table_impl(dev_entries, n_entries, nullptr, 0u, dev_workspace, workspace_bytes, device, static_cast<hipStream_t>(hip_stream));
+    });
+}
+
+uint64_t modgpu_rekey_digest_table_workspace_bytes(uint64_t n_entries) { return modgpu_rekey_table_workspace_bytes(n_entries); }
+
+int modgpu_rekey_digest_table_device(const modgpu_rekey_table_entry_t *dev_entries, uint64_t n_entries, modgpu_digest_result_t *dev_records, uint32_t side,
+                                     void *dev_workspace, uint64_t workspace_bytes, int device, void *hip_stream)
+{
+    return guarded([&]() -> int {
+        return rekey_digest_table_impl(dev_entries, n_entries, dev_records, side, dev_workspace, workspace_bytes, device, static_cast<hipStream_t>(hip_stream));
     });
 }
 
@@ -3135,7 +3173,17 @@ int modgpu_time_rekey_table_device(const void *dev_entries, uint64_t n_entries, 
 {
     return guarded([&]() -> int {
         return time_calls(device, hip_stream, iters, ms_per_call, [&](hipStream_t st) {
-            return rekey_table_impl(static_cast<const modgpu_rekey_table_entry_t *>(dev_entries), n_entries, dev_workspace, workspace_bytes, -1, st);
+            return rekey_table_impl(static_cast<const modgpu_rekey_table_entry_t *>(dev_entries), n_entries, nullptr, 0u, dev_workspace, workspace_bytes, -1, st);
+        });
+    });
+}
+
+int modgpu_time_rekey_digest_table_device(const void *dev_entries, uint64_t n_entries, void *dev_records, uint32_t side, void *dev_workspace,
+                                          uint64_t workspace_bytes, int device, void *hip_stream, int iters, float *ms_per_call)
+{
+    return guarded([&]() -> int {
+        return time_calls(device, hip_stream, iters, ms_per_call, [&](hipStream_t st) {
+            return rekey_digest_table_impl(static_cast<const modgpu_rekey_table_entry_t *>(dev_entries), n_entries, static_cast<modgpu_digest_result_t *>(dev_records), side, dev_workspace, workspace_bytes, -1, st);
         });
     });
 }
@@ -3217,6 +3265,7 @@ void modgpu_debug_set_table_grid(uint32_t grid) { force_table_grid(kCycleTable, 
 void modgpu_debug_set_move_grid(uint32_t grid) { g_move_grid.store(std::min<uint32_t>(grid, 4096u), std::memory_order_relaxed); }
 void modgpu_debug_set_move_table_grid(uint32_t grid) { force_table_grid(kMoveTable, grid); }
 void modgpu_debug_set_rekey_table_grid(uint32_t grid) { force_table_grid(kRekeyTable, grid); }
+void modgpu_debug_set_rekey_digest_table_grid(uint32_t grid) { force_table_grid(kRekeyDigestTable, grid); }
 
 void modgpu_debug_set_verify_table_grid(uint32_t grid) { force_table_grid(kVerifyTable, grid); }
 void modgpu_debug_set_rekey_verify_table_grid(uint32_t grid) { force_table_grid(kRekeyVerifyTable, grid); }
