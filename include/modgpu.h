@@ -893,6 +893,34 @@ int modgpu_cycle_file_to_device(const char *path, uint64_t file_off, void *dev_d
 int modgpu_cycle_device_to_file(const void *dev_src, uint64_t n, const char *path, int32_t key, uint64_t stream_off,
                                 int device);
 
+/* ---- transfers of a LIST of ranges: the files of a part onto or off the GPU in one call ----------------------------------------
+ * host_entries is a HOST array of modgpu_table_entry_t, the 40-byte entry of the table calls (one table builder serves both):
+ *   modgpu_cycle_host_to_device_list   upload: every entry's dst is device memory of `device`, its src host memory
+ *   modgpu_cycle_device_to_host_list   download: every entry's dst is host memory, its src device memory of `device`
+ * Per entry dst[j] = src[j] ^ ks(key)[stream_off + j], j < n -- exactly what the single transfer call above computes for it, and under
+ * the single calls' contract wherever it applies: SYNCHRONOUS, NO ORDERING against the caller's streams, THE SOURCE IS NEVER WRITTEN,
+ * any byte alignment on both sides of every entry, 64-bit offsets reduced mod the period, a key == 0 mod 2^31-1 copies, entries with
+ * n == 0 are skipped (their pointers may be NULL); n_entries == 0, or a list with no bytes, queues nothing and returns MODGPU_OK.  No
+ * GPU is MODGPU_ERR_NO_DEVICE; a GPU lost in the middle of the call or a kernel that stops responding is MODGPU_ERR_HIP after the
+ * single calls' bounded wait, the sources then intact and the destinations unspecified.
+ * ONE LAUNCH per call whatever n_entries is: path_stats().gpu_launches counts it, modgpu_last_launch reports it as variant 21 with
+ * `bytes` = the list's total and modgpu_xfer_kernel_source_hash().  The entries' bytes travel as one packed stream through the
+ * library's page-locked slots (page-locked caller memory too: it is copied like any other); the list is read, and a plan of 24 bytes
+ * per non-empty entry put into device memory, before the launch.  A list of more bytes than the single call's one-launch limit (about
+ * 63 GiB) IS CUT the way a single call is: one launch per ~63 GiB of the packed stream (modgpu_last_launch then reports the last, with
+ * that launch's bytes).  A piece of the stream that is made of very many tiny entries (a few bytes each) is correct and slow: its
+ * entries are done one after another.
+ * Refused before anything is queued, MODGPU_ERR_INVALID with modgpu_last_error() naming the LOWEST entry at fault ("entry <i>: ..."):
+ * a NULL list with n_entries > 0; n_entries above MODGPU_TABLE_MAX_ENTRIES; an entry with a NULL pointer and n > 0; an entry with
+ * nonzero flags; an entry of 2^39 bytes or more; an entry whose device side the runtime does not report as device memory of the
+ * call's device (the single call's rule, both ends of the range; entries whose device ranges touch end to start are looked up as one
+ * range).  Without a GPU these refusals are the same, except the last, which needs the device.
+ * NOT CHECKED: overlap.  In an upload the (device) destinations may not meet each other, in a download the (host) destinations may
+ * not meet each other; sources may overlap or repeat.  Bytes in ranges that break the rule are unspecified, but nothing outside the
+ * entries' [dst, dst+n) is ever written.  modgpu_table_validate checks a list against this rule. */
+int modgpu_cycle_host_to_device_list(const modgpu_table_entry_t *host_entries, uint64_t n_entries, int device);
+int modgpu_cycle_device_to_host_list(const modgpu_table_entry_t *host_entries, uint64_t n_entries, int device);
+
 /* ---- page-locked host memory -----------------------------------------------------------------
  * Replaces the `new char[total]` of CArk::LoadArkData / BuildArk (CArk.cpp:738, 780) for callers
  * that will cycle the buffer: the GPU's DMA engines and kernels reach these pages directly, so

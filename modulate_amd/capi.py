@@ -72,6 +72,8 @@ EXPORTS = {
     "modgpu_move_status": (_int, [_vp, _int, ctypes.POINTER(_u64)]),
     "modgpu_cycle_host_to_device": (_int, [_vp, _vp, _u64, _i32, _u64, _int]),
     "modgpu_cycle_device_to_host": (_int, [_vp, _vp, _u64, _i32, _u64, _int]),
+    "modgpu_cycle_host_to_device_list": (_int, [_vp, _u64, _int]),
+    "modgpu_cycle_device_to_host_list": (_int, [_vp, _u64, _int]),
     "modgpu_cycle_file_to_device": (_int, [ctypes.c_char_p, _u64, _vp, _u64, _i32, _u64, _int]),
     "modgpu_cycle_device_to_file": (_int, [_vp, _u64, ctypes.c_char_p, _i32, _u64, _int]),
     "modgpu_table_workspace_bytes": (_u64, [_u64]),
@@ -428,7 +430,8 @@ def debug_set_staged_mode(mode=0):
 
 
 HOST_TUNABLES = {"zerocopy_bytes": 0, "ring": 1, "split": 2, "chunk_min_bytes": 3, "ramp_bytes": 4, "lanes": 5, "ntcopy": 6, "file_sched": 7,
-                 "feed": 8, "feed_chunk_bytes": 9, "feed_patience_ms": 10, "file_feed": 11}
+                 "feed": 8, "feed_chunk_bytes": 9, "feed_patience_ms": 10, "file_feed": 11,
+                 "xfer_list_most_bytes": 12}
 
 
 def debug_set_host_tunable(name, value):
@@ -1608,6 +1611,45 @@ def cycle_device_to_file(dev_ptr, n, path, key, stream_off=0, device=-1):
     _check(lib().modgpu_cycle_device_to_file(_vp(dev_ptr), n, os.fsencode(path), as_int32(key), stream_off, device))
 
 
+def _xfer_list_table(entries, upload):
+    """(table, arrays to keep alive) of a list transfer: `entries` is a host table (TABLE_DTYPE array, taken as it stands) or a list of
+    (dev_ptr, array, key, stream_off) -- the array the host side of the entry, its source in an upload, its destination in a download"""
+    if isinstance(entries, np.ndarray):
+        return np.ascontiguousarray(entries, dtype=TABLE_DTYPE), ()
+    entries = list(entries)
+    t, keep = table(len(entries)), []
+    for i, (dev_ptr, buf, key, stream_off) in enumerate(entries):
+        p, n = _xfer_src(buf) if upload else _xfer_dst(buf)
+        keep.append(buf)
+        t[i]["dst"], t[i]["src"] = (_dev_addr(dev_ptr), p) if upload else (p, _dev_addr(dev_ptr))
+        t[i]["n"], t[i]["stream_off"], t[i]["key"] = n, stream_off, as_int32(key)
+    return t, keep
+
+
+def cycle_host_to_device_list(entries, device=-1, check=False):
+    """Upload of a list of ranges with the cipher in flight, ONE launch whatever the count (modgpu_cycle_host_to_device_list): for every
+    entry dev[j] = host[j] ^ ks(key)[stream_off + j].  `entries` is a host table (TABLE_DTYPE: dst the device side, src the host side) or
+    a list of (dev_ptr, array, key, stream_off).  check=True runs table_validate over the table first (the device destinations may not
+    meet each other; the call itself does not look).  Synchronous, and not ordered against the caller's streams (synchronise first)."""
+    t, keep = _xfer_list_table(entries, True)
+    if check:
+        table_validate(t)
+    _check(lib().modgpu_cycle_host_to_device_list(_vp(t.ctypes.data if t.size else 0), t.size, device))
+    del keep
+
+
+def cycle_device_to_host_list(entries, device=-1, check=False):
+    """Download of a list of ranges with the cipher in flight, ONE launch whatever the count (modgpu_cycle_device_to_host_list): for every
+    entry host[j] = dev[j] ^ ks(key)[stream_off + j].  `entries` is a host table (TABLE_DTYPE: dst the host side, src the device side) or
+    a list of (dev_ptr, array, key, stream_off), the arrays writable.  check=True runs table_validate over the table first (the host
+    destinations may not meet each other)."""
+    t, keep = _xfer_list_table(entries, False)
+    if check:
+        table_validate(t)
+    _check(lib().modgpu_cycle_device_to_host_list(_vp(t.ctypes.data if t.size else 0), t.size, device))
+    del keep
+
+
 XFER_FORMS = {None: 0, "kernel": 0, "dma": 1}
 
 
@@ -1782,13 +1824,38 @@ class DeviceBuffer:
         disjoint -- old_len bytes at offset give way to a hole of new_len bytes, and every surviving segment slides by the sum of the
         size changes before it, up or down, in one pass under `key` -- or rekeyed to key_to on the way (splice_moves, relayout).  Returns
         (new_used, holes), `holes` the (new_offset, new_len) of every edit with new_len > 0; raises ValueError if new_used exceeds the
-        buffer.  The caller then fills each hole with modgpu_cycle_host_to_device (cycle_host_to_device) at stream offset part_off +
-        new_offset, under the key the part now has."""
+        buffer.  `fill` then fills all the holes in one call (after the splice's stream has been synchronised), under the key the part
+        now has."""
         moves, new_used, holes = splice_moves(used, edits)
         if new_used > self.nbytes:
             raise ValueError(f"the spliced part needs {new_used} bytes, the buffer has {self.nbytes}")
         self.relayout(moves, key, key_to, part_off, workspace, stream)
         return new_used, holes
+
+    def upload_ranges(self, items, key, part_off=0):
+        """Uploads every (offset, array) of `items` into the part this buffer holds, each through the cipher from stream offset part_off
+        + offset under `key`, in ONE list transfer (cycle_host_to_device_list); the ranges may not meet each other.  Synchronous, not
+        ordered against the caller's streams."""
+        items = [(int(o), a) for o, a in items]
+        assert all(o >= 0 and o + _xfer_src(a)[1] <= self.nbytes for o, a in items)
+        cycle_host_to_device_list([(self.ptr + o, a, key, part_off + o) for o, a in items], self.device)
+
+    def download_ranges(self, ranges, key, outs, part_off=0):
+        """Downloads every (offset, n) of `ranges` of the part this buffer holds into the array of `outs` at the same index (n bytes,
+        writable), each through the cipher from stream offset part_off + offset under `key`, in ONE list transfer
+        (cycle_device_to_host_list).  Returns `outs`."""
+        ranges = [(int(o), int(n)) for o, n in ranges]
+        assert len(outs) == len(ranges) and all(o >= 0 and o + n <= self.nbytes and _xfer_dst(a)[1] == n for (o, n), a in zip(ranges, outs))
+        cycle_device_to_host_list([(self.ptr + o, a, key, part_off + o) for (o, _), a in zip(ranges, outs)], self.device)
+        return outs
+
+    def fill(self, holes, bufs, key, part_off=0):
+        """Fills the `holes` that `splice` returned -- (new_offset, new_len) each -- with the plaintext arrays `bufs`, one per hole and
+        new_len bytes long, under the key the part now has: ONE list transfer for all of them (upload_ranges).  Not ordered against the
+        caller's streams: synchronise the splice's stream first."""
+        holes = [(int(o), int(n)) for o, n in holes]
+        assert len(bufs) == len(holes) and all(_xfer_src(b)[1] == n for (_, n), b in zip(holes, bufs))
+        self.upload_ranges([(o, b) for (o, _), b in zip(holes, bufs)], key, part_off)
 
     def sync(self, stream=None):
         _check(self._lib.modgpu_sync(self.device, _vp(stream or 0)))

@@ -33,7 +33,30 @@ struct CycleXferArgs {
     uint32_t slot_phase;          // dev mod 16: a slot holds its chunk this far in, so that slot and device buffer are co-aligned mod 16
     uint32_t base;                // canonical state of the call's first byte
     uint32_t copy;                // 1: the identity keystream (key == 0 mod 2^31-1): the bytes are copied unchanged
+    // list mode (modgpu_launch_cycle_xfer_list; nullptr otherwise): the call's stream is the PACKED stream of a list of ranges
+    const struct XferListRec *list; // device memory: list_n records in packed order, then a terminator
+    uint32_t list_n;
 };
+
+// LIST MODE (modgpu_cycle_host_to_device_list / modgpu_cycle_device_to_host_list): the stream of the call is the entries' bytes laid end to
+// end, entry e from packed position start[e]; a slot holds its chunk of the packed stream from its first byte (slot_phase 0), `n` is the
+// list's total, `dev`, `base` and `copy` are not used.  A workgroup that has drawn a piece finds the last record whose start is not
+// behind the piece by a uniform binary search (bounded by list_n: a bad plan cannot send it out of the array) and walks the piece's
+// SEGMENTS, one per entry that reaches into it: each is done like a piece of the plain call -- the 16-byte grid on the segment's
+// destination, < 16 bytes bytewise at either edge, whole words through the v_alignbyte_b32 funnel, since slot position and device address
+// of a segment share no phase -- with the state of its first byte taken from the entry's base.  Neighbouring segments share 16-byte words
+// of a slot and neighbouring pieces belong to different workgroups: a whole-word store never reaches outside its own segment.  No barrier,
+// no LDS and no wait are added; a piece is counted once, after every segment's stores have been fenced.  A piece full of tiny entries runs
+// its segments one after another with few lanes busy: correct, and slow (a lane-parallel mapping for such runs is not built).
+// A runtime mode of the two FUNNEL instantiations; the plain ones do not have the loop.
+struct XferListRec {
+    uint8_t *dev;   // the entry's device side, byte j of the entry at dev + j (terminator: nullptr)
+    uint64_t start; // packed position of the entry's first byte; strictly increasing, record 0 at 0 (terminator: the list's total)
+    uint32_t base;  // canonical state of the entry's first byte (modgpu_state_at's arithmetic)
+    uint32_t copy;  // 1: this entry's key is 0 mod 2^31-1, its bytes are copied unchanged
+};
+constexpr int CYCLE_XFER_LIST = 21; // reporting only (modgpu_last_launch): a list transfer launch, either direction (`bytes` = the list's total)
+constexpr uint64_t kXferListEntryMax = 1ull << 39; // an entry's bytes stay below this: its 32 KiB steps fit the three-byte jump tables
 
 // How a source whose phase differs from the destination's by a non-whole number of dwords is read (only the direct form can meet one:
 // a staged chunk sits in its slot co-aligned with the device buffer):
@@ -43,6 +66,9 @@ enum XferForm : int { XFER_PLAIN = 0, XFER_FUNNEL = 1 };
 uint32_t modgpu_xfer_block();
 const char *modgpu_xfer_kernel_name(bool upload, int form);
 hipError_t modgpu_launch_cycle_xfer(const CycleXferArgs &a, bool upload, int form, uint32_t grid, hipStream_t stream);
+// a list launch (a.list set): always the funnel kernel of its direction.  A launch function of its own so that the CPU stand-in of the
+// runtime can supply it from a file of its own.
+hipError_t modgpu_launch_cycle_xfer_list(const CycleXferArgs &a, bool upload, uint32_t grid, hipStream_t stream);
 // The HIP device whose memory [p, p + n) is (both ends looked up with hipPointerGetAttributes), or -1: host memory, unknown, or
 // the two ends on different devices.  Lives here so that the CPU stand-in of the runtime can supply its own.
 int modgpu_xfer_device_of(const void *p, uint64_t n);

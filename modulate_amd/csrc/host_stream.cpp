@@ -172,6 +172,7 @@ constexpr uint32_t kFeedChunksMax = 8192;      // ready / done words per call (l
 constexpr uint64_t kFeedBelow = 2ull << 30;    // from here up a launch per 8 MiB chunk is as good or better (4 GiB, pageable: 49.3 against 48.7 GB/s, profiles/r05_pcie_feed.txt;
                                                // file -> pageable 46.4 / 47.0, profiles/r06_file_routes.txt)
 constexpr uint32_t kFeedGrid = 32;             // workgroups of the host-fed kernel: what saturates the link (profiles/r05_pcie_persist.txt)
+MODGPU_KNOB_STORAGE uint64_t kXferListMost = 0; // most packed bytes of a list transfer per launch; 0: the single call's one-launch limit (xfer_list_impl)
 MODGPU_KNOB_STORAGE uint64_t kFeedPatienceTicks = 1000000000ull; // 10 s of the 100 MHz wall clock: a chunk the host has not delivered by then never comes
 
 // ---- host-side timeline of the staged / pinned routes (modgpu_host_trace, reporting only) --------------------------------
@@ -399,9 +400,44 @@ void copy_bytes(uint8_t *dst, const uint8_t *src, uint64_t n)
     else std::memcpy(dst, src, n);
 }
 
+} // namespace
+// The host side of a list transfer (modgpu_cycle_host_to_device_list / _device_to_host_list): the PACKED stream, the non-empty entries'
+// bytes laid end to end in list order.  To the pipelines one more endpoint kind: fill_slot gathers a chunk from the entries' own memory,
+// drain_slot scatters one to it; a binary search over the starts gives the chunk's first entry.
+struct HostList {
+    struct Ent {
+        uint8_t *host, *dev; // the entry's two sides
+        uint64_t start, n;   // packed position of its first byte; its bytes (> 0)
+        uint64_t off;        // its stream offset, reduced mod the period
+        uint32_t key_res;    // its key mod 2^31-1 (0: copied)
+    };
+    std::vector<Ent> ent;
+    uint64_t total = 0;
+    size_t entry_at(uint64_t p) const // the entry that holds packed position p < total
+    {
+        return (size_t)(std::upper_bound(ent.begin(), ent.end(), p, [](uint64_t q, const Ent &e) { return q < e.start; }) - ent.begin()) - 1;
+    }
+};
+namespace {
+// packed positions [p, p + len) <-> buf[0 .. len): `up` gathers the entries' bytes into buf, else buf is scattered to them
+void list_copy(const HostList &l, uint8_t *buf, uint64_t p, uint64_t len, bool up)
+{
+    for (size_t e = l.entry_at(p); len > 0; ++e) {
+        const HostList::Ent &x = l.ent[e];
+        const uint64_t into = p - x.start, take = std::min<uint64_t>(x.n - into, len);
+        if (up) copy_bytes(buf, x.host + into, take);
+        else copy_bytes(x.host + into, buf, take);
+        buf += take, p += take, len -= take;
+    }
+}
+
 // `len` bytes at offset `off` of the source -> to[0 .. len)
 int fill_slot(const Endpoint &src, uint8_t *to, uint64_t off, uint64_t len)
 {
+    if (src.list) {
+        list_copy(*src.list, to, src.base + off, len, true);
+        return MODGPU_OK;
+    }
     if (src.mem) {
         copy_bytes(to, src.mem + off, len);
         return MODGPU_OK;
@@ -418,6 +454,10 @@ int fill_slot(const Endpoint &src, uint8_t *to, uint64_t off, uint64_t len)
 
 int drain_slot(const Endpoint &dst, const uint8_t *pinned, uint64_t off, uint64_t len)
 {
+    if (dst.list) {
+        list_copy(*dst.list, const_cast<uint8_t *>(pinned), dst.base + off, len, false); // (only read from)
+        return MODGPU_OK;
+    }
     if (dst.mem) {
         copy_bytes(dst.mem + off, pinned, len);
         return MODGPU_OK;
@@ -1022,6 +1062,8 @@ struct CallCtx {
     bool have_mask = false;
     StreamOutcome &outcome;
     bool through_slots = false; // the bytes pass through a page-locked slot with a host copy on a memory side (modgpu_path_stats: staged_bytes)
+    const XferListRec *list_dev = nullptr; // a list transfer: its plan in device memory, list_n records and the terminator (xfer_list_impl)
+    uint32_t list_n = 0;
     void account(uint64_t host_bytes = 0) const
     {
         g_stats.gpu_calls.fetch_add(1, std::memory_order_relaxed);
@@ -1211,12 +1253,16 @@ struct FeedCall {
         a.slot_phase = job.slot_phase;
         a.base = lcg::state_residue(lcg::key_residue(c.key), c.stream_off);
         a.copy = c.identity ? 1u : 0u;
+        a.list = c.list_dev;
+        a.list_n = c.list_n;
         const uint32_t pieces = (uint32_t)((a.n + kFeedPieceBytes - 1) / kFeedPieceBytes);
         const uint32_t grid = std::min<uint32_t>(kFeedGrid, pieces);
-        const hipError_t e = modgpu_launch_cycle_xfer(a, upload, XFER_PLAIN, grid, job.feed_stream); // (slot and buffer are co-aligned)
+        // (a plain call's slot and buffer are co-aligned; a list's segments share no phase with their slot positions: the funnel kernels)
+        const hipError_t e = c.list_dev ? modgpu_launch_cycle_xfer_list(a, upload, grid, job.feed_stream) : modgpu_launch_cycle_xfer(a, upload, XFER_PLAIN, grid, job.feed_stream);
         if (e != hipSuccess) return fail_hip(e, "cycle kernel launch (transfer)");
         job.feed_launched.store(true, std::memory_order_release);
-        note_xfer_launch(modgpu_xfer_kernel_name(upload, XFER_PLAIN), grid, c.n);
+        if (c.list_dev) note_xfer_list_launch(modgpu_xfer_kernel_name(upload, XFER_FUNNEL), grid, c.n);
+        else note_xfer_launch(modgpu_xfer_kernel_name(upload, XFER_PLAIN), grid, c.n);
         trace(MODGPU_TRACE_LAUNCHED, -1, 0, c.n);
         return MODGPU_OK;
     }
@@ -1436,7 +1482,7 @@ int xfer_pipelined(CallCtx &c, bool dma)
     Job job(c.src, c.dst, n, plan.chunk, c.key, c.stream_off);
     job.route = plan.route;
     job.dev = c.dev;
-    job.slot_phase = dma ? 0u : (uint32_t)(reinterpret_cast<uintptr_t>(upload ? c.dst.dev : c.src.dev) & 15u);
+    job.slot_phase = dma || c.list_dev ? 0u : (uint32_t)(reinterpret_cast<uintptr_t>(upload ? c.dst.dev : c.src.dev) & 15u); // (a list's slots hold the packed stream from their first byte)
     job.set_plan(cut_stream(n, plan.chunk, pipes, 0));
     trace(MODGPU_TRACE_SLOTS, -1, (uint64_t)pipes, plan.chunk);
     const bool host_direct = (upload ? c.src : c.dst).pinned;
@@ -1611,6 +1657,127 @@ int xfer_impl(const Endpoint &src, const Endpoint &dst, uint64_t n, int32_t key,
     return MODGPU_OK;
 }
 
+// A list of ranges, host memory on one side and the caller's device memory on the other (include/modgpu.h: the list transfers), as ONE
+// call of xfer_pipelined over the packed stream: the host side is a HostList endpoint, the device side the plan -- one XferListRec per
+// non-empty entry and a terminator, in device memory for the length of the call (the kernel's lookups must not cross PCIe).  Everything
+// is checked before anything is queued, and the text names the LOWEST entry at fault: first what the host alone can see, then -- once
+// the device is known -- the device sides below that entry.  A packed stream above the single call's one-launch limit is cut into
+// windows of that size the way xfer_impl cuts a single call: each window is a list call of its own, its first and last entry clipped.
+namespace {
+std::string entry_text(uint64_t i, const char *what) { return "entry " + std::to_string(i) + ": " + what; }
+} // namespace
+int xfer_list_impl(const modgpu_table_entry_t *ents, uint64_t n_entries, int device, bool upload)
+{
+    if (n_entries == 0) return MODGPU_OK;
+    if (!ents) return fail(MODGPU_ERR_INVALID, "a NULL list with n_entries > 0");
+    if (n_entries > MODGPU_TABLE_MAX_ENTRIES) return fail(MODGPU_ERR_INVALID, "more than 4194304 entries (the table calls' limit)");
+    constexpr uint64_t kNoEntry = ~0ull;
+    uint64_t bad = kNoEntry;
+    const char *why = nullptr;
+    bool any_bytes = false;
+    for (uint64_t i = 0; i < n_entries && bad == kNoEntry; ++i) {
+        const modgpu_table_entry_t &t = ents[i];
+        if (t.flags != 0) why = "nonzero flags";
+        else if (t.n == 0) continue;
+        else if (!t.dst || !t.src) why = "a NULL pointer with n > 0";
+        else if (t.n >= kXferListEntryMax) why = "2^39 bytes or more";
+        if (why) bad = i;
+        else any_bytes = true;
+    }
+    if (bad == kNoEntry && !any_bytes) return MODGPU_OK; // a list with no bytes queues nothing
+    int dev = 0;
+    DeviceScope scope(device);
+    int rc = scope.rc ? scope.rc : resolve_device(device, &dev);
+    if (rc) return bad != kNoEntry ? fail(MODGPU_ERR_INVALID, entry_text(bad, why)) : rc; // (a refusal is a refusal with or without a GPU)
+    if (dev >= kMaxDevices) return fail(MODGPU_ERR_INVALID, "device index beyond staging table");
+    int phys = -1;
+    HIP_TRY(hipGetDevice(&phys));
+    // The device sides of the non-empty entries below `bad`, both ends of each range (modgpu_xfer_device_of).  Entries whose device
+    // ranges touch, one beginning where the one before it ends -- the files of a part -- are looked up as ONE run, both ends of the run;
+    // only a run that is refused is gone through entry by entry, for the lowest one at fault.
+    auto dev_side = [&](const modgpu_table_entry_t &t) { return upload ? static_cast<const uint8_t *>(t.dst) : static_cast<const uint8_t *>(t.src); };
+    const uint64_t checked = bad != kNoEntry ? bad : n_entries;
+    for (uint64_t i = 0; i < checked;) {
+        if (ents[i].n == 0) {
+            ++i;
+            continue;
+        }
+        const uint8_t *const run = dev_side(ents[i]);
+        uint64_t len = ents[i].n, j = i + 1;
+        for (; j < checked && (ents[j].n == 0 || dev_side(ents[j]) == run + len); ++j) len += ents[j].n;
+        if (modgpu_xfer_device_of(run, len) != phys)
+            for (uint64_t k = i; k < j; ++k)
+                if (ents[k].n && modgpu_xfer_device_of(dev_side(ents[k]), ents[k].n) != phys)
+                    return fail(MODGPU_ERR_INVALID, entry_text(k, "its device side is not device memory of the call's device"));
+        i = j;
+    }
+    if (bad != kNoEntry) return fail(MODGPU_ERR_INVALID, entry_text(bad, why));
+    HostList hl;
+    for (uint64_t i = 0; i < n_entries; ++i) {
+        const modgpu_table_entry_t &t = ents[i];
+        if (t.n == 0) continue;
+        uint8_t *const d = static_cast<uint8_t *>(const_cast<void *>(upload ? t.dst : t.src)), *const h = static_cast<uint8_t *>(const_cast<void *>(upload ? t.src : t.dst));
+        hl.ent.push_back({h, d, hl.total, t.n, t.stream_off % 0x7FFFFFFEull, lcg::key_residue(t.key)});
+        hl.total += t.n;
+    }
+    if (injected_failure()) return fail(MODGPU_ERR_HIP, "injected failure (modgpu_debug_inject_failures)");
+    if (g_device_lost[dev].load(std::memory_order_acquire)) return fail_lost();
+    // which of the device's staging sets: the one on the node the first entry's host pages live on
+    int copy_node = -1;
+    cpu_set_t caller_mask;
+    CPU_ZERO(&caller_mask);
+    bool have_mask = false;
+    if (numa::enabled()) {
+        copy_node = numa::node_of_address(hl.ent[0].host + hl.ent[0].n / 2);
+        if (copy_node >= 0) have_mask = ::sched_getaffinity(0, sizeof caller_mask, &caller_mask) == 0;
+    }
+    const int gpu_node = copy_node >= 0 ? device_numa_node(dev) : -1;
+    const int set = copy_node >= 0 && copy_node < kNodeSets - 1 && gpu_node >= 0 && copy_node != gpu_node && have_mask ? 1 + copy_node : 0;
+    Staging &s = staging_of(dev, set);
+    if (set != 0) {
+        if (s.node.load(std::memory_order_relaxed) != copy_node) s.node.store(copy_node, std::memory_order_relaxed);
+        g_node_set_calls.fetch_add(1, std::memory_order_relaxed);
+    }
+    trace(MODGPU_TRACE_CALL_BEGIN, -1, 0, hl.total);
+    struct CallEnd { uint64_t n; ~CallEnd() { trace(MODGPU_TRACE_CALL_END, -1, 0, n); } } call_end{hl.total};
+    // the plan's device memory: made here, freed behind the call -- unless the call's kernel would not leave (feed_stop), which may still
+    // read it: then it stays, with the slots
+    struct DevPlan {
+        XferListRec *p = nullptr;
+        int dev;
+        ~DevPlan() { if (p && !g_device_lost[dev].load(std::memory_order_acquire)) (void)hipFree(p); }
+    } plan_mem;
+    plan_mem.dev = dev;
+    StreamOutcome outcome;
+    const uint64_t natural = (uint64_t)kFeedChunksMax * (kChunk - kFeedPieceBytes);
+    const uint64_t most = kXferListMost ? std::min(kXferListMost, natural) : natural;
+    std::vector<XferListRec> recs;
+    for (uint64_t at = 0; at < hl.total; at += most) {
+        const uint64_t len = std::min<uint64_t>(most, hl.total - at);
+        recs.clear();
+        for (size_t e = hl.entry_at(at); e < hl.ent.size() && hl.ent[e].start < at + len; ++e) {
+            const HostList::Ent &x = hl.ent[e];
+            const uint64_t into = x.start < at ? at - x.start : 0; // (the window's first entry may begin before the window)
+            recs.push_back({x.dev + into, x.start + into - at, x.key_res ? lcg::state_residue(x.key_res, (x.off + into) % 0x7FFFFFFEull) : 0u, x.key_res ? 0u : 1u});
+        }
+        const uint32_t n_recs = (uint32_t)recs.size();
+        recs.push_back({nullptr, len, 0u, 0u});
+        if (!plan_mem.p) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&plan_mem.p), (hl.ent.size() + 1) * sizeof(XferListRec))); // (room for any window's)
+        HIP_TRY(hipMemcpy(plan_mem.p, recs.data(), recs.size() * sizeof(XferListRec), hipMemcpyHostToDevice));
+        Endpoint host_side, dev_side_ep;
+        host_side.list = &hl;
+        host_side.base = at;
+        dev_side_ep.dev = recs[0].dev; // (marks the device side; the kernel takes every address from the plan)
+        const Endpoint &src = upload ? host_side : dev_side_ep, &dst = upload ? dev_side_ep : host_side;
+        CallCtx c{src, dst, len, 0, 0, dev, s, false, false, false, false, false, false, copy_node, caller_mask, have_mask, outcome};
+        c.list_dev = plan_mem.p;
+        c.list_n = n_recs;
+        rc = xfer_pipelined(c, false); // (always the transfer kernel: the testing flavour's DMA reference form has no list form)
+        if (rc) return rc;
+    }
+    return MODGPU_OK;
+}
+
 } // namespace modgpu
 
 // ---- file endpoints of the ABI -----------------------------------------------------------------
@@ -1666,6 +1833,7 @@ void modgpu_debug_set_host_tunable(int which, uint64_t value)
     case MODGPU_TUNABLE_FEED: kFeed = value != 0; break;
     case MODGPU_TUNABLE_FEED_CHUNK_BYTES: kFeedChunk = clamp(value, 32ull << 10, 8ull << 20); break;
     case MODGPU_TUNABLE_FILE_FEED: kFileFeed = value != 0; break;
+    case MODGPU_TUNABLE_XFER_LIST_MOST_BYTES: kXferListMost = value; break;
     case MODGPU_TUNABLE_FEED_PATIENCE_MS: kFeedPatienceTicks = clamp(value, 1, 600000) * 100000ull; break;
     default: break;
     }
@@ -1801,6 +1969,16 @@ int modgpu_cycle_device_to_host(uint8_t *host_dst, const void *dev_src, uint64_t
         dst.pinned = host_range_pinned(host_dst, n);
         return xfer_impl(src, dst, n, key, stream_off, device);
     });
+}
+
+int modgpu_cycle_host_to_device_list(const modgpu_table_entry_t *host_entries, uint64_t n_entries, int device)
+{
+    return guarded([&]() -> int { return xfer_list_impl(host_entries, n_entries, device, true); });
+}
+
+int modgpu_cycle_device_to_host_list(const modgpu_table_entry_t *host_entries, uint64_t n_entries, int device)
+{
+    return guarded([&]() -> int { return xfer_list_impl(host_entries, n_entries, device, false); });
 }
 
 int modgpu_cycle_file_to_device(const char *path, uint64_t file_off, void *dev_dst, uint64_t n, int32_t key, uint64_t stream_off, int device)

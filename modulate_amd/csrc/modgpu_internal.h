@@ -91,6 +91,8 @@ bool host_range_pinned(const void *p, uint64_t n);
 void note_feed_launch(uint32_t grid, uint64_t bytes);
 // the same for a transfer kernel's launch (cycle_xfer_kernel.h)
 void note_xfer_launch(const char *kernel, uint32_t grid, uint64_t bytes);
+// the same for a list transfer's launch (variant CYCLE_XFER_LIST; `bytes` = the packed stream's)
+void note_xfer_list_launch(const char *kernel, uint32_t grid, uint64_t bytes);
 // modgpu_cycle_device_to on one range, asynchronous on `stream` (current device; the transfer routes' DMA reference form)
 int cycle_to_device_impl(void *dst, const void *src, uint64_t n, int32_t key, uint64_t stream_off, hipStream_t stream);
 
@@ -103,6 +105,8 @@ struct Endpoint {
     uint64_t base = 0;
     bool pinned = false;    // mem is page-locked and device-visible: DMA'd directly, no staging copy
     uint8_t *dev = nullptr; // else, for the transfer routes (modgpu_cycle_host_to_device & co.): device memory of the call's device
+    const struct HostList *list = nullptr; // else, for the list transfers (host_stream.cpp): the PACKED stream of a list of host ranges, stream
+                                           // byte j at packed position base + j (gathered from / scattered to the entries' own memory)
 };
 struct Piece { uint64_t off, len; }; // a span of a stream, in stream bytes
 // What a call did besides succeeding or failing.
