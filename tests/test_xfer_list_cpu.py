@@ -2,7 +2,8 @@
 are declared, exported by both library flavours and listed; the header is still plain C99; without a GPU every refusal the host alone
 can see is MODGPU_ERR_INVALID and a valid list MODGPU_ERR_NO_DEVICE, with nothing launched and nothing computed on the host; the list
 mode adds no kernel to the transfer TU; and the host code -- validation, the packed stream through the pipelines, the plan, failures, a
-wedged kernel, two threads, the cut above the one-launch limit -- runs clean under ASan + UBSan and under TSan on the CPU stand-in of
+wedged kernel, two threads, the cut above the one-launch limit (windows inside long entries too), slots filled three times over at
+chunks of one and two pieces, entries above 8 MiB, 70 000 entries -- runs clean under ASan + UBSan and under TSan on the CPU stand-in of
 the HIP runtime, as a stand-alone program (tests/xfer_list_main.cpp: its own main, run directly, the sanitizer runtimes linked
 statically: the environment's preloads are left alone)."""
 import ctypes
@@ -117,12 +118,17 @@ def _run_main(flavour, env_extra):
     r = subprocess.run([os.path.join(ROOT, "modulate_amd", "_san", "xfer_list_main_" + flavour)], env=env, capture_output=True, text=True, timeout=900)
     lines = r.stdout.splitlines()
     assert r.returncode == 0 and not r.stderr.strip(), "\n".join(ln for ln in lines if not ln.startswith("ok  "))[-3000:] + r.stderr[-3000:]
-    assert lines[-1].endswith(", 0 failed") and int(lines[-1].split()[0]) == len(lines) - 1 == 56, lines[-1]
+    assert lines[-1].endswith(", 0 failed") and int(lines[-1].split()[0]) == len(lines) - 1 == 67, lines[-1]
     whats = ["the chunk size from the host trace", "phases and sizes", "boundaries", "empty entries", "only empty entries", "no entries", "one byte",
              "same bytes as the single calls one by one, both ways", "shared sources, both ways", "refusals queued nothing and wrote nothing",
              "a good list after the refusals", "two threads at once on separate buffers", "cut above the one-launch limit: 7 launches",
              "cut above the one-launch limit, boundaries list", "one launch again with the limit back",
-             "a wedged kernel: MODGPU_ERR_HIP within the host deadline, sources intact"]
+             "a wedged kernel: MODGPU_ERR_HIP within the host deadline, sources intact",
+             # the lists of the GPU suite's long cases: slots filled three times over, the second jump table's entries, windows inside entries, > 65 535 records
+             "cut at three pieces, phases and sizes", "cut at three pieces, boundaries list", "cut inside long entries: 7 launches",
+             "entries longer than 8 MiB", "seventy thousand entries"]
+    whats += [f"every slot refilled: feed chunk {knob}, chunks of {chunk}, {which}" for knob, chunk in ((32768, 32768), (65536, 32768), (131072, 65536))
+              for which in ("phases and sizes", "boundaries")]
     for d in ("up", "down"):
         whats += [f"refusal {d}: {w}" for w in ("null list", "too many entries", "null dst", "null src, the lowest of two", "flags", "2^39 bytes",
                                                 "host memory as the device side", "device range past its allocation",

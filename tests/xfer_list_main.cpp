@@ -2,7 +2,10 @@
 // HIP runtime, as a program of its own (built by `make xfer-list-main` from the library's host sources, once with ASan + UBSan and once
 // with TSan, runtimes linked statically; run directly by tests/test_xfer_list_cpu.py).  Every case lays its entries out in an arena of
 // stand-in device memory and two arenas of host memory with guard bytes between them, runs the list up and down, and compares EVERY
-// byte of all three arenas with a model computed here from lcg.h, byte by byte -- not from the device code or the stand-in's.  One `ok`
+// byte of all three arenas with a model computed here from lcg.h, byte by byte -- not from the device code or the stand-in's.  The lists
+// of the GPU suite's long cases run here too, all but the 2 GiB entry -- every slot filled three times at chunks of one and two pieces,
+// entries above 8 and 16 MiB, windows that begin and end inside an entry, 70 000 entries -- for the host half (fill_slot / drain_slot
+// on reused slots, clipped windows, the big plan) and for the conditions those cases put on their inputs.  One `ok`
 // line per case; nothing that depends on the run (addresses, times) is printed.  Exit status 0 = all of it held.
 #include <algorithm>
 #include <atomic>
@@ -215,6 +218,124 @@ std::vector<Spec> with_empties()
     return v;
 }
 
+// ---- the lists of the GPU suite's cases past one round of the slots, 8 MiB and 65 535 records (the same ones, but the 2 GiB entry) --
+constexpr uint64_t PIPES_MOST = 8, SLOT_ROUNDS = 3; // the pipelines a call can have (MODGPU_HOST_PIPES' default), two slots each
+uint64_t total_of(const std::vector<Spec> &v)
+{
+    uint64_t t = 0;
+    for (const Spec &s : v) t += s.n;
+    return t;
+}
+// `specs` behind as many copies of phases_and_sizes() as it takes for ceil(total / chunk) >= 3 x 2 x 8, the copies padded to a whole
+// number of chunks: every packed position of `specs` keeps its place in its piece and its chunk, in a slot that has been used before
+std::vector<Spec> refilled(const std::vector<Spec> &specs, uint64_t chunk)
+{
+    std::vector<Spec> head;
+    while (total_of(specs) + total_of(head) < SLOT_ROUNDS * 2 * PIPES_MOST * chunk)
+        for (const Spec &s : phases_and_sizes()) head.push_back(s);
+    const uint64_t pad = (chunk - total_of(head) % chunk) % chunk;
+    if (pad) head.push_back({pad, KEYS[1], OFFSETS[2], 9, 4});
+    head.insert(head.end(), specs.begin(), specs.end());
+    return head;
+}
+std::vector<Spec> long_entries() // ~32 MiB, entries above 8 and above 16 MiB: the kernel's second jump table at the indices 1 and 2
+{
+    return {{13, KEYS[1], 5, 3, 7},
+            {(8ull << 20) + 3 * PIECE + 77, KEYS[0], ~0ull - 2, 5, 11},
+            {4097, KEYS[2], (1ull << 32) + 5, 0, 9},
+            {(16ull << 20) + PIECE + 1, KEYS[1], PERIOD - 100, 12, 1},
+            {(8ull << 20) + 5, 0x7FFFFFFF, 3, 7, 14}};
+}
+std::vector<Spec> seventy_thousand() // 70 000 entries of 1..7 bytes, one of 40 000 bytes in the middle, empty and NULL entries scattered in
+{
+    std::vector<Spec> v;
+    for (uint32_t i = 0; i < 70000; ++i) {
+        if (i == 35000) v.push_back({40000, KEYS[1], OFFSETS[2], 5, 11});
+        if (i % 9973 == 17) v.push_back((i / 9973) % 2 ? Spec{0, PS4, 0, 0, 0, true} : Spec{0, PS3, 9, 3, 5, false});
+        v.push_back({1 + i % 7, KEYS[i % 6], OFFSETS[i % 7] + i, i % 16, (i * 11) % 16});
+    }
+    return v;
+}
+// per non-empty entry, the largest `steps` -- whole 32 KiB steps from a record's first byte to a segment's -- the kernel computes for it:
+// pieces are cut from each window's first byte, a window's first record begins where the window does, a segment begins at a record's
+// first byte or on a piece boundary
+std::vector<uint64_t> most_steps(const std::vector<Spec> &specs, uint64_t most = 0)
+{
+    std::vector<uint64_t> out;
+    const uint64_t total = total_of(specs);
+    uint64_t es = 0;
+    for (const Spec &s : specs) {
+        if (!s.n) continue;
+        uint64_t top = 0;
+        for (uint64_t at = most ? es - es % most : 0; at < es + s.n; at += most) {
+            const uint64_t first = std::max(es, at), end = std::min(es + s.n, most ? at + most : total);
+            const uint64_t last_piece = at + (end - 1 - at) / PIECE * PIECE;
+            if (last_piece > first) top = std::max(top, (last_piece - first) / PIECE);
+            if (!most) break;
+        }
+        out.push_back(top);
+        es += s.n;
+    }
+    return out;
+}
+struct SlotsEvent { // a window's `slots` event of the host trace
+    uint64_t pipes, chunk;
+};
+// round_trip with the host trace on: the `slots` event of every window, both ways
+std::string traced_round_trip(Layout &L, uint64_t expect_launches, std::vector<SlotsEvent> &slots)
+{
+    modgpu_host_trace(1);
+    const std::string err = round_trip(L, 0, expect_launches);
+    modgpu_host_trace(0);
+    std::vector<modgpu_host_trace_event_t> ev((size_t)std::max(modgpu_host_trace_read(nullptr, 0), 1));
+    const int n = std::min<int>(modgpu_host_trace_read(ev.data(), (int)ev.size()), (int)ev.size());
+    slots.clear();
+    for (int i = 0; i < n; ++i)
+        if (ev[i].kind == MODGPU_TRACE_SLOTS) slots.push_back({ev[i].chunk, ev[i].bytes});
+    return err;
+}
+// every window's chunk is `chunk` (0: whatever the library chose) and fills every slot of its pipelines at least three times
+std::string three_rounds(const std::vector<SlotsEvent> &slots, uint64_t total, uint64_t chunk)
+{
+    if (slots.size() != 2) return "slots events: " + std::to_string(slots.size());
+    for (const SlotsEvent &s : slots) {
+        if (chunk && s.chunk != chunk) return "chunk " + std::to_string(s.chunk) + ", not " + std::to_string(chunk);
+        if (s.pipes < 2 || (total + s.chunk - 1) / s.chunk < SLOT_ROUNDS * 2 * s.pipes)
+            return "slots are not filled three times: " + std::to_string((total + s.chunk - 1) / s.chunk) + " chunks on " + std::to_string(s.pipes) + " pipelines";
+    }
+    return "";
+}
+
+void every_slot_refilled()
+{
+    // a call of 8 MiB or less takes chunks of HALF the feed chunk, at least a piece: 32 and 64 KiB give one piece, 128 KiB two
+    const uint64_t knobs[][2] = {{32u << 10, 32u << 10}, {64u << 10, 32u << 10}, {128u << 10, 64u << 10}};
+    for (const auto &k : knobs) {
+        modgpu_debug_set_host_tunable(MODGPU_TUNABLE_FEED_CHUNK_BYTES, k[0]);
+        for (int which = 0; which < 2; ++which) {
+            Layout L(refilled(which ? boundaries(k[1]) : phases_and_sizes(), k[1]));
+            std::vector<SlotsEvent> slots;
+            std::string err = traced_round_trip(L, 1, slots);
+            if (err.empty()) err = three_rounds(slots, L.total(), k[1]);
+            if (err.empty() && L.total() > (8ull << 20)) err = "the list is above 8 MiB";
+            report("every slot refilled: feed chunk " + std::to_string(k[0]) + ", chunks of " + std::to_string(k[1]) + ", " + (which ? "boundaries" : "phases and sizes"),
+                   err.empty(), err.empty() ? "bytes=" + std::to_string(L.total()) : err);
+        }
+    }
+    modgpu_debug_set_host_tunable(MODGPU_TUNABLE_FEED_CHUNK_BYTES, 256u << 10);
+}
+
+void entries_longer_than_8_mib()
+{
+    Layout L(long_entries());
+    const std::vector<uint64_t> steps = most_steps(L.specs);
+    std::vector<SlotsEvent> slots;
+    std::string err = steps[1] >> 8 == 1 && (steps[1] & 255) < 255 && steps[3] >> 8 == 2 ? "" : "the entries do not reach the second jump table's indices 1 and 2";
+    if (err.empty()) err = traced_round_trip(L, 1, slots);
+    if (err.empty()) err = three_rounds(slots, L.total(), 0);
+    report("entries longer than 8 MiB", err.empty(), err.empty() ? "bytes=" + std::to_string(L.total()) : err);
+}
+
 bool error_names(uint64_t entry, const char *what)
 {
     const std::string e = modgpu_last_error();
@@ -349,8 +470,37 @@ void cut_above_the_limit()
     modgpu_debug_set_host_tunable(MODGPU_TUNABLE_XFER_LIST_MOST_BYTES, most);
     run_case("cut above the one-launch limit: " + std::to_string(want) + " launches", phases_and_sizes(), want);
     run_case("cut above the one-launch limit, boundaries list", boundaries(g_chunk), (Layout(boundaries(g_chunk)).total() + most - 1) / most);
+    // ... at three pieces: every window edge is a piece edge
+    const uint64_t edge = 3 * PIECE;
+    modgpu_debug_set_host_tunable(MODGPU_TUNABLE_XFER_LIST_MOST_BYTES, edge);
+    run_case("cut at three pieces, phases and sizes", phases_and_sizes(), (probe.total() + edge - 1) / edge);
+    run_case("cut at three pieces, boundaries list", boundaries(g_chunk), (Layout(boundaries(g_chunk)).total() + edge - 1) / edge);
+    // ... and the 32 MiB list at 5 MiB + 12345: windows that begin and end inside one entry, a clipped record's base from off + into
+    {
+        const uint64_t inside = (5ull << 20) + 12345;
+        Layout L(long_entries());
+        uint64_t es = 0;
+        bool lies_inside = false;
+        for (const Spec &s : L.specs) {
+            for (uint64_t w = 0; w + inside < L.total(); w += inside) lies_inside = lies_inside || (es < w && w + inside < es + s.n);
+            es += s.n;
+        }
+        modgpu_debug_set_host_tunable(MODGPU_TUNABLE_XFER_LIST_MOST_BYTES, inside);
+        std::string err = lies_inside ? round_trip(L, 0, (L.total() + inside - 1) / inside) : "no window lies inside one entry";
+        report("cut inside long entries: " + std::to_string((L.total() + inside - 1) / inside) + " launches", err.empty(), err);
+    } // (the same list in one launch: entries_longer_than_8_mib)
     modgpu_debug_set_host_tunable(MODGPU_TUNABLE_XFER_LIST_MOST_BYTES, 0);
     run_case("one launch again with the limit back", phases_and_sizes());
+}
+
+void many_entries()
+{
+    Layout L(seventy_thousand());
+    uint64_t records = 0, nulls = 0, empties = 0;
+    for (const Spec &s : L.specs) records += s.n ? 1 : 0, nulls += s.null_ptrs ? 1 : 0, empties += !s.n && !s.null_ptrs ? 1 : 0;
+    std::string err = records > 65535 && nulls >= 3 && empties >= 3 ? "" : "the list has no more than 65 535 records";
+    if (err.empty()) err = round_trip(L);
+    report("seventy thousand entries", err.empty(), err.empty() ? "records=" + std::to_string(records) + " bytes=" + std::to_string(L.total()) : err);
 }
 
 void wedged_kernel()
@@ -399,6 +549,9 @@ int main()
     injected_failures();
     two_threads();
     cut_above_the_limit();
+    every_slot_refilled();
+    entries_longer_than_8_mib();
+    many_entries();
     wedged_kernel();
     std::printf("%d cases, %d failed\n", g_cases, g_failed);
     return g_failed ? 1 : 0;
