@@ -726,7 +726,8 @@ int modgpu_rekey_digest_table_device(const modgpu_rekey_table_entry_t *dev_entri
  * record where it lies and compares it with the manifest, so that nobody downloads 32 bytes per entry, finalises them on the host and
  * compares in a loop -- and so that a captured graph that digests a part can decide without the host.  It takes the records of every
  * digest producer: modgpu_digest_device / _batch_device, modgpu_digest_table_device, modgpu_cycle_digest_table_device,
- * modgpu_rekey_digest_table_device.
+ * modgpu_rekey_digest_table_device, and the digesting list transfers (modgpu_cycle_host_to_device_list_digest / _device_to_host_list_digest,
+ * which are synchronous: dev_table_workspace NULL).
  * Entry i is BAD when the Adler-32 of dev_records[i] differs from dev_expect[i]; the Adler-32 is exactly what modgpu_digest_adler32
  * computes (the residues of s1, s2 and n mod 65521 first; A = (1 + s1) % m, B = (n + n * s1 - s2) % m; B << 16 | A; s1 and s2 may hold
  * any 64-bit value), and both halves are compared.
@@ -920,6 +921,30 @@ int modgpu_cycle_device_to_file(const void *dev_src, uint64_t n, const char *pat
  * entries' [dst, dst+n) is ever written.  modgpu_table_validate checks a list against this rule. */
 int modgpu_cycle_host_to_device_list(const modgpu_table_entry_t *host_entries, uint64_t n_entries, int device);
 int modgpu_cycle_device_to_host_list(const modgpu_table_entry_t *host_entries, uint64_t n_entries, int device);
+
+/* ---- list transfers WITH A DIGEST: one record of sums per entry, taken in the same launch while the bytes are in registers --------------
+ * The contract for the data is the list calls' above, word for word: synchronous, no ordering against the caller's streams, the source
+ * never written, any alignment, entries of n == 0 skipped, one launch per call (cut into windows above the one-launch limit), the same
+ * refusals with the same texts naming the lowest entry at fault, overlap not checked.  On top of that:
+ *   * dev_records is device memory of `device`, 32 bytes per entry of the list, dev_records[i] the record of host_entries[i] (empty
+ *     entries included).  It receives {s1, s2, n, 0} as modgpu_digest_device defines it (only the residues mod 65521 of s1 and s2
+ *     specified) of the side asked for: MODGPU_DIGEST_OUTPUT sums out[j] = src[j] ^ ks(key)[stream_off + j], what is stored;
+ *     MODGPU_DIGEST_INPUT sums src[j] as read -- a packer's plaintext checksums while the ciphertext goes up, an extractor's ciphertext
+ *     checksums while the plaintext comes down.  An empty entry gives {0, 0, 0, 0}; a key == 0 mod 2^31-1 is a copy with a checksum.
+ *   * Records are read back and closed with modgpu_digest_results / modgpu_digest_adler32, or checked where they lie with
+ *     modgpu_digest_check_device (dev_table_workspace NULL).
+ *   * THE CALL WRITES ITS RECORDS ITSELF, {0, 0, n, 0} each, before its first launch: nothing needs clearing, and calling twice on the
+ *     same records gives the same records.  An entry cut by a window boundary still ends with the record of the WHOLE entry.
+ *   * Further refusals, MODGPU_ERR_INVALID before anything is queued (nothing written, gpu_launches unchanged): dev_records NULL with
+ *     n_entries > 0; dev_records not 8-byte aligned; a `side` other than the two; a records range that the runtime does not report as
+ *     device memory of the call's device (both ends); a records range that meets an entry's device range ("entry <i>: ...").
+ *   * n_entries == 0 touches nothing and is MODGPU_OK.  A list with entries but no bytes still writes its records (no launch), so
+ *     without a GPU it is MODGPU_ERR_NO_DEVICE.  When a call fails the records are unspecified, like the destinations.
+ *   * modgpu_last_launch reports variant 22 with `bytes` = the launch's window of the packed stream. */
+int modgpu_cycle_host_to_device_list_digest(const modgpu_table_entry_t *host_entries, uint64_t n_entries, uint32_t side,
+                                            modgpu_digest_result_t *dev_records, int device);
+int modgpu_cycle_device_to_host_list_digest(const modgpu_table_entry_t *host_entries, uint64_t n_entries, uint32_t side,
+                                            modgpu_digest_result_t *dev_records, int device);
 
 /* ---- page-locked host memory -----------------------------------------------------------------
  * Replaces the `new char[total]` of CArk::LoadArkData / BuildArk (CArk.cpp:738, 780) for callers

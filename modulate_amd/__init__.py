@@ -39,6 +39,6 @@ from .capi import (  # noqa: F401
     debug_set_rekey_verify_table_grid,
     verify_rekey_device, verify_rekey_batch_device, time_verify_rekey_device, rekey_verify_kernel_source_hash,
     keep_kernel_source_hash, keep_policy, debug_set_keep, KEEP_OFF,
-    cycle_host_to_device, cycle_device_to_host, cycle_host_to_device_list, cycle_device_to_host_list, cycle_file_to_device, cycle_device_to_file, xfer_kernel_source_hash, debug_set_xfer_form, XFER_FORMS,
+    cycle_host_to_device, cycle_device_to_host, cycle_host_to_device_list, cycle_device_to_host_list, cycle_host_to_device_list_digest, cycle_device_to_host_list_digest, cycle_file_to_device, cycle_device_to_file, xfer_kernel_source_hash, debug_set_xfer_form, XFER_FORMS,
     host_loop_isa, cycle_scalar_host_isa, device_numa_node, numa_probe, host_policy, host_policy_engine, host_trace, host_trace_read, host_pool_stats, host_chunking, HOST_TRACE_KINDS,
 )

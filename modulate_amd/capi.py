@@ -74,6 +74,8 @@ EXPORTS = {
     "modgpu_cycle_device_to_host": (_int, [_vp, _vp, _u64, _i32, _u64, _int]),
     "modgpu_cycle_host_to_device_list": (_int, [_vp, _u64, _int]),
     "modgpu_cycle_device_to_host_list": (_int, [_vp, _u64, _int]),
+    "modgpu_cycle_host_to_device_list_digest": (_int, [_vp, _u64, ctypes.c_uint32, _vp, _int]),
+    "modgpu_cycle_device_to_host_list_digest": (_int, [_vp, _u64, ctypes.c_uint32, _vp, _int]),
     "modgpu_cycle_file_to_device": (_int, [ctypes.c_char_p, _u64, _vp, _u64, _i32, _u64, _int]),
     "modgpu_cycle_device_to_file": (_int, [_vp, _u64, ctypes.c_char_p, _i32, _u64, _int]),
     "modgpu_table_workspace_bytes": (_u64, [_u64]),
@@ -1650,6 +1652,41 @@ def cycle_device_to_host_list(entries, device=-1, check=False):
     del keep
 
 
+def _xfer_list_digest(name, entries, upload, side, records, device, check):
+    """a digesting list transfer: (the records as a DIGEST_RESULT_DTYPE array, their Adler-32 values as a uint32 array)"""
+    t, keep = _xfer_list_table(entries, upload)
+    if check:
+        table_validate(t)
+    if not t.size:
+        return _no_digest_results()
+    own = None
+    try:
+        if records is None:
+            records = own = DeviceBuffer(DIGEST_RESULT_DTYPE.itemsize * t.size, device)
+        _check(getattr(lib(), name)(_vp(t.ctypes.data), t.size, side, _vp(_dev_addr(records)), device))
+        return digest_results(records, t.size, device)
+    finally:
+        del keep
+        if own is not None:
+            own.free()
+
+
+def cycle_host_to_device_list_digest(entries, side=DIGEST_OUTPUT, records=None, device=-1, check=False):
+    """cycle_host_to_device_list with one digest record per entry, taken in the same launch (modgpu_cycle_host_to_device_list_digest):
+    record i is of what was stored in entry i's device range (side=DIGEST_OUTPUT) or of its host bytes as read (DIGEST_INPUT: a packer's
+    plaintext checksums while the ciphertext goes up).  `records` is device memory of 32 bytes per entry (a DeviceBuffer or an address;
+    it then holds the records afterwards, for digest_check_device); None: a buffer is made and freed.  Returns (the records as a
+    DIGEST_RESULT_DTYPE array, their Adler-32 values as a uint32 array)."""
+    return _xfer_list_digest("modgpu_cycle_host_to_device_list_digest", entries, True, side, records, device, check)
+
+
+def cycle_device_to_host_list_digest(entries, side=DIGEST_OUTPUT, records=None, device=-1, check=False):
+    """cycle_device_to_host_list with one digest record per entry, taken in the same launch (modgpu_cycle_device_to_host_list_digest):
+    record i is of what was stored in entry i's host array (side=DIGEST_OUTPUT: an extractor's plaintext checksums) or of its device
+    bytes as read (DIGEST_INPUT).  `records` and the return value as cycle_host_to_device_list_digest has them."""
+    return _xfer_list_digest("modgpu_cycle_device_to_host_list_digest", entries, False, side, records, device, check)
+
+
 XFER_FORMS = {None: 0, "kernel": 0, "dma": 1}
 
 
@@ -1848,6 +1885,30 @@ class DeviceBuffer:
         assert len(outs) == len(ranges) and all(o >= 0 and o + n <= self.nbytes and _xfer_dst(a)[1] == n for (o, n), a in zip(ranges, outs))
         cycle_device_to_host_list([(self.ptr + o, a, key, part_off + o) for (o, _), a in zip(ranges, outs)], self.device)
         return outs
+
+    def upload_ranges_digest(self, items, key, part_off=0, side=DIGEST_INPUT):
+        """`upload_ranges`, and one Adler-32 per item taken in the same launch (cycle_host_to_device_list_digest) -- of the array as read
+        (the plaintext, a packer's manifest), or with side=DIGEST_OUTPUT of what was stored -- returned as a uint32 array."""
+        items = [(int(o), a) for o, a in items]
+        assert all(o >= 0 and o + _xfer_src(a)[1] <= self.nbytes for o, a in items)
+        return cycle_host_to_device_list_digest([(self.ptr + o, a, key, part_off + o) for o, a in items], side, None, self.device)[1]
+
+    def download_ranges_checked(self, ranges, key, outs, expect, part_off=0, side=DIGEST_OUTPUT):
+        """`download_ranges`, one Adler-32 per range taken in the same launch (cycle_device_to_host_list_digest) -- of what was stored
+        in `outs`, or with side=DIGEST_INPUT of the device bytes as read -- and the call's records checked against `expect`, one Adler-32
+        per range (a host uint32 array), on the device where they lie (digest_check_device): (the Adler-32 values as a uint32 array,
+        (bad ranges, the lowest bad range or None, the bad ranges' indices as a uint64 array))."""
+        ranges = [(int(o), int(n)) for o, n in ranges]
+        expect = np.ascontiguousarray(expect, dtype=np.uint32)
+        assert len(outs) == len(ranges) == expect.size and all(o >= 0 and o + n <= self.nbytes and _xfer_dst(a)[1] == n for (o, n), a in zip(ranges, outs))
+        if not ranges:
+            return _no_digest_results()[1], _no_bad_entries()
+        records = DeviceBuffer(DIGEST_RESULT_DTYPE.itemsize * len(ranges), self.device)
+        try:
+            _, adlers = cycle_device_to_host_list_digest([(self.ptr + o, a, key, part_off + o) for (o, _), a in zip(ranges, outs)], side, records, self.device)
+            return adlers, digest_check_device(records, expect, len(ranges), device=self.device)
+        finally:
+            records.free()
 
     def fill(self, holes, bufs, key, part_off=0):
         """Fills the `holes` that `splice` returned -- (new_offset, new_len) each -- with the plaintext arrays `bufs`, one per hole and

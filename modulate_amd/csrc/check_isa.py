@@ -514,6 +514,29 @@ def digest_loop(k):
     return bad
 
 
+def xfer_list_digest(k):
+    """the funnel transfer kernels' list loop in digest mode (cycle_xfer_kernel.h: DIGEST MODE, one uniform branch per segment and per word
+    trip apart from the plain list loop).  The sums are taken with v_dot4_u32_u8; every 64-bit atomic of the kernel is a non-returning
+    global_atomic_add_x2 onto the entry's record (a trip would wait for a value that came back).  That the fold before them uses no LDS
+    and no barrier is what the kernel's LDS and barrier rules already say"""
+    bad = []
+    if "v_dot4_u32_u8" not in k.fn:
+        bad.append("%s: no v_dot4_u32_u8 (the list digest mode's byte and position sums)" % k.name)
+    wide = [(m.group(1), m.group(2)) for m in re.finditer(r"^\s+(global_atomic_\w+_x2)\b([^;\n]*)", k.fn, re.M)]
+    if not wide or any(op != "global_atomic_add_x2" for op, _ in wide):
+        bad.append("%s: 64-bit atomics %s, expected global_atomic_add_x2 only (the list digest mode's sums)" % (k.name, sorted({op for op, _ in wide})))
+    if any(" sc0" in args for _, args in wide):
+        bad.append("%s: a 64-bit atomic returns its value (sc0): the list digest mode's sums are non-returning global_atomic_add_x2" % k.name)
+    return bad
+
+
+def no_digest(k):
+    """the plain transfer kernels have no list loop and so no digest mode: no 64-bit atomic and no v_dot4"""
+    if re.search(r"^\s+global_atomic_\w+_x2\b", k.fn, re.M) or "v_dot4" in k.fn:
+        return ["%s: a 64-bit atomic or a v_dot4 in a plain transfer kernel (the digest mode belongs to the funnel kernels' list loop)" % k.name]
+    return []
+
+
 def lds_bytes(k, n, of):
     if k.md.get("group_segment_fixed_size", -1) != n:
         return ["%s: LDS is %s bytes, expected the %d of %s" % (k.name, k.md.get("group_segment_fixed_size"), n, of)]
@@ -665,10 +688,13 @@ TUS = (
     # count pinned: one uniform branch chooses between the two)
     TU("cycle_to_kernel.s", "the out-of-place kernel's TU",
        (Kind("modgpu_cycle_to_kernel", BUDGET + [keystream_blocks, TICKET, loads_nt, (stores, "nt sc1"), digest_loop]),)),
-    # transfer, each direction plain and funnel: host-fed trips; the upload <true, .> stores into HBM, the download across PCIe
+    # transfer, each direction plain and funnel: host-fed trips; the upload <true, .> stores into HBM, the download across PCIe; the
+    # funnel <., true> kernels hold the list loop and its digest mode, the plain ones neither
     TU("cycle_xfer_kernel.s", "the transfer kernels' TU",
-       (Kind("modgpu_cycle_xfer_kernel", XFER + [(stores, "nt sc1", "an upload store into HBM")], "^ILb1E"),
-        Kind("modgpu_cycle_xfer_kernel", XFER + [(stores, "sc1", "a download store across PCIe")]))),
+       (Kind("modgpu_cycle_xfer_kernel", XFER + [(stores, "nt sc1", "an upload store into HBM"), xfer_list_digest], "^ILb1ELb1E"),
+        Kind("modgpu_cycle_xfer_kernel", XFER + [(stores, "nt sc1", "an upload store into HBM"), no_digest], "^ILb1E"),
+        Kind("modgpu_cycle_xfer_kernel", XFER + [(stores, "sc1", "a download store across PCIe"), xfer_list_digest], "^ILb0ELb1E"),
+        Kind("modgpu_cycle_xfer_kernel", XFER + [(stores, "sc1", "a download store across PCIe"), no_digest]))),
     # rekey, plain and funnel: one uniform branch chooses between the stream loop and the move loop; the fixed registers, the ticket's
     # form, the cache policies, the budget (and, for every kernel, barriers at full EXEC) hold over both
     TU("cycle_rekey_kernel.s", "the rekey kernel's TU",

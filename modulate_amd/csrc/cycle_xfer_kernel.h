@@ -36,6 +36,10 @@ struct CycleXferArgs {
     // list mode (modgpu_launch_cycle_xfer_list; nullptr otherwise): the call's stream is the PACKED stream of a list of ranges
     const struct XferListRec *list; // device memory: list_n records in packed order, then a terminator
     uint32_t list_n;
+    // digest mode of a list launch (modgpu_launch_cycle_xfer_list_digest; nullptr / 0 otherwise): one record of sums per entry of the caller's list
+    struct XferDigestRecord *records;       // device memory: the caller's records, {0, 0, n, 0} at the first launch of the call
+    uint32_t side;                          // MODGPU_DIGEST_OUTPUT (0): the sums are of what is stored; MODGPU_DIGEST_INPUT (1): of the source as read
+    const struct XferListDigestRec *digest; // device memory: parallel to `list`, list_n of them
 };
 
 // LIST MODE (modgpu_cycle_host_to_device_list / modgpu_cycle_device_to_host_list): the stream of the call is the entries' bytes laid end to
@@ -58,6 +62,24 @@ struct XferListRec {
 constexpr int CYCLE_XFER_LIST = 21; // reporting only (modgpu_last_launch): a list transfer launch, either direction (`bytes` = the list's total)
 constexpr uint64_t kXferListEntryMax = 1ull << 39; // an entry's bytes stay below this: its 32 KiB steps fit the three-byte jump tables
 
+// DIGEST MODE of the list mode (modgpu_cycle_host_to_device_list_digest / modgpu_cycle_device_to_host_list_digest): every segment also sums
+// the bytes of one side -- what it stores, or what it read -- while they are in registers: S1 = sum of x[j], S2 = sum of j * x[j], j counted
+// from the ENTRY's first byte, both taken mod 65521 (include/modgpu.h: modgpu_digest_result_t; the sums are order-free, so any number of
+// workgroups, launches and windows add onto one record).  A lane sums its words with v_dot4_u32_u8 and its edge byte by itself, relative to
+// the segment's first byte; the segment's own position in its entry, (skip_mod + into) mod 65521, is folded in once per lane; each wave
+// reduces across its lanes and ONE lane sends a pair of non-returning 64-bit atomic adds at agent scope onto records[entry].  No LDS, no
+// barrier and no wait are added, and the atomics lie in front of the trip's closing fence.  A runtime mode behind one uniform branch whose
+// flag is opaque on every trip: the loop body, and its one keystream block, are shared with the plain list mode.
+struct XferDigestRecord { // modgpu_digest_result_t as the kernel sees it
+    unsigned long long s1, s2, n, reserved;
+};
+struct XferListDigestRec {
+    uint32_t entry;    // index of the plan record's entry in the caller's list: its record is records[entry]
+    uint32_t skip_mod; // bytes of the entry in front of the plan record's first byte, mod 65521 (non-zero only for a record clipped by a window)
+};
+constexpr uint32_t kXferDigestMod = 65521u;
+constexpr int CYCLE_XFER_LIST_DIGEST = 22; // reporting only (modgpu_last_launch): a digesting list transfer launch (`bytes` = the window's total)
+
 // How a source whose phase differs from the destination's by a non-whole number of dwords is read (only the direct form can meet one:
 // a staged chunk sits in its slot co-aligned with the device buffer):
 //   XFER_PLAIN   one dwordx4 per word at the source's own address (dword-aligned)
@@ -69,6 +91,8 @@ hipError_t modgpu_launch_cycle_xfer(const CycleXferArgs &a, bool upload, int for
 // a list launch (a.list set): always the funnel kernel of its direction.  A launch function of its own so that the CPU stand-in of the
 // runtime can supply it from a file of its own.
 hipError_t modgpu_launch_cycle_xfer_list(const CycleXferArgs &a, bool upload, uint32_t grid, hipStream_t stream);
+// the same launch in digest mode (a.records, a.side and a.digest set as well).  Again a function of its own for the stand-in's sake.
+hipError_t modgpu_launch_cycle_xfer_list_digest(const CycleXferArgs &a, bool upload, uint32_t grid, hipStream_t stream);
 // The HIP device whose memory [p, p + n) is (both ends looked up with hipPointerGetAttributes), or -1: host memory, unknown, or
 // the two ends on different devices.  Lives here so that the CPU stand-in of the runtime can supply its own.
 int modgpu_xfer_device_of(const void *p, uint64_t n);

@@ -1064,6 +1064,10 @@ struct CallCtx {
     bool through_slots = false; // the bytes pass through a page-locked slot with a host copy on a memory side (modgpu_path_stats: staged_bytes)
     const XferListRec *list_dev = nullptr; // a list transfer: its plan in device memory, list_n records and the terminator (xfer_list_impl)
     uint32_t list_n = 0;
+    // ... in digest mode (modgpu_cycle_*_list_digest): the caller's records, the side they are of, and the plan's digest records
+    XferDigestRecord *list_records = nullptr;
+    uint32_t list_side = 0;
+    const XferListDigestRec *list_digest_dev = nullptr;
     void account(uint64_t host_bytes = 0) const
     {
         g_stats.gpu_calls.fetch_add(1, std::memory_order_relaxed);
@@ -1255,13 +1259,18 @@ struct FeedCall {
         a.copy = c.identity ? 1u : 0u;
         a.list = c.list_dev;
         a.list_n = c.list_n;
+        a.records = c.list_records;
+        a.side = c.list_side;
+        a.digest = c.list_digest_dev;
         const uint32_t pieces = (uint32_t)((a.n + kFeedPieceBytes - 1) / kFeedPieceBytes);
         const uint32_t grid = std::min<uint32_t>(kFeedGrid, pieces);
         // (a plain call's slot and buffer are co-aligned; a list's segments share no phase with their slot positions: the funnel kernels)
-        const hipError_t e = c.list_dev ? modgpu_launch_cycle_xfer_list(a, upload, grid, job.feed_stream) : modgpu_launch_cycle_xfer(a, upload, XFER_PLAIN, grid, job.feed_stream);
+        const hipError_t e = !c.list_dev        ? modgpu_launch_cycle_xfer(a, upload, XFER_PLAIN, grid, job.feed_stream)
+                             : c.list_records ? modgpu_launch_cycle_xfer_list_digest(a, upload, grid, job.feed_stream)
+                                              : modgpu_launch_cycle_xfer_list(a, upload, grid, job.feed_stream);
         if (e != hipSuccess) return fail_hip(e, "cycle kernel launch (transfer)");
         job.feed_launched.store(true, std::memory_order_release);
-        if (c.list_dev) note_xfer_list_launch(modgpu_xfer_kernel_name(upload, XFER_FUNNEL), grid, c.n);
+        if (c.list_dev) note_xfer_list_launch(modgpu_xfer_kernel_name(upload, XFER_FUNNEL), grid, c.n, c.list_records != nullptr);
         else note_xfer_launch(modgpu_xfer_kernel_name(upload, XFER_PLAIN), grid, c.n);
         trace(MODGPU_TRACE_LAUNCHED, -1, 0, c.n);
         return MODGPU_OK;
@@ -1666,11 +1675,21 @@ int xfer_impl(const Endpoint &src, const Endpoint &dst, uint64_t n, int32_t key,
 namespace {
 std::string entry_text(uint64_t i, const char *what) { return "entry " + std::to_string(i) + ": " + what; }
 } // namespace
-int xfer_list_impl(const modgpu_table_entry_t *ents, uint64_t n_entries, int device, bool upload)
+// DIGEST MODE (`digest`: modgpu_cycle_*_list_digest): the same call with one record of sums per entry of the list.  What the host alone can
+// see of the records and the side is refused before the entries are looked at, what needs the device -- the records' own memory, and that
+// no entry's device range meets them -- once it is known.  The records are written ONCE, {0, 0, n_i, 0} each, before the first window;
+// every window's launch adds onto them, a clipped entry's plan record carrying how far into its entry it begins.
+static_assert(sizeof(XferDigestRecord) == sizeof(modgpu_digest_result_t) && sizeof(XferListDigestRec) == 8 && sizeof(XferListRec) % 8 == 0, "record layouts");
+int xfer_list_impl(const modgpu_table_entry_t *ents, uint64_t n_entries, int device, bool upload, bool digest, uint32_t side, modgpu_digest_result_t *records)
 {
     if (n_entries == 0) return MODGPU_OK;
     if (!ents) return fail(MODGPU_ERR_INVALID, "a NULL list with n_entries > 0");
     if (n_entries > MODGPU_TABLE_MAX_ENTRIES) return fail(MODGPU_ERR_INVALID, "more than 4194304 entries (the table calls' limit)");
+    if (digest) {
+        if (!records) return fail(MODGPU_ERR_INVALID, "NULL records with n_entries > 0");
+        if ((uintptr_t)records % 8 != 0) return fail(MODGPU_ERR_INVALID, "the records are not 8-byte aligned");
+        if (side != MODGPU_DIGEST_OUTPUT && side != MODGPU_DIGEST_INPUT) return fail(MODGPU_ERR_INVALID, "a side other than output (0) and input (1)");
+    }
     constexpr uint64_t kNoEntry = ~0ull;
     uint64_t bad = kNoEntry;
     const char *why = nullptr;
@@ -1684,7 +1703,7 @@ int xfer_list_impl(const modgpu_table_entry_t *ents, uint64_t n_entries, int dev
         if (why) bad = i;
         else any_bytes = true;
     }
-    if (bad == kNoEntry && !any_bytes) return MODGPU_OK; // a list with no bytes queues nothing
+    if (bad == kNoEntry && !any_bytes && !digest) return MODGPU_OK; // a list with no bytes queues nothing (in digest mode its records are still written)
     int dev = 0;
     DeviceScope scope(device);
     int rc = scope.rc ? scope.rc : resolve_device(device, &dev);
@@ -1697,6 +1716,8 @@ int xfer_list_impl(const modgpu_table_entry_t *ents, uint64_t n_entries, int dev
     // only a run that is refused is gone through entry by entry, for the lowest one at fault.
     auto dev_side = [&](const modgpu_table_entry_t &t) { return upload ? static_cast<const uint8_t *>(t.dst) : static_cast<const uint8_t *>(t.src); };
     const uint64_t checked = bad != kNoEntry ? bad : n_entries;
+    const uint64_t records_bytes = n_entries * sizeof(modgpu_digest_result_t);
+    if (digest && modgpu_xfer_device_of(records, records_bytes) != phys) return fail(MODGPU_ERR_INVALID, "the records are not device memory of the call's device");
     for (uint64_t i = 0; i < checked;) {
         if (ents[i].n == 0) {
             ++i;
@@ -1711,17 +1732,32 @@ int xfer_list_impl(const modgpu_table_entry_t *ents, uint64_t n_entries, int dev
                     return fail(MODGPU_ERR_INVALID, entry_text(k, "its device side is not device memory of the call's device"));
         i = j;
     }
+    if (digest) { // (below the lowest entry refused above: the lowest entry at fault is named)
+        const uintptr_t r0 = (uintptr_t)records, r1 = r0 + records_bytes;
+        for (uint64_t i = 0; i < checked; ++i) {
+            const uintptr_t d0 = (uintptr_t)dev_side(ents[i]);
+            if (ents[i].n && d0 < r1 && r0 < d0 + ents[i].n) return fail(MODGPU_ERR_INVALID, entry_text(i, "its device range meets the records"));
+        }
+    }
     if (bad != kNoEntry) return fail(MODGPU_ERR_INVALID, entry_text(bad, why));
     HostList hl;
+    std::vector<uint32_t> index; // digest mode: hl.ent[k] is entry index[k] of the caller's list
     for (uint64_t i = 0; i < n_entries; ++i) {
         const modgpu_table_entry_t &t = ents[i];
         if (t.n == 0) continue;
+        if (digest) index.push_back((uint32_t)i);
         uint8_t *const d = static_cast<uint8_t *>(const_cast<void *>(upload ? t.dst : t.src)), *const h = static_cast<uint8_t *>(const_cast<void *>(upload ? t.src : t.dst));
         hl.ent.push_back({h, d, hl.total, t.n, t.stream_off % 0x7FFFFFFEull, lcg::key_residue(t.key)});
         hl.total += t.n;
     }
     if (injected_failure()) return fail(MODGPU_ERR_HIP, "injected failure (modgpu_debug_inject_failures)");
     if (g_device_lost[dev].load(std::memory_order_acquire)) return fail_lost();
+    if (digest) { // the records as they are before the first launch: {0, 0, n_i, 0}, one copy (synchronous: in place before anything is launched)
+        std::vector<modgpu_digest_result_t> init(n_entries);
+        for (uint64_t i = 0; i < n_entries; ++i) init[i] = {0, 0, ents[i].n, 0};
+        HIP_TRY(hipMemcpy(records, init.data(), records_bytes, hipMemcpyHostToDevice));
+        if (hl.ent.empty()) return MODGPU_OK; // a list with no bytes: nothing else to do
+    }
     // which of the device's staging sets: the one on the node the first entry's host pages live on
     int copy_node = -1;
     cpu_set_t caller_mask;
@@ -1752,18 +1788,24 @@ int xfer_list_impl(const modgpu_table_entry_t *ents, uint64_t n_entries, int dev
     const uint64_t natural = (uint64_t)kFeedChunksMax * (kChunk - kFeedPieceBytes);
     const uint64_t most = kXferListMost ? std::min(kXferListMost, natural) : natural;
     std::vector<XferListRec> recs;
+    std::vector<XferListDigestRec> digs;
+    const size_t digs_at = (hl.ent.size() + 1) * sizeof(XferListRec); // the digest records lie behind the plan, in the same allocation
     for (uint64_t at = 0; at < hl.total; at += most) {
         const uint64_t len = std::min<uint64_t>(most, hl.total - at);
         recs.clear();
+        digs.clear();
         for (size_t e = hl.entry_at(at); e < hl.ent.size() && hl.ent[e].start < at + len; ++e) {
             const HostList::Ent &x = hl.ent[e];
             const uint64_t into = x.start < at ? at - x.start : 0; // (the window's first entry may begin before the window)
             recs.push_back({x.dev + into, x.start + into - at, x.key_res ? lcg::state_residue(x.key_res, (x.off + into) % 0x7FFFFFFEull) : 0u, x.key_res ? 0u : 1u});
+            if (digest) digs.push_back({index[e], (uint32_t)(into % kXferDigestMod)});
         }
         const uint32_t n_recs = (uint32_t)recs.size();
         recs.push_back({nullptr, len, 0u, 0u});
-        if (!plan_mem.p) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&plan_mem.p), (hl.ent.size() + 1) * sizeof(XferListRec))); // (room for any window's)
+        if (!plan_mem.p) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&plan_mem.p), digs_at + (digest ? hl.ent.size() * sizeof(XferListDigestRec) : 0))); // (room for any window's)
         HIP_TRY(hipMemcpy(plan_mem.p, recs.data(), recs.size() * sizeof(XferListRec), hipMemcpyHostToDevice));
+        XferListDigestRec *const digs_dev = reinterpret_cast<XferListDigestRec *>(reinterpret_cast<uint8_t *>(plan_mem.p) + digs_at);
+        if (digest) HIP_TRY(hipMemcpy(digs_dev, digs.data(), digs.size() * sizeof(XferListDigestRec), hipMemcpyHostToDevice));
         Endpoint host_side, dev_side_ep;
         host_side.list = &hl;
         host_side.base = at;
@@ -1772,6 +1814,11 @@ int xfer_list_impl(const modgpu_table_entry_t *ents, uint64_t n_entries, int dev
         CallCtx c{src, dst, len, 0, 0, dev, s, false, false, false, false, false, false, copy_node, caller_mask, have_mask, outcome};
         c.list_dev = plan_mem.p;
         c.list_n = n_recs;
+        if (digest) {
+            c.list_records = reinterpret_cast<XferDigestRecord *>(records);
+            c.list_side = side;
+            c.list_digest_dev = digs_dev;
+        }
         rc = xfer_pipelined(c, false); // (always the transfer kernel: the testing flavour's DMA reference form has no list form)
         if (rc) return rc;
     }
@@ -1973,12 +2020,22 @@ int modgpu_cycle_device_to_host(uint8_t *host_dst, const void *dev_src, uint64_t
 
 int modgpu_cycle_host_to_device_list(const modgpu_table_entry_t *host_entries, uint64_t n_entries, int device)
 {
-    return guarded([&]() -> int { return xfer_list_impl(host_entries, n_entries, device, true); });
+    return guarded([&]() -> int { return xfer_list_impl(host_entries, n_entries, device, true, false, 0, nullptr); });
 }
 
 int modgpu_cycle_device_to_host_list(const modgpu_table_entry_t *host_entries, uint64_t n_entries, int device)
 {
-    return guarded([&]() -> int { return xfer_list_impl(host_entries, n_entries, device, false); });
+    return guarded([&]() -> int { return xfer_list_impl(host_entries, n_entries, device, false, false, 0, nullptr); });
+}
+
+int modgpu_cycle_host_to_device_list_digest(const modgpu_table_entry_t *host_entries, uint64_t n_entries, uint32_t side, modgpu_digest_result_t *dev_records, int device)
+{
+    return guarded([&]() -> int { return xfer_list_impl(host_entries, n_entries, device, true, true, side, dev_records); });
+}
+
+int modgpu_cycle_device_to_host_list_digest(const modgpu_table_entry_t *host_entries, uint64_t n_entries, uint32_t side, modgpu_digest_result_t *dev_records, int device)
+{
+    return guarded([&]() -> int { return xfer_list_impl(host_entries, n_entries, device, false, true, side, dev_records); });
 }
 
 int modgpu_cycle_file_to_device(const char *path, uint64_t file_off, void *dev_dst, uint64_t n, int32_t key, uint64_t stream_off, int device)

@@ -679,10 +679,10 @@ void note_xfer_launch(const char *kernel, uint32_t grid, uint64_t bytes)
     g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
     t_last_launch = {kernel, CYCLE_XFER, grid, modgpu_xfer_block(), kFeedPieceBytes, bytes, grid, MODGPU_XFER_KERNEL_SOURCE_HASH};
 }
-void note_xfer_list_launch(const char *kernel, uint32_t grid, uint64_t bytes)
+void note_xfer_list_launch(const char *kernel, uint32_t grid, uint64_t bytes, bool digest)
 {
     g_stats.gpu_launches.fetch_add(1, std::memory_order_relaxed);
-    t_last_launch = {kernel, CYCLE_XFER_LIST, grid, modgpu_xfer_block(), kFeedPieceBytes, bytes, grid, MODGPU_XFER_KERNEL_SOURCE_HASH};
+    t_last_launch = {kernel, digest ? CYCLE_XFER_LIST_DIGEST : CYCLE_XFER_LIST, grid, modgpu_xfer_block(), kFeedPieceBytes, bytes, grid, MODGPU_XFER_KERNEL_SOURCE_HASH};
 }
 
 // n_parts buffers resident on the CURRENT device, each its own Cycle call (keystream from offs[i], or 0), asynchronous on

@@ -91,8 +91,8 @@ bool host_range_pinned(const void *p, uint64_t n);
 void note_feed_launch(uint32_t grid, uint64_t bytes);
 // the same for a transfer kernel's launch (cycle_xfer_kernel.h)
 void note_xfer_launch(const char *kernel, uint32_t grid, uint64_t bytes);
-// the same for a list transfer's launch (variant CYCLE_XFER_LIST; `bytes` = the packed stream's)
-void note_xfer_list_launch(const char *kernel, uint32_t grid, uint64_t bytes);
+// the same for a list transfer's launch (variant CYCLE_XFER_LIST, in digest mode CYCLE_XFER_LIST_DIGEST; `bytes` = the packed stream's)
+void note_xfer_list_launch(const char *kernel, uint32_t grid, uint64_t bytes, bool digest);
 // modgpu_cycle_device_to on one range, asynchronous on `stream` (current device; the transfer routes' DMA reference form)
 int cycle_to_device_impl(void *dst, const void *src, uint64_t n, int32_t key, uint64_t stream_off, hipStream_t stream);
 
