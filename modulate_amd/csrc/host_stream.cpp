@@ -51,6 +51,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <deque>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -508,9 +509,6 @@ struct Job {
     std::atomic<bool> feed_launched{false}; // the kernel is on feed_stream (it is launched while the pipelines copy their first chunks in)
     int dev = 0;                            // logical device (whose host-buffer routes are abandoned if the kernel stops responding)
     std::atomic<int64_t> feed_progress_ns{0}; // steady-clock time at which a pipeline last saw one of the call's chunks done: the kernel is alive
-    int copy_node = -1; // NUMA node the caller's pages live on (-1: unknown, or no pageable memory endpoint): picks the staging set (g_staging)
-    cpu_set_t caller_mask; // the calling thread's affinity mask: a worker is never put on a CPU the caller may not use
-    bool have_mask = false;
     Job(const Endpoint &s, const Endpoint &d, uint64_t n_, uint64_t chunk_, int32_t key_, uint64_t off_) : src(s), dst(d), n(n_), chunk(chunk_), key(key_), stream_off(off_) {}
     uint32_t slot_phase = 0; // xfer: a chunk sits this far into its slot (the device buffer's phase mod 16: co-aligned)
     bool fed() const { return route == Route::feed || route == Route::xfer; }
@@ -663,6 +661,22 @@ struct Pipe {
 
 // -- the routes: submit(p, c, slot) gets chunk c from the source to where the kernel works on it and has the kernel started (or
 //    told); wait(p, c, slot) returns once the chunk's result is whole -- in the slot, or in the destination on the direct routes.
+// chunk c into the slot's device buffer: page-locked caller memory is DMA'd from where it lies, anything else through the pinned slot
+int stage_h2d(Pipe &p, uint64_t c, int slot)
+{
+    Job &j = p.j;
+    Staging &s = p.s;
+    const uint64_t off = j.plan[c].off, len = j.plan[c].len;
+    if (p.src_direct) {
+        HIP_TRY(hipMemcpyAsync(s.dev[slot], j.src.mem + off, len, hipMemcpyHostToDevice, s.stream[slot]));
+    } else {
+        int rc = fill_slot(j.src, s.pinned[slot], off, len);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(s.dev[slot], s.pinned[slot], len, hipMemcpyHostToDevice, s.stream[slot]));
+    }
+    trace(MODGPU_TRACE_FILL_END, p.pipe, c, len);
+    return MODGPU_OK;
+}
 struct RouteDma {
     static bool drains(const Pipe &p) { return !p.dst_direct; }
     static int submit(Pipe &p, uint64_t c, int slot)
@@ -670,16 +684,10 @@ struct RouteDma {
         Job &j = p.j;
         Staging &s = p.s;
         const uint64_t off = j.plan[c].off, len = j.plan[c].len;
-        if (p.src_direct) {
-            HIP_TRY(hipMemcpyAsync(s.dev[slot], j.src.mem + off, len, hipMemcpyHostToDevice, s.stream[slot]));
-        } else {
-            int rc = fill_slot(j.src, s.pinned[slot], off, len);
-            if (rc) return rc;
-            HIP_TRY(hipMemcpyAsync(s.dev[slot], s.pinned[slot], len, hipMemcpyHostToDevice, s.stream[slot]));
-        }
-        trace(MODGPU_TRACE_FILL_END, p.pipe, c, len);
+        int rc = stage_h2d(p, c, slot);
+        if (rc) return rc;
         MODGPU_INJECT(p, c, MODGPU_STAGE_LAUNCH);
-        int rc = cycle_device_impl(s.dev[slot], len, j.key, j.stream_off + off, s.stream[slot]);
+        rc = cycle_device_impl(s.dev[slot], len, j.key, j.stream_off + off, s.stream[slot]);
         if (rc) return rc;
         trace(MODGPU_TRACE_LAUNCHED, p.pipe, c, len);
         if (p.dst_direct) {
@@ -788,16 +796,10 @@ struct RouteXferDma {
         Staging &s = p.s;
         const uint64_t off = j.plan[c].off, len = j.plan[c].len;
         if (j.dst.dev) { // upload
-            if (p.src_direct) {
-                HIP_TRY(hipMemcpyAsync(s.dev[slot], j.src.mem + off, len, hipMemcpyHostToDevice, s.stream[slot]));
-            } else {
-                int rc = fill_slot(j.src, s.pinned[slot], off, len);
-                if (rc) return rc;
-                HIP_TRY(hipMemcpyAsync(s.dev[slot], s.pinned[slot], len, hipMemcpyHostToDevice, s.stream[slot]));
-            }
-            trace(MODGPU_TRACE_FILL_END, p.pipe, c, len);
+            int rc = stage_h2d(p, c, slot);
+            if (rc) return rc;
             MODGPU_INJECT(p, c, MODGPU_STAGE_LAUNCH);
-            int rc = cycle_to_device_impl(j.dst.dev + off, s.dev[slot], len, j.key, j.stream_off + off, s.stream[slot]);
+            rc = cycle_to_device_impl(j.dst.dev + off, s.dev[slot], len, j.key, j.stream_off + off, s.stream[slot]);
             if (rc) return rc;
         } else { // download
             MODGPU_INJECT(p, c, MODGPU_STAGE_LAUNCH);
@@ -808,29 +810,11 @@ struct RouteXferDma {
         trace(MODGPU_TRACE_LAUNCHED, p.pipe, c, len);
         return MODGPU_OK;
     }
-    static int wait(Pipe &p, uint64_t, int slot)
-    {
-        HIP_TRY(hipStreamSynchronize(p.s.stream[slot]));
-        return MODGPU_OK;
-    }
+    static int wait(Pipe &p, uint64_t c, int slot) { return RouteDma::wait(p, c, slot); }
 };
-struct RouteFeed { // the kernel is there already, waiting for exactly this chunk's ready word
-    static bool drains(const Pipe &) { return true; }
-    static int submit(Pipe &p, uint64_t c, int slot)
-    {
-        Job &j = p.j;
-        const uint64_t off = j.plan[c].off, len = j.plan[c].len;
-        stall_until_the_kernel_has_left(p, c);
-        int rc = fill_slot(j.src, p.s.pinned[slot], off, len);
-        if (rc) return rc;
-        trace(MODGPU_TRACE_FILL_END, p.pipe, c, len);
-        MODGPU_INJECT(p, c, MODGPU_STAGE_LAUNCH);
-        __atomic_store_n(&j.feed_ready[c], 1u, __ATOMIC_RELEASE);
-        trace(MODGPU_TRACE_READY, p.pipe, c, len);
-        return MODGPU_OK;
-    }
-    static int wait(Pipe &p, uint64_t c, int) { return feed_wait(p.j, c); }
-};
+// The host-fed kernel of a host-to-host call is there already, waiting for exactly this chunk's ready word: RouteXfer's upload with a
+// host destination -- slot phase 0, every chunk drained.
+using RouteFeed = RouteXfer;
 // -- the core every route runs on: step i retires the chunk that used this step's slot `ring` steps ago, then submits chunk i
 template <class R> int retire(Pipe &p, uint64_t c, int slot)
 {
@@ -1049,25 +1033,57 @@ int finish_on_host(const Job &j, uint64_t *bytes_done)
 //   pipelined_call             everything else: the stream cut into pieces for up to kPipes pipelines on one of the five routes
 //                              above (plan_route says which), then -- if the GPU was lost under way -- the rescue
 namespace {
+// Which of the device's staging sets a call takes: the one on `copy_node`, the node its pageable pages (or its file's cached pages) were
+// found on (-1: unknown, or the CPU copies nothing), if that is not the GPU's own -- with the calling thread's affinity mask: a worker
+// is never put on a CPU the caller may not use.
+struct SetChoice {
+    Staging &s;
+    cpu_set_t caller_mask;
+    bool have_mask;
+};
+SetChoice choose_set(int dev, int copy_node)
+{
+    cpu_set_t caller_mask;
+    CPU_ZERO(&caller_mask);
+    const bool have_mask = copy_node >= 0 && ::sched_getaffinity(0, sizeof caller_mask, &caller_mask) == 0;
+    const int gpu_node = copy_node >= 0 ? device_numa_node(dev) : -1;
+    const int set = copy_node >= 0 && copy_node < kNodeSets - 1 && gpu_node >= 0 && copy_node != gpu_node && have_mask ? 1 + copy_node : 0;
+    Staging &s = staging_of(dev, set);
+    if (set != 0) { // (every caller of this set writes the same value: a set belongs to one node)
+        if (s.node.load(std::memory_order_relaxed) != copy_node) s.node.store(copy_node, std::memory_order_relaxed);
+        g_node_set_calls.fetch_add(1, std::memory_order_relaxed);
+    }
+    return {s, caller_mask, have_mask};
+}
+struct CallScope { // CALL_BEGIN now, CALL_END when the call returns, whichever way
+    const uint64_t n;
+    explicit CallScope(uint64_t n_) : n(n_) { trace(MODGPU_TRACE_CALL_BEGIN, -1, 0, n); }
+    ~CallScope() { trace(MODGPU_TRACE_CALL_END, -1, 0, n); }
+};
+// What a window of a list transfer adds to its call (send_window; a single call has none): the plan in device memory, `n` records and the
+// terminator, and in digest mode (modgpu_cycle_*_list_digest) the caller's records, the side they are of, and the plan's digest records
+struct ListPlan {
+    const XferListRec *dev = nullptr;
+    uint32_t n = 0;
+    XferDigestRecord *records = nullptr;
+    uint32_t side = 0;
+    const XferListDigestRec *digest_dev = nullptr;
+};
 struct CallCtx {
     const Endpoint &src, &dst;
     const uint64_t n;
     const int32_t key;
     const uint64_t stream_off;
     const int dev;
-    Staging &s;
-    const bool identity, in_place, src_direct, dst_direct, all_direct, host_may_finish;
-    int copy_node = -1;
-    cpu_set_t caller_mask;
-    bool have_mask = false;
+    const SetChoice set;
     StreamOutcome &outcome;
+    const ListPlan list = {};
+    Staging &s = set.s;
+    const bool identity = !list.dev && (int64_t)key % 0x7FFFFFFFll == 0; // keys == 0 mod m give the identity; a list's records carry their own
+    const bool src_direct = src.mem && src.pinned, dst_direct = dst.mem && dst.pinned; // that side is page-locked caller memory
+    const bool all_direct = (!src.mem || src_direct) && (!dst.mem || dst_direct);      // no side is pageable memory
+    bool in_place = false, host_may_finish = false;
     bool through_slots = false; // the bytes pass through a page-locked slot with a host copy on a memory side (modgpu_path_stats: staged_bytes)
-    const XferListRec *list_dev = nullptr; // a list transfer: its plan in device memory, list_n records and the terminator (xfer_list_impl)
-    uint32_t list_n = 0;
-    // ... in digest mode (modgpu_cycle_*_list_digest): the caller's records, the side they are of, and the plan's digest records
-    XferDigestRecord *list_records = nullptr;
-    uint32_t list_side = 0;
-    const XferListDigestRec *list_digest_dev = nullptr;
     void account(uint64_t host_bytes = 0) const
     {
         g_stats.gpu_calls.fetch_add(1, std::memory_order_relaxed);
@@ -1140,6 +1156,17 @@ struct RoutePlan {
     uint64_t chunk;
     bool memory_schedule; // cut and queued like a memory-to-memory call: ~64 chunks of >= 1 MiB, ramped, kernels on shared lanes
 };
+// The chunk of a host-fed call of n bytes: uniform, whole pieces, as small as the flag words allow since no chunk costs a launch.
+// (up to 8 MiB half-size chunks: the first copy in and the last copy out are what such a call waits for -- 4 MiB 25.3 -> 27.3,
+//  8 MiB 32.1 -> 33.2 GB/s median, level from 16 MiB; quarter-size chunks lose 10-25 % to the per-chunk flag traffic)
+uint64_t feed_chunk_bytes(uint64_t n)
+{
+    const uint64_t piece = kFeedPieceBytes;
+    const uint64_t want = n <= (8ull << 20) ? std::max<uint64_t>(kFeedChunk / 2, piece) : kFeedChunk;
+    return std::max<uint64_t>((want + piece - 1) / piece * piece, ((n + kFeedChunksMax - 1) / kFeedChunksMax + piece - 1) / piece * piece);
+}
+// a host-fed transfer takes at most kFeedChunksMax chunks of at most a slot less a piece: larger calls are cut into several, one launch each
+uint64_t one_launch_most() { return (uint64_t)kFeedChunksMax * (kChunk - kFeedPieceBytes); }
 RoutePlan plan_route(CallCtx &c)
 {
     const Endpoint &src = c.src, &dst = c.dst;
@@ -1170,19 +1197,40 @@ RoutePlan plan_route(CallCtx &c)
     // staging set that cannot have its worker threads does not take this route.
     const bool feedable = kFeed != 0 && staged_mode() == 0 && !c.identity && dst.mem && (src.mem ? !c.src_direct && !c.dst_direct : kFileFeed != 0);
     if (feedable && p.route == Route::slot_kernel) {
-        const uint64_t piece = kFeedPieceBytes;
-        // (up to 8 MiB half-size chunks: the first copy in and the last copy out are what such a call waits for -- 4 MiB 25.3 -> 27.3,
-        //  8 MiB 32.1 -> 33.2 GB/s median, level from 16 MiB; quarter-size chunks lose 10-25 % to the per-chunk flag traffic)
-        const uint64_t want = n <= (8ull << 20) ? std::max<uint64_t>(kFeedChunk / 2, piece) : kFeedChunk;
-        const uint64_t fc = std::max<uint64_t>((want + piece - 1) / piece * piece, ((n + kFeedChunksMax - 1) / kFeedChunksMax + piece - 1) / piece * piece);
+        const uint64_t piece = kFeedPieceBytes, fc = feed_chunk_bytes(n);
         const int pipes_wanted = (int)std::min<uint64_t>((uint64_t)kPipes, ((n + fc - 1) / fc + 1) / 2);
         if (fc <= kChunk && (n + piece - 1) / piece < kFeedPiecesMax && n < kFeedBelow &&
-            (pipes_wanted <= 1 || ensure_workers(c.s, pipes_wanted - 1, c.dev, physical_of(c.dev), c.caller_mask, c.have_mask) >= pipes_wanted - 1)) {
+            (pipes_wanted <= 1 || ensure_workers(c.s, pipes_wanted - 1, c.dev, physical_of(c.dev), c.set.caller_mask, c.set.have_mask) >= pipes_wanted - 1)) {
             p.chunk = fc;
             p.route = Route::feed;
         } else if (through_slots) p.route = Route::in_dst; // (no host-fed kernel to be had: the destination itself, as from 2 GiB up)
     }
     return p;
+}
+
+// What every host-fed launch is told, whichever kernel: the abort word and the counters that slot `lead` keeps, the size, the patience,
+// the cut and where the keystream begins.  Returns the grid.
+template <class Args> uint32_t feed_args(Args &a, const CallCtx &c, const Staging &s, int lead, uint64_t chunk, int pipes)
+{
+    a.abort = s.feed_flags_dev[lead] + 2 * kFeedChunksMax;
+    a.work = s.feed_work[lead]; // (all zero: feed_reserve, and reset_feed_counters behind every call)
+    a.n = c.n;
+    a.patience_ticks = kFeedPatienceTicks;
+    a.chunk_bytes = (uint32_t)chunk;
+    a.pipes = (uint32_t)pipes;
+    a.base = lcg::state_residue(lcg::key_residue(c.key), c.stream_off);
+    return std::min<uint32_t>(kFeedGrid, (uint32_t)((c.n + kFeedPieceBytes - 1) / kFeedPieceBytes));
+}
+// The first `words` counters go back to zero behind a call -- asynchronously, ON THE SLOT'S OWN STREAM: in front of its next launch
+// (never the NULL stream: round 6, feed_reserve).  Counters that cannot be cleared cannot be trusted any more: they are given up, and
+// the next call that leads with this slot makes new ones.
+void reset_feed_counters(Staging &s, int slot, uint64_t words, hipStream_t stream)
+{
+    if (hipMemsetAsync(s.feed_work[slot], 0, words * sizeof(uint32_t), stream) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipFree(s.feed_work[slot]);
+        s.feed_work[slot] = nullptr;
+    }
 }
 
 // What a host-fed call needs around its pipelines: flag words cleared and handed to the job BEFORE the pipelines start, the one
@@ -1212,25 +1260,25 @@ struct FeedCall {
         job.feed_stream = s.stream[lead_slot];
         return MODGPU_OK;
     }
+    // what both kernels are told alike: the slots, the ready and done words, and what every host-fed launch takes (feed_args)
+    template <class Args> int common_args(Args &a, uint32_t &grid) const
+    {
+        Staging &s = c.s;
+        for (int k = 0; k < pipes * 2; ++k) HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&a.slot[k]), s.pinned[slots[(size_t)k]], 0));
+        a.ready = s.feed_flags_dev[lead_slot];
+        a.done = s.feed_flags_dev[lead_slot] + kFeedChunksMax;
+        grid = feed_args(a, c, s, lead_slot, plan.chunk, pipes);
+        return MODGPU_OK;
+    }
     // (~15 us of host time: made after the workers have been posted, while every pipeline copies its first chunk in -- the kernel is
     //  there by the time the first chunk is marked ready, and a 4 MiB call is 20 us shorter than with the launch in front,
     //  profiles/r05_pcie_feed.txt)
     int launch()
     {
-        Staging &s = c.s;
         CycleFeedArgs a{};
-        for (int k = 0; k < pipes * 2; ++k) HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&a.slot[k]), s.pinned[slots[(size_t)k]], 0));
-        a.ready = s.feed_flags_dev[lead_slot];
-        a.done = s.feed_flags_dev[lead_slot] + kFeedChunksMax;
-        a.abort = s.feed_flags_dev[lead_slot] + 2 * kFeedChunksMax;
-        a.work = s.feed_work[lead_slot]; // (all zero: feed_reserve, finish)
-        a.n = c.n;
-        a.patience_ticks = kFeedPatienceTicks;
-        a.chunk_bytes = (uint32_t)plan.chunk;
-        a.pipes = (uint32_t)pipes;
-        a.base = lcg::state_residue(lcg::key_residue(c.key), c.stream_off);
-        const uint32_t pieces = (uint32_t)((a.n + kFeedPieceBytes - 1) / kFeedPieceBytes);
-        const uint32_t grid = std::min<uint32_t>(kFeedGrid, pieces);
+        uint32_t grid = 0;
+        const int rc = common_args(a, grid);
+        if (rc) return rc;
         const hipError_t e = modgpu_launch_cycle_feed(a, grid, job.feed_stream);
         if (e != hipSuccess) return fail_hip(e, "cycle kernel launch (host-fed)");
         job.feed_launched.store(true, std::memory_order_release);
@@ -1241,43 +1289,32 @@ struct FeedCall {
     // the transfer kernel instead (Route::xfer): the same slots, words and stream, the caller's device buffer on the other side
     int launch_xfer()
     {
-        Staging &s = c.s;
         const bool upload = c.dst.dev != nullptr;
         CycleXferArgs a{};
-        for (int k = 0; k < pipes * 2; ++k) HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&a.slot[k]), s.pinned[slots[(size_t)k]], 0));
+        uint32_t grid = 0;
+        const int rc = common_args(a, grid);
+        if (rc) return rc;
         a.dev = upload ? c.dst.dev : c.src.dev;
-        a.ready = s.feed_flags_dev[lead_slot];
-        a.done = s.feed_flags_dev[lead_slot] + kFeedChunksMax;
-        a.abort = s.feed_flags_dev[lead_slot] + 2 * kFeedChunksMax;
-        a.work = s.feed_work[lead_slot];
-        a.n = c.n;
-        a.patience_ticks = kFeedPatienceTicks;
-        a.chunk_bytes = (uint32_t)plan.chunk;
-        a.pipes = (uint32_t)pipes;
         a.slot_phase = job.slot_phase;
-        a.base = lcg::state_residue(lcg::key_residue(c.key), c.stream_off);
         a.copy = c.identity ? 1u : 0u;
-        a.list = c.list_dev;
-        a.list_n = c.list_n;
-        a.records = c.list_records;
-        a.side = c.list_side;
-        a.digest = c.list_digest_dev;
-        const uint32_t pieces = (uint32_t)((a.n + kFeedPieceBytes - 1) / kFeedPieceBytes);
-        const uint32_t grid = std::min<uint32_t>(kFeedGrid, pieces);
+        a.list = c.list.dev;
+        a.list_n = c.list.n;
+        a.records = c.list.records;
+        a.side = c.list.side;
+        a.digest = c.list.digest_dev;
         // (a plain call's slot and buffer are co-aligned; a list's segments share no phase with their slot positions: the funnel kernels)
-        const hipError_t e = !c.list_dev        ? modgpu_launch_cycle_xfer(a, upload, XFER_PLAIN, grid, job.feed_stream)
-                             : c.list_records ? modgpu_launch_cycle_xfer_list_digest(a, upload, grid, job.feed_stream)
+        const hipError_t e = !c.list.dev        ? modgpu_launch_cycle_xfer(a, upload, XFER_PLAIN, grid, job.feed_stream)
+                             : c.list.records ? modgpu_launch_cycle_xfer_list_digest(a, upload, grid, job.feed_stream)
                                               : modgpu_launch_cycle_xfer_list(a, upload, grid, job.feed_stream);
         if (e != hipSuccess) return fail_hip(e, "cycle kernel launch (transfer)");
         job.feed_launched.store(true, std::memory_order_release);
-        if (c.list_dev) note_xfer_list_launch(modgpu_xfer_kernel_name(upload, XFER_FUNNEL), grid, c.n, c.list_records != nullptr);
+        if (c.list.dev) note_xfer_list_launch(modgpu_xfer_kernel_name(upload, XFER_FUNNEL), grid, c.n, c.list.records != nullptr);
         else note_xfer_launch(modgpu_xfer_kernel_name(upload, XFER_PLAIN), grid, c.n);
         trace(MODGPU_TRACE_LAUNCHED, -1, 0, c.n);
         return MODGPU_OK;
     }
     void finish(int rc)
     {
-        Staging &s = c.s;
         // rc == OK: every chunk is done and drained, the kernel has drawn its last ticket and leaves by itself (an error of the stream here
         // cannot undo the result, which is whole in the destination: the next call on this device meets whatever is wrong with it).
         // Otherwise whichever pipeline failed has told the kernel to leave and waited for it; make sure before the slots go back.  Either way
@@ -1287,12 +1324,7 @@ struct FeedCall {
         (void)hipGetLastError();
         t_err = keep;
         if (!gone) return; // (slots, flag words and counters stay with the kernel that would not leave: SlotLease keeps them out of circulation)
-        // the counters go back to zero behind the call (asynchronously, on the slot's own stream: in front of its next launch)
-        if (hipMemsetAsync(s.feed_work[lead_slot], 0, (chunks + 2) * sizeof(uint32_t), job.feed_stream) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(s.feed_work[lead_slot]); // (cannot be trusted any more: the next call that leads with this slot makes new ones)
-            s.feed_work[lead_slot] = nullptr;
-        }
+        reset_feed_counters(c.s, lead_slot, chunks + 2, job.feed_stream);
     }
 };
 
@@ -1318,6 +1350,48 @@ int rescue_on_host(CallCtx &c, const Job &job, int rc)
     g_stats.scalar_bytes.fetch_add(host_bytes, std::memory_order_relaxed);
     t_err = "finished on the host loop after: " + why;
     return MODGPU_OK;
+}
+
+// Runs a call's `pipes` pipelines (each on `ring` of `slots`) around its one launch, if it has one (`launch` is empty on the routes
+// that launch per chunk), and returns the call's rc with t_err set: the lowest failing pipeline's error, unless the launch failed --
+// then the launch's.  began = false: a call of one pipeline whose launch failed -- nothing has run.
+int run_pipelines(CallCtx &c, Job &job, const std::vector<int> &slots, int pipes, int ring, const std::function<int()> &launch, bool &began)
+{
+    Staging &s = c.s;
+    if (pipes <= 1) {
+        if (launch) {
+            const int rc = launch();
+            began = rc == MODGPU_OK;
+            if (rc) return rc;
+        }
+        const int rc = run_pipe(s, slots.data(), ring, job, 0, 1);
+        return rc == kStopped ? MODGPU_OK : rc;
+    }
+    auto call = std::make_shared<Call>(s, job, pipes, ring, physical_of(c.dev), slots);
+    const int workers = ensure_workers(s, pipes - 1, c.dev, physical_of(c.dev), c.set.caller_mask, c.set.have_mask);
+    post_to_workers(s, call, std::min(pipes - 1, workers)); // (pipelines nobody is there for are run by this thread, after its own)
+    trace(MODGPU_TRACE_POSTED, -1, (uint64_t)pipes, 0);
+    // (the launch AFTER the post: see FeedCall::launch)
+    const int rc_launch = launch ? launch() : MODGPU_OK;
+    const std::string launch_err = rc_launch ? t_err : std::string();
+    if (rc_launch) job.failed.store(true, std::memory_order_release); // no kernel: the pipelines stop at their next step; none has drained anything (nothing was ever marked done)
+    call->help(false); // pipeline 0 starts now, on the calling thread; then whatever no worker has picked up yet
+    call->wait();
+    { // entries of this call that no worker has picked up are of no use to anybody now
+        std::lock_guard<std::mutex> lock(s.mu);
+        s.requests.erase(std::remove(s.requests.begin(), s.requests.end(), call), s.requests.end());
+    }
+    int rc = MODGPU_OK;
+    for (int p = 0; p < pipes && rc == MODGPU_OK; ++p)
+        if (call->rcs[(size_t)p]) {
+            t_err = call->errs[(size_t)p];
+            rc = call->rcs[(size_t)p];
+        }
+    if (rc_launch) {
+        t_err = launch_err;
+        rc = rc_launch;
+    }
+    return rc;
 }
 
 int pipelined_call(CallCtx &c)
@@ -1348,9 +1422,6 @@ int pipelined_call(CallCtx &c)
     if (lease.ids.empty()) return fail_lost();
     pipes = (int)lease.ids.size() / ring;
     job.set_plan(cut_stream(c.n, plan.chunk, pipes, plan.memory_schedule && !feed ? kRamp : 0));
-    job.copy_node = c.copy_node;
-    job.have_mask = c.have_mask;
-    if (c.have_mask) job.caller_mask = c.caller_mask;
     for (int k = 0; k < (feed ? 0 : plan.memory_schedule ? kLanes : kFileLanes) && k < (int)lease.ids.size(); ++k) job.lanes.push_back(nullptr); // (streams exist after staging_reserve)
     trace(MODGPU_TRACE_SLOTS, -1, (uint64_t)pipes, plan.chunk);
     int rc = staging_reserve(s, lease.ids, plan.chunk, plan.route == Route::dma, !(c.src_direct && c.dst_direct) && plan.route != Route::in_dst);
@@ -1361,44 +1432,9 @@ int pipelined_call(CallCtx &c)
         rc = fed.prepare(pipes);
         if (rc) return rc;
     }
-
-    if (pipes <= 1) {
-        if (feed) {
-            rc = fed.launch();
-            if (rc) return rc; // nothing of the caller's has been touched
-        }
-        rc = run_pipe(s, lease.ids.data(), ring, job, 0, 1);
-        if (rc == kStopped) rc = MODGPU_OK;
-    } else {
-        auto call = std::make_shared<Call>(s, job, pipes, ring, physical_of(c.dev), lease.ids);
-        const int workers = ensure_workers(s, pipes - 1, c.dev, physical_of(c.dev), c.caller_mask, c.have_mask);
-        post_to_workers(s, call, std::min(pipes - 1, workers)); // (pipelines nobody is there for are run by this thread, after its own)
-        trace(MODGPU_TRACE_POSTED, -1, (uint64_t)pipes, 0);
-        int rc_launch = MODGPU_OK;
-        std::string launch_err;
-        if (feed) {
-            rc_launch = fed.launch();
-            if (rc_launch) { // no kernel: the pipelines stop at their next step; none has drained anything (nothing was ever marked done)
-                launch_err = t_err;
-                job.failed.store(true, std::memory_order_release);
-            }
-        }
-        call->help(false); // pipeline 0 starts now, on the calling thread; then whatever no worker has picked up yet
-        call->wait();
-        { // entries of this call that no worker has picked up are of no use to anybody now
-            std::lock_guard<std::mutex> lock(s.mu);
-            s.requests.erase(std::remove(s.requests.begin(), s.requests.end(), call), s.requests.end());
-        }
-        for (int p = 0; p < pipes && rc == MODGPU_OK; ++p)
-            if (call->rcs[(size_t)p]) {
-                t_err = call->errs[(size_t)p];
-                rc = call->rcs[(size_t)p];
-            }
-        if (rc_launch) {
-            t_err = launch_err;
-            rc = rc_launch;
-        }
-    }
+    bool began = true;
+    rc = run_pipelines(c, job, lease.ids, pipes, ring, feed ? std::function<int()>([&] { return fed.launch(); }) : nullptr, began);
+    if (!began) return rc; // nothing of the caller's has been touched
     c.outcome.touched = job.touched.load();
     if (feed) fed.finish(rc);
     if (rc == MODGPU_OK) {
@@ -1428,19 +1464,12 @@ int xfer_direct(CallCtx &c)
     CycleXferArgs a{};
     HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&a.host), h.mem, 0));
     a.dev = d;
-    a.abort = s.feed_flags_dev[slot] + 2 * kFeedChunksMax;
     s.feed_flags[slot][2 * kFeedChunksMax] = 0;
-    a.work = s.feed_work[slot]; // (zero: feed_reserve, and behind every call below)
-    a.n = c.n;
-    a.patience_ticks = kFeedPatienceTicks;
-    a.chunk_bytes = kFeedPieceBytes;
-    a.pipes = 1;
-    a.base = lcg::state_residue(lcg::key_residue(c.key), c.stream_off);
+    const uint32_t grid = feed_args(a, c, s, slot, kFeedPieceBytes, 1);
     a.copy = c.identity ? 1u : 0u;
     const uint8_t *const from = upload ? h.mem : d;
     const uint8_t *const to = upload ? d : h.mem;
     const int form = ((reinterpret_cast<uintptr_t>(from) - reinterpret_cast<uintptr_t>(to)) & 3u) != 0 ? XFER_FUNNEL : XFER_PLAIN;
-    const uint32_t grid = std::min<uint32_t>(kFeedGrid, (uint32_t)((c.n + kFeedPieceBytes - 1) / kFeedPieceBytes));
     if (injected_at(0, 1, MODGPU_STAGE_FILL) || injected_at(0, 1, MODGPU_STAGE_LAUNCH)) return injected_here();
     const hipError_t e = modgpu_launch_cycle_xfer(a, upload, form, grid, s.stream[slot]);
     if (e != hipSuccess) return fail_hip(e, "cycle kernel launch (transfer, page-locked caller memory)");
@@ -1449,12 +1478,7 @@ int xfer_direct(CallCtx &c)
     hipError_t w = injected_at(0, 1, MODGPU_STAGE_SYNC) ? hipErrorLaunchFailure : hipSuccess;
     const hipError_t q = hipStreamSynchronize(s.stream[slot]);
     if (w == hipSuccess) w = q;
-    // the counters go back to zero behind the call, on the slot's own stream (never the NULL stream: round 6)
-    if (hipMemsetAsync(s.feed_work[slot], 0, 2 * sizeof(uint32_t), s.stream[slot]) != hipSuccess) {
-        (void)hipGetLastError();
-        (void)hipFree(s.feed_work[slot]);
-        s.feed_work[slot] = nullptr;
-    }
+    reset_feed_counters(s, slot, 2, s.stream[slot]);
     if (w != hipSuccess) return fail_hip(w, "hipStreamSynchronize (transfer kernel on the caller's page-locked memory)");
     c.account();
     return MODGPU_OK;
@@ -1473,8 +1497,7 @@ int xfer_pipelined(CallCtx &c, bool dma)
     if (dma) {
         plan.chunk = std::min<uint64_t>(kChunk, std::max<uint64_t>(kChunkMin, ((n / kSplit) + 0xFFFFF) & ~0xFFFFFull));
     } else { // the host-fed call's chunks: as small as the flag words allow, with room for the slot phase in every slot
-        const uint64_t want = n <= (8ull << 20) ? std::max<uint64_t>(kFeedChunk / 2, piece) : kFeedChunk;
-        plan.chunk = std::max<uint64_t>((want + piece - 1) / piece * piece, ((n + kFeedChunksMax - 1) / kFeedChunksMax + piece - 1) / piece * piece);
+        plan.chunk = feed_chunk_bytes(n);
         if (plan.chunk > kChunk - piece) return fail(MODGPU_ERR_INVALID, "transfer too large for one host-fed call"); // (xfer_impl cuts calls below this)
     }
     const uint64_t n_chunks = (n + plan.chunk - 1) / plan.chunk;
@@ -1482,7 +1505,7 @@ int xfer_pipelined(CallCtx &c, bool dma)
     const int ring = 2;
     // the kernel draws chunks in stream order and waits for whichever pipeline owns the next one: the pipelines must run side by side,
     // so a call has no more of them than there are threads to run them
-    if (!dma && pipes > 1) pipes = std::min(pipes, 1 + ensure_workers(s, pipes - 1, c.dev, physical_of(c.dev), c.caller_mask, c.have_mask));
+    if (!dma && pipes > 1) pipes = std::min(pipes, 1 + ensure_workers(s, pipes - 1, c.dev, physical_of(c.dev), c.set.caller_mask, c.set.have_mask));
     if (c.dst.fd >= 0 && n >= (8ull << 20)) (void)::posix_fallocate(c.dst.fd, (off_t)c.dst.base, (off_t)n);
     SlotLease lease(s, c.dev);
     lease.acquire(pipes * ring, ring);
@@ -1491,54 +1514,20 @@ int xfer_pipelined(CallCtx &c, bool dma)
     Job job(c.src, c.dst, n, plan.chunk, c.key, c.stream_off);
     job.route = plan.route;
     job.dev = c.dev;
-    job.slot_phase = dma || c.list_dev ? 0u : (uint32_t)(reinterpret_cast<uintptr_t>(upload ? c.dst.dev : c.src.dev) & 15u); // (a list's slots hold the packed stream from their first byte)
+    job.slot_phase = dma || c.list.dev ? 0u : (uint32_t)(reinterpret_cast<uintptr_t>(upload ? c.dst.dev : c.src.dev) & 15u); // (a list's slots hold the packed stream from their first byte)
     job.set_plan(cut_stream(n, plan.chunk, pipes, 0));
     trace(MODGPU_TRACE_SLOTS, -1, (uint64_t)pipes, plan.chunk);
-    const bool host_direct = (upload ? c.src : c.dst).pinned;
-    int rc = staging_reserve(s, lease.ids, plan.chunk + (dma ? 0 : 16), dma, !(dma && host_direct));
+    c.through_slots = !(dma && (upload ? c.src : c.dst).pinned); // (everything but page-locked memory in the DMA form: a file's and a list's bytes too)
+    int rc = staging_reserve(s, lease.ids, plan.chunk + (dma ? 0 : 16), dma, c.through_slots);
     if (rc) return rc;
     FeedCall fed{c, job, lease.ids, plan};
     if (!dma) {
         rc = fed.prepare(pipes);
         if (rc) return rc;
     }
-    if (pipes <= 1) {
-        if (!dma) {
-            rc = fed.launch_xfer();
-            if (rc) return rc;
-        }
-        rc = run_pipe(s, lease.ids.data(), ring, job, 0, 1);
-        if (rc == kStopped) rc = MODGPU_OK;
-    } else {
-        auto call = std::make_shared<Call>(s, job, pipes, ring, physical_of(c.dev), lease.ids);
-        const int workers = ensure_workers(s, pipes - 1, c.dev, physical_of(c.dev), c.caller_mask, c.have_mask);
-        post_to_workers(s, call, std::min(pipes - 1, workers));
-        trace(MODGPU_TRACE_POSTED, -1, (uint64_t)pipes, 0);
-        int rc_launch = MODGPU_OK;
-        std::string launch_err;
-        if (!dma) {
-            rc_launch = fed.launch_xfer();
-            if (rc_launch) {
-                launch_err = t_err;
-                job.failed.store(true, std::memory_order_release);
-            }
-        }
-        call->help(false);
-        call->wait();
-        {
-            std::lock_guard<std::mutex> lock(s.mu);
-            s.requests.erase(std::remove(s.requests.begin(), s.requests.end(), call), s.requests.end());
-        }
-        for (int p = 0; p < pipes && rc == MODGPU_OK; ++p)
-            if (call->rcs[(size_t)p]) {
-                t_err = call->errs[(size_t)p];
-                rc = call->rcs[(size_t)p];
-            }
-        if (rc_launch) {
-            t_err = launch_err;
-            rc = rc_launch;
-        }
-    }
+    bool began = true;
+    rc = run_pipelines(c, job, lease.ids, pipes, ring, dma ? nullptr : std::function<int()>([&] { return fed.launch_xfer(); }), began);
+    if (!began) return rc;
     if (!dma) fed.finish(rc);
     if (rc == MODGPU_OK) c.account();
     return rc;
@@ -1569,9 +1558,6 @@ int stream_impl(const Endpoint &src, const Endpoint &dst, uint64_t n, int32_t ke
     const bool src_direct = src.mem && src.pinned, dst_direct = dst.mem && dst.pinned;
     // which of the device's staging sets: the one on the node the caller's PAGEABLE pages live on, if that is not the GPU's own
     int copy_node = -1;
-    cpu_set_t caller_mask;
-    CPU_ZERO(&caller_mask);
-    bool have_mask = false;
     if (numa::enabled() && n > kZeroCopyMax) {
         // (what decides is the side the CPU READS across the socket link: a copy whose source is remote runs at 6-12 GB/s per thread
         //  instead of 28, one whose destination is remote hardly suffers, profiles/r05_staged_numa.txt)
@@ -1580,24 +1566,16 @@ int stream_impl(const Endpoint &src, const Endpoint &dst, uint64_t n, int32_t ke
             copy_node = numa::node_of_file_page(src.fd, src.base + n / 2);
             if (copy_node < 0 && pages) copy_node = numa::node_of_address(pages + n / 2);
         } else if (pages) copy_node = numa::node_of_address(pages + n / 2);
-        if (copy_node >= 0) have_mask = ::sched_getaffinity(0, sizeof caller_mask, &caller_mask) == 0;
     }
-    const int gpu_node = copy_node >= 0 ? device_numa_node(dev) : -1;
-    const int set = copy_node >= 0 && copy_node < kNodeSets - 1 && gpu_node >= 0 && copy_node != gpu_node && have_mask ? 1 + copy_node : 0;
-    Staging &s = staging_of(dev, set);
-    if (set != 0) { // (every caller of this set writes the same value: a set belongs to one node)
-        if (s.node.load(std::memory_order_relaxed) != copy_node) s.node.store(copy_node, std::memory_order_relaxed);
-        g_node_set_calls.fetch_add(1, std::memory_order_relaxed);
-    }
+    const SetChoice set = choose_set(dev, copy_node);
     struct InFlight { // (reporting: did host-buffer calls ever overlap on a GPU?  modgpu_host_pool_stats)
         InFlight() { if (g_calls_in_flight.fetch_add(1, std::memory_order_relaxed) > 0) g_calls_overlapped.fetch_add(1, std::memory_order_relaxed); }
         ~InFlight() { g_calls_in_flight.fetch_sub(1, std::memory_order_relaxed); }
     } in_flight;
-    trace(MODGPU_TRACE_CALL_BEGIN, -1, 0, n);
-    struct CallEnd { uint64_t n; ~CallEnd() { trace(MODGPU_TRACE_CALL_END, -1, 0, n); } } call_end{n};
-
-    CallCtx c{src, dst, n, key, stream_off, dev, s, identity, in_place, src_direct, dst_direct,
-              (!src.mem || src_direct) && (!dst.mem || dst_direct), host_may_finish, copy_node, caller_mask, have_mask, outcome};
+    const CallScope scope_of_call(n);
+    CallCtx c{src, dst, n, key, stream_off, dev, set, outcome};
+    c.in_place = in_place;
+    c.host_may_finish = host_may_finish;
     if (in_place && src_direct && !identity && (n <= kZeroCopyMax || pinned_mode() != 1)) return in_place_on_locked_pages(c);
     if (n <= kZeroCopyMax && src.mem && dst.mem && !identity) return one_slot_call(c);
     return pipelined_call(c);
@@ -1625,31 +1603,16 @@ int xfer_impl(const Endpoint &src, const Endpoint &dst, uint64_t n, int32_t key,
     const bool direct = h.mem && h.pinned;
     // which of the device's staging sets: the one on the node the caller's pageable pages (or the file's cached pages) live on
     int copy_node = -1;
-    cpu_set_t caller_mask;
-    CPU_ZERO(&caller_mask);
-    bool have_mask = false;
-    if (numa::enabled() && !direct) {
-        copy_node = h.mem ? numa::node_of_address(h.mem + n / 2) : upload ? numa::node_of_file_page(h.fd, h.base + n / 2) : -1;
-        if (copy_node >= 0) have_mask = ::sched_getaffinity(0, sizeof caller_mask, &caller_mask) == 0;
-    }
-    const int gpu_node = copy_node >= 0 ? device_numa_node(dev) : -1;
-    const int set = copy_node >= 0 && copy_node < kNodeSets - 1 && gpu_node >= 0 && copy_node != gpu_node && have_mask ? 1 + copy_node : 0;
-    Staging &s = staging_of(dev, set);
-    if (set != 0) {
-        if (s.node.load(std::memory_order_relaxed) != copy_node) s.node.store(copy_node, std::memory_order_relaxed);
-        g_node_set_calls.fetch_add(1, std::memory_order_relaxed);
-    }
-    trace(MODGPU_TRACE_CALL_BEGIN, -1, 0, n);
-    struct CallEnd { uint64_t n; ~CallEnd() { trace(MODGPU_TRACE_CALL_END, -1, 0, n); } } call_end{n};
-    const bool identity = (int64_t)key % 0x7FFFFFFFll == 0;
+    if (numa::enabled() && !direct) copy_node = h.mem ? numa::node_of_address(h.mem + n / 2) : upload ? numa::node_of_file_page(h.fd, h.base + n / 2) : -1;
+    const SetChoice set = choose_set(dev, copy_node);
+    const CallScope scope_of_call(n);
     const bool dma = xfer_form() == 1;
     StreamOutcome outcome;
     if (direct && !dma) {
-        CallCtx c{src, dst, n, key, stream_off, dev, s, identity, false, src.pinned, dst.pinned, true, false, copy_node, caller_mask, have_mask, outcome};
+        CallCtx c{src, dst, n, key, stream_off, dev, set, outcome};
         return xfer_direct(c);
     }
-    // a host-fed call takes at most kFeedChunksMax chunks of at most a slot less a piece: larger calls are cut into several, one launch each
-    const uint64_t most = dma ? n : (uint64_t)kFeedChunksMax * (kChunk - kFeedPieceBytes);
+    const uint64_t most = dma ? n : one_launch_most();
     for (uint64_t at = 0; at < n; at += most) {
         Endpoint ps = src, pd = dst;
         for (Endpoint *e : {&ps, &pd}) {
@@ -1658,8 +1621,7 @@ int xfer_impl(const Endpoint &src, const Endpoint &dst, uint64_t n, int32_t key,
             else e->base += at;
         }
         const uint64_t len = std::min<uint64_t>(most, n - at);
-        CallCtx c{ps, pd, len, key, (stream_off + at) % 0x7FFFFFFEull, dev, s, identity, false, ps.mem && ps.pinned, pd.mem && pd.pinned, direct, false,
-                  copy_node, caller_mask, have_mask, outcome};
+        CallCtx c{ps, pd, len, key, (stream_off + at) % 0x7FFFFFFEull, dev, set, outcome};
         rc = xfer_pipelined(c, dma);
         if (rc) return rc;
     }
@@ -1672,30 +1634,35 @@ int xfer_impl(const Endpoint &src, const Endpoint &dst, uint64_t n, int32_t key,
 // is checked before anything is queued, and the text names the LOWEST entry at fault: first what the host alone can see, then -- once
 // the device is known -- the device sides below that entry.  A packed stream above the single call's one-launch limit is cut into
 // windows of that size the way xfer_impl cuts a single call: each window is a list call of its own, its first and last entry clipped.
-namespace {
-std::string entry_text(uint64_t i, const char *what) { return "entry " + std::to_string(i) + ": " + what; }
-} // namespace
 // DIGEST MODE (`digest`: modgpu_cycle_*_list_digest): the same call with one record of sums per entry of the list.  What the host alone can
 // see of the records and the side is refused before the entries are looked at, what needs the device -- the records' own memory, and that
 // no entry's device range meets them -- once it is known.  The records are written ONCE, {0, 0, n_i, 0} each, before the first window;
 // every window's launch adds onto them, a clipped entry's plan record carrying how far into its entry it begins.
 static_assert(sizeof(XferDigestRecord) == sizeof(modgpu_digest_result_t) && sizeof(XferListDigestRec) == 8 && sizeof(XferListRec) % 8 == 0, "record layouts");
-int xfer_list_impl(const modgpu_table_entry_t *ents, uint64_t n_entries, int device, bool upload, bool digest, uint32_t side, modgpu_digest_result_t *records)
+namespace {
+std::string entry_text(uint64_t i, const char *what) { return "entry " + std::to_string(i) + ": " + what; }
+constexpr uint64_t kNoEntry = ~0ull;
+struct ListCall { // the caller's arguments, as the steps below share them
+    const modgpu_table_entry_t *ents;
+    uint64_t n_entries;
+    bool upload, digest;
+    uint32_t side;
+    modgpu_digest_result_t *records;
+    uint64_t records_bytes() const { return n_entries * sizeof(modgpu_digest_result_t); }
+};
+// What the host alone can see.  A refusal that names no entry is returned at once; the lowest entry at fault is left in bad / why,
+// to be named once the device sides below it have been looked at.
+int check_list_host_side(const ListCall &l, uint64_t &bad, const char *&why, bool &any_bytes)
 {
-    if (n_entries == 0) return MODGPU_OK;
-    if (!ents) return fail(MODGPU_ERR_INVALID, "a NULL list with n_entries > 0");
-    if (n_entries > MODGPU_TABLE_MAX_ENTRIES) return fail(MODGPU_ERR_INVALID, "more than 4194304 entries (the table calls' limit)");
-    if (digest) {
-        if (!records) return fail(MODGPU_ERR_INVALID, "NULL records with n_entries > 0");
-        if ((uintptr_t)records % 8 != 0) return fail(MODGPU_ERR_INVALID, "the records are not 8-byte aligned");
-        if (side != MODGPU_DIGEST_OUTPUT && side != MODGPU_DIGEST_INPUT) return fail(MODGPU_ERR_INVALID, "a side other than output (0) and input (1)");
+    if (!l.ents) return fail(MODGPU_ERR_INVALID, "a NULL list with n_entries > 0");
+    if (l.n_entries > MODGPU_TABLE_MAX_ENTRIES) return fail(MODGPU_ERR_INVALID, "more than 4194304 entries (the table calls' limit)");
+    if (l.digest) {
+        if (!l.records) return fail(MODGPU_ERR_INVALID, "NULL records with n_entries > 0");
+        if ((uintptr_t)l.records % 8 != 0) return fail(MODGPU_ERR_INVALID, "the records are not 8-byte aligned");
+        if (l.side != MODGPU_DIGEST_OUTPUT && l.side != MODGPU_DIGEST_INPUT) return fail(MODGPU_ERR_INVALID, "a side other than output (0) and input (1)");
     }
-    constexpr uint64_t kNoEntry = ~0ull;
-    uint64_t bad = kNoEntry;
-    const char *why = nullptr;
-    bool any_bytes = false;
-    for (uint64_t i = 0; i < n_entries && bad == kNoEntry; ++i) {
-        const modgpu_table_entry_t &t = ents[i];
+    for (uint64_t i = 0; i < l.n_entries && bad == kNoEntry; ++i) {
+        const modgpu_table_entry_t &t = l.ents[i];
         if (t.flags != 0) why = "nonzero flags";
         else if (t.n == 0) continue;
         else if (!t.dst || !t.src) why = "a NULL pointer with n > 0";
@@ -1703,21 +1670,16 @@ int xfer_list_impl(const modgpu_table_entry_t *ents, uint64_t n_entries, int dev
         if (why) bad = i;
         else any_bytes = true;
     }
-    if (bad == kNoEntry && !any_bytes && !digest) return MODGPU_OK; // a list with no bytes queues nothing (in digest mode its records are still written)
-    int dev = 0;
-    DeviceScope scope(device);
-    int rc = scope.rc ? scope.rc : resolve_device(device, &dev);
-    if (rc) return bad != kNoEntry ? fail(MODGPU_ERR_INVALID, entry_text(bad, why)) : rc; // (a refusal is a refusal with or without a GPU)
-    if (dev >= kMaxDevices) return fail(MODGPU_ERR_INVALID, "device index beyond staging table");
-    int phys = -1;
-    HIP_TRY(hipGetDevice(&phys));
-    // The device sides of the non-empty entries below `bad`, both ends of each range (modgpu_xfer_device_of).  Entries whose device
-    // ranges touch, one beginning where the one before it ends -- the files of a part -- are looked up as ONE run, both ends of the run;
-    // only a run that is refused is gone through entry by entry, for the lowest one at fault.
-    auto dev_side = [&](const modgpu_table_entry_t &t) { return upload ? static_cast<const uint8_t *>(t.dst) : static_cast<const uint8_t *>(t.src); };
-    const uint64_t checked = bad != kNoEntry ? bad : n_entries;
-    const uint64_t records_bytes = n_entries * sizeof(modgpu_digest_result_t);
-    if (digest && modgpu_xfer_device_of(records, records_bytes) != phys) return fail(MODGPU_ERR_INVALID, "the records are not device memory of the call's device");
+    return MODGPU_OK;
+}
+// The device sides of the non-empty entries below `checked`, both ends of each range (modgpu_xfer_device_of).  Entries whose device
+// ranges touch, one beginning where the one before it ends -- the files of a part -- are looked up as ONE run, both ends of the run;
+// only a run that is refused is gone through entry by entry, for the lowest one at fault.
+int check_list_device_side(const ListCall &l, uint64_t checked, int phys)
+{
+    const modgpu_table_entry_t *const ents = l.ents;
+    auto dev_side = [&](const modgpu_table_entry_t &t) { return l.upload ? static_cast<const uint8_t *>(t.dst) : static_cast<const uint8_t *>(t.src); };
+    if (l.digest && modgpu_xfer_device_of(l.records, l.records_bytes()) != phys) return fail(MODGPU_ERR_INVALID, "the records are not device memory of the call's device");
     for (uint64_t i = 0; i < checked;) {
         if (ents[i].n == 0) {
             ++i;
@@ -1732,94 +1694,105 @@ int xfer_list_impl(const modgpu_table_entry_t *ents, uint64_t n_entries, int dev
                     return fail(MODGPU_ERR_INVALID, entry_text(k, "its device side is not device memory of the call's device"));
         i = j;
     }
-    if (digest) { // (below the lowest entry refused above: the lowest entry at fault is named)
-        const uintptr_t r0 = (uintptr_t)records, r1 = r0 + records_bytes;
+    if (l.digest) { // (below the lowest entry refused above: the lowest entry at fault is named)
+        const uintptr_t r0 = (uintptr_t)l.records, r1 = r0 + l.records_bytes();
         for (uint64_t i = 0; i < checked; ++i) {
             const uintptr_t d0 = (uintptr_t)dev_side(ents[i]);
             if (ents[i].n && d0 < r1 && r0 < d0 + ents[i].n) return fail(MODGPU_ERR_INVALID, entry_text(i, "its device range meets the records"));
         }
     }
-    if (bad != kNoEntry) return fail(MODGPU_ERR_INVALID, entry_text(bad, why));
-    HostList hl;
-    std::vector<uint32_t> index; // digest mode: hl.ent[k] is entry index[k] of the caller's list
-    for (uint64_t i = 0; i < n_entries; ++i) {
-        const modgpu_table_entry_t &t = ents[i];
+    return MODGPU_OK;
+}
+// the packed stream of the non-empty entries, and in digest mode `index`: hl.ent[k] is entry index[k] of the caller's list
+void pack_list(const ListCall &l, HostList &hl, std::vector<uint32_t> &index)
+{
+    for (uint64_t i = 0; i < l.n_entries; ++i) {
+        const modgpu_table_entry_t &t = l.ents[i];
         if (t.n == 0) continue;
-        if (digest) index.push_back((uint32_t)i);
-        uint8_t *const d = static_cast<uint8_t *>(const_cast<void *>(upload ? t.dst : t.src)), *const h = static_cast<uint8_t *>(const_cast<void *>(upload ? t.src : t.dst));
+        if (l.digest) index.push_back((uint32_t)i);
+        uint8_t *const d = static_cast<uint8_t *>(const_cast<void *>(l.upload ? t.dst : t.src)), *const h = static_cast<uint8_t *>(const_cast<void *>(l.upload ? t.src : t.dst));
         hl.ent.push_back({h, d, hl.total, t.n, t.stream_off % 0x7FFFFFFEull, lcg::key_residue(t.key)});
         hl.total += t.n;
     }
+}
+// the plan's device memory: made by the first window, freed behind the call -- unless the call's kernel would not leave (feed_stop),
+// which may still read it: then it stays, with the slots
+struct DevPlan {
+    XferListRec *p;
+    int dev;
+    ~DevPlan() { if (p && !g_device_lost[dev].load(std::memory_order_acquire)) (void)hipFree(p); }
+};
+// One window [at, at + len) of the packed stream, a list call of its own: its plan records (the first and last entry clipped) and digest
+// records into device memory, then xfer_pipelined over a HostList endpoint.
+int send_window(const ListCall &l, const HostList &hl, const std::vector<uint32_t> &index, uint64_t at, uint64_t len, int dev, const SetChoice &set, DevPlan &plan_mem)
+{
+    const bool digest = l.digest;
+    std::vector<XferListRec> recs;
+    std::vector<XferListDigestRec> digs;
+    const size_t digs_at = (hl.ent.size() + 1) * sizeof(XferListRec); // the digest records lie behind the plan, in the same allocation
+    for (size_t e = hl.entry_at(at); e < hl.ent.size() && hl.ent[e].start < at + len; ++e) {
+        const HostList::Ent &x = hl.ent[e];
+        const uint64_t into = x.start < at ? at - x.start : 0; // (the window's first entry may begin before the window)
+        recs.push_back({x.dev + into, x.start + into - at, x.key_res ? lcg::state_residue(x.key_res, (x.off + into) % 0x7FFFFFFEull) : 0u, x.key_res ? 0u : 1u});
+        if (digest) digs.push_back({index[e], (uint32_t)(into % kXferDigestMod)});
+    }
+    const uint32_t n_recs = (uint32_t)recs.size();
+    recs.push_back({nullptr, len, 0u, 0u});
+    if (!plan_mem.p) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&plan_mem.p), digs_at + (digest ? hl.ent.size() * sizeof(XferListDigestRec) : 0))); // (room for any window's)
+    HIP_TRY(hipMemcpy(plan_mem.p, recs.data(), recs.size() * sizeof(XferListRec), hipMemcpyHostToDevice));
+    XferListDigestRec *const digs_dev = reinterpret_cast<XferListDigestRec *>(reinterpret_cast<uint8_t *>(plan_mem.p) + digs_at);
+    if (digest) HIP_TRY(hipMemcpy(digs_dev, digs.data(), digs.size() * sizeof(XferListDigestRec), hipMemcpyHostToDevice));
+    Endpoint host_side, dev_side_ep;
+    host_side.list = &hl;
+    host_side.base = at;
+    dev_side_ep.dev = recs[0].dev; // (marks the device side; the kernel takes every address from the plan)
+    const Endpoint &src = l.upload ? host_side : dev_side_ep, &dst = l.upload ? dev_side_ep : host_side;
+    ListPlan list{plan_mem.p, n_recs};
+    if (digest) list = {plan_mem.p, n_recs, reinterpret_cast<XferDigestRecord *>(l.records), l.side, digs_dev};
+    StreamOutcome outcome;
+    CallCtx c{src, dst, len, 0, 0, dev, set, outcome, list};
+    return xfer_pipelined(c, false); // (always the transfer kernel: the testing flavour's DMA reference form has no list form)
+}
+} // namespace
+int xfer_list_impl(const modgpu_table_entry_t *ents, uint64_t n_entries, int device, bool upload, bool digest, uint32_t side, modgpu_digest_result_t *records)
+{
+    if (n_entries == 0) return MODGPU_OK;
+    const ListCall l{ents, n_entries, upload, digest, side, records};
+    uint64_t bad = kNoEntry;
+    const char *why = nullptr;
+    bool any_bytes = false;
+    int rc = check_list_host_side(l, bad, why, any_bytes);
+    if (rc) return rc;
+    if (bad == kNoEntry && !any_bytes && !digest) return MODGPU_OK; // a list with no bytes queues nothing (in digest mode its records are still written)
+    int dev = 0;
+    DeviceScope scope(device);
+    rc = scope.rc ? scope.rc : resolve_device(device, &dev);
+    if (rc) return bad != kNoEntry ? fail(MODGPU_ERR_INVALID, entry_text(bad, why)) : rc; // (a refusal is a refusal with or without a GPU)
+    if (dev >= kMaxDevices) return fail(MODGPU_ERR_INVALID, "device index beyond staging table");
+    int phys = -1;
+    HIP_TRY(hipGetDevice(&phys));
+    rc = check_list_device_side(l, bad != kNoEntry ? bad : n_entries, phys);
+    if (rc) return rc;
+    if (bad != kNoEntry) return fail(MODGPU_ERR_INVALID, entry_text(bad, why));
+    HostList hl;
+    std::vector<uint32_t> index;
+    pack_list(l, hl, index);
     if (injected_failure()) return fail(MODGPU_ERR_HIP, "injected failure (modgpu_debug_inject_failures)");
     if (g_device_lost[dev].load(std::memory_order_acquire)) return fail_lost();
     if (digest) { // the records as they are before the first launch: {0, 0, n_i, 0}, one copy (synchronous: in place before anything is launched)
         std::vector<modgpu_digest_result_t> init(n_entries);
         for (uint64_t i = 0; i < n_entries; ++i) init[i] = {0, 0, ents[i].n, 0};
+        const uint64_t records_bytes = l.records_bytes();
         HIP_TRY(hipMemcpy(records, init.data(), records_bytes, hipMemcpyHostToDevice));
         if (hl.ent.empty()) return MODGPU_OK; // a list with no bytes: nothing else to do
     }
     // which of the device's staging sets: the one on the node the first entry's host pages live on
-    int copy_node = -1;
-    cpu_set_t caller_mask;
-    CPU_ZERO(&caller_mask);
-    bool have_mask = false;
-    if (numa::enabled()) {
-        copy_node = numa::node_of_address(hl.ent[0].host + hl.ent[0].n / 2);
-        if (copy_node >= 0) have_mask = ::sched_getaffinity(0, sizeof caller_mask, &caller_mask) == 0;
-    }
-    const int gpu_node = copy_node >= 0 ? device_numa_node(dev) : -1;
-    const int set = copy_node >= 0 && copy_node < kNodeSets - 1 && gpu_node >= 0 && copy_node != gpu_node && have_mask ? 1 + copy_node : 0;
-    Staging &s = staging_of(dev, set);
-    if (set != 0) {
-        if (s.node.load(std::memory_order_relaxed) != copy_node) s.node.store(copy_node, std::memory_order_relaxed);
-        g_node_set_calls.fetch_add(1, std::memory_order_relaxed);
-    }
-    trace(MODGPU_TRACE_CALL_BEGIN, -1, 0, hl.total);
-    struct CallEnd { uint64_t n; ~CallEnd() { trace(MODGPU_TRACE_CALL_END, -1, 0, n); } } call_end{hl.total};
-    // the plan's device memory: made here, freed behind the call -- unless the call's kernel would not leave (feed_stop), which may still
-    // read it: then it stays, with the slots
-    struct DevPlan {
-        XferListRec *p = nullptr;
-        int dev;
-        ~DevPlan() { if (p && !g_device_lost[dev].load(std::memory_order_acquire)) (void)hipFree(p); }
-    } plan_mem;
-    plan_mem.dev = dev;
-    StreamOutcome outcome;
-    const uint64_t natural = (uint64_t)kFeedChunksMax * (kChunk - kFeedPieceBytes);
-    const uint64_t most = kXferListMost ? std::min(kXferListMost, natural) : natural;
-    std::vector<XferListRec> recs;
-    std::vector<XferListDigestRec> digs;
-    const size_t digs_at = (hl.ent.size() + 1) * sizeof(XferListRec); // the digest records lie behind the plan, in the same allocation
+    const SetChoice set = choose_set(dev, numa::enabled() ? numa::node_of_address(hl.ent[0].host + hl.ent[0].n / 2) : -1);
+    const CallScope scope_of_call(hl.total);
+    DevPlan plan_mem{nullptr, dev};
+    const uint64_t most = kXferListMost ? std::min(kXferListMost, one_launch_most()) : one_launch_most();
     for (uint64_t at = 0; at < hl.total; at += most) {
-        const uint64_t len = std::min<uint64_t>(most, hl.total - at);
-        recs.clear();
-        digs.clear();
-        for (size_t e = hl.entry_at(at); e < hl.ent.size() && hl.ent[e].start < at + len; ++e) {
-            const HostList::Ent &x = hl.ent[e];
-            const uint64_t into = x.start < at ? at - x.start : 0; // (the window's first entry may begin before the window)
-            recs.push_back({x.dev + into, x.start + into - at, x.key_res ? lcg::state_residue(x.key_res, (x.off + into) % 0x7FFFFFFEull) : 0u, x.key_res ? 0u : 1u});
-            if (digest) digs.push_back({index[e], (uint32_t)(into % kXferDigestMod)});
-        }
-        const uint32_t n_recs = (uint32_t)recs.size();
-        recs.push_back({nullptr, len, 0u, 0u});
-        if (!plan_mem.p) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&plan_mem.p), digs_at + (digest ? hl.ent.size() * sizeof(XferListDigestRec) : 0))); // (room for any window's)
-        HIP_TRY(hipMemcpy(plan_mem.p, recs.data(), recs.size() * sizeof(XferListRec), hipMemcpyHostToDevice));
-        XferListDigestRec *const digs_dev = reinterpret_cast<XferListDigestRec *>(reinterpret_cast<uint8_t *>(plan_mem.p) + digs_at);
-        if (digest) HIP_TRY(hipMemcpy(digs_dev, digs.data(), digs.size() * sizeof(XferListDigestRec), hipMemcpyHostToDevice));
-        Endpoint host_side, dev_side_ep;
-        host_side.list = &hl;
-        host_side.base = at;
-        dev_side_ep.dev = recs[0].dev; // (marks the device side; the kernel takes every address from the plan)
-        const Endpoint &src = upload ? host_side : dev_side_ep, &dst = upload ? dev_side_ep : host_side;
-        CallCtx c{src, dst, len, 0, 0, dev, s, false, false, false, false, false, false, copy_node, caller_mask, have_mask, outcome};
-        c.list_dev = plan_mem.p;
-        c.list_n = n_recs;
-        if (digest) {
-            c.list_records = reinterpret_cast<XferDigestRecord *>(records);
-            c.list_side = side;
-            c.list_digest_dev = digs_dev;
-        }
-        rc = xfer_pipelined(c, false); // (always the transfer kernel: the testing flavour's DMA reference form has no list form)
+        rc = send_window(l, hl, index, at, std::min<uint64_t>(most, hl.total - at), dev, set, plan_mem);
         if (rc) return rc;
     }
     return MODGPU_OK;

@@ -143,8 +143,12 @@ void run_feed(void *arg)
 } // namespace
 uint32_t modgpu_feed_block() { return 256u; }
 const char *modgpu_feed_kernel_name() { return "shim feed"; }
+// modgpu_shim_fail_next_feed_launch(1): the next host-fed launch is refused by the "runtime" -- nothing is queued
+static std::atomic<int> g_fail_next_feed_launch{0};
+extern "C" void modgpu_shim_fail_next_feed_launch(int on) { g_fail_next_feed_launch.store(on ? 1 : 0); }
 hipError_t modgpu_launch_cycle_feed(const CycleFeedArgs &a, uint32_t, hipStream_t stream)
 {
+    if (g_fail_next_feed_launch.exchange(0) != 0) return hipErrorLaunchFailure;
     shim::enqueue(stream, run_feed, new CycleFeedArgs(a));
     return hipSuccess;
 }

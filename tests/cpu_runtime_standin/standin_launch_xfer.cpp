@@ -96,8 +96,12 @@ const char *modgpu_xfer_kernel_name(bool upload, int form)
 {
     return upload ? (form == XFER_FUNNEL ? "shim xfer up funnel" : "shim xfer up") : (form == XFER_FUNNEL ? "shim xfer down funnel" : "shim xfer down");
 }
+// modgpu_shim_fail_next_xfer_launch(1): the next transfer launch is refused by the "runtime" -- nothing is queued
+static std::atomic<int> g_fail_next_xfer_launch{0};
+extern "C" void modgpu_shim_fail_next_xfer_launch(int on) { g_fail_next_xfer_launch.store(on ? 1 : 0); }
 hipError_t modgpu_launch_cycle_xfer(const CycleXferArgs &a, bool upload, int, uint32_t, hipStream_t stream)
 {
+    if (g_fail_next_xfer_launch.exchange(0) != 0) return hipErrorLaunchFailure;
     shim::enqueue(stream, run_xfer, new XferLaunch{a, upload});
     return hipSuccess;
 }
